@@ -174,7 +174,7 @@ __global__ void __launch_bounds__(256) k_cl_clear(u32 nb1, u32* __restrict__ wsu
 	const u32* __restrict__ jointBodyMask, u32 keepJointLists)
 {
 	u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-	if (i < nb1) compLabel[i] = i;               // components of what the curve phases leave over: every body its own
+	if (i < nb1) { compLabel[i] = i; compLabel[nb1 + i] = i; } // components of what the curve phases leave over: every body its own (both label buffers)
 	if (i < 5u) counters[CTR_CL_LEFT + i] = 0;
 	if (i == 0u) counters[CTR_CL_SCRATCH] = 0;   // append cursor of the solve launch's row scratch
 	if (i < CL_MAX_TASKS && !keepJointLists) jointCount[i] = 0; // (between two refreshes the joints' tasks do not change: their lists are kept, see launch_cluster_build)
@@ -428,31 +428,37 @@ __global__ void __launch_bounds__(256) k_cl_joint_assign_cached(u32 numJoints, c
 // What the curve phases leave over (a few per cent of the manifolds: those cut by every curve's chunk borders, in small clumps where
 // the borders cross) is not cut again: its connected components (bodies joined by left-over manifolds) are found and whole components
 // are dealt to the tasks of ONE more phase, so nothing is left for a further phase and the rest task stays empty (each phase costs a
-// hand-over and its slowest task's colours in EVERY iteration).  Union-find on the global label array (label[b] = a body of b's
-// component with a smaller or equal id; k_cl_clear set label[b] = b), a fixed number of rounds — a component that has not
-// converged by then only sends the manifolds whose ends still disagree to the rest task.  Components are
+// hand-over and its slowest task's colours in EVERY iteration).  Union-find on a global label array (label[b] = a body of b's
+// component with a smaller or equal id; k_cl_clear set label[b] = b in both of its buffers), a fixed number of rounds, each reading
+// the labels the previous round left and writing the next buffer (k_cl_comp_round), so that the labels after every round, and with
+// them the schedule, do not depend on how the manifolds of a round interleave — a component that has not converged by then only
+// sends the manifolds whose ends still disagree to the rest task.  Components are
 // dealt to tasks by a hash of their label (the clumps are tens of manifolds against tasks of hundreds: the load evens out), a
 // component too large for a task is sent to the rest task.
 #define CL_COMP_ROUNDS 4u
+static_assert(CL_COMP_ROUNDS % 2u == 0u, "the last round must write the first label buffer: the weights and the assignment read it");
 #define CL_COMP_MAX_WEIGHT (64u * 1400u) // a component heavier than this cannot be a task's (k_cl_color's tables): rest task
 #define CL_COMP_BLOCKS 64u               // workgroups of the component kernels (they stride over the list: its length is only known on the device)
 #define CL_LD(P_) __hip_atomic_load((P_), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
 MI_DEV u32 clFind(u32* label, u32 x) { u32 r = CL_LD(&label[x]); for (u32 h = 0; h < 16u; ++h) { u32 up = CL_LD(&label[r]); if (up == r) break; r = up; } return r; }
-// One round: every left-over manifold hooks the larger of its ends' roots under the smaller one, then shortens its ends' paths.  Rounds
-// are separate launches; inside a round hooks and shortcuts of different manifolds interleave freely: a label always names a body of
-// the same component with a smaller or equal id, so whatever the interleaving the labels only ever merge what belongs together, and
-// a link lost to a concurrent hook is found again by the next round (the manifold that made it is looked at in every round).
-__global__ void __launch_bounds__(256) k_cl_comp_round(const u32* __restrict__ counters, u32 nb, u32 leftCap, const u32* __restrict__ leftList, const uint4* __restrict__ actIds, u32* label)
+// One round: every left-over manifold hooks the larger of its ends' roots under the smaller one, and points both ends at the
+// smaller root.  A round reads the labels of the previous round (labelIn, not written during the round) and lowers those of the next
+// (labelOut) with atomicMin only, so what a round produces does not depend on how its manifolds interleave: the components, the
+// weights and so the whole schedule repeat from run to run.  labelOut still holds the labels of two rounds ago, which are valid
+// (a body of the same component, smaller or equal id) and never below what this round writes into them.
+MI_DEV u32 clFindIn(const u32* __restrict__ label, u32 x) { u32 r = label[x]; for (u32 h = 0; h < 16u; ++h) { u32 up = label[r]; if (up == r) break; r = up; } return r; }
+__global__ void __launch_bounds__(256) k_cl_comp_round(const u32* __restrict__ counters, u32 nb, u32 leftCap, const u32* __restrict__ leftList, const uint4* __restrict__ actIds,
+	const u32* __restrict__ labelIn, u32* __restrict__ labelOut)
 {
 	const u32 n = min(counters[CTR_CL_LEFT], leftCap);
 	for (u32 i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
 	{
 		uint4 ids = actIds[leftList[i]];
 		if (ids.x >= nb || ids.y >= nb) continue;
-		u32 ra = clFind(label, ids.x), rb = clFind(label, ids.y);
-		if (ra != rb) atomicMin(&label[max(ra, rb)], min(ra, rb));
-		atomicMin(&label[ids.x], clFind(label, ids.x));
-		atomicMin(&label[ids.y], clFind(label, ids.y));
+		const u32 ra = clFindIn(labelIn, ids.x), rb = clFindIn(labelIn, ids.y), lo = min(ra, rb);
+		if (ra != rb) atomicMin(&labelOut[max(ra, rb)], lo);
+		atomicMin(&labelOut[ids.x], lo);
+		atomicMin(&labelOut[ids.y], lo);
 	}
 }
 // Weight of every component (at its label) and of the lot (counters[CTR_CL_LEFT + 2], zeroed by k_cl_clear).
@@ -1481,7 +1487,7 @@ void launch_cluster_build(World& w, u32 numPairs)
 	w.clJointTask.ensure(std::max(nj, 1u), w.stream); w.clJointPos.ensure(std::max(nj, 1u), w.stream); w.clJointList.ensure(std::max(nj, 1u), w.stream); w.clTaskJoints.ensure(std::max(nj, 1u), w.stream);
 	w.clJointClassStart.ensure((size_t)CL_MAX_TASKS * (CL_MAX_JOINT_CLASSES + 2u), w.stream);
 	if (w.lastError) return;
-	w.clCompLabel.ensure(nb1, w.stream); w.clLeftList.ensure(w.pairCap, w.stream);
+	w.clCompLabel.ensure(2 * nb1, w.stream); w.clLeftList.ensure(w.pairCap, w.stream);
 	if (w.lastError) return;
 	// A world whose curve phases left nothing over in the last step (ragdolls standing apart: every island interior to its task) skips
 	// the component phase's six launches; what the curves do leave over in this step then goes to the rest task, as without the
@@ -1534,7 +1540,9 @@ void launch_cluster_build(World& w, u32 numPairs)
 	if (leftList && parts < CL_MAX_PARTS)
 	{
 		u32* compWeight = w.clWsum.p + (size_t)(CL_MAX_PARTS - 1) * nb1; // (the last curve's weight sums are not in use: zeroed by k_cl_clear)
-		for (u32 r = 0; r < CL_COMP_ROUNDS; ++r) hipLaunchKernelGGL(k_cl_comp_round, dim3(CL_COMP_BLOCKS), block, 0, w.stream, w.dCounters.p, nb, leftCap, w.clLeftList.p, w.actIds.p, w.clCompLabel.p);
+		for (u32 r = 0; r < CL_COMP_ROUNDS; ++r) // (the label buffers alternate: round r reads buffer r & 1 and writes the other)
+			hipLaunchKernelGGL(k_cl_comp_round, dim3(CL_COMP_BLOCKS), block, 0, w.stream, w.dCounters.p, nb, leftCap, w.clLeftList.p, w.actIds.p,
+				(const u32*)(w.clCompLabel.p + (size_t)(r & 1u) * nb1), w.clCompLabel.p + (size_t)((r + 1u) & 1u) * nb1);
 		hipLaunchKernelGGL(k_cl_comp_weights, dim3(CL_COMP_BLOCKS), block, 0, w.stream, w.dCounters.p, nb, leftCap, w.clLeftList.p, w.actIds.p, w.clCompLabel.p, compWeight);
 		hipLaunchKernelGGL(k_cl_comp_assign, dim3(CL_COMP_BLOCKS), block, 0, w.stream, w.dCounters.p, nb, parts, w.clusterTaskWeightLater, leftCap, w.clLeftList.p, w.actIds.p, w.clCompLabel.p, compWeight,
 			w.clTaskKey.p, w.clTaskPos.p, w.clTaskCount.p, w.clPhaseMask.p);

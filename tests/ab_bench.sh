@@ -4,7 +4,7 @@ A=$1; B=$2; R=${3:-3}; shift 3 || true
 for i in $(seq 1 $R); do
   for L in $A $B; do
     cp $L directx-renderer-kurth_amd/libmi_physics.so
-    timeout -k 10 200 python bench.py --steps 20 --warmup 5 --no-cpu-baseline "$@" 2>/dev/null | python -c "
+    timeout -k 10 200 python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline "$@" 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); s=d['stage_ms']; print('$L', round(d['value'],1), round(d['ms_per_step'],4), s['msCollidersBroad'], s['msNarrow'], s['msSolverSetup'], s['msSolve'])"
   done
 done

@@ -1,6 +1,6 @@
 """Developer probe: follow-mode parity of the cluster sweep on small scenes, printed step by step (not a test)."""
-import sys
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tests")
+import os, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import numpy as np
 import directx_renderer_kurth_amd as mi
 from directx_renderer_kurth_amd import scenes

@@ -1,7 +1,7 @@
 """Developer tool: timeline of the cluster contact sweep (mi_debug_flow_trace): per workgroup and iteration, when each task had its
 shared bodies, finished its colours, and the cost of every colour step of iteration 10."""
-import sys
-sys.path.insert(0, "/root/repo")
+import os, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import directx_renderer_kurth_amd as mi
 from directx_renderer_kurth_amd import scenes

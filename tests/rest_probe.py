@@ -1,6 +1,6 @@
 """Developer tool: max penetration / kinetic energy of rest_stacks over time, device (production order) vs the oracle's two reference orders."""
-import sys
-sys.path.insert(0, "/root/repo")
+import os, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import directx_renderer_kurth_amd as mi
 from directx_renderer_kurth_amd import scenes

@@ -1,6 +1,6 @@
 """Developer tool: per-step overhead of the slab wrapper (state hand-over + ownership bookkeeping + exchange) at world_size 1."""
 import os, sys, time
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, torch.distributed as dist
 import directx_renderer_kurth_amd as mi
 from directx_renderer_kurth_amd import scenes, parallel

@@ -8,8 +8,8 @@ rank's real per-step sequence — mi_slab_pack, mi_slab_unpack, mi_step_internal
 projected speed-up = unsplit ms/step / slowest rank's ms/step.  It is a projection: no message travels over a link (at ~0.4 MB per
 neighbour and step against 150 GB/s per xGMI link the wire time is ~3 us), ranks do not wait for each other, and every rank's
 neighbours are the unsplit world, not other slabs.  usage: python tests/slab_projection.py [bodies] [settle] [steps]"""
-import sys, time
-sys.path.insert(0, "/root/repo")
+import os, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 import directx_renderer_kurth_amd as mi

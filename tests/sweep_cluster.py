@@ -1,7 +1,7 @@
 """Developer tool: solve / setup time of C3 at two points of the run for a list of environment settings (one world per setting).
 usage: python tests/sweep_cluster.py "MI_CLUSTER_TASK=800" "MI_CLUSTER_TASK=1000 MI_CLUSTER_TASK_LATER=500" ..."""
 import os, sys
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import directx_renderer_kurth_amd as mi
 from directx_renderer_kurth_amd import scenes
 s = scenes.by_name("c3")
