@@ -364,7 +364,7 @@ __global__ void __launch_bounds__(256) k_cl_assign_cached(u32* counters, u32 nb,
 			}
 		}
 	}
-	// manifolds still unassigned when phase q + 1 starts (statistics; the host adapts the number of phases from them)
+	// manifolds still unassigned when phase q + 1 starts (statistics)
 	const bool goesOn = live && phase == numParts && numCached < numParts && !dumpAll; // left by the cached phases, with a pipeline phase to go to
 	for (u32 q = 0; q < numCached; ++q)
 	{
@@ -960,7 +960,7 @@ struct ClArgs
 	u32* counters; const ClTask* tasks; const u32* bodyList; const u32* phaseMask; const u32* sharedSlot;
 	const u32* mKeySorted; const u32* mLocal; const u32* cEntry;
 	const float4* rowPlanes; const float4* rowShared; float2* rowLambda; float4* rowScratch; u32 scratchContacts;
-	u32 predictDiv, pollSleep; // pacing of the hand-over polls (MI_CLUSTER_PREDICT_DIV / MI_CLUSTER_POLL_SLEEP)
+	u32 predictDiv, pollSleep; // pacing of the hand-over polls (CL_PREDICT_DIV / CL_POLL_SLEEP)
 	float4* vel; u64* flow; u64* trace; // trace: developer timeline (mi_debug_flow_trace), normally null
 	size_t rowCap; u32 nb, flowBytes, epoch, itBegin, itEnd, ldsFloat4s;
 	// joints run by the sweep (null / 0 when the world has none or they keep their own launches): per phase-0 task the class offsets
@@ -1438,6 +1438,11 @@ bool cluster_available(World& w)
 	return true;
 }
 
+// Cell shifts of the phases' Morton curves (phase 0 unshifted).
+static const ClShifts CL_SHIFTS = { { { 0, 0, 0 }, { 13, 9, 15 }, { 27, 21, 31 }, { 7, 29, 5 } } };
+static const u32 CL_SORT_INTERVAL = 8;           // steps between re-sorts of the bodies along the curves (= refreshes of the cached chunks)
+static const u32 CL_CHUNK_HEADROOM_PERCENT = 10; // the cached chunks are cut this much short: the pile may grow until the next refresh
+
 // Everything between "manifolds exist" and "rows can be initialised": order of the bodies, tasks, local colouring, final slot order.
 void launch_cluster_build(World& w, u32 numPairs)
 {
@@ -1460,22 +1465,22 @@ void launch_cluster_build(World& w, u32 numPairs)
 	// their size per step, so the order is refreshed every few steps only (four radix sorts of all bodies), at once when bodies were
 	// added and after a snapshot was taken or restored (so that a restored world and its original keep making the same choices).
 	const u32 P = CL_MAX_PARTS;
-	const u32 parts = w.useComponents ? std::min(w.clusterParts, CL_MAX_PARTS - 1u) : w.clusterParts; // curve phases (the component phase comes on top)
+	const u32 parts = CL_CURVE_PARTS;
 	// the curves in use and the one behind them (phase p attributes what it leaves over along curve p + 1) are sorted; all of them the first
 	// time and when the body count changed, so that every rank array holds valid positions (each sort is ~80 us at 100 k bodies)
-	const u32 sortParts = (w.clusterSortBodies != nb) ? P : std::min(P, parts + 1u);
+	const u32 sortParts = (w.clusterSortBodies != nb) ? P : parts + 1u;
 	bool refresh = false; // this step re-sorts the bodies and re-cuts the chunks; the steps in between reuse the stored chunks
-	if (w.clusterSortDue || w.clusterSortAge >= w.clusterSortInterval || w.clusterSortBodies != nb || w.clusterSortedParts < sortParts)
+	if (w.clusterSortDue || w.clusterSortAge >= CL_SORT_INTERVAL || w.clusterSortBodies != nb)
 	{
 		refresh = true;
-		ClShifts sh; u32 maxShift = 0;
-		for (u32 p = 0; p < CL_MAX_PARTS; ++p) for (u32 k = 0; k < 3; ++k) { sh.s[p][k] = w.clusterShift[p][k]; maxShift = std::max(maxShift, sh.s[p][k]); }
+		u32 maxShift = 0;
+		for (const auto& s : CL_SHIFTS.s) for (u32 v : s) maxShift = std::max(maxShift, v);
 		hipLaunchKernelGGL(k_cl_bbox, dim3(std::min<u32>(bgrid.x, 64u)), block, 0, w.stream, nb, w.cog.p, w.simMask.p, w.dCounters.p);
-		hipLaunchKernelGGL(k_cl_keys, bgrid, block, 0, w.stream, nb, P, sh, maxShift, w.cog.p, w.simMask.p, w.dCounters.p, w.clKeys.p, w.clVals.p);
+		hipLaunchKernelGGL(k_cl_keys, bgrid, block, 0, w.stream, nb, P, CL_SHIFTS, maxShift, w.cog.p, w.simMask.p, w.dCounters.p, w.clKeys.p, w.clVals.p);
 		for (u32 p = 0; p < sortParts; ++p)
 			prim_sort_pairs_u32(w, w.clKeys.p + (size_t)p * nb, w.clKeysSorted.p + (size_t)p * nb, w.clVals.p + (size_t)p * nb, w.clSorted.p + (size_t)p * nb, nb, 30);
 		hipLaunchKernelGGL(k_cl_ranks, bgrid, block, 0, w.stream, nb, sortParts, w.clSorted.p, w.clRank.p);
-		w.clusterSortDue = false; w.clusterSortAge = 0; w.clusterSortBodies = nb; w.clusterSortedParts = sortParts; // (curves sorted by THIS refresh: one more phase in use than that forces the next refresh at once, so the order never depends on an older sort)
+		w.clusterSortDue = false; w.clusterSortAge = 0; w.clusterSortBodies = nb;
 	}
 	w.clusterSortAge++;
 	// tasks
@@ -1492,12 +1497,12 @@ void launch_cluster_build(World& w, u32 numPairs)
 	// A world whose curve phases left nothing over in the last step (ragdolls standing apart: every island interior to its task) skips
 	// the component phase's six launches; what the curves do leave over in this step then goes to the rest task, as without the
 	// component phase, and the next step runs the components again (World::countPreviousStep).
-	u32* leftList = (w.useComponents && !w.compIdle) ? w.clLeftList.p : nullptr; const u32 leftCap = (u32)w.pairCap;
+	u32* leftList = !w.compIdle ? w.clLeftList.p : nullptr; const u32 leftCap = (u32)w.pairCap;
 	const u32 firstFlags = withJoints ? CL_WEIGHT_ISLANDS : 0u; // (goes with the first phase's weight)
 	const u32 maxTasks = std::min<u32>(CL_MAX_TASKS / CL_TASKS_PER_PHASE, w.clusterBlocks) - std::min<u32>(8u, w.clusterBlocks / 8u); // per phase, with a margin for the chunks' rounding
 	w.clChunk.ensure((size_t)CL_MAX_PARTS * nb1, w.stream);
 	if (w.lastError) return;
-	if (!w.useChunkCache || w.clChunkParts < parts || w.clChunkJointVersion != w.jointVersion || w.clChunkWithJoints != withJoints) refresh = true;
+	if (w.clChunkJointVersion != w.jointVersion || w.clChunkWithJoints != withJoints) refresh = true;
 	// The joints' tasks follow their islands' chunks, which change at a refresh only: in between, the task lists of the joints (task,
 	// position, counts, the scattered list) are kept as the refresh step built them — two launches less per step for a ragdoll world.
 	const bool keepJointLists = !refresh && nj != 0u && w.clJointListsValid;
@@ -1505,8 +1510,7 @@ void launch_cluster_build(World& w, u32 numPairs)
 		nj ? w.clJointBodyMask.p : (const u32*)nullptr, keepJointLists ? 1u : 0u);
 	if (refresh)
 	{
-		// (with the cache on, the chunks are cut 4 % short: the pile may grow until the next refresh)
-		const u32 weight0 = w.useChunkCache ? w.clusterTaskWeight - (u32)((u64)w.clusterTaskWeight * w.chunkHeadroomPercent / 100u) : w.clusterTaskWeight, weightLater = (w.useChunkCache && w.chunkCachedPhases > 1u) ? w.clusterTaskWeightLater - (u32)((u64)w.clusterTaskWeightLater * w.chunkHeadroomPercent / 100u) : w.clusterTaskWeightLater;
+		const u32 weight0 = w.clusterTaskWeight - (u32)((u64)w.clusterTaskWeight * CL_CHUNK_HEADROOM_PERCENT / 100u), weightLater = w.clusterTaskWeightLater - (u32)((u64)w.clusterTaskWeightLater * CL_CHUNK_HEADROOM_PERCENT / 100u);
 		hipLaunchKernelGGL(k_cl_weights0, mgrid, block, 0, w.stream, w.dCounters.p, nb, w.actIds.p, w.clRank.p, rep, w.clWsum.p, w.clTaskKey.p);
 		if (nj) hipLaunchKernelGGL(k_cl_joint_weights, dim3((nj + 255) / 256), block, 0, w.stream, nj, w.clJointTable.p, w.clRank.p, rep, w.clWsum.p);
 		for (u32 p = 0; p < parts; ++p)
@@ -1517,27 +1521,18 @@ void launch_cluster_build(World& w, u32 numPairs)
 				w.clRank.p + (size_t)std::min(p + 1, CL_MAX_PARTS - 1) * nb1, wsumNext, w.clTaskKey.p, w.clTaskPos.p, w.clTaskCount.p, w.clPhaseMask.p, w.dCounters.p + CTR_CL_STATUS, p == 0 ? rep : nullptr, leftList, leftCap);
 			if (p == 0 && nj) // (cum still holds phase 0's scan)
 				hipLaunchKernelGGL(k_cl_joint_assign, dim3((nj + 255) / 256), block, 0, w.stream, nj, nb, weight0 | firstFlags, maxTasks, w.clJointTable.p, w.clRank.p, rep, w.clCum.p, w.clJointTask.p, w.clJointPos.p, w.clJointCount.p, w.clPhaseMask.p, w.dCounters.p + CTR_CL_STATUS);
-			if (w.useChunkCache)
-				hipLaunchKernelGGL(k_cl_store_chunks, bgrid, block, 0, w.stream, nb, p ? weightLater : (weight0 | firstFlags), maxTasks, w.clRank.p + (size_t)p * nb1, w.clCum.p, p == 0 ? rep : nullptr, w.clChunk.p + (size_t)p * nb1);
+			hipLaunchKernelGGL(k_cl_store_chunks, bgrid, block, 0, w.stream, nb, p ? weightLater : (weight0 | firstFlags), maxTasks, w.clRank.p + (size_t)p * nb1, w.clCum.p, p == 0 ? rep : nullptr, w.clChunk.p + (size_t)p * nb1);
 		}
-		w.clChunkParts = parts; w.clChunkJointVersion = w.jointVersion; w.clChunkWithJoints = withJoints;
+		w.clChunkJointVersion = w.jointVersion; w.clChunkWithJoints = withJoints;
 	}
 	else
 	{
-		const u32 cached = std::min(parts, w.chunkCachedPhases);
-		hipLaunchKernelGGL(k_cl_assign_cached, mgrid, block, 0, w.stream, w.dCounters.p, nb, parts, cached, withJoints ? 1u : 0u, w.actIds.p, w.clChunk.p,
-			w.clRank.p + (size_t)std::min(cached, CL_MAX_PARTS - 1) * nb1, w.clWsum.p + (size_t)std::min(cached, CL_MAX_PARTS - 1) * nb1, w.clTaskKey.p, w.clTaskPos.p, w.clTaskCount.p, w.clPhaseMask.p, leftList, leftCap);
+		hipLaunchKernelGGL(k_cl_assign_cached, mgrid, block, 0, w.stream, w.dCounters.p, nb, parts, parts, withJoints ? 1u : 0u, w.actIds.p, w.clChunk.p,
+			w.clRank.p + (size_t)parts * nb1, w.clWsum.p + (size_t)parts * nb1, w.clTaskKey.p, w.clTaskPos.p, w.clTaskCount.p, w.clPhaseMask.p, leftList, leftCap);
 		if (nj && !keepJointLists) hipLaunchKernelGGL(k_cl_joint_assign_cached, dim3((nj + 255) / 256), block, 0, w.stream, nj, w.clJointTable.p, w.clChunk.p, w.clJointTask.p, w.clJointPos.p, w.clJointCount.p, w.clPhaseMask.p);
-		for (u32 p = cached; p < parts; ++p) // the later phases: the per-step pipeline on what is left
-		{
-			u32* wsum = w.clWsum.p + (size_t)p * nb1; u32* wsumNext = w.clWsum.p + (size_t)std::min(p + 1, CL_MAX_PARTS - 1) * nb1;
-			prim_exclusive_scan_u32(w, wsum, w.clCum.p, nb + 1);
-			hipLaunchKernelGGL(k_cl_assign, mgrid, block, 0, w.stream, w.dCounters.p, nb, p, parts, p ? w.clusterTaskWeightLater : (w.clusterTaskWeight | firstFlags), maxTasks, w.actIds.p, w.clRank.p + (size_t)p * nb1, w.clCum.p,
-				w.clRank.p + (size_t)std::min(p + 1, CL_MAX_PARTS - 1) * nb1, wsumNext, w.clTaskKey.p, w.clTaskPos.p, w.clTaskCount.p, w.clPhaseMask.p, w.dCounters.p + CTR_CL_STATUS, (const u32*)nullptr, leftList, leftCap);
-		}
 	}
 	// what the curve phases left over: whole connected components to the tasks of one more phase (index = parts)
-	if (leftList && parts < CL_MAX_PARTS)
+	if (leftList)
 	{
 		u32* compWeight = w.clWsum.p + (size_t)(CL_MAX_PARTS - 1) * nb1; // (the last curve's weight sums are not in use: zeroed by k_cl_clear)
 		for (u32 r = 0; r < CL_COMP_ROUNDS; ++r) // (the label buffers alternate: round r reads buffer r & 1 and writes the other)
@@ -1549,12 +1544,15 @@ void launch_cluster_build(World& w, u32 numPairs)
 	}
 	hipLaunchKernelGGL(k_cl_offsets, dim3(1), dim3(1024), 0, w.stream, w.dCounters.p, parts, w.clTaskCount.p, w.clTaskStart.p, nj ? w.clJointCount.p : (u32*)nullptr, nj ? w.clJointStart.p : (u32*)nullptr);
 	if (nj && !keepJointLists) hipLaunchKernelGGL(k_cl_joint_scatter, dim3((nj + 255) / 256), block, 0, w.stream, nj, w.clJointTask.p, w.clJointPos.p, w.clJointStart.p, w.clJointList.p);
-	w.clJointListsValid = nj != 0u && w.useChunkCache;
+	w.clJointListsValid = nj != 0u;
 	hipLaunchKernelGGL(k_cl_scatter, mgrid, block, 0, w.stream, w.dCounters.p, w.clTaskKey.p, w.clTaskPos.p, w.clTaskStart.p, w.clPre.p);
 	hipLaunchKernelGGL(k_cl_color, dim3(w.clusterBlocks), dim3(CL_LANES), clColorLdsBytes(), w.stream, w.dCounters.p, nb, w.clTaskStart.p, w.clPre.p, w.actIds.p,
 		w.clPhaseMask.p, (ClTask*)w.clTasks.p, w.clBodyList.p, w.mOrder.p, w.mKeySorted.p, w.clLocal.p, w.clEntry.p, w.clSharedSlot.p,
 		nj ? w.clJointStart.p : (const u32*)nullptr, w.clJointList.p, w.clJointTable.p, w.clTaskJoints.p, w.clJointClassStart.p, w.flowTrace.p);
 }
+
+static const u32 CL_PREDICT_DIV = 4; // a lane sleeps through 1 - 1/CL_PREDICT_DIV of its previous wait for a hand-over before it polls
+static const u32 CL_POLL_SLEEP = 1;  // pause between two polls (k_cl_solve: 0 none, 1 short, 2 long)
 
 // Iterations [itBegin, itEnd) of the contact sweep in one launch.
 void launch_cluster_solve(World& w, u32 itBegin, u32 itEnd)
@@ -1582,7 +1580,7 @@ void launch_cluster_solve(World& w, u32 itBegin, u32 itEnd)
 	A.rowScratch = w.clRowScratch.p; A.scratchContacts = (u32)scratchContacts;
 	A.counters = w.dCounters.p; A.tasks = (const ClTask*)w.clTasks.p; A.bodyList = w.clBodyList.p; A.phaseMask = w.clPhaseMask.p; A.sharedSlot = w.clSharedSlot.p;
 	A.mKeySorted = w.mKeySorted.p; A.mLocal = w.clLocal.p; A.cEntry = w.clEntry.p;
-	A.rowPlanes = w.rowPlanes.p; A.rowShared = w.rowShared.p; A.rowLambda = w.rowLambda.p; A.vel = w.vel.p; A.flow = w.flow.p; A.trace = w.flowTrace.p; A.predictDiv = w.clusterPredictDiv; A.pollSleep = w.clusterPollSleep;
+	A.rowPlanes = w.rowPlanes.p; A.rowShared = w.rowShared.p; A.rowLambda = w.rowLambda.p; A.vel = w.vel.p; A.flow = w.flow.p; A.trace = w.flowTrace.p; A.predictDiv = CL_PREDICT_DIV; A.pollSleep = CL_POLL_SLEEP;
 	A.rowCap = w.rowCap; A.nb = w.nb; A.flowBytes = (u32)(words * sizeof(u64)); A.epoch = w.flowEpoch << 16; A.itBegin = itBegin; A.itEnd = itEnd;
 	A.ldsFloat4s = w.clusterLdsBytes / 16u;
 	const bool withJoints = cluster_solves_joints(w);

@@ -1264,7 +1264,6 @@ void launch_narrowphase(World& w, u32 numPairs)
 		hipDeviceProp_t prop; MI_CHECK(hipGetDeviceProperties(&prop, w.device)); numCUs = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
 		MI_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&epaPerCU[0], k_epa<0>, 64 * EPA_WAVES_PER_BLOCK, 0));
 		MI_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&epaPerCU[1], k_epa<1>, 64 * EPA_WAVES_PER_BLOCK, 0));
-		if (const char* e = getenv("MI_EPA_BLOCKS_PER_CU")) epaPerCU[0] = epaPerCU[1] = std::max(1, atoi(e));
 		for (int& v : epaPerCU) if (v < 1) v = 3;
 	}
 	u32 epaBlocks = std::min<u32>((numPairs + EPA_WAVES_PER_BLOCK - 1) / EPA_WAVES_PER_BLOCK, (u32)(numCUs * epaPerCU[0]));

@@ -201,6 +201,8 @@ void launch_active_list(World& w, u32 numPairs)
 		(const u64*)w.pairsSorted.p, (const u64*)nullptr, 0u, w.nb, w.bodyMask.p);
 }
 
+static const u32 FULL_COLORING_INTERVAL = 16; // a colouring from scratch at least every this many steps
+
 void launch_coloring(World& w, u32 numPairs)
 {
 	if (!numPairs) return;
@@ -211,7 +213,7 @@ void launch_coloring(World& w, u32 numPairs)
 	bool sizeChanged = w.colorHash[0].cap < tableSize;
 	for (int t = 0; t < 2; ++t) if (w.colorHash[t].cap < tableSize) w.colorHash[t].ensure(tableSize, w.stream);
 	if (sizeChanged) w.colorHashSize = 0;
-	bool warm = w.useWarmColoring && w.colorHashSize == tableSize && !w.forceFullColoring && w.stepsSinceFullColoring < w.fullColoringInterval && w.nc < (1u << 28)
+	bool warm = w.colorHashSize == tableSize && !w.forceFullColoring && w.stepsSinceFullColoring < FULL_COLORING_INTERVAL && w.nc < (1u << 28)
 		&& w.hCounters[CTR_NUM_COLORS] < 48;
 	w.stepsSinceFullColoring = warm ? w.stepsSinceFullColoring + 1 : 0;
 	w.forceFullColoring = false;
@@ -224,13 +226,11 @@ void launch_coloring(World& w, u32 numPairs)
 	u32 rounds = w.coloringRounds; // one launch per round: no grid barrier, nothing that needs the whole chip
 	for (u32 r = 0; r <= rounds; ++r)
 		hipLaunchKernelGGL(k_color_round, (r == rounds) ? grid : rgrid, block, 0, w.stream, w.dCounters.p, nb, r, rounds, w.actIds.p, w.mColor.p, w.bodyMask.p, w.claim.p);
-	if (w.useWarmColoring) // remember this step's colours for the next one (in the other table)
-	{
-		u32 other = w.colorHashCur ^ 1u;
-		MI_CHECK(hipMemsetAsync(w.colorHash[other].p, 0, sizeof(u64) * tableSize, w.stream));
-		hipLaunchKernelGGL(k_color_store, grid, block, 0, w.stream, w.dCounters.p, w.actIds.p, w.mColor.p, (const u64*)w.pairsSorted.p, w.colorHash[other].p, tableSize - 1);
-		w.colorHashCur = other; w.colorHashSize = tableSize;
-	}
+	// remember this step's colours for the next one (in the other table)
+	const u32 other = w.colorHashCur ^ 1u;
+	MI_CHECK(hipMemsetAsync(w.colorHash[other].p, 0, sizeof(u64) * tableSize, w.stream));
+	hipLaunchKernelGGL(k_color_store, grid, block, 0, w.stream, w.dCounters.p, w.actIds.p, w.mColor.p, (const u64*)w.pairsSorted.p, w.colorHash[other].p, tableSize - 1);
+	w.colorHashCur = other; w.colorHashSize = tableSize;
 	hipLaunchKernelGGL(k_color_keys, grid, block, 0, w.stream, w.dCounters.p, numPairs, w.actIds.p, w.mColor.p, w.mKey.p, w.mIdx.p);
 	csort_pairs_u32(w, w.mKey.p, w.mKeySorted.p, w.mIdx.p, w.mOrder.p, numPairs, KEY_INACTIVE + 1);
 	hipLaunchKernelGGL(k_color_offsets, dim3(1), dim3(512), 0, w.stream, w.dCounters.p, numPairs, w.mKeySorted.p);
@@ -354,7 +354,7 @@ MI_DEV void solveManifold(u32 s, u32 count, u32 nb, size_t rowCap, const float4*
 }
 
 // One colour of the schedule.  The slot range and the contact-count boundaries are read from the device counters (written by
-// k_color_offsets), so the launch carries no per-step arguments and the whole 30-iteration sweep replays as one hipGraph.
+// k_color_offsets), so the launch carries no per-step arguments.
 // Slots below b3/b2/b1 hold manifolds with 4/>=3/>=2 contacts.  Grid-stride: a stale (smaller) grid stays correct.
 __global__ void __launch_bounds__(256) k_solve_color(u32 color, const u32* __restrict__ counters, u32 nb, size_t rowCap, const float4* __restrict__ rowPlanes,
 	const float4* __restrict__ rowShared, float2* __restrict__ rowLambda, const uint4* __restrict__ rowIds, float4* __restrict__ vel)

@@ -79,11 +79,6 @@ enum
 	CTR_KEY_START = 96,     // (MI_MAX_COLORS+1)*4 + 1 words: first schedule slot of key colour*4 + (4-count); last = numManifolds
 	CTR_COLOR_BARRIER = 360,// 4 words: grid barrier of the fused colouring kernel (arrivals, 3 x manifolds left)
 	CTR_SAP_AXIS = 368,     // 2 words: the reference sweep's sorting axis (collision_broad.cpp:443-444) for internal step k at [k & 1]: written by step k - 1 from its AABB centres, read by k_classify
-	CTR_SAP_MASKED = 370,   // colliders with an empty AABB (bodies simulated by another GPU): not part of the axis statistic
-	CTR_REGION_START = 384, // 9 words: first position in flowOrder of XCD region r; [8] = numManifolds
-	CTR_REGION_CUTS = 400,  // 7 floats: region r holds bodies with cuts[r-1] <= x < cuts[r]
-	CTR_REGION_RANGE = 408, // 2 floats: [lo, hi] of the histogram that produces the next cuts
-	CTR_REGION_MINMAX = 410,// 2 words: running min / max of x (order-preserving integer encoding) for the next range
 	CTR_EVENT_COUNT = 416,  // append cursor of the event ring (trigger enter/leave, collision begin/end), reset by mi_drain_events
 	CTR_EVENT_OVERFLOW = 417,// bit 0: the event ring was full, events were dropped; bit 1: a pair-set table was full
 	CTR_TERRAIN_BASE = 418, // first manifold slot of the terrain contacts (= number of pair manifold slots)
@@ -106,6 +101,7 @@ enum
 // Cluster sweep (k_cluster.hip): up to CL_MAX_PARTS partition phases + the rest phase; task key = phase * CL_MAX_TASKS + task.
 #define MI_REPLAY_WIDTH 8u // lanes of the reference's SIMD batches (constraints.cpp: CONSTRAINT_SIMD_WIDTH with AVX)
 #define CL_MAX_PARTS 4u
+#define CL_CURVE_PARTS 2u // curve phases a step uses; the component phase comes on top (phase index CL_CURVE_PARTS)
 #define CL_MAX_PHASES (CL_MAX_PARTS + 1u)
 #define CL_MAX_TASKS 512u
 #define CL_BODY_STRIDE 4096u
@@ -194,17 +190,16 @@ struct World
 	u32 scheduleReferenceBatches(const std::vector<uint4>& ids, u32 numPositions);
 	bool useCluster = true;               // MI_PHYSICS_NO_CLUSTER=1: launch-per-colour sweep only
 	bool lastStepCluster = false, backupVelocities = false;
-	u32 clusterPredictDiv = 4, clusterPollSleep = 1, clusterBlocksLimit = 0, clusterFailStreak = 0, clusterParts = 2, clusterTaskWeight = 64u * 1000u, clusterTaskWeightLater = 64u * 500u, clusterShift[CL_MAX_PARTS][3] = { { 0, 0, 0 }, { 13, 9, 15 }, { 27, 21, 31 }, { 7, 29, 5 } }; // MI_CLUSTER_PARTS / _TASK / _SHIFT
-	bool clusterPartsFixed = false;       // MI_CLUSTER_PARTS given: no adaptation
-	bool clusterSortDue = true; u32 clusterSortAge = 0, clusterSortInterval = 8, clusterSortBodies = 0, clusterSortedParts = 0; // body order along the curves: refreshed every few steps (MI_CLUSTER_SORT_INTERVAL)
+	u32 clusterBlocksLimit = 0, clusterFailStreak = 0, clusterTaskWeight = 64u * 1000u, clusterTaskWeightLater = 64u * 500u; // MI_CLUSTER_BLOCKS / _TASK / _TASK_LATER
+	bool clusterSortDue = true; u32 clusterSortAge = 0, clusterSortBodies = 0; // body order along the curves: refreshed every few steps
 	u32 clusterLdsBytes = 0, clusterBlocks = 0, clusterCooldown = 0;
 	DevBuf<u32> clKeys, clKeysSorted, clVals, clSorted, clRank, clWsum, clCum, clPhaseMask, clTaskKey, clTaskPos, clPre, clLocal, clEntry, clTaskCount, clTaskStart, clBodyList, clSharedSlot; // clEntry: the contact schedule of every task (at 4 x its first manifold position): manifold position | contact << 12
 	DevBuf<uint8_t> clTasks;
 	DevBuf<float4> clRowScratch;
 	DevBuf<u32> clJointBodyMask; bool clJointListsValid = false; // per body: 1 if a joint of the sweep touches it (phase-0 bit of its phase mask); the joints' task lists of the last refresh are still good
-	DevBuf<u32> clCompLabel, clLeftList; bool useComponents = true; // the component phase (MI_CLUSTER_NO_COMPONENTS=1: curve phases + rest task only)
+	DevBuf<u32> clCompLabel, clLeftList;  // the component phase
 	bool compIdle = false;                    // the last step's curve phases left nothing over (and its rest task was empty): this step skips the component phase's launches (what is left over goes to the rest task)
-	DevBuf<u32> clChunk; u32 clChunkParts = 0, clChunkJointVersion = ~0u; bool clChunkWithJoints = false, useChunkCache = true; u32 chunkHeadroomPercent = 10, chunkCachedPhases = CL_MAX_PARTS; // chunk of every body per phase, kept between re-sorts (MI_CLUSTER_NO_CHUNK_CACHE=1: the full partition pipeline every step)
+	DevBuf<u32> clChunk; u32 clChunkJointVersion = ~0u; bool clChunkWithJoints = false; // chunk of every body per curve phase, kept between re-sorts (~0u: none cut yet)
 	// joints inside the cluster sweep: island representative per body (jointed bodies must share a task), the joints of all types in
 	// (type, colour) order {type | class << 8, index in the type's colour-sorted arrays, body a, body b}, and the per-step lists
 	DevBuf<u32> clRep, clJointTask, clJointPos, clJointCount, clJointStart, clJointList; DevBuf<uint4> clJointTable; DevBuf<uint2> clTaskJoints; DevBuf<u32> clJointClassStart;
@@ -234,9 +229,8 @@ struct World
 	// settings snapshot for the running step
 	u32 iterations = 30;
 	u32 coloringRounds = 24;     // adaptive: last useful round of the previous step + margin (launch-per-round colouring only)
-	DevBuf<u64> colorHash[2]; u32 colorHashCur = 0, colorHashSize = 0, stepsSinceFullColoring = 0, fullColoringInterval = 16; // warm-started colouring (MI_PHYSICS_NO_WARM_COLORING=1: from scratch every step)
-	bool useWarmColoring = true, forceFullColoring = true;
-	bool useFusedColoring = true; u32 colorMaxBlocks = 0; // all colouring rounds in one launch with a grid barrier (MI_PHYSICS_NO_FUSED_COLORING=1: one launch per round)
+	DevBuf<u64> colorHash[2]; u32 colorHashCur = 0, colorHashSize = 0, stepsSinceFullColoring = 0; // warm-started colouring
+	bool forceFullColoring = true;
 	u32 lastNumManifolds = 0;    // sizes the colouring-round launches of the next step
 	mi_stats stats = {};
 	// Stage timing: HIP events of the last STAGE_RING timed steps, read back without stalling every step (mi_get_stats harvests them)
@@ -248,18 +242,7 @@ struct World
 	// Counts of the steps since the last mi_get_stats (the host learns a step's counts at its next synchronisation)
 	double sumContacts = 0, sumManifolds = 0, sumColors = 0, sumPairs = 0, sumProbes = 0; u32 sumSteps = 0, countedStep = 0, prevNumPairs = 0;
 	void countPreviousStep(); void refreshCounters();
-
-	// The N-iteration solver sweep (joint colours + contact colours per iteration) replayed as one hipGraph.  Launch arguments are
-	// step-invariant (ranges live in dCounters), so a graph is rebuilt only when the colour count, a colour's size class, the joint
-	// schedule or a buffer address changes.
-	struct SolveGraph
-	{
-		hipGraphExec_t exec = nullptr; hipGraph_t graph = nullptr;
-		u32 numColors = 0, firstTail = 0, iterations = 0; bool serial = false; u32 jointVersion = 0; u64 bufferVersion = 0;
-		u32 gridBlocks[MI_MAX_COLORS] = {};
-	} solveGraph;
-	u32 jointVersion = 0; u64 bufferVersion = 0;
-	bool useGraph = false;
+	u32 jointVersion = 0;                 // bumped by every upload of the joints
 
 	World(int dev);
 	~World();
@@ -296,8 +279,6 @@ void launch_active_list(World& w, u32 numPairs);           // manifolds with con
 void launch_cluster_build(World& w, u32 numPairs);         // body order, tasks, local colouring, final slot order (k_cluster.hip)
 void launch_cluster_solve(World& w, u32 itBegin, u32 itEnd);
 bool cluster_solves_joints(const World& w);                // the cluster sweep of this step runs the joints too (one launch for all iterations)
-u32 flow_num_regions(const World& w);
-void flow_choose_regions(World& w);
 void launch_integrate_velocities(World& w, float dt);
 void launch_joint_init(World& w, float dt);
 void launch_joint_solve_iteration(World& w);
@@ -308,6 +289,5 @@ void launch_slab_unpack(World& w, const void* left, const void* right, u32 capac
 void launch_validate(World& w, u32 stage, u32 numPairs); // stage 0: world colliders + AABBs, 1: contacts, 2: body update records, 3: poses + velocities after the step
 void launch_copy_pose0(World& w);
 void launch_lerp_pose(World& w, float t);
-size_t primitives_temp_bytes(size_t maxItems);
 void csort_pairs_u32(World& w, const u32* keys, u32* keysOut, const u32* vals, u32* valsOut, u32 n, u32 numBuckets); // stable, keys < numBuckets <= 272
 void csort_pairs_u64(World& w, const u32* keys, u32* keysOut, const u64* vals, u64* valsOut, u32 n, u32 numBuckets);

@@ -49,30 +49,14 @@ World::World(int dev) : device(dev)
 	// (device-scope events: a stage's time stamp needs no system-scope fence, and the host reads the counters from pinned memory behind an event it waits for)
 	for (auto& e : stageEvents) MI_CHECK(hipEventCreateWithFlags(&e, hipEventDisableSystemFence));
 	MI_CHECK(hipEventCreateWithFlags(&countersEvent, hipEventDisableTiming));
-	// The launch-per-colour sweep (the fallback solver) as plain launches: a hipGraph of its ~600 kernel nodes has to be re-instantiated
-	// whenever the number of colours changes (58 times in 260 steps of config 3, tens of ms each: 25 ms/step against 3 ms/step).
-	// MI_PHYSICS_GRAPH=1 replays it as a graph (pays off only where the colour count is stable: small resting scenes).
-	useGraph = getenv("MI_PHYSICS_GRAPH") != nullptr && getenv("MI_PHYSICS_NO_GRAPH") == nullptr;
 	validate = getenv("MI_PHYSICS_VALIDATE") != nullptr;
 	useCluster = getenv("MI_PHYSICS_NO_CLUSTER") == nullptr;
 	useClusterJoints = getenv("MI_CLUSTER_NO_JOINTS") == nullptr; // LDS cluster contact sweep (one launch) vs global colouring + one launch per colour
-	useFusedColoring = false;                                // the launch sweep colours with one launch per round (no grid barrier)
-	useWarmColoring = getenv("MI_PHYSICS_NO_WARM_COLORING") == nullptr;
-	if (const char* e = getenv("MI_COLOR_FULL_INTERVAL")) fullColoringInterval = (u32)atoi(e);
 	if (const char* e = getenv("MI_FLOW_TEST_ABORT")) flowTestAbortStep = (u32)atoi(e); // tests: make the cluster sweep of that internal step give up
-	if (getenv("MI_CLUSTER_NO_COMPONENTS")) { useComponents = false; clusterParts = 3; } else clusterPartsFixed = true; // with the component phase: two curve phases + the components, no adaptation
-	if (const char* e = getenv("MI_CLUSTER_PARTS")) { clusterParts = std::min<u32>(CL_MAX_PARTS, std::max(1, atoi(e))); clusterPartsFixed = true; }
-	if (const char* e = getenv("MI_CLUSTER_SORT_INTERVAL")) clusterSortInterval = (u32)std::max(1, atoi(e));
 	if (const char* e = getenv("MI_CLUSTER_TASK")) { clusterTaskWeight = 64u * (u32)std::max(16, atoi(e)); clusterTaskWeightLater = std::min(clusterTaskWeight, clusterTaskWeightLater); }  // manifolds per task
 	if (getenv("MI_PHYSICS_REPLAY")) replayReferenceOrder = true;
-	if (getenv("MI_CLUSTER_NO_CHUNK_CACHE")) useChunkCache = false;
-	if (const char* e = getenv("MI_CLUSTER_CHUNK_PHASES")) chunkCachedPhases = (u32)std::min(4, std::max(1, atoi(e)));
-	if (const char* e = getenv("MI_CLUSTER_CHUNK_HEADROOM")) chunkHeadroomPercent = (u32)std::min(50, std::max(0, atoi(e)));
-	if (const char* e = getenv("MI_CLUSTER_PREDICT_DIV")) clusterPredictDiv = (u32)std::max(2, atoi(e));
-	if (const char* e = getenv("MI_CLUSTER_POLL_SLEEP")) clusterPollSleep = (u32)std::max(0, atoi(e));
 	if (const char* e = getenv("MI_CLUSTER_BLOCKS")) clusterBlocksLimit = (u32)std::max(1, atoi(e));
 	if (const char* e = getenv("MI_CLUSTER_TASK_LATER")) clusterTaskWeightLater = 64u * (u32)std::max(16, atoi(e)); // ... of the phases after the first
-	if (const char* e = getenv("MI_CLUSTER_SHIFT")) { int a = 0, b = 0, c = 0; if (sscanf(e, "%d,%d,%d", &a, &b, &c) == 3) for (u32 p = 1; p < CL_MAX_PARTS; ++p) { clusterShift[p][0] = (u32)a * p; clusterShift[p][1] = (u32)b * p; clusterShift[p][2] = (u32)c * p; } }
 	if (dCounters.p)
 	{
 		u32 box[6] = { 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u }; // empty bounding box (k_cl_bbox accumulates, k_cl_offsets resets)
@@ -386,7 +370,7 @@ void World::upload()
 	}
 	activeDirty = true; estActiveBodies = nb; estActiveCols = nc; // (the lists are rebuilt at the next step; until the host has seen their lengths the launches are sized for everything)
 	MI_CHECK(hipStreamSynchronize(stream));
-	topologyDirty = false; stateOnDevice = true; bufferVersion++;
+	topologyDirty = false; stateOnDevice = true;
 	jointsDirty = true; // the static dummy index (= nb) moved
 }
 
@@ -487,7 +471,7 @@ static void ensurePairBuffers(World& w, size_t numPairs)
 	w.rowPlanes.ensure((size_t)MI_MAX_CONTACTS_PER_MANIFOLD * MI_ROW_PLANES * cap, w.stream); w.rowShared.ensure(cap, w.stream);
 	w.rowLambda.ensure((size_t)MI_MAX_CONTACTS_PER_MANIFOLD * cap, w.stream); w.rowIds.ensure(cap, w.stream);
 	if (w.lastError) return; // an allocation failed: the capacities stay, the step returns the error
-	w.pairCap = cap; w.rowCap = cap; w.bufferVersion++;
+	w.pairCap = cap; w.rowCap = cap;
 }
 
 static void readCounters(World& w)
@@ -509,7 +493,7 @@ static void enqueueSolverSweep(World& w, u32 iters, const u32* gridBlocks, u32 n
 static const u32 TAIL_MAX_MANIFOLDS = 2048; // colours at the end of the schedule no larger than this go to the one-workgroup tail kernel
 
 // The launch-per-colour sweep (the fallback of the cluster sweep and the reference it is tested against): per iteration all joint
-// colours by type, then all contact colours, replayed as one hipGraph.
+// colours by type, then all contact colours.
 static void runSolverSweep(World& w, u32 iters, u32 numColors)
 {
 	const u32* keyStart = w.hCounters + CTR_KEY_START;
@@ -528,33 +512,7 @@ static void runSolverSweep(World& w, u32 iters, u32 numColors)
 	u32 numJointKernels = 0;
 	for (auto& js : w.joints) numJointKernels += js.colorStart.empty() ? 0 : (u32)js.colorStart.size() - 1;
 	if (!numColors && !serial && !numJointKernels) return;
-
-	World::SolveGraph& g = w.solveGraph;
-	if (!w.useGraph)
-	{
-		enqueueSolverSweep(w, iters, need, numColors, firstTail, serial);
-		return;
-	}
-	bool reuse = g.exec && g.numColors == numColors && g.iterations == iters && g.serial == serial && g.jointVersion == w.jointVersion && g.bufferVersion == w.bufferVersion;
-	if (g.firstTail != firstTail) reuse = false;
-	for (u32 c = 0; reuse && c < numColors && c < g.firstTail; ++c)
-	{
-		// kernels grid-stride, so a cached grid stays correct; rebuild only when it is badly sized (> 2 passes or > 4x too wide)
-		if (need[c] > 2 * g.gridBlocks[c] || (g.gridBlocks[c] > 4 * std::max(need[c], 1u) && g.gridBlocks[c] > 8)) reuse = false;
-	}
-	if (!reuse)
-	{
-		if (g.exec) { (void)hipGraphExecDestroy(g.exec); g.exec = nullptr; }
-		if (g.graph) { (void)hipGraphDestroy(g.graph); g.graph = nullptr; }
-		for (u32 c = 0; c < MI_MAX_COLORS; ++c) g.gridBlocks[c] = (c < numColors) ? std::max(1u, need[c] + need[c] / 4) : 0;
-		MI_CHECK(hipStreamBeginCapture(w.stream, hipStreamCaptureModeThreadLocal));
-		enqueueSolverSweep(w, iters, g.gridBlocks, numColors, firstTail, serial);
-		MI_CHECK(hipStreamEndCapture(w.stream, &g.graph));
-		if (g.graph) MI_CHECK(hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0));
-		g.numColors = numColors; g.firstTail = firstTail; g.iterations = iters; g.serial = serial; g.jointVersion = w.jointVersion; g.bufferVersion = w.bufferVersion;
-		w.stats.numGraphBuilds++;
-	}
-	if (g.exec) MI_CHECK(hipGraphLaunch(g.exec, w.stream));
+	enqueueSolverSweep(w, iters, need, numColors, firstTail, serial);
 }
 
 // The reference's greedy batch scheduler for W-wide SIMD solves (scheduleConstraintsSIMD, constraints.cpp:51-184), restated for the
@@ -657,8 +615,8 @@ static void solveWithLaunchSweep(World& w, u32 numPairs, float dt, u32 iters)
 void World::recoverFlow()
 {
 	stats.numFlowRecoveries++;
-	// why: bit 6 = the cluster build did not fit (too many tasks in a phase, a task beyond the colouring tables or LDS): try again soon
-	// with one more partition phase; anything else = a lane timed out (GPU shared with another persistent kernel): stay away for a while
+	// why: bit 6 = the cluster build did not fit (too many tasks in a phase, a task beyond the colouring tables or LDS): try again soon;
+	// anything else = a lane timed out (GPU shared with another persistent kernel): stay away for a while
 	u32 why = hCounters[CTR_FLOW_STATUS];
 	if (getenv("MI_CLUSTER_DEBUG"))
 	{
@@ -667,13 +625,13 @@ void World::recoverFlow()
 		(void)hipMemcpyAsync(c.data(), dCounters.p, CTR_WORDS * sizeof(u32), hipMemcpyDeviceToHost, stream);
 		(void)hipStreamSynchronize(stream);
 		fprintf(stderr, "[mi_physics] step %u: cluster sweep gave up: status %u, build status %u, parts %u, tasks %u %u %u %u %u, manifolds %u %u %u %u %u (active %u), remain %u %u %u %u %u; components: listed %u tasks %u weight %u ends disagree %u largest too-big %u; scratch rows %u\n", stats.numInternalSteps, c[CTR_FLOW_STATUS] | why,
-			c[CTR_CL_STATUS], clusterParts, c[CTR_CL_NUM_TASKS], c[CTR_CL_NUM_TASKS + 1], c[CTR_CL_NUM_TASKS + 2], c[CTR_CL_NUM_TASKS + 3], c[CTR_CL_NUM_TASKS + 4],
+			c[CTR_CL_STATUS], CL_CURVE_PARTS, c[CTR_CL_NUM_TASKS], c[CTR_CL_NUM_TASKS + 1], c[CTR_CL_NUM_TASKS + 2], c[CTR_CL_NUM_TASKS + 3], c[CTR_CL_NUM_TASKS + 4],
 			c[CTR_CL_PHASE_COUNT], c[CTR_CL_PHASE_COUNT + 1], c[CTR_CL_PHASE_COUNT + 2], c[CTR_CL_PHASE_COUNT + 3], c[CTR_CL_PHASE_COUNT + 4], c[CTR_NUM_ACTIVE],
 			c[CTR_CL_REMAIN + 1], c[CTR_CL_REMAIN + 2], c[CTR_CL_REMAIN + 3], c[CTR_CL_REMAIN + 4], c[CTR_CL_REMAIN + 5],
 			c[CTR_CL_LEFT], c[CTR_CL_LEFT + 1], c[CTR_CL_LEFT + 2], c[CTR_CL_LEFT + 3], c[CTR_CL_LEFT + 4], c[CTR_CL_SCRATCH]);
 	}
 	// (a world that keeps not fitting backs off: 4, 8, ... 256 steps of launch sweep between attempts)
-	if ((why & 64u) && !(why & 1u)) { clusterCooldown = std::min(256u, 4u << std::min(clusterFailStreak, 6u)); ++clusterFailStreak; if (!clusterPartsFixed && clusterParts < CL_MAX_PARTS) ++clusterParts; }
+	if ((why & 64u) && !(why & 1u)) { clusterCooldown = std::min(256u, 4u << std::min(clusterFailStreak, 6u)); ++clusterFailStreak; }
 	else clusterCooldown = 256;
 	coloringRounds = 64;
 	const size_t nb1 = (size_t)nb + 1;
@@ -734,21 +692,12 @@ void World::countPreviousStep()
 		stats.clusterTasks[p] = (had && lastStepCluster) ? hCounters[CTR_CL_NUM_TASKS + p] : 0;
 		stats.clusterManifolds[p] = (had && lastStepCluster) ? hCounters[CTR_CL_PHASE_COUNT + p] : 0;
 	}
-	stats.clusterSharedBodies = (had && lastStepCluster) ? hCounters[CTR_CL_SHARED] : 0; stats.clusterParts = lastStepCluster ? clusterParts : 0;
-	// Partition phases of the next step: one more when the rest task is filling up (it has hard limits), one fewer when the last
-	// one found nothing to do (each costs a sort of the bodies).
+	stats.clusterSharedBodies = (had && lastStepCluster) ? hCounters[CTR_CL_SHARED] : 0; stats.clusterParts = lastStepCluster ? CL_CURVE_PARTS : 0;
 	if (had && lastStepCluster) clusterFailStreak = 0; // (a give-up never gets here: recoverFlow clears lastStepCluster)
-	compIdle = had && lastStepCluster && useComponents && hCounters[CTR_CL_LEFT] == 0u && hCounters[CTR_CL_PHASE_COUNT + CL_MAX_PARTS] == 0u;
+	compIdle = had && lastStepCluster && hCounters[CTR_CL_LEFT] == 0u && hCounters[CTR_CL_PHASE_COUNT + CL_MAX_PARTS] == 0u;
 	if (had && lastStepCluster && (stats.numInternalSteps % 50u) == 0u && getenv("MI_CLUSTER_DEBUG"))
 		fprintf(stderr, "[mi_physics] step %u: component phase: %u manifolds left by the curve phases, %u tasks, weight %u, %u with ends in different components after the rounds, largest component sent to the rest task %u\n", stats.numInternalSteps,
 			hCounters[CTR_CL_LEFT], hCounters[CTR_CL_LEFT + 1], hCounters[CTR_CL_LEFT + 2], hCounters[CTR_CL_LEFT + 3], hCounters[CTR_CL_LEFT + 4]);
-	if (had && lastStepCluster && !clusterPartsFixed)
-	{
-		// (every phase costs a hand-over per iteration: the last partition phase is dropped as soon as what it holds would fit the rest task too)
-		const u32 rest = hCounters[CTR_CL_PHASE_COUNT + CL_MAX_PARTS], last = hCounters[CTR_CL_PHASE_COUNT + clusterParts - 1];
-		if (rest > 960u && clusterParts < CL_MAX_PARTS) ++clusterParts;
-		else if (clusterParts > 1 && last + rest < 800u && hCounters[CTR_CL_REMAIN + clusterParts - 1] < 800u) --clusterParts;
-	}
 	sumContacts += stats.numContacts; sumManifolds += stats.numCollisions; sumColors += stats.numColors; sumPairs += prevTruePairs; sumProbes += stats.flowProbes; sumSteps++;
 }
 
@@ -1231,10 +1180,9 @@ int mi_snapshot_save(mi_world* world, void* buffer, uint64_t capacity)
 	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
 	BlobWriter out; serialize(*W, out);
 	if (W->lastError) return W->lastError;
-	W->refreshCounters();     // the last step is counted now (and has had its say on the number of partition phases), not at the next step:
+	W->refreshCounters();     // the last step is counted now, not at the next step:
 	W->clusterSortDue = true; // the restored world orders its bodies at its first step: so does this one at its next ...
 	W->compIdle = false;      // ... and runs the component phase in it, as a world without a last step does (the step has been counted above)
-	if (!W->clusterPartsFixed) W->clusterParts = 3; // ... and both start from the default number of partition phases (without the component phase: with it the number is fixed)
 	W->clusterCooldown = 0; W->clusterFailStreak = 0; // ... with the cluster sweep on
 	if (!buffer || capacity < out.bytes.size()) { W->fail(MI_ERR_CAPACITY, "mi_snapshot_save: buffer too small (ask mi_snapshot_size)"); return MI_ERR_CAPACITY; }
 	memcpy(buffer, out.bytes.data(), out.bytes.size());

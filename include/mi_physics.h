@@ -61,7 +61,7 @@ typedef struct mi_stats
 {
 	uint32_t numRigidBodies, numColliders, numBroadphaseOverlaps, numCollisions, numContacts;
 	uint32_t numColors, numJoints, numInternalSteps;
-	uint32_t numGraphBuilds, coloringRounds; /* solver-sweep hipGraph (re)builds so far; colouring round budget of the last step */
+	uint32_t numGraphBuilds, coloringRounds; /* unused (kept for layout compatibility); colouring round budget of the last step */
 	uint32_t flowProbes;                     /* unused (kept for layout compatibility) */
 	uint32_t numFlowRecoveries;              /* steps whose cluster contact sweep gave up and was redone with the launch sweep (should stay 0) */
 	float msCollidersBroad, msNarrow, msSolverSetup, msSolve, msIntegrate, msTotal; /* HIP-event times, mean over the timed steps since the previous mi_get_stats (timing enabled only) */
