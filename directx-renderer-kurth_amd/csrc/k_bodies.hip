@@ -169,8 +169,8 @@ u32 active_grid(u32 estimate, u32 total) { return (u32)((std::min<u64>(total, (u
 
 void launch_build_colliders(World& w)
 {
+	launch_active_lists(w); // (also in a world without colliders: the body kernels walk the list of simulated bodies)
 	if (!w.nc) return;
-	launch_active_lists(w);
 	const u32 blocks = std::max(1u, active_grid(w.estActiveCols, w.nc));
 	w.sapPartial.ensure((size_t)blocks * 7, w.stream);
 	if (w.lastError) return;

@@ -1237,7 +1237,7 @@ __global__ void __launch_bounds__(64) k_zone_overlap(u32* __restrict__ counters,
 	}
 }
 
-void launch_narrowphase(World& w, u32 numPairs)
+void launch_narrowphase(World& w, u32 numPairs, u32 stepParity)
 {
 	if (!numPairs)
 	{
@@ -1245,7 +1245,7 @@ void launch_narrowphase(World& w, u32 numPairs)
 		return;
 	}
 	dim3 grid((numPairs + 255) / 256), block(256);
-	hipLaunchKernelGGL(k_classify, grid, block, 0, w.stream, w.dCounters.p, w.nb, w.pairs.p, w.colWorld.p, w.aabbMin.p, w.stats.numInternalSteps & 1u, w.pairKey.p, (u64*)w.pairsSorted.p + numPairs, numPairs);
+	hipLaunchKernelGGL(k_classify, grid, block, 0, w.stream, w.dCounters.p, w.nb, w.pairs.p, w.colWorld.p, w.aabbMin.p, stepParity, w.pairKey.p, (u64*)w.pairsSorted.p + numPairs, numPairs);
 	// sort (bucket key, packed pair): unsorted packed pairs live in the upper half of pairsSorted, sorted ones in the lower half
 	csort_pairs_u64(w, w.pairKey.p, w.pairKeySorted.p, (const u64*)w.pairsSorted.p + numPairs, (u64*)w.pairsSorted.p, numPairs, 64);
 	hipLaunchKernelGGL(k_bucket_offsets, dim3(1), dim3(64), 0, w.stream, w.dCounters.p, w.pairKeySorted.p);

@@ -128,6 +128,7 @@ struct World
 	u32 terrainSlotCap() const { return terrainChunksPerDim ? std::max(terrainMinSlots, terrainSlotsPerCollider * (u32)colliders.size()) : 0u; }
 	u32 prevTruePairs = 0;                // broadphase overlaps of the last step (prevNumPairs counts the terrain slots too)
 	bool prevSlabOverflow = false;        // CTR_PAIR_OVERFLOW of the last step
+	u32 stepAxis = 0;                     // sorting axis of the last step (CTR_SAP_AXIS of its parity): the narrowphase of a recovered step is run again with it
 	hipEvent_t countersEvent = nullptr;   // behind the step's asynchronous read of the counters
 	// cloth_component (cloth.h:5-60): parameters + host mirror of the particle state (authoritative until the first step; refreshed by downloadCloths)
 	struct HClothConstraint { u32 a, b; float restDistance, inverseMassSum; u32 color; };
@@ -261,7 +262,7 @@ u32 active_grid(u32 estimate, u32 total);
 void launch_build_colliders(World& w);
 void launch_broadphase_count(World& w);                    // grid build + pair count + scan; leaves numPairs in dCounters
 void launch_broadphase_write(World& w, u32 numPairs, bool slabOverflow);       // slabOverflow: some collider has more partners than its slab holds (CTR_PAIR_OVERFLOW)
-void launch_narrowphase(World& w, u32 numPairs);            // numPairs may exceed the device's pair count (a launch sized before the host knows it)
+void launch_narrowphase(World& w, u32 numPairs, u32 stepParity); // numPairs may exceed the device's pair count (a launch sized before the host knows it); stepParity: the internal step's k & 1 (its sorting-axis word)
 void launch_zone_overlap(World& w, u32 numPairs);           // force-field / trigger overlap tests on the classified pairs (once per step)
 void launch_integrate_forces(World& w, float dt);
 void launch_heightmap(World& w, u32 numPairs, u32 slotCap);  // terrain contacts appended after the pair manifolds (physics.cpp:1236-1249)

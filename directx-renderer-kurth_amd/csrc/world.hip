@@ -609,9 +609,10 @@ static void solveWithLaunchSweep(World& w, u32 numPairs, float dt, u32 iters)
 
 // The cluster sweep of the last step gave up (CTR_FLOW_STATUS != 0: a task did not fit its tables or LDS, more tasks than
 // workgroups, or — only when the GPU is shared with another persistent kernel — a lane timed out waiting for a body): its
-// velocities are garbage and k_integrate_velocities skipped itself.  The manifolds of that step are still in place: restore the
-// pre-solve velocities, colour globally, rebuild the rows in that order, run joints + contacts as launches, integrate.  The
-// cluster sweep then stays off for a while.
+// velocities are garbage and k_integrate_velocities skipped itself.  The manifolds of that step are in place (when the give-up is
+// noticed at the next step's first synchronisation, stepInternal has just launched that step's narrowphase again, with that step's
+// sorting axis): restore the pre-solve velocities, colour globally, rebuild the rows in that order, run joints + contacts as
+// launches, integrate.  The cluster sweep then stays off for a while.
 void World::recoverFlow()
 {
 	stats.numFlowRecoveries++;
@@ -751,13 +752,25 @@ int World::stepInternal(float dt, u32 iters)
 			early = true;
 			launch_broadphase_write(*this, guess, prevSlabOverflow);
 			if (T) MI_CHECK(hipEventRecord(ev[1], stream));
-			launch_narrowphase(*this, guess);
+			launch_narrowphase(*this, guess, stats.numInternalSteps & 1u);
 		}
 	}
 	MI_CHECK(hipEventSynchronize(countersEvent));          // sync #1: number of overlapping pairs
 	if (hCounters[CTR_FLOW_STATUS])                        // the cluster sweep of the previous step gave up
 	{
 		flowPending = false;
+		if (early)
+		{
+			// The early pair list + narrowphase just launched overwrote the previous step's pairs and manifolds.  The poses have not
+			// moved since (that step's integration skipped itself), so the broadphase in the buffers is the previous step's: write its
+			// pair list and run its narrowphase again, with ITS sorting axis.  This step's pair count has put the axis of step + 1 into
+			// the word of the previous step's parity; the previous step's own axis is put back from the host (the word is written
+			// again by this step's broadphase below).
+			const u32 prevParity = (stats.numInternalSteps - 1u) & 1u;
+			MI_CHECK(hipMemsetD32Async((hipDeviceptr_t)(dCounters.p + CTR_SAP_AXIS + prevParity), (int)stepAxis, 1, stream));
+			launch_broadphase_write(*this, prevTruePairs, prevSlabOverflow);
+			launch_narrowphase(*this, prevTruePairs, prevParity);
+		}
 		recoverFlow();                                     // redo the previous step's solve + integration with the launch sweep (synchronises)
 		launch_build_colliders(*this);                     // ... and this step's start, which ran on the stale poses
 		launch_broadphase_count(*this);
@@ -765,9 +778,11 @@ int World::stepInternal(float dt, u32 iters)
 		early = false;
 	}
 	flowPending = false;
+	stepAxis = hCounters[CTR_SAP_AXIS + (stats.numInternalSteps & 1u)]; // (this step's sorting axis, written by the previous step's broadphase: kept for a recovery at the next step)
 	estActiveBodies = hCounters[CTR_ACTIVE_BODIES]; estActiveCols = hCounters[CTR_ACTIVE_COLS]; // lengths of the active lists: size the next launches
 	if (hCounters[CTR_ACTIVE_OVERFLOW])                    // more active colliders than the pair kernels were laid out for (the lists grew by more than 12 % in one step)
 	{
+		launch_build_colliders(*this);                     // the first count consumed the cell size and the bucket sizes: rebuild them (the lists are current)
 		launch_broadphase_count(*this);                    // (now with the right bound)
 		readCounters(*this);
 		early = false;
@@ -792,7 +807,7 @@ int World::stepInternal(float dt, u32 iters)
 	{
 		launch_broadphase_write(*this, truePairs, slabOverflow);
 		if (T) MI_CHECK(hipEventRecord(ev[1], stream));
-		launch_narrowphase(*this, truePairs);
+		launch_narrowphase(*this, truePairs, stats.numInternalSteps & 1u);
 	}
 	launch_zone_overlap(*this, early ? guess : truePairs);
 	prevSlabOverflow = slabOverflow;

@@ -126,8 +126,9 @@ def test_launch_sweep_follow(mi, oracle):
 def test_cluster_abort_is_recovered(mi, oracle, name, abort_step, steps):
     """Safety net of the persistent kernel: if the cluster sweep of a step gives up (injected here: MI_FLOW_TEST_ABORT), the device
     skips that step's integration and the host redoes solve + integration with the launch sweep from the saved pre-solve
-    velocities — at the next step's first synchronisation (abort in the middle of the run) or when results are read (abort in the
-    last step).  The oracle follows whichever schedule the device reports for the step, so every step still matches."""
+    velocities.  Here results are read after every step, so the give-up is always settled by that read (World::resolvePendingFlow);
+    a give-up first noticed at the next step's synchronisation is tested in test_gpu_step_branches.py.  The oracle follows whichever
+    schedule the device reports for the step, so every step still matches."""
     from directx_renderer_kurth_amd import scenes
     scene = scenes.by_name(name)
     g = _world(mi, scene, MI_FLOW_TEST_ABORT=abort_step)

@@ -1,0 +1,287 @@
+"""The host branches of World::stepInternal that run only when a world changes shape from one step to the next, against the CPU
+oracle in follow mode: the active collider list growing past the pair kernels' bound (a simulate mask switched back on), a world
+with bodies and joints but no collider, a give-up of the cluster sweep noticed at the next step's first synchronisation (after
+that step's early pair list and narrowphase have been launched), and the pair list outgrowing its early guess or a collider
+outgrowing its pair slab.  Every test also shows from the world itself that its branch was taken."""
+import os
+
+import numpy as np
+import pytest
+import torch    # (before the physics library loads the HIP runtime)
+
+from parity_util import follow_step
+
+pytestmark = pytest.mark.gpu
+
+KINDS = {"distance": 0, "ball": 1, "fixed": 2, "hinge": 3, "cone_twist": 4, "slider": 5}
+RESERVE_PAIRS = 1 << 16   # pair buffers large enough that every step launches its pair list + narrowphase before it knows the count
+
+
+def _world(mi, scene, reserve_pairs=0, **env):
+    old = {k: os.environ.get(k) for k in env}
+    try:
+        for k, v in env.items():
+            os.environ[k] = str(v)
+        return scene.instantiate(mi.World(reserve_pairs=reserve_pairs))    # the switches are read when the world is created
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
+def _check(r, i, what=""):
+    assert r["pairs_equal"], "%sstep %d: broadphase pair set differs" % (what, i)
+    assert r["counts_equal"], "%sstep %d: contact counts differ" % (what, i)
+    assert r["vel_err"] <= 1e-4 * max(1.0, r["vel_scale"]), "%sstep %d: velocity error %g (scale %g)" % (what, i, r["vel_err"], r["vel_scale"])
+    assert r["pos_err"] <= 1e-4 and r["rot_err"] <= 1e-4, "%sstep %d: pose error %g / %g" % (what, i, r["pos_err"], r["rot_err"])
+
+
+def _active_colliders(scene, mask):
+    """Colliders of the simulated bodies + the static ones: the length of the device's active collider list under `mask`."""
+    from directx_renderer_kurth_amd import scenes
+    return sum(1 for c in scene.colliders if c[0] == scenes.STATIC or mask[c[0]])
+
+
+def _set_mask(g, o, mask):
+    m = torch.from_numpy(np.ascontiguousarray(mask, np.uint8)).cuda()
+    torch.cuda.synchronize()
+    g.state_from_device_buffers(0, 0, m.data_ptr())
+    g.synchronize()    # (the copy from the tensor is asynchronous on the world's stream: keep it alive until here)
+    del m
+    o.set_sim_mask(mask)
+
+
+# ---- A: the active collider list grows past the bound the pair kernels were laid out for ------------------------------------------
+@pytest.mark.parametrize("grow_to", [None, 2600], ids=["all", "part"])
+def test_active_list_growth_follows_the_oracle(mi, oracle, grow_to):
+    """c3_small (3 001 colliders) simulated in full, then only a compact block of 350 bodies for 3 steps, then `grow_to` bodies
+    around the same block again (None: all).  In the step after the switch the active collider list is longer than the last known
+    length + 12 % + 2 048, so the step repeats its broadphase with the right bound (world.hip: CTR_ACTIVE_OVERFLOW) — from the
+    rebuilt cell size and bucket sizes; every step follows the masked oracle exactly."""
+    from directx_renderer_kurth_amd import scenes
+    scene = scenes.by_name("c3_small")
+    g = scene.instantiate(mi.World())
+    o = scene.instantiate(oracle.OracleWorld(solver=oracle.SOLVER_CUSTOM))
+    nb = scene.num_bodies
+    for i in range(10):
+        _check(follow_step(g, o, scene.dt, 30), i)
+    pos = o.transforms(1)[:, :3].astype(np.float64)
+    centre = pos[np.argmin(np.abs(pos[:, 0] - np.median(pos[:, 0])) + np.abs(pos[:, 2] - np.median(pos[:, 2])) + 0.1 * pos[:, 1])]
+    by_distance = np.argsort(np.linalg.norm(pos - centre, axis=1), kind="stable")
+    small = np.zeros(nb, np.uint8); small[by_distance[:350]] = 1
+    large = np.ones(nb, np.uint8) if grow_to is None else np.zeros(nb, np.uint8)
+    if grow_to is not None:
+        large[by_distance[:grow_to]] = 1
+    _set_mask(g, o, small)
+    for i in range(3):
+        r = follow_step(g, o, scene.dt, 30)
+        _check(r, i, "subset ")
+        assert r["num_pairs"] > 0
+    before, after = _active_colliders(scene, small), _active_colliders(scene, large)
+    print("active colliders: %d -> %d (the pair kernels' bound after the subset steps: %d)" % (before, after, before + before // 8 + 2048))
+    assert after > before + before // 8 + 2048
+    _set_mask(g, o, large)
+    for i in range(15):
+        r = follow_step(g, o, scene.dt, 30)
+        _check(r, i, "grown ")
+    assert g.stats()["numFlowRecoveries"] == 0
+
+
+# ---- B: bodies and joints, no collider -------------------------------------------------------------------------------------------
+def _colliderless_scene():
+    from directx_renderer_kurth_amd import scenes
+    s = scenes.Scene("no_colliders", dt=1.0 / 60.0)
+    # distance chain from global points under a kinematic anchor
+    prev = s.add_body((-3.0, 6.0, 0.0), kinematic=True)
+    for i in range(4):
+        cur = s.add_body((-3.0 + 0.7 * (i + 1), 6.0, 0.0))
+        s.add_joint("distance", prev, cur, (-3.0 + 0.7 * i, 6.0, 0.0), (-3.0 + 0.7 * (i + 1), 6.0, 0.0))
+        prev = cur
+    # ball joint from local points to a kinematic body
+    k = s.add_body((2.0, 6.0, 0.0), kinematic=True)
+    b = s.add_body((2.5, 5.6, 0.0))
+    s.add_joint("ball_local", k, b, (0.25, -0.2, 0.0), (-0.25, 0.2, 0.0))
+    # hinge and slider to kinematic bodies
+    k = s.add_body((5.0, 6.0, 0.0), kinematic=True)
+    b = s.add_body((5.8, 6.0, 0.0))
+    s.add_joint("hinge", k, b, (5.4, 6.0, 0.0), (0.0, 0.0, 1.0))
+    k = s.add_body((8.0, 6.0, 0.0), kinematic=True)
+    b = s.add_body((8.0, 5.5, 0.3))
+    s.add_joint("slider", k, b, (8.0, 5.75, 0.15), (1.0, 0.0, 0.0))
+    slider = b
+    # one free body
+    free = s.add_body((11.0, 8.0, 0.0))
+    return s, free, slider
+
+
+def test_world_without_colliders_follows_the_oracle(mi, oracle):
+    """No collider at all: the step builds the active body list anyway (the body kernels walk it), so gravity and the joints act.
+    60 steps from identical inputs (resync, as for every jointed world), 1e-4; the free body falls."""
+    scene, free, slider = _colliderless_scene()
+    g = scene.instantiate(mi.World())
+    o = scene.instantiate(oracle.OracleWorld(solver=oracle.SOLVER_CUSTOM))
+    assert g.num_colliders == 0
+    jc = {}
+    for j in scene.joints:
+        k = KINDS[j[0][:-6] if j[0].endswith("_local") else j[0]]
+        jc[k] = jc.get(k, 0) + 1
+    y0 = g.transforms(1)[free, 1]
+    worst = 0.0
+    for i in range(60):
+        r = follow_step(g, o, scene.dt, 30, jc, resync=True)
+        _check(r, i)
+        assert r["num_pairs"] == 0
+        worst = max(worst, r["vel_err"])
+    drop = float(y0 - g.transforms(1)[free, 1])
+    moved = np.abs(g.transforms(1)[:, :3] - np.array([b[0] for b in scene.bodies], np.float32)).max(axis=1)
+    print("world without colliders: free body fell %.3f m, worst velocity error %.2e, bodies moved %s" % (drop, worst, np.round(moved, 3).tolist()))
+    assert drop > 1.0
+    swinging = [i for i, b in enumerate(scene.bodies) if not b[2] and i not in (free, slider)]   # (the slider's body hangs on its rail)
+    assert (moved[swinging] > 1e-2).all(), "a jointed dynamic body never moved"
+
+
+# ---- C: a give-up of the cluster sweep noticed at the next step ------------------------------------------------------------------
+def _spreading_scene(oracle):
+    """3 072 bodies in 32 x 32 columns of 3 (x and z variance nearly equal), the x coordinates pulled in by 5 % and moving apart at
+    0.4 x per second: the sweep's sorting axis is z for the first steps, then x."""
+    from directx_renderer_kurth_amd import scenes
+    scene = scenes.c3_mixed(3072, area=40.0, column_height=3)
+    o = scene.instantiate(oracle.OracleWorld(solver=oracle.SOLVER_CUSTOM))
+    t, v = o.transforms(1).copy(), o.velocities().copy()
+    t[:, 0] *= 0.95
+    v[:, 0] = 0.4 * t[:, 0]
+    return scene, t, v
+
+
+def _order_sensitive(g, axis_now, axis_other):
+    """Colliding equal-type pairs of the last step whose boxes start in one order on axis_now and in the other on axis_other."""
+    slots, counts, _, _ = g.manifolds()
+    cols, aabbs = g.world_colliders()
+    sl = slots[counts > 0].astype(np.int64)
+    sl = sl[(sl[:, 0] < len(cols)) & (sl[:, 1] < len(cols))]
+    same = cols["type"][sl[:, 0]] == cols["type"][sl[:, 1]]
+    d_now = aabbs[sl[:, 0], axis_now] - aabbs[sl[:, 1], axis_now]
+    d_other = aabbs[sl[:, 0], axis_other] - aabbs[sl[:, 1], axis_other]
+    return int((same & (d_now * d_other < 0)).sum())
+
+
+@pytest.mark.parametrize("flip", [True, False], ids=["axis_changes", "axis_stays"])
+def test_give_up_noticed_at_next_step(mi, oracle, flip):
+    """The cluster sweep of step a gives up (MI_FLOW_TEST_ABORT=a).  World R reads results after every step, so the give-up is
+    resolved by the read, and R follows the oracle.  World N only steps: the give-up is found at step a + 1's first
+    synchronisation, after that step's pair list and narrowphase were launched over step a's.  Step a is then redone from its own
+    narrowphase, oriented by step a's sorting axis: N ends bit-equal to R.  The abort step is one after which the axis changes
+    (and at least one colliding equal-type pair is ordered differently on the two axes), or, as a control, one where it stays."""
+    scene, t0, v0 = _spreading_scene(oracle)
+    # dry run (no abort): the axis of every step and the pairs that the two axes order differently
+    d = _world(mi, scene, RESERVE_PAIRS)
+    d.write_state(t0, v0)
+    axes, sensitive, pairs = [], [], []
+    for i in range(40):
+        d.step_internal(scene.dt, 30)
+        ax = d.sorting_axis()[0]
+        axes.append(ax)
+        sensitive.append([_order_sensitive(d, ax, k) for k in range(3)])
+        pairs.append(len(d.pairs()))
+    d.close()
+    cand = [i for i in range(5, len(axes) - 1) if (axes[i + 1] != axes[i]) == flip and (not flip or sensitive[i][axes[i + 1]] > 0)]
+    print("dry run: sorting axes", "".join(map(str, axes)), "candidate abort steps", cand[:5])
+    assert cand, "no step with%s an axis change" % ("" if flip else "out")
+    a = cand[0]
+    if flip:
+        print("abort at step %d: axis %d -> %d, %d colliding equal-type pairs ordered differently" % (a, axes[a], axes[a + 1], sensitive[a][axes[a + 1]]))
+    # the early launch of step a + 1 fits the pair buffers (so step a + 1 does overwrite step a's pair list and narrowphase)
+    assert pairs[a] + pairs[a] // 8 + 4096 <= RESERVE_PAIRS
+    steps = a + 3
+
+    r_world = _world(mi, scene, RESERVE_PAIRS, MI_FLOW_TEST_ABORT=a)
+    o = scene.instantiate(oracle.OracleWorld(solver=oracle.SOLVER_CUSTOM))
+    r_world.write_state(t0, v0); o.write_state(t0, v0)
+    for i in range(steps):
+        r = follow_step(r_world, o, scene.dt, 30)
+        _check(r, i)
+        assert r["axis_equal"] or r["axis_near_tie"], "step %d: sorting axis differs from the reference's" % i
+        assert r["orient_bad"] == 0 or not r["axis_equal"], "step %d: %d candidate pairs not in the reference's A/B order" % (i, r["orient_bad"])
+    n_world = _world(mi, scene, RESERVE_PAIRS, MI_FLOW_TEST_ABORT=a)
+    n_world.write_state(t0, v0)
+    for i in range(steps):
+        n_world.step_internal(scene.dt, 30)
+    st_r, st_n = r_world.stats(), n_world.stats()
+    assert st_r["numFlowRecoveries"] == 1 and st_n["numFlowRecoveries"] == 1, (st_r["numFlowRecoveries"], st_n["numFlowRecoveries"])
+    tn, tr = n_world.transforms(1), r_world.transforms(1)
+    vn, vr = n_world.velocities(), r_world.velocities()
+    print("give-up at step %d noticed in the next step: pose difference %g, velocity difference %g" % (a, np.abs(tn - tr).max(), np.abs(vn - vr).max()))
+    assert np.array_equal(tn, tr) and np.array_equal(vn, vr)
+
+
+# ---- D: the pair list outgrows its early guess, a collider outgrows its pair slab ---------------------------------------------
+def test_pair_count_jump_redoes_the_narrowphase(mi, oracle):
+    """c3_small settles for 8 steps, then 1 000 of its bodies are packed into a 10 x 10 x 10 lattice of 0.6 m above the pile (the same
+    state written into both worlds): the pair count of the next step jumps past the early guess (last count + 12 % + 4 096), so the
+    pair list and narrowphase launched before the count was known are launched again; every step follows the oracle exactly."""
+    from directx_renderer_kurth_amd import scenes
+    scene = scenes.by_name("c3_small")
+    g = scene.instantiate(mi.World(reserve_pairs=RESERVE_PAIRS))
+    o = scene.instantiate(oracle.OracleWorld(solver=oracle.SOLVER_CUSTOM))
+    for i in range(8):
+        r = follow_step(g, o, scene.dt, 30)
+        _check(r, i)
+    prev_pairs, redone = r["num_pairs"], g.stats()["numNarrowphaseRedone"]
+    t, v = o.transforms(1).copy(), o.velocities().copy()
+    idx = np.arange(0, scene.num_bodies, 3)[:1000]
+    lattice = np.stack(np.meshgrid(np.arange(10), np.arange(10), np.arange(10), indexing="ij"), -1).reshape(-1, 3).astype(np.float32)
+    t[idx, :3] = lattice * 0.6 + np.array([30.0, 60.0, 30.0], np.float32)
+    v[idx] = 0.0
+    g.write_state(t, v); o.write_state(t, v)
+    r = follow_step(g, o, scene.dt, 30)
+    _check(r, 0, "teleport ")
+    st = g.stats()
+    print("pair count %d -> %d (early guess %d), narrowphase redone %d -> %d" % (prev_pairs, r["num_pairs"], prev_pairs + prev_pairs // 8 + 4096, redone, st["numNarrowphaseRedone"]))
+    assert r["num_pairs"] > prev_pairs + prev_pairs // 8 + 4096
+    assert r["num_pairs"] + r["num_pairs"] // 8 + 4096 <= RESERVE_PAIRS
+    assert st["numNarrowphaseRedone"] == redone + 1
+    for i in range(5):
+        r = follow_step(g, o, scene.dt, 30)
+        _check(r, i + 1, "after the teleport ")
+    assert g.stats()["numNarrowphaseRedone"] == redone + 1
+
+
+def _slab_scene():
+    """A bed of 36 x 25 small spheres (spaced apart, on the ground) and one large flat dynamic box falling onto it: the box's box
+    overlaps ~200 spheres at once."""
+    from directx_renderer_kurth_amd import scenes
+    s = scenes.Scene("slab_overflow", dt=1.0 / 120.0)
+    s.add_collider(scenes.STATIC, scenes.AABB, (-30.0, -8.0, -30.0, 30.0, 0.0, 30.0), scenes.DEFAULT_MATERIAL)
+    rng = np.random.default_rng(1729)
+    for ix in range(36):
+        for iz in range(25):
+            b = s.add_body(((ix - 17.5) * 0.56 + rng.uniform(-0.02, 0.02), 0.25 + rng.uniform(0.0, 0.002), (iz - 12.0) * 0.56 + rng.uniform(-0.02, 0.02)))
+            s.add_collider(b, scenes.SPHERE, (0.0, 0.0, 0.0, 0.25), scenes.DEFAULT_MATERIAL)
+    big = s.add_body((0.13, 0.95, -0.07))
+    s.add_collider(big, scenes.OBB, (0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 4.0, 0.2, 4.0), scenes.DEFAULT_MATERIAL)
+    return s
+
+
+def test_pair_slab_overflow_follows_the_oracle(mi, oracle):
+    """The step in which a collider first has more than PAIR_SLAB (32) partners: its pairs are written by the second pair pass
+    (k_pairs<MODE_WRITE>), and the pair list launched early without that pass is launched again.  Every step follows the oracle."""
+    scene = _slab_scene()
+    g = scene.instantiate(mi.World(reserve_pairs=RESERVE_PAIRS))
+    o = scene.instantiate(oracle.OracleWorld(solver=oracle.SOLVER_CUSTOM))
+    first, most = None, 0
+    for i in range(60):
+        redone = g.stats()["numNarrowphaseRedone"]
+        r = follow_step(g, o, scene.dt, 30)
+        _check(r, i)
+        p = g.pairs()
+        most = int(np.bincount(p[:, 0].astype(np.int64)).max()) if len(p) else 0
+        if most > 32:
+            first = i
+            assert g.stats()["numNarrowphaseRedone"] == redone + 1, "the step that first overflowed a pair slab did not redo its narrowphase"
+            break
+    print("first step with more than 32 partners of one collider: %s (largest partner count %d)" % (first, most))
+    assert first is not None and first > 0, "no collider ever had more than 32 partners"
+    for i in range(5):
+        _check(follow_step(g, o, scene.dt, 30), first + 1 + i)
