@@ -720,9 +720,11 @@ MI_DEV int updateGJKSimplex(GjkSimplex& s, const SupportPoint& a, V3& dir)
 	return 2;
 }
 
-template <int FAMILY>
-MI_DEV bool gjkPair(const SupShapes& sh, GjkSimplex& sx)
+// COUNT: *iters = loop entries, counted as the oracle's g_gjkMaxItersSeen counts them (0 when a first support point already separates)
+template <int FAMILY, bool COUNT = false>
+MI_DEV bool gjkPair(const SupShapes& sh, GjkSimplex& sx, u32* iters = nullptr)
 {
+	if (COUNT) *iters = 0;
 	V3 dir = v3(1.f, 0.1f, -0.2f);
 	sx.c = supportPair<FAMILY>(sh, dir);
 	if (dot(sx.c.mk, dir) < 0.f) return false;
@@ -733,6 +735,7 @@ MI_DEV bool gjkPair(const SupShapes& sh, GjkSimplex& sx)
 	sx.numPoints = 2;
 	for (u32 it = 0; it < GJK_MAX_ITERATIONS; ++it)
 	{
+		if (COUNT) *iters = it + 1;
 		if (sqlen(dir) < 0.0001f) return false;
 		SupportPoint a = supportPair<FAMILY>(sh, dir);
 		if (dot(a.mk, dir) < 0.f) return false;
@@ -799,9 +802,10 @@ __device__ __forceinline__ void epaSetTri(EpaWave& e, u32 t, u32 a, u32 b, u32 c
 // the two groups' loops and exits diverge freely, every cross-lane operation (shuffles below EPA_GROUP, ballots cut to the group's
 // bits) stays inside a group, and WAVE_SYNC orders a group's LDS traffic whatever the other group is doing.
 template <int FAMILY>
-__device__ void epaWave(EpaWave& e, u32 lane, u32 groupShift, const GjkSimplex& g, const SupShapes& sh, V3& outPoint, V3& outNormal, float& outDepth)
+__device__ void epaWave(EpaWave& e, u32 lane, u32 groupShift, const GjkSimplex& g, const SupShapes& sh, V3& outPoint, V3& outNormal, float& outDepth, u32* __restrict__ counters)
 {
 	u32 numTris = 4, numPoints = 4, numEdges = 6;
+	u32 maxBorder = 0; bool outOfMemory = false; // for the high-water marks (CTR_NARROW_LIMITS), as the oracle records them
 	if (lane == 0)
 	{
 		epaSetPoint(e, 0, g.a); epaSetPoint(e, 1, g.b); epaSetPoint(e, 2, g.c); epaSetPoint(e, 3, g.d);
@@ -855,9 +859,10 @@ __device__ void epaWave(EpaWave& e, u32 lane, u32 groupShift, const GjkSimplex& 
 			if (flag && pos < EPA_MAX_BORDER) e.border[pos] = i;
 			nBorder += __popc(mask);
 		}
-		if (nBorder > EPA_MAX_BORDER) break;                                     // "out of memory" exits, as the serial code's pushes would hit them
-		if (numPoints >= EPA_MAX_POINTS) break;
-		if (numEdges + nBorder > EPA_MAX_EDGES || numTris + nBorder > EPA_MAX_TRIANGLES) break;
+		if (nBorder > EPA_MAX_BORDER) { outOfMemory = true; break; }             // "out of memory" exits, as the serial code's pushes would hit them
+		maxBorder = max(maxBorder, nBorder);
+		if (numPoints >= EPA_MAX_POINTS) { outOfMemory = true; break; }
+		if (numEdges + nBorder > EPA_MAX_EDGES || numTris + nBorder > EPA_MAX_TRIANGLES) { outOfMemory = true; break; }
 		u32 newPoint = numPoints++;
 		if (lane == 0) epaSetPoint(e, newPoint, np);
 		WAVE_SYNC();
@@ -898,6 +903,15 @@ __device__ void epaWave(EpaWave& e, u32 lane, u32 groupShift, const GjkSimplex& 
 	outPoint = 0.5f * (pointA + pointB);
 	outNormal = tn;
 	outDepth = tdist;
+	if (lane == 0) // one update per polytope: the counts only grow, so their final values are this polytope's maxima
+	{
+		// (read first: the marks settle within a step or two, after which no polytope issues the same-address atomics — unguarded,
+		// they cost c3 0.86 ms per step)
+		if (numTris > counters[CTR_NARROW_LIMITS + 1]) atomicMax(&counters[CTR_NARROW_LIMITS + 1], numTris);
+		if (numEdges > counters[CTR_NARROW_LIMITS + 2]) atomicMax(&counters[CTR_NARROW_LIMITS + 2], numEdges);
+		if (maxBorder > counters[CTR_NARROW_LIMITS + 3]) atomicMax(&counters[CTR_NARROW_LIMITS + 3], maxBorder);
+		if (outOfMemory) atomicAdd(&counters[CTR_NARROW_LIMITS + 4], 1u);
+	}
 	WAVE_SYNC(); // the next instance reuses this LDS block
 }
 
@@ -1060,7 +1074,10 @@ __global__ void __launch_bounds__(256) k_gjk(u32* __restrict__ counters, const u
 		if (r != 2) { writeManifold(manifolds, slot, m, r == 1, A, B, slot); return; }
 	}
 	GjkSimplex sx;
-	if (!gjkPair<FAMILY>(sh, sx))
+	u32 iters;
+	const bool gjkHit = gjkPair<FAMILY, true>(sh, sx, &iters);
+	if (iters > counters[CTR_NARROW_LIMITS]) atomicMax(&counters[CTR_NARROW_LIMITS], iters); // (read first: once the mark has settled, no lane issues the same-address atomic)
+	if (!gjkHit)
 	{
 		Man m; m.count = 0; m.n = v3(0.f, 1.f, 0.f);
 		writeManifold(manifolds, slot, m, false, A, B, slot);
@@ -1082,7 +1099,7 @@ __global__ void __launch_bounds__(256) k_gjk(u32* __restrict__ counters, const u
 #define EPA_WAVES_PER_BLOCK 4
 #define EPA_PER_WAVE (64 / EPA_GROUP)
 template <int FAMILY>
-__global__ void __launch_bounds__(64 * EPA_WAVES_PER_BLOCK) __attribute__((amdgpu_waves_per_eu(FAMILY == 0 ? 3 : 2, FAMILY == 0 ? 3 : 3))) k_epa(const u32* __restrict__ counters, const u32* __restrict__ keySorted, const u64* __restrict__ pairSorted,
+__global__ void __launch_bounds__(64 * EPA_WAVES_PER_BLOCK) __attribute__((amdgpu_waves_per_eu(FAMILY == 0 ? 3 : 2, FAMILY == 0 ? 3 : 3))) k_epa(u32* __restrict__ counters, const u32* __restrict__ keySorted, const u64* __restrict__ pairSorted,
 	const ColliderRec* __restrict__ colWorld, ManifoldRec* __restrict__ manifolds, const u32* __restrict__ epaList, const float4* __restrict__ gjkSimplex,
 	const float4* __restrict__ hullInfo, const float4* __restrict__ hullVerts, u32 listCap)
 {
@@ -1110,7 +1127,7 @@ __global__ void __launch_bounds__(64 * EPA_WAVES_PER_BLOCK) __attribute__((amdgp
 			sx.d.a = v3(s6.w, s7.x, s7.y); sx.d.b = v3(s7.z, s7.w, s8.x); sx.d.mk = v3(s8.y, s8.z, s8.w);
 		}
 		V3 point, normal; float depth;
-		epaWave<FAMILY>(e, lane, group * EPA_GROUP, sx, sh, point, normal, depth);
+		epaWave<FAMILY>(e, lane, group * EPA_GROUP, sx, sh, point, normal, depth, counters);
 		if (lane == 0)
 		{
 			Man m; m.count = 0; m.n = v3(0.f, 1.f, 0.f);
@@ -1211,7 +1228,7 @@ MI_DEV bool overlapColliders(u32 key, const ColliderRec& A, const ColliderRec& B
 		default: break;
 	}
 	SupShapes sh; Obb o; GjkSimplex sx;
-	if (key % 6 == 5) { gjkOperands<1>(key, A, B, hullInfo, hullVerts, sh, o); return gjkPair<1>(sh, sx); } // x vs hull
+	if (key % 6 == 5) { gjkOperands<1>(key, A, B, hullInfo, hullVerts, sh, o); return gjkPair<1>(sh, sx); } // x vs hull (trigger / force-field checks are not counted in CTR_NARROW_LIMITS)
 	if (key == 9 || key == 10 || key == 14 || key == 15 || key == 16) { gjkOperands<0>(key, A, B, hullInfo, hullVerts, sh, o); return gjkPair<0>(sh, sx); } // no closed form for parallel cylinders here (:790-797)
 	return false;
 }

@@ -95,6 +95,7 @@ enum
 	CTR_CELL_SIZE_USED = 380, // float bits: the cell size the current sorted order was built with (CTR_CELL_SIZE is reset for the next step's atomicMax before the last pair kernel runs)
 	CTR_CL_SCRATCH = 371,   // cluster sweep: append cursor of the global row scratch (contacts that fit neither registers nor LDS), reset before every launch
 	CTR_VALIDATE = 448,     // 2 words: non-finite values found by the debug guard (MI_PHYSICS_VALIDATE=1), first offender (stage << 28 | index)
+	CTR_NARROW_LIMITS = 450,// 5 words: high-water marks of the GJK / EPA caps since the world was created (k_gjk, k_epa): GJK iterations, EPA triangles, edges, border edges; EPA runs that left through an out-of-memory exit (mi_debug_narrow_limits)
 	CTR_CL_REMAIN = 442,    // 6 words: manifolds still unassigned when partition phase p starts ([0] unused: all active ones)
 	CTR_WORDS = 512,
 };

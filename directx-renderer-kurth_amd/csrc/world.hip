@@ -2293,6 +2293,14 @@ int mi_debug_sorting_axis(mi_world* world, uint32_t out[2])
 	out[0] = k ? words[(k - 1u) & 1u] : 0u; out[1] = words[k & 1u];
 	return W->lastError;
 }
+int mi_debug_narrow_limits(mi_world* world, uint32_t out[8])
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	u32 words[5] = { 0, 0, 0, 0, 0 };
+	d2h(W, words, W->dCounters.p + CTR_NARROW_LIMITS, sizeof(words));
+	for (u32 i = 0; i < 8; ++i) out[i] = i < 5 ? words[i] : 0u;
+	return W->lastError;
+}
 uint32_t mi_debug_num_colors(mi_world* world) { CHECK_WORLD(0); return MI_MAX_COLORS + 1; }
 int mi_debug_read_schedule(mi_world* world, uint32_t* outManifoldSlots, uint32_t* outColorStart)
 {

@@ -263,6 +263,9 @@ int mi_debug_read_pairs(mi_world* w, uint32_t* outPairs2);                      
  * equal-type pairs: A = the collider whose box starts first on it, collision_broad.cpp:127 + collision_narrow.cpp:2374), out[1] = the
  * axis of largest AABB-centre variance of the last step = the next step's axis. */
 int mi_debug_sorting_axis(mi_world* w, uint32_t out[2]);
+/* High-water marks of the narrowphase's fixed-size GJK / EPA state since the world was created: [0] GJK iterations, [1] EPA triangles,
+   [2] EPA edges, [3] EPA border edges of one expansion, [4] EPA runs that stopped at an out-of-memory exit; [5..7] zero. */
+int mi_debug_narrow_limits(mi_world* w, uint32_t out[8]);
 int mi_debug_read_world_colliders(mi_world* w, void* outColliders64, float* outAabbs6); /* worldSpaceColliders / worldSpaceAABBs */
 uint32_t mi_debug_num_manifold_slots(mi_world* w);
 /* Per candidate pair after prune/classify/bucket (collision_narrow.cpp:2346-2453): ordered collider pair, contact count, and up to 4

@@ -415,7 +415,7 @@ static inline bool gjkIntersectionTest(const A& shapeA, const B& shapeB, gjk_sim
 // Same caps as the device kernels (k_narrow.hip).  Measured high-water marks with the reference's 1024-entry arrays on the golden
 // poses and the config-3/4 scenes: 98 triangles, 100 edges, 8 border edges, 16 GJK iterations — these caps never bind there.
 static const u32 EPA_MAX_POINTS = 24, EPA_MAX_TRIANGLES = 128, EPA_MAX_EDGES = 160, EPA_MAX_BORDER = 32;
-extern u32 g_epaMaxTriangles, g_epaMaxEdges, g_epaMaxBorder;
+extern u32 g_epaMaxTriangles, g_epaMaxEdges, g_epaMaxBorder, g_epaOutOfMemory;
 
 struct epa_triangle { u16 a, b, c, edgeOppositeA, edgeOppositeB, edgeOppositeC; vec3 normal; float distanceToOrigin; };
 struct epa_edge { u16 a, b; u16 triangleA, triangleB; };
@@ -575,7 +575,7 @@ static inline epa_status epaCollisionInfo(const gjk_simplex& gjkSimplex, const A
 		gjk_support_point a = support(shapeA, shapeB, tri.normal);
 		float d = dot(a.minkowski, tri.normal);
 		if (d - tri.distanceToOrigin < 0.01f) { returnCode = epa_success; break; }
-		if (!epaSimplex.addNewPointAndUpdate(a)) { returnCode = epa_out_of_memory; break; }
+		if (!epaSimplex.addNewPointAndUpdate(a)) { returnCode = epa_out_of_memory; ++g_epaOutOfMemory; break; }
 	}
 
 	epa_triangle& tri = epaSimplex.triangles[closestIndex];

@@ -452,6 +452,12 @@ def solve_contacts(rb_global, contacts, body_pairs, order, iterations, dt):
 
 
 def stats():
-    out = np.zeros(4, np.uint32)
+    """High-water marks of the GJK / EPA caps over every narrowphase since the library was loaded or stats_reset(), and the number
+    of EPA runs that stopped at an out-of-memory exit (the device's World.narrow_limits() has the same keys)."""
+    out = np.zeros(8, np.uint32)
     _lib().orc_stats(_p(out))
-    return dict(gjk_max_iters=int(out[0]), epa_max_triangles=int(out[1]), epa_max_edges=int(out[2]), epa_max_border=int(out[3]))
+    return dict(gjk_max_iters=int(out[0]), epa_max_triangles=int(out[1]), epa_max_edges=int(out[2]), epa_max_border=int(out[3]), epa_out_of_memory=int(out[4]))
+
+
+def stats_reset():
+    _lib().orc_stats_reset()

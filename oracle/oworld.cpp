@@ -17,7 +17,7 @@
 namespace orc {
 
 u32 g_gjkMaxItersSeen = 0;
-u32 g_epaMaxTriangles = 0, g_epaMaxEdges = 0, g_epaMaxBorder = 0;
+u32 g_epaMaxTriangles = 0, g_epaMaxEdges = 0, g_epaMaxBorder = 0, g_epaOutOfMemory = 0;
 
 static const float GRAVITY = -9.81f; // physics.h:11
 static const u32 STATIC_BODY = 0xFFFFFFFFu;
@@ -1660,6 +1660,7 @@ void orc_solve_contacts(void* rb104, u32 numBodiesPlusDummy, const void* contact
 	for (u32 i = 0; i < numContacts; ++i) { outImpulses2[2 * i] = cons[i].impulseInNormalDir; outImpulses2[2 * i + 1] = cons[i].impulseInTangentDir; }
 }
 
-void orc_stats(u32* out4) { out4[0] = g_gjkMaxItersSeen; out4[1] = g_epaMaxTriangles; out4[2] = g_epaMaxEdges; out4[3] = g_epaMaxBorder; }
+void orc_stats(u32* out5) { out5[0] = g_gjkMaxItersSeen; out5[1] = g_epaMaxTriangles; out5[2] = g_epaMaxEdges; out5[3] = g_epaMaxBorder; out5[4] = g_epaOutOfMemory; }
+void orc_stats_reset() { g_gjkMaxItersSeen = 0; g_epaMaxTriangles = 0; g_epaMaxEdges = 0; g_epaMaxBorder = 0; g_epaOutOfMemory = 0; }
 
 } // extern "C"

@@ -156,6 +156,8 @@ def test_cluster_follow_c3_full_size(mi, oracle):
     o = scene.instantiate(oracle.OracleWorld(solver=oracle.SOLVER_CUSTOM))
     o.write_state(g.transforms(1), g.velocities())
     o.set_sorting_axis(g.sorting_axis()[1])   # the oracle takes over mid-run: also the sweep's current sorting axis
+    settled = g.narrow_limits()
+    oracle.stats_reset()
     for i in range(3):
         r = follow_step(g, o, scene.dt, 30, own_narrowphase=True)
         assert r["pairs_equal"], "step %d: broadphase pair set differs (%d pairs)" % (i, r["num_pairs"])
@@ -169,6 +171,14 @@ def test_cluster_follow_c3_full_size(mi, oracle):
         assert r["pos_err"] <= 1e-4
     st = g.stats()
     assert st["numFlowRecoveries"] == 0 and st["clusterTasks"][0] >= 100, st
+    # GJK / EPA high-water marks: the device's cover all 243 steps, the oracle's the 3 it followed (on the device's pairs)
+    dev, orc = g.narrow_limits(), oracle.stats()
+    print("c3 full size GJK/EPA marks: device after 240 steps", settled, "after 243", dev, "oracle over the 3 followed", orc)
+    if dev == settled:   # the followed steps set no new mark on the device: the oracle's over the same pairs can be no higher
+        assert all(orc[k] <= dev[k] for k in dev)
+    else:                # the followed steps hold the device's maxima: the oracle must reach the same ones
+        assert all(orc[k] == dev[k] for k in dev if dev[k] != settled[k])
+    assert dev["gjk_max_iters"] < 64 and dev["epa_max_triangles"] < 128 and dev["epa_max_edges"] < 160 and dev["epa_max_border"] < 32 and dev["epa_out_of_memory"] == 0
     print("c3 full size:", {k: r[k] for k in ("num_pairs", "num_manifolds", "num_contacts", "vel_err", "pos_err", "orient_bad", "orient_ties", "own_start_ties", "own_missing_on_device", "own_extra_on_device")}, "tasks", st["clusterTasks"])
 
 

@@ -25,6 +25,7 @@ def _joint_counts(scene):
 
 def _run(mi, oracle, scene, steps, resync, vel_tol, pos_tol):
     g, o = _worlds(mi, oracle, scene)
+    oracle.stats_reset()   # the oracle's GJK / EPA marks from here on cover the device's pairs only (follow mode)
     jc = _joint_counts(scene)
     worst = {}
     ties = 0
@@ -42,6 +43,11 @@ def _run(mi, oracle, scene, steps, resync, vel_tol, pos_tol):
     assert worst["pos_err"] <= pos_tol and worst["rot_err"] <= pos_tol
     for k in ("contact_point_err", "contact_depth_err", "contact_normal_err"):
         assert worst.get(k, 0.0) <= 1e-5 * (1.0 + 100.0), k  # 1e-5 abs + 1e-5 rel on coordinates up to ~100 m
+    dev, orc = g.narrow_limits(), oracle.stats()
+    print(scene.name, "GJK/EPA high-water marks: device", dev, "oracle", orc)
+    if not scene.fields and not scene.triggers:   # (the oracle also counts the GJK of trigger / force-field checks, the device does not)
+        assert dev == orc
+    assert dev["gjk_max_iters"] < 64 and dev["epa_max_triangles"] < 128 and dev["epa_max_edges"] < 160 and dev["epa_max_border"] < 32 and dev["epa_out_of_memory"] == 0
     return worst
 
 
