@@ -78,6 +78,7 @@ EXPORTED_SYMBOLS = [
     "mi_debug_read_world_colliders", "mi_debug_num_manifold_slots", "mi_debug_read_manifolds", "mi_debug_num_colors", "mi_debug_read_schedule",
     "mi_debug_read_joint_order", "mi_debug_read_body_state", "mi_debug_flow_trace",
     "mi_debug_set_replay", "mi_debug_num_replay_batches", "mi_debug_read_replay_batches",
+    "mi_device_state", "mi_joint_device_pods", "mi_test_physics_interaction_batch",
 ]
 
 
@@ -91,16 +92,26 @@ def build(force=False):
 
 
 LOCOMOTION_LIB_PATH = os.path.join(_HERE, "libmi_locomotion.so")
-LOCOMOTION_SYMBOLS = ["getPhysicsStateSize", "getPhysicsActionSize", "getPhysicsRanges", "resetPhysics", "updatePhysics", "setPhysicsSeed"]
+LOCOMOTION_SYMBOLS = ["getPhysicsStateSize", "getPhysicsActionSize", "getPhysicsRanges", "resetPhysics", "updatePhysics", "setPhysicsSeed",
+                      "resetPhysicsBatch", "updatePhysicsBatch", "updatePhysicsBatchDevice", "resetPhysicsBatchEnvs", "observePhysicsBatch",
+                      "getPhysicsBatchWorld", "getPhysicsBatchStream", "getPhysicsBatchPushes"]
+_HIPCC = "/opt/rocm/bin/hipcc"
 
 
 def build_locomotion():
-    """Host-side C++ over the C-ABI: the reference's ragdoll RL environment (learned_locomotion.cpp:395-489) as libmi_locomotion.so."""
-    src = os.path.join(_HERE, "host", "locomotion_env.cpp")
-    if os.path.exists(LOCOMOTION_LIB_PATH) and os.path.getmtime(LOCOMOTION_LIB_PATH) >= max(os.path.getmtime(src), os.path.getmtime(_LIB_PATH)):
+    """libmi_locomotion.so: the reference's ragdoll RL environment (learned_locomotion.cpp:395-489) as host C++ over the C-ABI (g++),
+    plus the batched environments of host/locomotion_batch.hip (hipcc, gfx950, strict fp32 like libmi_physics.so)."""
+    host = os.path.join(_HERE, "host")
+    include = "-I" + os.path.join(os.path.dirname(_HERE), "include")
+    cpp, hip = os.path.join(host, "locomotion_env.cpp"), os.path.join(host, "locomotion_batch.hip")
+    deps = [cpp, hip, os.path.join(host, "locomotion_shared.h"), os.path.join(os.path.dirname(_HERE), "include", "mi_physics.h"), _LIB_PATH]
+    if os.path.exists(LOCOMOTION_LIB_PATH) and os.path.getmtime(LOCOMOTION_LIB_PATH) >= max(os.path.getmtime(p) for p in deps):
         return LOCOMOTION_LIB_PATH
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-Wall", "-I" + os.path.join(os.path.dirname(_HERE), "include"), src,
-                           "-L" + _HERE, "-lmi_physics", "-Wl,-rpath,$ORIGIN", "-o", LOCOMOTION_LIB_PATH])
+    cpp_o, hip_o = os.path.join(host, "locomotion_env.o"), os.path.join(host, "locomotion_batch.o")
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-Wall", include, "-c", cpp, "-o", cpp_o])
+    subprocess.check_call([_HIPCC, "-std=c++17", "-O3", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", "-Wall", include, "-c", hip, "-o", hip_o])
+    subprocess.check_call([_HIPCC, "-shared", "-fPIC", "--offload-arch=gfx950", cpp_o, hip_o, "-L" + _HERE, "-lmi_physics", "-Wl,-rpath,$ORIGIN",
+                           "-o", LOCOMOTION_LIB_PATH])
     return LOCOMOTION_LIB_PATH
 
 
@@ -504,3 +515,97 @@ class World:
         cog = np.zeros((n, 4), np.float32); inv = np.zeros((n, 12), np.float32)
         self._check(self.lib.mi_debug_read_body_state(self.w, _p(cog), _p(inv), C.c_uint32(n)))
         return cog, inv
+
+
+class _BorrowedWorld(World):
+    """A World over a handle someone else owns (the batched environments' world): closing it does not destroy the world."""
+
+    def __init__(self, handle):
+        self.lib = load_library()
+        self.w = C.c_void_p(handle)
+        self.timer = C.c_float(0.0)
+
+    def close(self):
+        self.w = None
+
+
+class LocomotionBatch:
+    """N ragdoll environments of libmi_locomotion.so stepped together in one world (host/locomotion_batch.hip).  One instance per
+    process: the library holds one batch, as it holds one single environment.  step() takes a [n, 27] numpy array, or a ROCm torch
+    tensor, which goes to updatePhysicsBatchDevice on the world's stream and returns device tensors.  For the tensor path, import
+    torch before the first World or LocomotionBatch: the process then runs one HIP runtime, the one torch loads."""
+
+    def __init__(self, n, seed=None):
+        build_locomotion()
+        lib = C.CDLL(LOCOMOTION_LIB_PATH)
+        lib.setPhysicsSeed.argtypes = [C.c_ulonglong]
+        lib.getPhysicsBatchWorld.restype = C.c_void_p
+        lib.getPhysicsBatchStream.restype = C.c_void_p
+        self.lib, self.n = lib, int(n)
+        self.state_size, self.action_size = lib.getPhysicsStateSize(), lib.getPhysicsActionSize()
+        if seed is not None:
+            lib.setPhysicsSeed(C.c_ulonglong(seed))
+        self.reset()
+
+    def _check(self, code, what, count=False):
+        """Status codes are 0 or an MI_ERR_*; a count (updatePhysicsBatch) is >= 0 or a negated MI_ERR_*."""
+        if code < 0 or (code and not count):
+            raise PhysicsError("%s failed (%d)" % (what, code))
+        return code
+
+    def reset(self):
+        """Builds the world and resets every environment; returns the states [n, 66]."""
+        states = np.zeros((self.n, self.state_size), np.float32)
+        self._check(self.lib.resetPhysicsBatch(C.c_uint32(self.n), _p(states)), "resetPhysicsBatch")
+        return states
+
+    def step(self, actions):
+        """(states [n, 66], rewards [n], fallen [n] int32) after one update with `actions` [n, 27]."""
+        if hasattr(actions, "is_cuda") and actions.is_cuda:
+            return self._step_device(actions)
+        a = np.ascontiguousarray(actions, np.float32).reshape(self.n, self.action_size)
+        states = np.zeros((self.n, self.state_size), np.float32); rewards = np.zeros(self.n, np.float32); fallen = np.zeros(self.n, np.int32)
+        self._check(self.lib.updatePhysicsBatch(_p(a), _p(states), _p(rewards), _p(fallen)), "updatePhysicsBatch", count=True)
+        return states, rewards, fallen
+
+    def _step_device(self, actions):
+        import torch
+        a = actions.detach().to(torch.float32).contiguous().reshape(self.n, self.action_size)
+        dev = a.device
+        states = torch.empty((self.n, self.state_size), dtype=torch.float32, device=dev)
+        rewards = torch.empty(self.n, dtype=torch.float32, device=dev); fallen = torch.empty(self.n, dtype=torch.int32, device=dev)
+        ext = torch.cuda.ExternalStream(self.lib.getPhysicsBatchStream(), device=dev)
+        ext.wait_stream(torch.cuda.current_stream(dev))      # the actions are ready
+        with torch.cuda.stream(ext):
+            code = self.lib.updatePhysicsBatchDevice(C.c_void_p(a.data_ptr()), C.c_void_p(states.data_ptr()), C.c_void_p(rewards.data_ptr()), C.c_void_p(fallen.data_ptr()))
+            for t in (a, states, rewards, fallen):
+                t.record_stream(ext)
+        self._check(code, "updatePhysicsBatchDevice")
+        torch.cuda.current_stream(dev).wait_stream(ext)      # the outputs are ready for the caller's stream
+        return states, rewards, fallen
+
+    def reset_envs(self, ids, states=None):
+        """Resets the listed environments; writes their rows of `states` ([n, 66], a new zero array if None) and returns it."""
+        ids = np.ascontiguousarray(ids, np.uint32).ravel()
+        states = np.zeros((self.n, self.state_size), np.float32) if states is None else states
+        assert states.dtype == np.float32 and states.shape == (self.n, self.state_size) and states.flags.c_contiguous
+        self._check(self.lib.resetPhysicsBatchEnvs(_p(ids), C.c_uint32(len(ids)), _p(states)), "resetPhysicsBatchEnvs")
+        return states
+
+    def observe(self):
+        """(states, rewards, fallen) of the environments as they are, without stepping."""
+        states = np.zeros((self.n, self.state_size), np.float32); rewards = np.zeros(self.n, np.float32); fallen = np.zeros(self.n, np.int32)
+        self._check(self.lib.observePhysicsBatch(_p(states), _p(rewards), _p(fallen)), "observePhysicsBatch")
+        return states, rewards, fallen
+
+    def pushes(self):
+        """The pushes of the last update: 1 + the pushed body per environment, or 0."""
+        out = np.zeros(self.n, np.int32)
+        if self.lib.getPhysicsBatchPushes(_p(out)) < 0:
+            raise PhysicsError("getPhysicsBatchPushes failed")
+        return out
+
+    @property
+    def world(self):
+        """The batch's world as a World (not owned: closing it leaves the world alive)."""
+        return _BorrowedWorld(self.lib.getPhysicsBatchWorld())

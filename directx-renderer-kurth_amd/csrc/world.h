@@ -245,6 +245,16 @@ struct World
 	double sumContacts = 0, sumManifolds = 0, sumColors = 0, sumPairs = 0, sumProbes = 0; u32 sumSteps = 0, countedStep = 0, prevNumPairs = 0;
 	void countPreviousStep(); void refreshCounters();
 	u32 jointVersion = 0;                 // bumped by every upload of the joints
+	// Device-written joint PODs (mi_joint_device_pods): once a caller has the device array, JointSet::dPods is authoritative and
+	// every host entry point that reads or changes JointSet::pods pulls it back first (pullJointPods).  jointGeneration changes
+	// with every joint add / delete / set: the caller's pointer and slots are stale from then on.
+	bool jointPodsOnDevice = false;
+	u32 jointGeneration = 0;
+	void pullJointPods();
+	void jointsChanged();                 // jointsDirty + a new jointGeneration
+	// mi_test_physics_interaction_batch: colliders of every body (CSR), hull triangles as global vertex indices; rebuilt after upload()
+	DevBuf<u32> bodyColStart, bodyColList; DevBuf<uint4> hullTris; DevBuf<uint2> hullTriRange; bool interactTablesValid = false;
+	void buildInteractTables();
 
 	World(int dev);
 	~World();
@@ -290,6 +300,7 @@ void launch_slab_pack(World& w, void* left, void* right, u32 capacity);
 void launch_slab_unpack(World& w, const void* left, const void* right, u32 capacity);
 void launch_validate(World& w, u32 stage, u32 numPairs); // stage 0: world colliders + AABBs, 1: contacts, 2: body update records, 3: poses + velocities after the step
 void launch_copy_pose0(World& w);
+void launch_interaction_batch(World& w, u32 numRays, u32 firstBody, u32 bodiesPerRay, const float* dRays, int32_t* dOutBody); // k_interact.hip
 void launch_lerp_pose(World& w, float t);
 void csort_pairs_u32(World& w, const u32* keys, u32* keysOut, const u32* vals, u32* valsOut, u32 n, u32 numBuckets); // stable, keys < numBuckets <= 272
 void csort_pairs_u64(World& w, const u32* keys, u32* keysOut, const u64* vals, u64* valsOut, u32 n, u32 numBuckets);

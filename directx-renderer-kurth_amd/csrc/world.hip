@@ -3,11 +3,13 @@
 // previous step's physics_transform1 -> broadphase -> narrowphase -> gravity/force integration -> constraint init (with
 // post-gravity velocities) -> N solver iterations (joints by type, then contacts) -> velocity integration.
 #include "world.h"
+#include "ray_tests.h"
 #include <cstdio>
 #include <cstring>
 #include <cmath>
 #include <algorithm>
 #include <map>
+#include <atomic>
 
 static thread_local std::string g_createError;
 static thread_local World* g_currentWorld = nullptr;
@@ -77,6 +79,7 @@ World::~World()
 	colLocal.release(); colWorld.release(); pairs.release(); pairsSorted.release(); manifolds.release(); bodyMask.release(); claim.release();
 	rowLambda.release(); rowIds.release(); tempStorage.release(); actIds.release(); epaList.release(); gjkSimplex.release(); pairSlab.release(); simMask.release();
 	for (auto& js : joints) { js.dPods.release(); js.dPairs.release(); js.dUpdate.release(); }
+	bodyColStart.release(); bodyColList.release(); hullTris.release(); hullTriRange.release();
 	for (auto& e : stageEvents) if (e) (void)hipEventDestroy(e);
 	if (countersEvent) (void)hipEventDestroy(countersEvent);
 	if (hCounters) (void)hipHostFree(hCounters);
@@ -279,6 +282,8 @@ void World::downloadState()
 void World::upload()
 {
 	if (!topologyDirty) return;
+	pullJointPods();            // device-written motors survive the joint re-upload this forces
+	interactTablesValid = false;
 	if (stateOnDevice) downloadState(); // bodies added mid-simulation: pull the live state first
 	u32 newNb = (u32)bodies.size(), newNc = (u32)colliders.size();
 	std::vector<float4> hp(2 * (size_t)newNb), hv(2 * ((size_t)newNb + 1)), hprops(5 * (size_t)newNb), hf(2 * (size_t)newNb);
@@ -371,7 +376,28 @@ void World::upload()
 	activeDirty = true; estActiveBodies = nb; estActiveCols = nc; // (the lists are rebuilt at the next step; until the host has seen their lengths the launches are sized for everything)
 	MI_CHECK(hipStreamSynchronize(stream));
 	topologyDirty = false; stateOnDevice = true;
-	jointsDirty = true; // the static dummy index (= nb) moved
+	jointsChanged(); // the static dummy index (= nb) moved
+}
+
+// Joint generations are drawn from one counter for all worlds, so a restored world never repeats a generation of its source.
+static std::atomic<u32> g_jointGeneration{ 0 };
+void World::jointsChanged() { jointsDirty = true; jointGeneration = ++g_jointGeneration; }
+
+// Device copy -> host copy of every joint POD (mi_joint_device_pods).  Nothing to do while the joints are dirty: the last pull
+// happened when they became dirty, and the host copy has changed since.
+void World::pullJointPods()
+{
+	if (!jointPodsOnDevice || jointsDirty) return;
+	for (u32 t = 0; t < MI_JOINT_TYPES; ++t)
+	{
+		JointSet& js = joints[t];
+		const u32 m = (u32)js.order.size(), podSize = MI_JOINT_POD_SIZE[t];
+		if (!m || !js.dPods.p) continue;
+		std::vector<uint8_t> hp((size_t)m * podSize);
+		MI_CHECK(hipMemcpyAsync(hp.data(), js.dPods.p, hp.size(), hipMemcpyDeviceToHost, stream));
+		MI_CHECK(hipStreamSynchronize(stream));
+		for (u32 slot = 0; slot < m; ++slot) memcpy(js.pods.data() + (size_t)js.order[slot] * podSize, hp.data() + (size_t)slot * podSize, podSize);
+	}
 }
 
 // Greedy colouring of each joint type on the host (joints change rarely): joint i gets the lowest colour free at both bodies.
@@ -1121,6 +1147,7 @@ namespace
 	void serialize(World& w, BlobWriter& out)
 	{
 		w.forceFullColoring = true; // the image has no colour history: this world and the restored one both colour from scratch next step
+		w.pullJointPods();
 		w.upload();
 		if (w.stateOnDevice) w.downloadState();
 		out.pod(SNAPSHOT_MAGIC); out.pod(SNAPSHOT_VERSION);
@@ -1280,7 +1307,7 @@ mi_world* mi_world_restore(const mi_world_desc* desc, const void* buffer, uint64
 	}
 	w.clothsDirty = true;
 	w.collisionBeginEvents = (flags & 1u) != 0; w.collisionEndEvents = (flags & 2u) != 0;
-	w.topologyDirty = true; w.jointsDirty = true; w.fieldsDirty = true;
+	w.topologyDirty = true; w.jointsChanged(); w.fieldsDirty = true;
 	w.restoredTriggerKeys = triggerKeys; w.restoredCollisionKeys = collisionKeys; // entered into the sets when the first step sizes them
 	return world;
 }
@@ -1659,11 +1686,12 @@ static uint32_t pushJoint(World* w, u32 type, u32 a, u32 b, const void* pod)
 		w->fail(MI_ERR_INVALID_ARGUMENT, "constraint: body out of range or deleted");
 		return 0xFFFFFFFFu;
 	}
+	w->pullJointPods();
 	JointSet& js = w->joints[type];
 	u32 sz = MI_JOINT_POD_SIZE[type];
 	js.pods.insert(js.pods.end(), (const uint8_t*)pod, (const uint8_t*)pod + sz);
 	js.a.push_back(a); js.b.push_back(b); js.alive.push_back(1);
-	w->jointsDirty = true;
+	w->jointsChanged();
 	return js.count() - 1;
 }
 
@@ -1759,6 +1787,7 @@ int mi_constraint_get(mi_world* world, uint32_t type, uint32_t id, void* pod)
 {
 	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
 	if (type >= MI_JOINT_TYPES || id >= W->joints[type].count() || !W->joints[type].alive[id]) return MI_ERR_INVALID_ARGUMENT;
+	W->pullJointPods();
 	memcpy(pod, W->joints[type].pods.data() + (size_t)id * MI_JOINT_POD_SIZE[type], MI_JOINT_POD_SIZE[type]);
 	return MI_OK;
 }
@@ -1766,22 +1795,25 @@ int mi_constraint_set(mi_world* world, uint32_t type, uint32_t id, const void* p
 {
 	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
 	if (type >= MI_JOINT_TYPES || id >= W->joints[type].count() || !W->joints[type].alive[id]) return MI_ERR_INVALID_ARGUMENT;
+	W->pullJointPods();
 	memcpy(W->joints[type].pods.data() + (size_t)id * MI_JOINT_POD_SIZE[type], pod, MI_JOINT_POD_SIZE[type]);
-	W->jointsDirty = true;
+	W->jointsChanged();
 	return MI_OK;
 }
 int mi_delete_constraint(mi_world* world, uint32_t type, uint32_t id)
 {
 	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
 	if (type >= MI_JOINT_TYPES || id >= W->joints[type].count() || !W->joints[type].alive[id]) return MI_ERR_INVALID_ARGUMENT;
-	W->joints[type].alive[id] = 0; W->jointsDirty = true;
+	W->pullJointPods();
+	W->joints[type].alive[id] = 0; W->jointsChanged();
 	return MI_OK;
 }
 int mi_delete_all_constraints(mi_world* world)
 {
 	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	W->pullJointPods();
 	for (auto& js : W->joints) { std::fill(js.alive.begin(), js.alive.end(), 0); js.order.clear(); js.colorStart.clear(); }
-	W->jointsDirty = true;
+	W->jointsChanged();
 	return MI_OK;
 }
 
@@ -1790,9 +1822,10 @@ int mi_delete_all_constraints_from_body(mi_world* world, uint32_t body)
 {
 	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
 	if (body >= W->bodies.size()) return MI_ERR_INVALID_ARGUMENT;
+	W->pullJointPods();
 	for (auto& js : W->joints)
 		for (u32 i = 0; i < js.count(); ++i)
-			if (js.alive[i] && (js.a[i] == body || js.b[i] == body)) { js.alive[i] = 0; W->jointsDirty = true; }
+			if (js.alive[i] && (js.a[i] == body || js.b[i] == body)) { js.alive[i] = 0; W->jointsChanged(); }
 	return MI_OK;
 }
 
@@ -1827,101 +1860,38 @@ int mi_delete_body(mi_world* world, uint32_t body)
 }
 
 // ---- testPhysicsInteraction (physics.h:404, physics.cpp:556-628): ray vs every collider of every rigid body, in the body's frame;
-// the closest hit gets force = direction * strength at the hit point.  Host code, like the reference's (an editor interaction).
-// Ray tests: bounding_volumes.cpp:197-394, 677-705; pointInTriangle: math.cpp:1273-1290.
-struct HRay { V3 origin, direction; };
-static bool rayPlane(const HRay& r, V3 normal, float d, float& outT)
+// the closest hit gets force = direction * strength at the hit point.  Host code, like the reference's (an editor interaction); the
+// ray tests live in ray_tests.h, shared with the batched kernel of mi_test_physics_interaction_batch (k_interact.hip).
+// Tables of the batched ray test: every body's colliders (CSR over HBody::colliders) and the hull triangles as indices into hullVerts
+// (the vertex pool upload() builds, in the same order).
+void World::buildInteractTables()
 {
-	float ndotd = dot(r.direction, normal);
-	if (fabsf(ndotd) < 1e-6f) return false;
-	outT = -(dot(r.origin, normal) + d) / ndotd;
-	return true;
-}
-static bool rayAABB(const HRay& r, V3 lo, V3 hi, float& outT)
-{
-	V3 invDir = v3(1.f / r.direction.x, 1.f / r.direction.y, 1.f / r.direction.z);
-	float tx1 = (lo.x - r.origin.x) * invDir.x, tx2 = (hi.x - r.origin.x) * invDir.x;
-	outT = fminf(tx1, tx2);
-	float tmax = fmaxf(tx1, tx2);
-	float ty1 = (lo.y - r.origin.y) * invDir.y, ty2 = (hi.y - r.origin.y) * invDir.y;
-	outT = fmaxf(outT, fminf(ty1, ty2)); tmax = fminf(tmax, fmaxf(ty1, ty2));
-	float tz1 = (lo.z - r.origin.z) * invDir.z, tz2 = (hi.z - r.origin.z) * invDir.z;
-	outT = fmaxf(outT, fminf(tz1, tz2)); tmax = fminf(tmax, fmaxf(tz1, tz2));
-	return tmax >= outT && outT > 0.f;
-}
-static bool raySphere(const HRay& r, V3 center, float radius, float& outT)
-{
-	V3 m = r.origin - center;
-	float b = dot(m, r.direction), c = dot(m, m) - radius * radius;
-	if (c > 0.f && b > 0.f) return false;
-	float discr = b * b - c;
-	if (discr < 0.f) return false;
-	outT = -b - sqrtf(discr);
-	if (outT < 0.f) outT = 0.f;
-	return true;
-}
-static bool rayDisk(const HRay& r, V3 pos, V3 normal, float radius, float& outT)
-{
-	if (rayPlane(r, normal, -dot(normal, pos), outT)) return length(r.origin + outT * r.direction - pos) <= radius;
-	return false;
-}
-static bool rayCylinder(const HRay& r, V3 pa, V3 pb, float radius, float& outT)
-{
-	V3 axis = pb - pa;
-	float height = length(axis);
-	Q4 q = rotateFromTo(axis, v3(0.f, 1.f, 0.f));
-	V3 o = q * (r.origin - pa), d = q * r.direction;
-	const float epsilon = 1e-6f;
-	float y = -1.f;
-	if (o.x * o.x + o.z * o.z > radius * radius)
+	std::vector<u32> start(1, 0u), list;
+	for (const HBody& b : bodies) { list.insert(list.end(), b.colliders.begin(), b.colliders.end()); start.push_back((u32)list.size()); }
+	std::vector<uint4> tris; std::vector<uint2> range;
+	u32 firstVertex = 0;
+	for (const HHull& g : hulls)
 	{
-		float a = d.x * d.x + d.z * d.z, b = d.x * o.x + d.z * o.z, c = o.x * o.x + o.z * o.z - radius * radius;
-		float delta = b * b - a * c;
-		if (delta < epsilon) return false;
-		outT = (-b - sqrtf(delta)) / a;
-		if (outT <= epsilon) return false;
-		y = o.y + outT * d.y;
+		range.push_back(make_uint2((u32)tris.size(), (u32)(g.triangles.size() / 3)));
+		for (size_t f = 0; f + 2 < g.triangles.size(); f += 3) tris.push_back(make_uint4(firstVertex + g.triangles[f], firstVertex + g.triangles[f + 1], firstVertex + g.triangles[f + 2], 0u));
+		firstVertex += (u32)(g.vertices.size() / 3);
 	}
-	if (y > height + epsilon || y < -epsilon)
-	{
-		HRay lr{ o, d };
-		float dist;
-		if (d.y < 0.f && rayDisk(lr, v3(0.f, height, 0.f), v3(0.f, 1.f, 0.f), radius, dist)) outT = dist;
-		if (d.y > 0.f && rayDisk(lr, v3(0.f, 0.f, 0.f), v3(0.f, -1.f, 0.f), radius, dist)) outT = dist;
-		y = o.y + outT * d.y;
-	}
-	return y > -epsilon && y < height + epsilon;
+	bodyColStart.ensure(start.size(), stream); bodyColList.ensure(std::max<size_t>(list.size(), 1), stream);
+	hullTris.ensure(std::max<size_t>(tris.size(), 1), stream); hullTriRange.ensure(std::max<size_t>(range.size(), 1), stream);
+	MI_CHECK(hipMemcpyAsync(bodyColStart.p, start.data(), sizeof(u32) * start.size(), hipMemcpyHostToDevice, stream));
+	if (!list.empty()) MI_CHECK(hipMemcpyAsync(bodyColList.p, list.data(), sizeof(u32) * list.size(), hipMemcpyHostToDevice, stream));
+	if (!tris.empty()) MI_CHECK(hipMemcpyAsync(hullTris.p, tris.data(), sizeof(uint4) * tris.size(), hipMemcpyHostToDevice, stream));
+	if (!range.empty()) MI_CHECK(hipMemcpyAsync(hullTriRange.p, range.data(), sizeof(uint2) * range.size(), hipMemcpyHostToDevice, stream));
+	MI_CHECK(hipStreamSynchronize(stream));
+	interactTablesValid = true;
 }
-static bool rayCapsule(const HRay& r, V3 pa, V3 pb, float radius, float& outT)
+
+struct HostHulls
 {
-	outT = MI_FLT_MAX;
-	float t; bool result = false;
-	if (rayCylinder(r, pa, pb, radius, t)) { outT = t; result = true; }
-	if (raySphere(r, pa, radius, t)) { outT = fminf(outT, t); result = true; }
-	if (raySphere(r, pb, radius, t)) { outT = fminf(outT, t); result = true; }
-	return result;
-}
-static bool pointInTriangleH(V3 point, V3 a, V3 b, V3 c)
-{
-	V3 e10 = b - a, e20 = c - a;
-	float aa = dot(e10, e10), bb = dot(e10, e20), cc = dot(e20, e20);
-	float ac_bb = (aa * cc) - (bb * bb);
-	V3 vp = point - a;
-	float d = dot(vp, e10), e = dot(vp, e20);
-	float x = (d * cc) - (e * bb), y = (e * aa) - (d * bb), z = x + y - ac_bb;
-	u32 ux, uy, uz; memcpy(&ux, &x, 4); memcpy(&uy, &y, 4); memcpy(&uz, &z, 4);
-	return ((uz & ~(ux | uy)) & 0x80000000u) != 0;
-}
-static bool rayTriangle(const HRay& r, V3 a, V3 b, V3 c, float& outT)
-{
-	V3 normal = noz(cross(b - a, c - a));
-	float d = -dot(normal, a);
-	float nDotR = dot(r.direction, normal);
-	if (fabsf(nDotR) <= 1e-6f) return false;
-	outT = -(dot(r.origin, normal) + d) / nDotR;
-	V3 q = r.origin + outT * r.direction;
-	return outT >= 0.f && pointInTriangleH(q, a, b, c);
-}
+	const std::vector<World::HHull>& hulls;
+	u32 numTriangles(u32 g) const { return (u32)(hulls[g].triangles.size() / 3); }
+	V3 vertex(u32 g, u32 f, u32 k) const { const World::HHull& h = hulls[g]; const float* p = &h.vertices[3 * h.triangles[3 * f + k]]; return v3(p[0], p[1], p[2]); }
+};
 
 int mi_test_physics_interaction(mi_world* world, const float origin[3], const float direction[3], float strength)
 {
@@ -1930,50 +1900,18 @@ int mi_test_physics_interaction(mi_world* world, const float origin[3], const fl
 	if (W->stateOnDevice) W->downloadState(); // physics_transform1 of every body
 	HRay r{ v3(origin[0], origin[1], origin[2]), v3(direction[0], direction[1], direction[2]) };
 	float minT = MI_FLT_MAX; int minBody = -1; V3 force = v3s(0.f), torque = v3s(0.f);
+	const HostHulls hulls{ W->hulls };
 	for (const World::HCollider& c : W->colliders)
 	{
 		if (c.body == MI_STATIC_BODY || W->bodies[c.body].removed) continue;
 		const World::HBody& rb = W->bodies[c.body];
 		Q4 rot = q4(rb.rot[0], rb.rot[1], rb.rot[2], rb.rot[3]); V3 pos = v3(rb.pos[0], rb.pos[1], rb.pos[2]);
-		HRay lr{ conjugate(rot) * (r.origin - pos), conjugate(rot) * r.direction };
-		const float* s = c.shape;
-		float t = 0.f; bool hit = false;
-		switch (c.type)
-		{
-			case MI_SPHERE: hit = raySphere(lr, v3(s[0], s[1], s[2]), s[3], t); break;
-			case MI_CAPSULE: hit = rayCapsule(lr, v3(s[0], s[1], s[2]), v3(s[3], s[4], s[5]), s[6], t); break;
-			case MI_CYLINDER: hit = rayCylinder(lr, v3(s[0], s[1], s[2]), v3(s[3], s[4], s[5]), s[6], t); break;
-			case MI_AABB: hit = rayAABB(lr, v3(s[0], s[1], s[2]), v3(s[3], s[4], s[5]), t); break;
-			case MI_OBB:
-			{
-				Q4 q = q4(s[0], s[1], s[2], s[3]); V3 ce = v3(s[4], s[5], s[6]), ra = v3(s[7], s[8], s[9]);
-				HRay br{ conjugate(q) * (lr.origin - ce), conjugate(q) * lr.direction };
-				hit = rayAABB(br, v3s(0.f) - ra, ra, t);
-			} break;
-			case MI_HULL:
-			{
-				Q4 q = q4(s[0], s[1], s[2], s[3]); V3 hp = v3(s[4], s[5], s[6]);
-				const World::HHull& g = W->hulls[(u32)s[7]];
-				HRay hr{ conjugate(q) * (lr.origin - hp), conjugate(q) * lr.direction };
-				float best = MI_FLT_MAX;
-				for (size_t f = 0; f + 2 < g.triangles.size(); f += 3)
-				{
-					const float* pa = &g.vertices[3 * g.triangles[f]]; const float* pb = &g.vertices[3 * g.triangles[f + 1]]; const float* pc = &g.vertices[3 * g.triangles[f + 2]];
-					float tt;
-					if (rayTriangle(hr, v3(pa[0], pa[1], pa[2]), v3(pb[0], pb[1], pb[2]), v3(pc[0], pc[1], pc[2]), tt) && tt < best) { best = tt; hit = true; }
-				}
-				t = best;
-			} break;
-			default: break;
-		}
+		HRay lr; float t;
+		bool hit = rayBodyCollider(r, rot, pos, c.type, c.shape, hulls, lr, t);
 		if (hit && t < minT)
 		{
 			minT = t; minBody = (int)c.body;
-			V3 localHit = lr.origin + t * lr.direction;
-			V3 globalHit = rot * localHit + pos;                                   // transformPosition (scale 1)
-			V3 cogPosition = pos + rot * v3(rb.localCOG[0], rb.localCOG[1], rb.localCOG[2]); // getGlobalCOGPosition (rigid_body.cpp:83-87)
-			force = r.direction * strength;
-			torque = cross(globalHit - cogPosition, force);
+			interactionPush(r, lr, t, rot, pos, v3(rb.localCOG[0], rb.localCOG[1], rb.localCOG[2]), strength, force, torque);
 		}
 	}
 	if (minBody < 0) return 0;
@@ -2158,6 +2096,52 @@ int mi_device_pointers(mi_world* world, void** pose, void** vel, void** stream)
 	W->resolvePendingFlow();
 	W->upload();
 	if (pose) *pose = W->pose.p; if (vel) *vel = W->vel.p; if (stream) *stream = (void*)W->stream;
+	return W->lastError;
+}
+
+int mi_device_state(mi_world* world, struct mi_device_state* out)
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	if (!out) return MI_ERR_INVALID_ARGUMENT;
+	W->resolvePendingFlow();
+	W->upload();
+	out->pose = W->pose.p; out->pose0 = W->pose0.p; out->poseLerp = W->poseLerp.p; out->vel = W->vel.p; out->force = W->force.p;
+	out->stream = (void*)W->stream; out->numBodies = W->nb; out->reserved = 0;
+	return W->lastError;
+}
+
+int mi_joint_device_pods(mi_world* world, uint32_t type, void** dPods, uint32_t* outSlotOfId, uint32_t numIds, uint32_t* outGeneration)
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	if (type >= MI_JOINT_TYPES) return MI_ERR_INVALID_ARGUMENT;
+	W->resolvePendingFlow();
+	W->upload(); W->uploadJoints();
+	if (W->lastError) return W->lastError;
+	W->jointPodsOnDevice = true;
+	const JointSet& js = W->joints[type];
+	if (dPods) *dPods = js.order.empty() ? nullptr : js.dPods.p;
+	if (outSlotOfId)
+	{
+		for (u32 i = 0; i < numIds; ++i) outSlotOfId[i] = 0xFFFFFFFFu;
+		for (u32 slot = 0; slot < (u32)js.order.size(); ++slot) if (js.order[slot] < numIds) outSlotOfId[js.order[slot]] = slot;
+	}
+	if (outGeneration) *outGeneration = W->jointGeneration;
+	return MI_OK;
+}
+
+int mi_test_physics_interaction_batch(mi_world* world, uint32_t numRays, uint32_t firstBody, uint32_t bodiesPerRay, const float* dRays, int32_t* dOutBody)
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	W->resolvePendingFlow();
+	W->upload();
+	if (!numRays) return W->lastError;
+	if (!dRays || !dOutBody || (uint64_t)firstBody + (uint64_t)numRays * bodiesPerRay > W->nb)
+	{
+		W->fail(MI_ERR_INVALID_ARGUMENT, "mi_test_physics_interaction_batch: body range outside the world");
+		return MI_ERR_INVALID_ARGUMENT;
+	}
+	if (!W->interactTablesValid) W->buildInteractTables();
+	launch_interaction_batch(*W, numRays, firstBody, bodiesPerRay, dRays, dOutBody);
 	return W->lastError;
 }
 

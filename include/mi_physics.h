@@ -229,6 +229,29 @@ uint32_t mi_num_colliders(mi_world* w);
  * {v.xyz, invMass},{w.xyz,0}.  The caller may read/write them on `stream` between steps (ghost-body refresh). */
 int mi_device_pointers(mi_world* w, void** pose, void** vel, void** stream);
 
+/* Device state for callers that drive many bodies from kernels of their own (batched environments, libmi_locomotion.so).  Resolves a
+ * pending step first, as mi_device_pointers does.  Pointers stay valid until the next add call.  Layouts: pose, pose0 (the pose at the
+ * start of the last mi_step), poseLerp (the interpolated pose mi_read_transforms reads with which = 0): 2 x float4 per body
+ * {pos.xyz,0},{quat}; vel: {v.xyz, invMass},{w.xyz,0}; force: {force.xyz,0},{torque.xyz,0}.  Between steps, on `stream`, a caller may
+ *   - add to force: the next step integrates the accumulators and clears them;
+ *   - write vel.xyz: vel[2i].w holds invMass and must be kept;
+ *   - teleport a body: write the same pose into pose, pose0 and poseLerp, as mi_set_transform does. */
+struct mi_device_state { void* pose; void* pose0; void* poseLerp; void* vel; void* force; void* stream; uint32_t numBodies, reserved; }; /* the tag names it: the function has its name */
+int mi_device_state(mi_world* w, struct mi_device_state* out);
+
+/* The device POD array of one joint type (the POD layout of mi_constraint_get, in solve order) and the slot of every joint id
+ * 0 .. numIds-1 in it (0xFFFFFFFF: deleted).  Motor fields written into it on the world's stream between steps take effect at the
+ * next step.  From the first call on, the device copy is authoritative: mi_constraint_get / _set, the add and delete calls and
+ * mi_snapshot_save pull it back first.  The pointer and the slots hold until *outGeneration changes: any joint add, delete or set
+ * and a restore give a new generation.  outSlotOfId may be NULL. */
+int mi_joint_device_pods(mi_world* w, uint32_t type, void** dPods, uint32_t* outSlotOfId, uint32_t numIds, uint32_t* outGeneration);
+
+/* mi_test_physics_interaction for many rays as one kernel on the world's stream, with no host synchronisation.  dRays (device):
+ * 8 floats per ray {origin.xyz, strength, direction.xyz, enabled}; ray i only tests the colliders of the bodies
+ * [firstBody + i * bodiesPerRay, firstBody + (i + 1) * bodiesPerRay), so rays never share a body.  The closest hit gets the force
+ * and torque of mi_test_physics_interaction, added to the accumulators.  dOutBody[i] (device) = 1 + the pushed body, or 0. */
+int mi_test_physics_interaction_batch(mi_world* w, uint32_t numRays, uint32_t firstBody, uint32_t bodiesPerRay, const float* dRays, int32_t* dOutBody);
+
 /* Spatial-slab runs (one world per GPU holding ALL bodies, each simulating its slab + ghosts): copy the whole pose / velocity arrays
  * (layout as mi_device_pointers) to / from caller-owned DEVICE buffers, and set the per-body simulate mask (1 byte per body, device
  * memory; 0 = body lives on another GPU: no AABB, no integration).  The halo exchange itself (RCCL send/recv of boundary bodies) is
