@@ -94,7 +94,9 @@ def build(force=False):
 LOCOMOTION_LIB_PATH = os.path.join(_HERE, "libmi_locomotion.so")
 LOCOMOTION_SYMBOLS = ["getPhysicsStateSize", "getPhysicsActionSize", "getPhysicsRanges", "resetPhysics", "updatePhysics", "setPhysicsSeed",
                       "resetPhysicsBatch", "updatePhysicsBatch", "updatePhysicsBatchDevice", "resetPhysicsBatchEnvs", "observePhysicsBatch",
-                      "getPhysicsBatchWorld", "getPhysicsBatchStream", "getPhysicsBatchPushes"]
+                      "getPhysicsBatchWorld", "getPhysicsBatchStream", "getPhysicsBatchPushes",
+                      "setPhysicsPolicy", "inferPhysicsPolicy", "updatePhysicsPolicy", "inferPhysicsBatchDevice", "updatePhysicsBatchPolicy",
+                      "updatePhysicsBatchPolicyDevice", "rolloutPhysicsBatchDevice"]
 _HIPCC = "/opt/rocm/bin/hipcc"
 
 
@@ -104,11 +106,11 @@ def build_locomotion():
     host = os.path.join(_HERE, "host")
     include = "-I" + os.path.join(os.path.dirname(_HERE), "include")
     cpp, hip = os.path.join(host, "locomotion_env.cpp"), os.path.join(host, "locomotion_batch.hip")
-    deps = [cpp, hip, os.path.join(host, "locomotion_shared.h"), os.path.join(os.path.dirname(_HERE), "include", "mi_physics.h"), _LIB_PATH]
+    deps = [cpp, hip, os.path.join(host, "locomotion_shared.h"), os.path.join(host, "locomotion_policy.h"), os.path.join(os.path.dirname(_HERE), "include", "mi_physics.h"), _LIB_PATH]
     if os.path.exists(LOCOMOTION_LIB_PATH) and os.path.getmtime(LOCOMOTION_LIB_PATH) >= max(os.path.getmtime(p) for p in deps):
         return LOCOMOTION_LIB_PATH
     cpp_o, hip_o = os.path.join(host, "locomotion_env.o"), os.path.join(host, "locomotion_batch.o")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-Wall", include, "-c", cpp, "-o", cpp_o])
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-ffp-contract=off", "-Wall", include, "-c", cpp, "-o", cpp_o])
     subprocess.check_call([_HIPCC, "-std=c++17", "-O3", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", "-Wall", include, "-c", hip, "-o", hip_o])
     subprocess.check_call([_HIPCC, "-shared", "-fPIC", "--offload-arch=gfx950", cpp_o, hip_o, "-L" + _HERE, "-lmi_physics", "-Wl,-rpath,$ORIGIN",
                            "-o", LOCOMOTION_LIB_PATH])
@@ -529,6 +531,70 @@ class _BorrowedWorld(World):
         self.w = None
 
 
+POLICY_NAMES = ("mlp_extractor.policy_net.0.weight", "mlp_extractor.policy_net.0.bias", "mlp_extractor.policy_net.2.weight",
+                "mlp_extractor.policy_net.2.bias", "action_net.weight", "action_net.bias")
+_locomotion_lib = None
+_policy_hidden = 0  # H of the policy the library holds (it holds one, for the single environment and the batch)
+
+
+def _load_locomotion():
+    global _locomotion_lib
+    if _locomotion_lib is None:
+        build_locomotion()
+        lib = C.CDLL(LOCOMOTION_LIB_PATH)
+        lib.setPhysicsSeed.argtypes = [C.c_ulonglong]
+        lib.getPhysicsBatchWorld.restype = C.c_void_p
+        lib.getPhysicsBatchStream.restype = C.c_void_p
+        _locomotion_lib = lib
+    return _locomotion_lib
+
+
+def _policy_arrays(args):
+    """The six arrays W1 [H, 66], b1 [H], W2 [H, H], b2 [H], W3 [27, H], b3 [27] as contiguous float32, shapes checked; `args` is the
+    six of them, or one mapping with the stable-baselines names (POLICY_NAMES) whose values are arrays or tensors."""
+    if len(args) == 1 and hasattr(args[0], "keys"):
+        args = [args[0][k] for k in POLICY_NAMES]
+    if len(args) != 6:
+        raise ValueError("a policy is six arrays: w1, b1, w2, b2, w3, b3")
+    arrays = [np.ascontiguousarray(a.detach().cpu().numpy() if hasattr(a, "detach") else a, dtype=np.float32) for a in args]
+    h = arrays[1].size
+    shapes = [(h, 66), (h,), (h, h), (h,), (27, h), (27,)]
+    for a, shape in zip(arrays, shapes):
+        if a.shape != shape:
+            raise ValueError("policy array of shape %s where %s is expected" % (a.shape, shape))
+    return h, arrays
+
+
+def set_policy(*args):
+    """setPhysicsPolicy: the 66 -> H -> H -> 27 tanh network of the learned controller, for the single environment and the batch."""
+    global _policy_hidden
+    h, arrays = _policy_arrays(args)
+    code = _load_locomotion().setPhysicsPolicy(C.c_uint32(h), *[_p(a) for a in arrays])
+    if code:
+        raise PhysicsError("setPhysicsPolicy failed (%d)" % code)
+    _policy_hidden = h
+
+
+def infer_policy(state, hidden=False):
+    """inferPhysicsPolicy: the network on one state [66], on the host.  Returns the action [27], with hidden also (tanh(z1), tanh(z2))."""
+    state = np.ascontiguousarray(state, np.float32).reshape(66)
+    action = np.zeros(27, np.float32)
+    ab = np.zeros(2 * max(_policy_hidden, 1), np.float32)
+    code = _load_locomotion().inferPhysicsPolicy(_p(state), _p(action), _p(ab) if hidden else None)
+    if code:
+        raise PhysicsError("inferPhysicsPolicy failed (%d)" % code)
+    return (action, ab[:_policy_hidden], ab[_policy_hidden:]) if hidden else action
+
+
+def update_policy():
+    """updatePhysicsPolicy: one closed-loop update of the single environment.  Returns (state [66], reward, fallen)."""
+    state = np.zeros(66, np.float32); reward = C.c_float(0.0)
+    code = _load_locomotion().updatePhysicsPolicy(_p(state), C.byref(reward))
+    if code < 0:
+        raise PhysicsError("updatePhysicsPolicy failed (%d)" % code)
+    return state, reward.value, bool(code)
+
+
 class LocomotionBatch:
     """N ragdoll environments of libmi_locomotion.so stepped together in one world (host/locomotion_batch.hip).  One instance per
     process: the library holds one batch, as it holds one single environment.  step() takes a [n, 27] numpy array, or a ROCm torch
@@ -536,11 +602,7 @@ class LocomotionBatch:
     torch before the first World or LocomotionBatch: the process then runs one HIP runtime, the one torch loads."""
 
     def __init__(self, n, seed=None):
-        build_locomotion()
-        lib = C.CDLL(LOCOMOTION_LIB_PATH)
-        lib.setPhysicsSeed.argtypes = [C.c_ulonglong]
-        lib.getPhysicsBatchWorld.restype = C.c_void_p
-        lib.getPhysicsBatchStream.restype = C.c_void_p
+        lib = _load_locomotion()
         self.lib, self.n = lib, int(n)
         self.state_size, self.action_size = lib.getPhysicsStateSize(), lib.getPhysicsActionSize()
         if seed is not None:
@@ -574,15 +636,84 @@ class LocomotionBatch:
         dev = a.device
         states = torch.empty((self.n, self.state_size), dtype=torch.float32, device=dev)
         rewards = torch.empty(self.n, dtype=torch.float32, device=dev); fallen = torch.empty(self.n, dtype=torch.int32, device=dev)
-        ext = torch.cuda.ExternalStream(self.lib.getPhysicsBatchStream(), device=dev)
-        ext.wait_stream(torch.cuda.current_stream(dev))      # the actions are ready
-        with torch.cuda.stream(ext):
-            code = self.lib.updatePhysicsBatchDevice(C.c_void_p(a.data_ptr()), C.c_void_p(states.data_ptr()), C.c_void_p(rewards.data_ptr()), C.c_void_p(fallen.data_ptr()))
-            for t in (a, states, rewards, fallen):
-                t.record_stream(ext)
+        code = self._on_stream(dev, (a, states, rewards, fallen), lambda: self.lib.updatePhysicsBatchDevice(
+            C.c_void_p(a.data_ptr()), C.c_void_p(states.data_ptr()), C.c_void_p(rewards.data_ptr()), C.c_void_p(fallen.data_ptr())))
         self._check(code, "updatePhysicsBatchDevice")
-        torch.cuda.current_stream(dev).wait_stream(ext)      # the outputs are ready for the caller's stream
         return states, rewards, fallen
+
+    def _on_stream(self, dev, tensors, call):
+        """Runs `call` (which enqueues on the world's stream) between the two stream hand-overs of the tensor path."""
+        import torch
+        ext = torch.cuda.ExternalStream(self.lib.getPhysicsBatchStream(), device=dev)
+        ext.wait_stream(torch.cuda.current_stream(dev))      # the inputs are ready
+        with torch.cuda.stream(ext):
+            code = call()
+            for t in tensors:
+                t.record_stream(ext)
+        torch.cuda.current_stream(dev).wait_stream(ext)      # the outputs are ready for the caller's stream
+        return code
+
+    # ---- the learned controller (host/locomotion_policy.h, k_loco_policy) ----
+    def set_policy(self, *args):
+        """The controller's network: six arrays w1 [H, 66], b1, w2 [H, H], b2, w3 [27, H], b3, or one mapping with the stable-baselines
+        names (POLICY_NAMES).  Replaces the previous one; the library keeps it across reset()."""
+        set_policy(*args)
+
+    @property
+    def hidden(self):
+        return _policy_hidden
+
+    def act(self, states, hidden=False):
+        """The network on `states` [count, 66], any count, on the device, touching no environment: numpy in, numpy out; ROCm tensor in,
+        tensors out.  Returns the raw actions [count, 27]; with hidden=True (actions, a [count, H], b [count, H]), the two tanh vectors."""
+        import torch
+        if not self.hidden:
+            raise PhysicsError("act: no policy set")
+        on_device = hasattr(states, "is_cuda") and states.is_cuda
+        s = states.detach() if on_device else torch.from_numpy(np.ascontiguousarray(states, np.float32)).cuda()
+        s = s.to(torch.float32).contiguous().reshape(-1, self.state_size)
+        count, dev = s.shape[0], s.device
+        actions = torch.empty((count, self.action_size), dtype=torch.float32, device=dev)
+        ab = torch.empty((count, 2 * self.hidden), dtype=torch.float32, device=dev) if hidden else None
+        code = self._on_stream(dev, [t for t in (s, actions, ab) if t is not None], lambda: self.lib.inferPhysicsBatchDevice(
+            C.c_uint32(count), C.c_void_p(s.data_ptr()), C.c_void_p(actions.data_ptr()), C.c_void_p(ab.data_ptr()) if hidden else None))
+        self._check(code, "inferPhysicsBatchDevice")
+        out = (actions, ab[:, :self.hidden], ab[:, self.hidden:]) if hidden else (actions,)
+        if not on_device:
+            torch.cuda.synchronize(dev)
+            out = tuple(t.cpu().numpy() for t in out)
+        return out if hidden else out[0]
+
+    def step_policy(self, device=False):
+        """One closed-loop update: the policy on the current states, smoothing, motors, push, step.  Returns (states, rewards, fallen) as
+        numpy arrays; with device=True ROCm tensors (states, rewards, fallen, actions), actions being the raw network outputs, enqueued
+        without a host synchronisation."""
+        if not device:
+            states = np.zeros((self.n, self.state_size), np.float32); rewards = np.zeros(self.n, np.float32); fallen = np.zeros(self.n, np.int32)
+            self._check(self.lib.updatePhysicsBatchPolicy(_p(states), _p(rewards), _p(fallen)), "updatePhysicsBatchPolicy", count=True)
+            return states, rewards, fallen
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device())
+        states = torch.empty((self.n, self.state_size), dtype=torch.float32, device=dev); actions = torch.empty((self.n, self.action_size), dtype=torch.float32, device=dev)
+        rewards = torch.empty(self.n, dtype=torch.float32, device=dev); fallen = torch.empty(self.n, dtype=torch.int32, device=dev)
+        code = self._on_stream(dev, (states, rewards, fallen, actions), lambda: self.lib.updatePhysicsBatchPolicyDevice(
+            C.c_void_p(states.data_ptr()), C.c_void_p(rewards.data_ptr()), C.c_void_p(fallen.data_ptr()), C.c_void_p(actions.data_ptr())))
+        self._check(code, "updatePhysicsBatchPolicyDevice")
+        return states, rewards, fallen, actions
+
+    def rollout(self, steps, auto_reset=True):
+        """`steps` closed-loop updates enqueued back to back on the device.  Returns ROCm tensors (states [steps, n, 66], actions
+        [steps, n, 27], rewards [steps, n], fallen [steps, n] int32): row t holds the raw action taken at update t and the state, reward
+        and fallen after it.  With auto_reset every environment that has fallen after an update is reset on the device before the next
+        (its row keeps the terminal state; its random stream goes on)."""
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device())
+        states = torch.empty((steps, self.n, self.state_size), dtype=torch.float32, device=dev); actions = torch.empty((steps, self.n, self.action_size), dtype=torch.float32, device=dev)
+        rewards = torch.empty((steps, self.n), dtype=torch.float32, device=dev); fallen = torch.empty((steps, self.n), dtype=torch.int32, device=dev)
+        code = self._on_stream(dev, (states, actions, rewards, fallen), lambda: self.lib.rolloutPhysicsBatchDevice(
+            C.c_uint32(steps), C.c_int(1 if auto_reset else 0), C.c_void_p(states.data_ptr()), C.c_void_p(actions.data_ptr()), C.c_void_p(rewards.data_ptr()), C.c_void_p(fallen.data_ptr())))
+        self._check(code, "rolloutPhysicsBatchDevice")
+        return states, actions, rewards, fallen
 
     def reset_envs(self, ids, states=None):
         """Resets the listed environments; writes their rows of `states` ([n, 66], a new zero array if None) and returns it."""

@@ -7,16 +7,23 @@
 // Each environment restates the single one: the same builder, the same smoothing and motors, the same push draws from its own
 // xorshift64 (seed ^ e * 0x9E3779B97F4A7C15; env 0 draws what the single environment draws), the same step settings, the same
 // state and reward formulas (locomotion_shared.h), read from the interpolated pose as the single environment reads it.
+//
+// The controller (learned_locomotion::update, locomotion_policy.h) closes the loop on the device: k_loco_policy reads the current
+// states, runs the network, smooths and writes the motors, in place of k_loco_actions, so an update driven by the policy has the same
+// launches as one driven by given actions.  dStates always holds the state of every environment as it is now (what
+// observePhysicsBatch returns): every entry point that moves the environments refreshes it.  rolloutPhysicsBatchDevice enqueues
+// whole trajectories, with the fallen environments reset from their flags on the device.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <vector>
 
-#include "locomotion_shared.h"
+#include "locomotion_policy.h"
 
 namespace
 {
 	constexpr uint32_t NUM_MOTOR_JOINTS = NUM_CONE_TWIST + NUM_HINGE;
 	constexpr float GRID_PITCH = 8.f;
+	constexpr uint32_t POLICY_TILE = 4; // environments per workgroup of k_loco_policy, all four in the registers of every lane
 
 	// Per environment, fixed at resetPhysicsBatch: the spawn pose of every part (pose layout of the world: {pos, 0}, {quat}) and the
 	// training targets of resetTraining.
@@ -37,6 +44,8 @@ namespace
 		int32_t* dPushes = nullptr;   // n: 1 + pushed body, or 0
 		uint32_t* dSlots = nullptr;   // n x 13: POD slot of each env's 7 cone-twist, then 6 hinge joints
 		float* dActions = nullptr; float* dStates = nullptr; float* dRewards = nullptr; int32_t* dFallen = nullptr; uint32_t* dIds = nullptr;
+		float* dPolicy = nullptr;     // the policy, transposed to [in][out]: W1T, b1, W2T, b2, W3T, b3 back to back
+		uint32_t hidden = 0;          // 0: no policy uploaded
 		void* pods[2] = { nullptr, nullptr }; // cone-twist, hinge
 		uint32_t generation[2] = { ~0u, ~0u };
 	};
@@ -48,7 +57,7 @@ namespace
 	{
 		if (!b) return;
 		if (b->stream) (void)hipStreamSynchronize(b->stream);
-		void* bufs[] = { b->dInit, b->dSmoothed, b->dRng, b->dRays, b->dPushes, b->dSlots, b->dActions, b->dStates, b->dRewards, b->dFallen, b->dIds };
+		void* bufs[] = { b->dInit, b->dSmoothed, b->dRng, b->dRays, b->dPushes, b->dSlots, b->dActions, b->dStates, b->dRewards, b->dFallen, b->dIds, b->dPolicy };
 		for (void* p : bufs) if (p) (void)hipFree(p);
 		if (b->world) mi_world_destroy(b->world);
 		delete b;
@@ -82,6 +91,83 @@ namespace
 		writeMotors(e, smoothed, slots, conePods, hingePods);
 	}
 
+	// One layer of applyLayer for POLICY_TILE environments: lane = output unit, weights transposed to [in][out] (one coalesced line per
+	// input), the tile's inputs in LDS as [in][tile] (one broadcast read per input).  Per unit and environment the products are added
+	// in ascending input order, product rounded, then added (-ffp-contract=off), then the bias: the sums of applyLayer, bit for bit.
+	__device__ float4 policyLayer(const float* __restrict__ weightsT, const float* __restrict__ bias, uint32_t inputSize, uint32_t outputSize, const float4* from, uint32_t unit, bool activation)
+	{
+		float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
+		if (unit >= outputSize) return sum;
+		#pragma unroll 8
+		for (uint32_t x = 0; x < inputSize; ++x)
+		{
+			const float w = weightsT[(size_t)x * outputSize + unit];
+			const float4 f = from[x];
+			sum.x += w * f.x; sum.y += w * f.y; sum.z += w * f.z; sum.w += w * f.w;
+		}
+		const float b = bias[unit];
+		sum.x += b; sum.y += b; sum.z += b; sum.w += b;
+		if (activation) { sum.x = tanhf(sum.x); sum.y = tanhf(sum.y); sum.z = tanhf(sum.z); sum.w = tanhf(sum.w); }
+		return sum;
+	}
+	static_assert(POLICY_TILE == 4, "policyLayer carries the tile as one float4");
+
+	// Kernel P: learned_locomotion::update for a tile of POLICY_TILE environments per workgroup: states -> three layers -> raw action;
+	// with APPLY also smoothAction and the motor PODs, i.e. everything k_loco_actions does.  blockDim.x >= max(hidden, 64), a multiple
+	// of 64.  actionsOut (count x 27, raw network outputs) and hiddenOut (count x 2H: tanh(z1), tanh(z2)) may be null.
+	template <bool APPLY>
+	__global__ void __launch_bounds__(POLICY_MAX_HIDDEN) k_loco_policy(uint32_t count, uint32_t hidden, const float* __restrict__ states, const float* __restrict__ policy,
+		float* __restrict__ actionsOut, float* __restrict__ hiddenOut, float* __restrict__ smoothedAll, const uint32_t* __restrict__ slots, uint8_t* conePods, uint8_t* hingePods)
+	{
+		__shared__ float4 input[STATE_SIZE], hiddenA[POLICY_MAX_HIDDEN], hiddenB[POLICY_MAX_HIDDEN];
+		__shared__ float smoothed[POLICY_TILE][ACTION_SIZE];
+		const uint32_t first = blockIdx.x * POLICY_TILE, t = threadIdx.x;
+		const float* w1 = policy; const float* b1 = w1 + (size_t)STATE_SIZE * hidden;
+		const float* w2 = b1 + hidden; const float* b2 = w2 + (size_t)hidden * hidden;
+		const float* w3 = b2 + hidden; const float* b3 = w3 + (size_t)hidden * ACTION_SIZE;
+		for (uint32_t i = t; i < POLICY_TILE * STATE_SIZE; i += blockDim.x)
+		{
+			const uint32_t r = i / STATE_SIZE, x = i % STATE_SIZE;
+			((float*)input)[POLICY_TILE * x + r] = first + r < count ? states[(size_t)STATE_SIZE * (first + r) + x] : 0.f;
+		}
+		__syncthreads();
+		const float4 a = policyLayer(w1, b1, STATE_SIZE, hidden, input, t, true);
+		if (t < hidden) hiddenA[t] = a;
+		__syncthreads();
+		const float4 b = policyLayer(w2, b2, hidden, hidden, hiddenA, t, true);
+		if (t < hidden) hiddenB[t] = b;
+		__syncthreads();
+		const float4 out = policyLayer(w3, b3, hidden, ACTION_SIZE, hiddenB, t, false);
+		const float av[POLICY_TILE] = { a.x, a.y, a.z, a.w }, bv[POLICY_TILE] = { b.x, b.y, b.z, b.w }, ov[POLICY_TILE] = { out.x, out.y, out.z, out.w };
+		#pragma unroll
+		for (uint32_t r = 0; r < POLICY_TILE; ++r)
+		{
+			const uint32_t e = first + r;
+			if (e >= count) continue;
+			if (hiddenOut && t < hidden) { hiddenOut[(size_t)2 * hidden * e + t] = av[r]; hiddenOut[(size_t)2 * hidden * e + hidden + t] = bv[r]; }
+			if (t < ACTION_SIZE)
+			{
+				if (actionsOut) actionsOut[(size_t)ACTION_SIZE * e + t] = ov[r];
+				if (APPLY) // smoothAction, one element per lane
+				{
+					const float s = lerpf(smoothedAll[(size_t)ACTION_SIZE * e + t], ov[r], 0.1f);
+					smoothedAll[(size_t)ACTION_SIZE * e + t] = s; smoothed[r][t] = s;
+				}
+			}
+		}
+		if (APPLY) // writeMotors, one joint per lane
+		{
+			__syncthreads();
+			const uint32_t r = t / NUM_MOTOR_JOINTS, j = t % NUM_MOTOR_JOINTS, e = first + r;
+			if (r < POLICY_TILE && e < count)
+			{
+				if (j < NUM_CONE_TWIST) setConeTwistMotors(*(cone_twist_pod*)(conePods + (size_t)slots[NUM_MOTOR_JOINTS * e + j] * sizeof(cone_twist_pod)), smoothed[r], j);
+				else setHingeMotors(*(hinge_pod*)(hingePods + (size_t)slots[NUM_MOTOR_JOINTS * e + j] * sizeof(hinge_pod)), smoothed[r], j - NUM_CONE_TWIST);
+			}
+		}
+	}
+	static_assert(POLICY_TILE * NUM_MOTOR_JOINTS <= 64 && ACTION_SIZE <= 64, "one wave covers the tile's joints and actions");
+
 	// Kernel B: the random push of updatePhysics (:322-330), drawn in its order, as a ray for mi_test_physics_interaction_batch.
 	__global__ void __launch_bounds__(64) k_loco_push_rays(uint32_t n, uint64_t* __restrict__ rngAll, const float4* __restrict__ poseLerp, float4* __restrict__ rays)
 	{
@@ -104,12 +190,15 @@ namespace
 	}
 
 	// Kernel C: getState, hasFallen and getReward of every listed environment (all when ids is null), into row e of the outputs.
-	__global__ void __launch_bounds__(64) k_loco_gather(uint32_t count, const uint32_t* __restrict__ ids, const env_init* __restrict__ init, const float* __restrict__ smoothedAll,
-		const float4* __restrict__ poseLerp, const float4* __restrict__ vel, float* __restrict__ states, float* __restrict__ rewards, int32_t* __restrict__ fallen)
+	// With a mask only the environments whose mask word is set; mirror (may be null) receives a second copy of the state rows.
+	__global__ void __launch_bounds__(64) k_loco_gather(uint32_t count, const uint32_t* __restrict__ ids, const int32_t* __restrict__ mask, const env_init* __restrict__ init,
+		const float* __restrict__ smoothedAll, const float4* __restrict__ poseLerp, const float4* __restrict__ vel, float* __restrict__ states, float* __restrict__ mirror,
+		float* __restrict__ rewards, int32_t* __restrict__ fallen)
 	{
 		const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
 		if (i >= count) return;
 		const uint32_t e = ids ? ids[i] : i;
+		if (mask && !mask[e]) return;
 		ragdoll_view v;
 		loadView(v, poseLerp, vel, NUM_BODY_PARTS * e);
 		const training& t = init[e].train;
@@ -118,16 +207,18 @@ namespace
 		const bool failure = hasFallen(out);
 		rewards[e] = failure ? 0.f : getReward(v, t);
 		fallen[e] = failure ? 1 : 0;
+		if (mirror) for (int k = 0; k < STATE_SIZE; ++k) mirror[(size_t)STATE_SIZE * e + k] = out[k];
 	}
 
-	// Reset of the listed environments: spawn pose into the three pose copies, velocities and accumulators zeroed (vel.w = invMass
+	// Reset of the listed environments (with a mask instead of ids: of every environment whose mask word is set): spawn pose into the three pose copies, velocities and accumulators zeroed (vel.w = invMass
 	// kept), smoothed action zeroed and applied (resetTraining's applyAction(zero)).
-	__global__ void __launch_bounds__(64) k_loco_reset(uint32_t count, const uint32_t* __restrict__ ids, const env_init* __restrict__ init, float* __restrict__ smoothedAll,
+	__global__ void __launch_bounds__(64) k_loco_reset(uint32_t count, const uint32_t* __restrict__ ids, const int32_t* __restrict__ mask, const env_init* __restrict__ init, float* __restrict__ smoothedAll,
 		const uint32_t* __restrict__ slots, uint8_t* conePods, uint8_t* hingePods, float4* pose, float4* pose0, float4* poseLerp, float4* vel, float4* force)
 	{
 		const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
 		if (i >= count) return;
-		const uint32_t e = ids[i];
+		const uint32_t e = ids ? ids[i] : i;
+		if (mask && !mask[e]) return;
 		for (int k = 0; k < 2 * NUM_BODY_PARTS; ++k)
 		{
 			const size_t j = 2 * (size_t)NUM_BODY_PARTS * e + k;
@@ -174,32 +265,67 @@ namespace
 
 	dim3 blocks(uint32_t n) { return dim3((n + 63) / 64); }
 
-	int launchReset(batch& b, const uint32_t* dIds, uint32_t count)
+	int launchReset(batch& b, const uint32_t* dIds, const int32_t* dMask, uint32_t count)
 	{
 		if (int e = refreshPods(b)) return e;
-		hipLaunchKernelGGL(k_loco_reset, blocks(count), dim3(64), 0, b.stream, count, dIds, b.dInit, b.dSmoothed, b.dSlots, (uint8_t*)b.pods[0], (uint8_t*)b.pods[1],
+		hipLaunchKernelGGL(k_loco_reset, blocks(count), dim3(64), 0, b.stream, count, dIds, dMask, b.dInit, b.dSmoothed, b.dSlots, (uint8_t*)b.pods[0], (uint8_t*)b.pods[1],
 			(float4*)b.ds.pose, (float4*)b.ds.pose0, (float4*)b.ds.poseLerp, (float4*)b.ds.vel, (float4*)b.ds.force);
 		return ok(hipGetLastError(), "reset kernel") ? 0 : MI_ERR_HIP;
 	}
 
-	int launchGather(batch& b, const uint32_t* dIds, uint32_t count, float* dStates, float* dRewards, int32_t* dFallen)
+	// The rows go to dStates; when that is not the batch's own current-state buffer (or is null), b.dStates receives them too.
+	int launchGather(batch& b, const uint32_t* dIds, const int32_t* dMask, uint32_t count, float* dStates, float* dRewards, int32_t* dFallen)
 	{
-		hipLaunchKernelGGL(k_loco_gather, blocks(count), dim3(64), 0, b.stream, count, dIds, b.dInit, b.dSmoothed, (const float4*)b.ds.poseLerp, (const float4*)b.ds.vel, dStates, dRewards, dFallen);
+		float* primary = dStates ? dStates : b.dStates;
+		hipLaunchKernelGGL(k_loco_gather, blocks(count), dim3(64), 0, b.stream, count, dIds, dMask, b.dInit, b.dSmoothed, (const float4*)b.ds.poseLerp, (const float4*)b.ds.vel,
+			primary, primary == b.dStates ? nullptr : b.dStates, dRewards, dFallen);
 		return ok(hipGetLastError(), "gather kernel") ? 0 : MI_ERR_HIP;
 	}
 
-	// One update of every environment, reading dActions, writing the three outputs (device pointers), all on the world's stream.
-	int launchUpdate(batch& b, const float* dActions, float* dStates, float* dRewards, int32_t* dFallen)
+	// The network on count rows of dStatesIn, on the world's stream.  With apply: rows are the environments, smoothed and motors written.
+	int launchPolicy(batch& b, bool apply, uint32_t count, const float* dStatesIn, float* dActionsOut, float* dHiddenOut)
+	{
+		const dim3 grid((count + POLICY_TILE - 1) / POLICY_TILE), block(64 * ((b.hidden + 63) / 64));
+		if (apply) hipLaunchKernelGGL(k_loco_policy<true>, grid, block, 0, b.stream, count, b.hidden, dStatesIn, (const float*)b.dPolicy, dActionsOut, dHiddenOut, b.dSmoothed, (const uint32_t*)b.dSlots, (uint8_t*)b.pods[0], (uint8_t*)b.pods[1]);
+		else hipLaunchKernelGGL(k_loco_policy<false>, grid, block, 0, b.stream, count, b.hidden, dStatesIn, (const float*)b.dPolicy, dActionsOut, dHiddenOut, (float*)nullptr, (const uint32_t*)nullptr, (uint8_t*)nullptr, (uint8_t*)nullptr);
+		return ok(hipGetLastError(), "policy kernel") ? 0 : MI_ERR_HIP;
+	}
+
+	// The policy of setPhysicsPolicy, transposed to [in][out] once, here.
+	int uploadPolicy(batch& b)
+	{
+		locomotion_policy p;
+		if (!locomotionPolicy(&p)) return 0;
+		const uint32_t h = p.hidden;
+		std::vector<float> t(policyFloats(h));
+		float* q = t.data();
+		auto transposed = [&](const float* w, uint32_t outputs, uint32_t inputs) { for (uint32_t x = 0; x < inputs; ++x) for (uint32_t y = 0; y < outputs; ++y) *q++ = w[(size_t)y * inputs + x]; };
+		auto plain = [&](const float* v, uint32_t count) { memcpy(q, v, sizeof(float) * count); q += count; };
+		transposed(p.w1, h, STATE_SIZE); plain(p.b1, h); transposed(p.w2, h, h); plain(p.b2, h); transposed(p.w3, ACTION_SIZE, h); plain(p.b3, ACTION_SIZE);
+		if (!ok(hipStreamSynchronize(b.stream), "policy")) return MI_ERR_HIP; // nothing in flight reads the old one
+		if (b.dPolicy) (void)hipFree(b.dPolicy);
+		b.dPolicy = nullptr; b.hidden = 0;
+		if (!ok(hipMalloc(&b.dPolicy, sizeof(float) * t.size()), "alloc")) return MI_ERR_HIP;
+		if (!ok(hipMemcpyAsync(b.dPolicy, t.data(), sizeof(float) * t.size(), hipMemcpyHostToDevice, b.stream), "policy") || !ok(hipStreamSynchronize(b.stream), "policy")) return MI_ERR_HIP;
+		b.hidden = h;
+		return 0;
+	}
+
+	// One update of every environment, all on the world's stream, writing the three outputs (device pointers; dStates may be null, the
+	// batch's current-state buffer receives the states in any case).  With dActions: applyAction of these.  Without: the policy on the
+	// current states, its raw outputs to dActionsOut (may be null).
+	int launchUpdate(batch& b, const float* dActions, float* dActionsOut, float* dStates, float* dRewards, int32_t* dFallen)
 	{
 		if (int e = refreshPods(b)) return e;
-		hipLaunchKernelGGL(k_loco_actions, blocks(b.n), dim3(64), 0, b.stream, b.n, dActions, b.dSmoothed, b.dSlots, (uint8_t*)b.pods[0], (uint8_t*)b.pods[1]);
+		if (dActions) hipLaunchKernelGGL(k_loco_actions, blocks(b.n), dim3(64), 0, b.stream, b.n, dActions, b.dSmoothed, b.dSlots, (uint8_t*)b.pods[0], (uint8_t*)b.pods[1]);
+		else if (int e = launchPolicy(b, true, b.n, b.dStates, dActionsOut, nullptr)) return e;
 		hipLaunchKernelGGL(k_loco_push_rays, blocks(b.n), dim3(64), 0, b.stream, b.n, b.dRng, (const float4*)b.ds.poseLerp, (float4*)b.dRays);
 		if (!ok(hipGetLastError(), "action / push kernels")) return MI_ERR_HIP;
 		if (int e = mi_test_physics_interaction_batch(b.world, b.n, 0, NUM_BODY_PARTS, b.dRays, b.dPushes)) return e;
 		mi_physics_settings s = { 1, 60, 4, 30, 0, 1, 0, 1, 1, 1 };
 		float timer = 0.f;
 		if (int e = mi_step(b.world, &timer, &s, 1.f / 60.f)) return e;
-		return launchGather(b, nullptr, b.n, dStates, dRewards, dFallen);
+		return launchGather(b, nullptr, nullptr, b.n, dStates, dRewards, dFallen);
 	}
 
 	int copyOut(batch& b, float* outStates, float* outRewards, int32_t* outFallen)
@@ -272,8 +398,9 @@ extern "C"
 			&& ok(hipMemsetAsync(b->dPushes, 0, sizeof(int32_t) * n, b->stream), "pushes");
 		if (!good) { release(b); return MI_ERR_HIP; }
 		B = b;
-		int e = launchReset(*b, b->dIds, numEnvs);
-		if (!e) e = launchGather(*b, nullptr, numEnvs, b->dStates, b->dRewards, b->dFallen);
+		int e = launchReset(*b, b->dIds, nullptr, numEnvs);
+		if (!e) e = launchGather(*b, nullptr, nullptr, numEnvs, b->dStates, b->dRewards, b->dFallen);
+		if (!e) e = uploadPolicy(*b);
 		if (!e) e = copyOut(*b, outStates, nullptr, nullptr);
 		return e;
 	}
@@ -285,7 +412,7 @@ extern "C"
 		if (!B || !actions) return -MI_ERR_INVALID_STATE;
 		batch& b = *B;
 		if (!ok(hipMemcpyAsync(b.dActions, actions, sizeof(float) * ACTION_SIZE * b.n, hipMemcpyHostToDevice, b.stream), "actions")) return -MI_ERR_HIP;
-		if (int e = launchUpdate(b, b.dActions, b.dStates, b.dRewards, b.dFallen)) return -e;
+		if (int e = launchUpdate(b, b.dActions, nullptr, b.dStates, b.dRewards, b.dFallen)) return -e;
 		std::vector<int32_t> fallen(b.n);
 		if (int e = copyOut(b, outStates, outRewards, fallen.data())) return -e;
 		int count = 0;
@@ -298,7 +425,7 @@ extern "C"
 	int updatePhysicsBatchDevice(const float* dActions, float* dStates, float* dRewards, int32_t* dFallen)
 	{
 		if (!B || !dActions || !dStates || !dRewards || !dFallen) return MI_ERR_INVALID_STATE;
-		return launchUpdate(*B, dActions, dStates, dRewards, dFallen);
+		return launchUpdate(*B, dActions, nullptr, dStates, dRewards, dFallen);
 	}
 
 	// Resets the listed environments (host ids) and writes their rows of outStates (host, numEnvs x 66); other rows are untouched.
@@ -312,8 +439,8 @@ extern "C"
 		uint32_t* dList = nullptr;
 		if (!ok(hipMalloc(&dList, sizeof(uint32_t) * count), "alloc")) return MI_ERR_HIP;
 		int e = ok(hipMemcpyAsync(dList, envIds, sizeof(uint32_t) * count, hipMemcpyHostToDevice, b.stream), "ids") ? 0 : MI_ERR_HIP;
-		if (!e) e = launchReset(b, dList, count);
-		if (!e) e = launchGather(b, dList, count, b.dStates, b.dRewards, b.dFallen);
+		if (!e) e = launchReset(b, dList, nullptr, count);
+		if (!e) e = launchGather(b, dList, nullptr, count, b.dStates, b.dRewards, b.dFallen);
 		std::vector<float> states((size_t)STATE_SIZE * b.n);
 		if (!e) e = copyOut(b, states.data(), nullptr, nullptr);
 		(void)hipFree(dList);
@@ -325,7 +452,7 @@ extern "C"
 	int observePhysicsBatch(float* outStates, float* outRewards, int32_t* outFallen)
 	{
 		if (!B) return MI_ERR_INVALID_STATE;
-		if (int e = launchGather(*B, nullptr, B->n, B->dStates, B->dRewards, B->dFallen)) return e;
+		if (int e = launchGather(*B, nullptr, nullptr, B->n, B->dStates, B->dRewards, B->dFallen)) return e;
 		return copyOut(*B, outStates, outRewards, outFallen);
 	}
 
@@ -341,4 +468,58 @@ extern "C"
 		for (uint32_t i = 0; i < B->n; ++i) count += outBodies[i] != 0;
 		return count;
 	}
+
+	// The network alone on count rows of dStates (device, count x 66) into dActions (count x 27), on the world's stream; dHidden (may be
+	// NULL, count x 2H) receives tanh(z1), tanh(z2) of every row: a parity facility.  Touches no environment.
+	int inferPhysicsBatchDevice(uint32_t count, const float* dStates, float* dActions, float* dHidden)
+	{
+		if (!B || !B->hidden) return MI_ERR_INVALID_STATE;
+		if (!count || !dStates || !dActions) return MI_ERR_INVALID_ARGUMENT;
+		return launchPolicy(*B, false, count, dStates, dActions, dHidden);
+	}
+
+	// One closed-loop update of every environment, host buffers out (any may be NULL).  Returns what updatePhysicsBatch returns.
+	int updatePhysicsBatchPolicy(float* outStates, float* outRewards, int32_t* outFallen)
+	{
+		if (!B || !B->hidden) return -MI_ERR_INVALID_STATE;
+		batch& b = *B;
+		if (int e = launchUpdate(b, nullptr, nullptr, b.dStates, b.dRewards, b.dFallen)) return -e;
+		std::vector<int32_t> fallen(b.n);
+		if (int e = copyOut(b, outStates, outRewards, fallen.data())) return -e;
+		int count = 0;
+		for (uint32_t i = 0; i < b.n; ++i) count += fallen[i] != 0;
+		if (outFallen) memcpy(outFallen, fallen.data(), sizeof(int32_t) * b.n);
+		return count;
+	}
+
+	// The same into device buffers, enqueued on the world's stream without a host synchronisation; dActions (may be NULL, n x 27)
+	// receives the raw, unsmoothed network outputs.
+	int updatePhysicsBatchPolicyDevice(float* dStates, float* dRewards, int32_t* dFallen, float* dActions)
+	{
+		if (!B || !B->hidden || !dStates || !dRewards || !dFallen) return MI_ERR_INVALID_STATE;
+		return launchUpdate(*B, nullptr, dActions, dStates, dRewards, dFallen);
+	}
+
+	// `steps` closed-loop updates enqueued back to back: row t of dStates [steps][n][66] (may be NULL), dActions [steps][n][27] (may be
+	// NULL), dRewards [steps][n], dFallen [steps][n] holds the action taken at update t and the state, reward and fallen after it.
+	// With autoReset every environment whose fallen is 1 after an update (the last one included) is reset on the device before the
+	// next: spawn pose, zero velocities, zero smoothed action, motors rewritten, its random stream left alone; row t keeps the
+	// terminal state, and the policy's next input is the reset state.  No host synchronisation beyond those of mi_step.
+	int rolloutPhysicsBatchDevice(uint32_t steps, int autoReset, float* dStates, float* dActions, float* dRewards, int32_t* dFallen)
+	{
+		if (!B || !B->hidden || !dRewards || !dFallen) return MI_ERR_INVALID_STATE;
+		batch& b = *B;
+		const size_t n = b.n;
+		for (uint32_t t = 0; t < steps; ++t)
+		{
+			int32_t* fallen = dFallen + n * t;
+			if (int e = launchUpdate(b, nullptr, dActions ? dActions + ACTION_SIZE * n * t : nullptr, dStates ? dStates + STATE_SIZE * n * t : nullptr, dRewards + n * t, fallen)) return e;
+			if (!autoReset) continue;
+			if (int e = launchReset(b, nullptr, fallen, b.n)) return e;
+			if (int e = launchGather(b, nullptr, fallen, b.n, b.dStates, b.dRewards, b.dFallen)) return e;
+		}
+		return 0;
+	}
 }
+
+int locomotionBatchPolicyChanged() { return B ? uploadPolicy(*B) : 0; }

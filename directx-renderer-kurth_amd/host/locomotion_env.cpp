@@ -8,6 +8,8 @@
 //     int  updatePhysics(float* action, float* outState, float* outReward);   // returns 1 when the ragdoll has fallen
 // One addition: setPhysicsSeed(uint64) — the reference seeds its random pushes with time(0); here the seed is explicit (default
 // fixed) so that runs are reproducible.  resetPhysics also fills outState (the reference leaves it untouched).
+// The controller half (learned_locomotion::update, :44-68) is here too: setPhysicsPolicy keeps a network (locomotion_policy.h),
+// inferPhysicsPolicy runs it on one state, updatePhysicsPolicy drives the single environment from it.
 // Everything physical happens in libmi_physics.so on the GPU; this file is host logic only, like the reference's.
 //
 // Build: directx_renderer_kurth_amd.build_locomotion() compiles this file with g++ and locomotion_batch.hip (the batched environments)
@@ -15,7 +17,7 @@
 #include <cstdio>
 #include <vector>
 
-#include "locomotion_shared.h"
+#include "locomotion_policy.h"
 
 namespace
 {
@@ -71,9 +73,48 @@ namespace
 
 	environment* env = nullptr;
 	uint64_t seed = 0x9E3779B97F4A7C15ull;
+
+	// The policy of setPhysicsPolicy: one block of policyFloats(hidden) floats, the six arrays back to back.
+	uint32_t policyHidden = 0;
+	std::vector<float> policyData;
+
+	// updatePhysics after its applyAction (:469-489): push draw, step, state, reward, fallen.
+	int stepAfterAction(float* outState, float* outReward)
+	{
+		if (env->rng.f01() < 0.02f) // a random push every ~50 steps
+		{
+			uint32_t bodyPartIndex = env->rng.u32Between(0, NUM_BODY_PARTS - 1);
+			vec3 part = env->view.transform[bodyPartIndex].position + v3(0.f, 0.2f, 0.f);
+			float dx = env->rng.between(-1.f, 1.f), dz = env->rng.between(-1.f, 1.f);
+			vec3 direction = normalize(v3(dx, 0.f, dz));
+			vec3 origin = part - direction * 5.f;
+			mi_test_physics_interaction(env->world, &origin.x, &direction.x, 1000.f);
+		}
+		mi_physics_settings s = { 1, 60, 4, 30, 0, 1, 0, 1, 1, 1 };
+		float timer = 0.f;
+		mi_step(env->world, &timer, &s, 1.f / 60.f);
+		env->snapshot();
+		getState(env->view, env->train, env->lastSmoothedAction, outState);
+		bool failure = hasFallen(outState);
+		*outReward = 0.f;
+		if (!failure) { *outReward = getReward(env->view, env->train); env->totalReward += *outReward; }
+		return failure ? 1 : 0;
+	}
 }
 
 uint64_t locomotionSeed() { return seed; }
+
+bool locomotionPolicy(locomotion_policy* out)
+{
+	if (!policyHidden) return false;
+	const uint32_t h = policyHidden;
+	const float* p = policyData.data();
+	out->hidden = h;
+	out->w1 = p; p += (size_t)h * STATE_SIZE; out->b1 = p; p += h;
+	out->w2 = p; p += (size_t)h * h; out->b2 = p; p += h;
+	out->w3 = p; p += (size_t)ACTION_SIZE * h; out->b3 = p;
+	return true;
+}
 
 extern "C"
 {
@@ -115,23 +156,46 @@ extern "C"
 	{
 		if (!env || !env->world) { if (outReward) *outReward = 0.f; return 1; }
 		env->applyAction(action);
-		if (env->rng.f01() < 0.02f) // a random push every ~50 steps
-		{
-			uint32_t bodyPartIndex = env->rng.u32Between(0, NUM_BODY_PARTS - 1);
-			vec3 part = env->view.transform[bodyPartIndex].position + v3(0.f, 0.2f, 0.f);
-			float dx = env->rng.between(-1.f, 1.f), dz = env->rng.between(-1.f, 1.f);
-			vec3 direction = normalize(v3(dx, 0.f, dz));
-			vec3 origin = part - direction * 5.f;
-			mi_test_physics_interaction(env->world, &origin.x, &direction.x, 1000.f);
-		}
-		mi_physics_settings s = { 1, 60, 4, 30, 0, 1, 0, 1, 1, 1 };
-		float timer = 0.f;
-		mi_step(env->world, &timer, &s, 1.f / 60.f);
-		env->snapshot();
-		getState(env->view, env->train, env->lastSmoothedAction, outState);
-		bool failure = hasFallen(outState);
-		*outReward = 0.f;
-		if (!failure) { *outReward = getReward(env->view, env->train); env->totalReward += *outReward; }
-		return failure ? 1 : 0;
+		return stepAfterAction(outState, outReward);
+	}
+
+	// Replaces the policy (layout: locomotion_policy.h).  Kept for the single environment and uploaded to the batch, if one exists; may
+	// be called before or after either reset.  A bad argument returns MI_ERR_INVALID_ARGUMENT and leaves the previous policy active.
+	int setPhysicsPolicy(uint32_t hidden, const float* w1, const float* b1, const float* w2, const float* b2, const float* w3, const float* b3)
+	{
+		if (!hidden || hidden > POLICY_MAX_HIDDEN || !w1 || !b1 || !w2 || !b2 || !w3 || !b3) return MI_ERR_INVALID_ARGUMENT;
+		std::vector<float> data(policyFloats(hidden));
+		float* p = data.data();
+		auto put = [&](const float* from, size_t count) { memcpy(p, from, sizeof(float) * count); p += count; };
+		put(w1, (size_t)hidden * STATE_SIZE); put(b1, hidden); put(w2, (size_t)hidden * hidden); put(b2, hidden); put(w3, (size_t)ACTION_SIZE * hidden); put(b3, ACTION_SIZE);
+		policyData.swap(data);
+		policyHidden = hidden;
+		return locomotionBatchPolicyChanged();
+	}
+
+	// The network on one state, on the host: needs no world and no GPU.  hidden (2 x H floats, may be NULL) receives tanh(z1), tanh(z2).
+	int inferPhysicsPolicy(const float* state, float* action, float* hidden)
+	{
+		locomotion_policy p;
+		if (!locomotionPolicy(&p)) return MI_ERR_INVALID_STATE;
+		if (!state || !action) return MI_ERR_INVALID_ARGUMENT;
+		float ab[2 * POLICY_MAX_HIDDEN];
+		inferPolicy(p, state, ab, ab + p.hidden, action);
+		if (hidden) memcpy(hidden, ab, sizeof(float) * 2 * p.hidden);
+		return MI_OK;
+	}
+
+	// learned_locomotion::update (:44-68) on the single environment: its state as it is -> network -> applyAction, then the rest of
+	// updatePhysics.  Returns what updatePhysics returns, or -MI_ERR_INVALID_STATE without a policy.
+	int updatePhysicsPolicy(float* outState, float* outReward)
+	{
+		locomotion_policy p;
+		if (!locomotionPolicy(&p)) return -MI_ERR_INVALID_STATE;
+		if (!env || !env->world) { if (outReward) *outReward = 0.f; return 1; }
+		float state[STATE_SIZE], action[ACTION_SIZE], ab[2 * POLICY_MAX_HIDDEN];
+		getState(env->view, env->train, env->lastSmoothedAction, state);
+		inferPolicy(p, state, ab, ab + p.hidden, action);
+		env->applyAction(action);
+		return stepAfterAction(outState, outReward);
 	}
 }
