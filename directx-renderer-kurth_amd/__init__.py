@@ -18,6 +18,8 @@ STATIC = 0xFFFFFFFF
 SPHERE, CAPSULE, CYLINDER, AABB, OBB, HULL = range(6)
 DISTANCE, BALL, FIXED, HINGE, CONE_TWIST, SLIDER = range(6)
 CONSTRAINT_POD_BYTES = (28, 24, 40, 104, 120, 72)
+JOINT_UPDATE_FLOATS = (20, 20, 36, 56, 80, 72)   # MI_JOINT_UPDATE_FLOATS (csrc/world.h)
+JOINT_PATH_LAUNCH_SWEEP, JOINT_PATH_CLUSTER, JOINT_PATH_INTERLEAVED, JOINT_PATH_NONE = range(4)
 
 COLLIDER_DTYPE = np.dtype([("shape", "<f4", 10), ("restitution", "<f4"), ("friction", "<f4"), ("density", "<f4"),
                            ("type", "<u4"), ("objectType", "<u4"), ("objectIndex", "<u4")])
@@ -76,7 +78,7 @@ EXPORTED_SYMBOLS = [
     "mi_set_transform", "mi_write_transforms", "mi_write_velocities", "mi_step", "mi_step_internal", "mi_synchronize", "mi_read_transforms", "mi_read_velocities", "mi_read_mass_properties",
     "mi_get_stats", "mi_enable_validation", "mi_enable_stage_timing", "mi_num_bodies", "mi_num_colliders", "mi_device_pointers", "mi_state_to_device_buffers", "mi_state_from_device_buffers", "mi_slab_configure", "mi_slab_message_bytes", "mi_slab_pack", "mi_slab_unpack", "mi_slab_read_codes", "mi_debug_num_pairs", "mi_debug_read_pairs", "mi_debug_sorting_axis", "mi_debug_narrow_limits",
     "mi_debug_read_world_colliders", "mi_debug_num_manifold_slots", "mi_debug_read_manifolds", "mi_debug_num_colors", "mi_debug_read_schedule",
-    "mi_debug_read_joint_order", "mi_debug_read_body_state", "mi_debug_flow_trace",
+    "mi_debug_read_joint_order", "mi_debug_read_joint_update", "mi_debug_read_body_state", "mi_debug_flow_trace",
     "mi_debug_set_replay", "mi_debug_num_replay_batches", "mi_debug_read_replay_batches",
     "mi_device_state", "mi_joint_device_pods", "mi_test_physics_interaction_batch",
 ]
@@ -494,6 +496,13 @@ class World:
         out = np.zeros(max(n, 1), np.uint32)
         self._check(self.lib.mi_debug_read_joint_order(self.w, ctype, _p(out)))
         return out[:n]
+
+    def joint_update(self, ctype, n):
+        """(update records [n, JOINT_UPDATE_FLOATS[ctype]] of the last step in joint order, raw float32 with the flag words as bits;
+        JOINT_PATH_* of that step).  The record layouts are the comments of csrc/k_joints.hip."""
+        out = np.zeros((max(n, 1), JOINT_UPDATE_FLOATS[ctype]), np.float32); path = C.c_uint32(0)
+        self._check(self.lib.mi_debug_read_joint_update(self.w, ctype, _p(out), C.c_uint32(n * JOINT_UPDATE_FLOATS[ctype]), C.byref(path)))
+        return out[:n], int(path.value)
 
     def flow_trace(self, enable=True, num_slots=0):
         out = np.zeros((max(1, num_slots), 32), np.uint64)

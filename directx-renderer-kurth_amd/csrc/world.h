@@ -192,6 +192,7 @@ struct World
 	u32 scheduleReferenceBatches(const std::vector<uint4>& ids, u32 numPositions);
 	bool useCluster = true;               // MI_PHYSICS_NO_CLUSTER=1: launch-per-colour sweep only
 	bool lastStepCluster = false, backupVelocities = false;
+	u32 lastJointPath = 3;                // where the last step solved its joints (MI_JOINT_PATH_*, mi_debug_read_joint_update)
 	u32 clusterBlocksLimit = 0, clusterFailStreak = 0, clusterTaskWeight = 64u * 1000u, clusterTaskWeightLater = 64u * 500u; // MI_CLUSTER_BLOCKS / _TASK / _TASK_LATER
 	bool clusterSortDue = true; u32 clusterSortAge = 0, clusterSortBodies = 0; // body order along the curves: refreshed every few steps
 	u32 clusterLdsBytes = 0, clusterBlocks = 0, clusterCooldown = 0;

@@ -671,6 +671,7 @@ void World::recoverFlow()
 	solveWithLaunchSweep(*this, prevNumPairs, pendingDt, pendingIters);
 	launch_integrate_velocities(*this, pendingDt);
 	lastStepCluster = false;
+	if (lastJointPath != MI_JOINT_PATH_NONE) lastJointPath = MI_JOINT_PATH_LAUNCH_SWEEP;
 }
 
 // Before the host looks at results: has the last step's cluster sweep completed?  (One extra 4-byte read, only after a cluster step.)
@@ -870,6 +871,11 @@ int World::stepInternal(float dt, u32 iters)
 		if (T) MI_CHECK(hipEventRecord(ev[3], stream)); // (the launch sweep is enqueued behind its own synchronisation: setup and solve are not separated here)
 	}
 	lastStepCluster = clusterStep;
+	{
+		bool anyJoint = false;
+		for (auto& js : joints) anyJoint = anyJoint || !js.order.empty();
+		lastJointPath = !anyJoint ? MI_JOINT_PATH_NONE : !clusterStep ? MI_JOINT_PATH_LAUNCH_SWEEP : (cluster_solves_joints(*this) ? MI_JOINT_PATH_CLUSTER : MI_JOINT_PATH_INTERLEAVED);
+	}
 	if (T) MI_CHECK(hipEventRecord(ev[4], stream));
 
 	launch_integrate_velocities(*this, dt);
@@ -2311,6 +2317,16 @@ int mi_debug_read_joint_order(mi_world* world, uint32_t type, uint32_t* out)
 	W->uploadJoints();
 	memcpy(out, W->joints[type].order.data(), sizeof(u32) * W->joints[type].order.size());
 	return MI_OK;
+}
+int mi_debug_read_joint_update(mi_world* world, uint32_t type, float* out, uint32_t capacityFloats, uint32_t* outPath)
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	if (type >= MI_JOINT_TYPES || (!out && capacityFloats)) return MI_ERR_INVALID_ARGUMENT;
+	W->uploadJoints();
+	size_t n = std::min<size_t>(capacityFloats, W->joints[type].order.size() * MI_JOINT_UPDATE_FLOATS[type]);
+	d2h(W, out, W->joints[type].dUpdate.p, sizeof(float) * n); // (resolves a pending cluster sweep first: a give-up redoes the step with the launch sweep)
+	if (outPath) *outPath = W->lastJointPath;
+	return W->lastError;
 }
 int mi_debug_read_body_state(mi_world* world, float* outCog4, float* outInvInertia12, uint32_t n)
 {

@@ -298,6 +298,13 @@ int mi_debug_read_manifolds(mi_world* w, uint32_t* outPairs2, uint32_t* outCount
 uint32_t mi_debug_num_colors(mi_world* w);
 int mi_debug_read_schedule(mi_world* w, uint32_t* outManifoldSlots, uint32_t* outColorStart /* numColors+1 */);
 int mi_debug_read_joint_order(mi_world* w, uint32_t type, uint32_t* outJointIds);
+/* The joint update records of the last step (what k_*_init wrote and the solve accumulated its impulses into): numJoints(type) records in
+ * joint ORDER (mi_debug_read_joint_order), each MI_JOINT_UPDATE_FLOATS = {20, 20, 36, 56, 80, 72}[type] floats long (layouts: the comments of
+ * csrc/k_joints.hip); at most capacityFloats are copied, after the stream has drained.  *outPath (may be null) tells where that step solved
+ * its joints: in the launch sweep, inside the cluster sweep, in launches of their own between one cluster launch per iteration, or
+ * nowhere (no step yet, or a world without joints). */
+enum { MI_JOINT_PATH_LAUNCH_SWEEP = 0, MI_JOINT_PATH_CLUSTER = 1, MI_JOINT_PATH_INTERLEAVED = 2, MI_JOINT_PATH_NONE = 3 };
+int mi_debug_read_joint_update(mi_world* w, uint32_t type, float* out, uint32_t capacityFloats, uint32_t* outPath);
 int mi_debug_read_body_state(mi_world* w, float* outCog4, float* outInvInertia12, uint32_t nPlusOne); /* rbGlobal: {cog.xyz, invMass}, 3 x float4 columns */
 /* Replay of the reference's own Gauss-Seidel order (SURVEY section 7 / 8c "replay mode"): on != 0 makes the following steps run the reference's
  * greedy 8-wide batch scheduler (scheduleConstraintsSIMD, constraints.cpp:51-184) over the step's contacts in emission order and sweep

@@ -453,6 +453,7 @@ struct hinge_constraint_update
 	float limitImpulse, limitBias, limitSign;
 	float motorImpulse, maxMotorImpulse, motorVelocity;
 	vec3 motorAndLimitImpulseToAngularVelocityA, motorAndLimitImpulseToAngularVelocityB;
+	float angle; // kept for orc_read_joint_decisions: the relative angle the limits and the position motor saw (0 when nothing read it)
 };
 static inline void initializeHingeConstraint(hinge_constraint_update& out, const rigid_body_global_state* rbs, const hinge_constraint& in, constraint_body_pair bp, float dt)
 {
@@ -493,6 +494,7 @@ static inline void initializeHingeConstraint(hinge_constraint_update& out, const
 	out.limitImpulse = out.limitBias = out.limitSign = 0.f;
 	out.motorImpulse = out.maxMotorImpulse = out.motorVelocity = 0.f;
 	out.motorAndLimitImpulseToAngularVelocityA = out.motorAndLimitImpulseToAngularVelocityB = vec3(0.f);
+	out.angle = 0.f;
 
 	if (in.minRotationLimit <= 0.f || in.maxRotationLimit >= 0.f || in.maxMotorTorque > 0.f)
 	{
@@ -500,6 +502,7 @@ static inline void initializeHingeConstraint(hinge_constraint_update& out, const
 		float angle = jointAtan2(jointDot(localHingeCompareA, in.localHingeBitangentA), jointDot(localHingeCompareA, in.localHingeTangentA)); // (wide path: constraints.cpp:1545, polynomial atan2)
 		bool minLimitViolated = in.minRotationLimit <= 0.f && angle <= in.minRotationLimit;
 		bool maxLimitViolated = in.maxRotationLimit >= 0.f && angle >= in.maxRotationLimit;
+		out.angle = angle;
 		out.solveLimit = minLimitViolated || maxLimitViolated;
 		out.solveMotor = in.maxMotorTorque > 0.f;
 		if (out.solveLimit || out.solveMotor)
@@ -593,6 +596,7 @@ struct cone_twist_constraint_update
 	vec3 twistMotorAndLimitImpulseToAngularVelocityA, twistMotorAndLimitImpulseToAngularVelocityB;
 	vec3 swingMotorImpulseToAngularVelocityA, swingMotorImpulseToAngularVelocityB;
 	vec3 swingLimitImpulseToAngularVelocityA, swingLimitImpulseToAngularVelocityB;
+	quat swingRotation; float swingAngle, twistAngle; // kept for orc_read_joint_decisions: what rotateFromTo / getAxisRotation / atan2 gave
 };
 static inline void initializeConeTwistConstraint(cone_twist_constraint_update& out, const rigid_body_global_state* rbs, const cone_twist_constraint& in, constraint_body_pair bp, float dt)
 {
@@ -621,6 +625,7 @@ static inline void initializeConeTwistConstraint(cone_twist_constraint_update& o
 	vec3 swingAxis; float swingAngle;
 	jointGetAxisRotation(swingRotation, swingAxis, swingAngle);
 	if (swingAngle < 0.f) { swingAngle *= -1.f; swingAxis *= -1.f; }
+	out.swingRotation = swingRotation; out.swingAngle = swingAngle; out.twistAngle = twistAngle;
 
 	out.solveSwingLimit = in.swingLimit >= 0.f && swingAngle >= in.swingLimit;
 	if (out.solveSwingLimit)

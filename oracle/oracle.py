@@ -316,6 +316,17 @@ class OracleWorld:
     def clear_follow(self):
         self.lib.orc_clear_follow(self.w)
 
+    JOINT_DECISION_FLOATS = 24
+
+    def joint_decisions(self, ctype, n):
+        """What the joints of one type decided and accumulated in the last step, [n, 24] in storage order (= constraint ids): flags,
+        limit signs, motor target velocities, impulses and bounds, the angles and the swing rotation (layout: oworld.cpp, at the fill)."""
+        out = np.zeros((max(n, 1), self.JOINT_DECISION_FLOATS), np.float32)
+        self.lib.orc_read_joint_decisions.restype = C.c_uint32
+        got = self.lib.orc_read_joint_decisions(self.w, C.c_uint32(ctype), _p(out), C.c_uint32(n * self.JOINT_DECISION_FLOATS))
+        assert got == n, (got, n)
+        return out[:n]
+
     def set_joint_order(self, ctype, order):
         order = np.ascontiguousarray(order, np.uint32)
         self.lib.orc_set_joint_order(self.w, C.c_uint32(ctype), _p(order), C.c_uint32(len(order)))

@@ -64,6 +64,7 @@ struct physics_settings
 
 enum solver_mode : u32 { solver_scalar = 0, solver_wide8 = 1, solver_custom_order = 2, solver_replay = 3 };
 
+static const u32 ORC_JOINT_DECISION_FLOATS = 24;
 struct world
 {
 	std::vector<body> bodies;
@@ -126,6 +127,7 @@ struct world
 	std::vector<u32> slotOrder;
 	std::vector<u8> slotCounts;          // contacts per candidate slot of the last narrowphase (override mode)
 	std::vector<u32> jointOrder[6];
+	std::vector<float> jointDecisions[6];          // per joint of the last step, ORC_JOINT_DECISION_FLOATS each (orc_read_joint_decisions)
 };
 
 // ---------------------------------------------------------------------------------------------------
@@ -961,6 +963,42 @@ static void physicsStepInternal(world& w, u32 iterations, u32 mode, float dt)
 		}
 	}
 
+	// What the joints of this step decided and accumulated, in storage order (orc_read_joint_decisions): 0 flags (hinge / slider: 1 limit,
+	// 2 motor; cone-twist: 1 swing limit, 2 twist limit, 4 swing motor, 8 twist motor) | 1 limit sign (cone-twist: twist) | 2 motor velocity |
+	// 3 swing motor velocity | 4 twist motor velocity | 5 limit impulse (cone-twist: twist) | 6 swing impulse | 7 motor impulse | 8 swing motor
+	// impulse | 9 twist motor impulse | 10-12 max motor / swing motor / twist motor impulse | 13 distance: u != 0 | 14 any bias != 0 |
+	// 15 hinge angle / twist angle | 16 swing angle | 17-20 swing rotation | 21-23 global swing motor axis
+	{
+		const u32 F = ORC_JOINT_DECISION_FLOATS;
+		auto nz3 = [](vec3 v) { return v.x != 0.f || v.y != 0.f || v.z != 0.f; };
+		size_t counts[6] = { dU.size(), bU.size(), fU.size(), hU.size(), cU.size(), sU.size() };
+		for (int t = 0; t < 6; ++t) w.jointDecisions[t].assign(counts[t] * F, 0.f);
+		for (size_t i = 0; i < dU.size(); ++i) { float* o = &w.jointDecisions[0][i * F]; o[13] = nz3(dU[i].u) ? 1.f : 0.f; o[14] = dU[i].bias != 0.f ? 1.f : 0.f; }
+		for (size_t i = 0; i < bU.size(); ++i) w.jointDecisions[1][i * F + 14] = nz3(bU[i].bias) ? 1.f : 0.f;
+		for (size_t i = 0; i < fU.size(); ++i) w.jointDecisions[2][i * F + 14] = (nz3(fU[i].translationBias) || nz3(fU[i].rotationBias)) ? 1.f : 0.f;
+		for (size_t i = 0; i < hU.size(); ++i)
+		{
+			float* o = &w.jointDecisions[3][i * F]; const hinge_constraint_update& u = hU[i];
+			o[0] = (float)((u.solveLimit ? 1 : 0) | (u.solveMotor ? 2 : 0)); o[1] = u.limitSign; o[2] = u.motorVelocity; o[5] = u.limitImpulse; o[7] = u.motorImpulse; o[10] = u.maxMotorImpulse;
+			o[14] = (nz3(u.translationBias) || u.rotationBias.x != 0.f || u.rotationBias.y != 0.f) ? 1.f : 0.f; o[15] = u.angle;
+		}
+		for (size_t i = 0; i < cU.size(); ++i)
+		{
+			float* o = &w.jointDecisions[4][i * F]; const cone_twist_constraint_update& u = cU[i];
+			o[0] = (float)((u.solveSwingLimit ? 1 : 0) | (u.solveTwistLimit ? 2 : 0) | (u.solveSwingMotor ? 4 : 0) | (u.solveTwistMotor ? 8 : 0));
+			o[1] = u.twistLimitSign; o[3] = u.swingMotorVelocity; o[4] = u.twistMotorVelocity; o[5] = u.twistImpulse; o[6] = u.swingImpulse; o[8] = u.swingMotorImpulse; o[9] = u.twistMotorImpulse;
+			o[11] = u.maxSwingMotorImpulse; o[12] = u.maxTwistMotorImpulse; o[14] = nz3(u.bias) ? 1.f : 0.f; o[15] = u.twistAngle; o[16] = u.swingAngle;
+			o[17] = u.swingRotation.x; o[18] = u.swingRotation.y; o[19] = u.swingRotation.z; o[20] = u.swingRotation.w;
+			o[21] = u.globalSwingMotorAxis.x; o[22] = u.globalSwingMotorAxis.y; o[23] = u.globalSwingMotorAxis.z;
+		}
+		for (size_t i = 0; i < sU.size(); ++i)
+		{
+			float* o = &w.jointDecisions[5][i * F]; const slider_constraint_update& u = sU[i];
+			o[0] = (float)((u.solveLimit ? 1 : 0) | (u.solveMotor ? 2 : 0)); o[1] = u.limitSign; o[2] = u.motorVelocity; o[5] = u.limitImpulse; o[7] = u.motorImpulse; o[10] = u.maxMotorImpulse;
+			o[14] = (u.translationBias.x != 0.f || u.translationBias.y != 0.f || nz3(u.rotationBias)) ? 1.f : 0.f;
+		}
+	}
+
 	stageEnd(3);
 	for (u32 i = 0; i < numRigidBodies; ++i) { if (i < w.simOff.size() && w.simOff[i]) continue; integrateVelocity(w.bodies[i], w.rbGlobal[i], w.bodies[i].transform1, dt); }
 	stageEnd(4);
@@ -1535,6 +1573,13 @@ void orc_set_follow(world* w, const u32* pairs2, u32 numPairs, const u32* slotOr
 	w->slotOrder.assign(slotOrder, slotOrder + numOrder);
 }
 void orc_clear_follow(world* w) { w->usePairOverride = false; }
+u32 orc_read_joint_decisions(world* w, u32 type, float* out, u32 capacityFloats)
+{
+	if (type >= 6) return 0;
+	u32 n = (u32)std::min<size_t>(capacityFloats, w->jointDecisions[type].size());
+	if (n) memcpy(out, w->jointDecisions[type].data(), n * sizeof(float));
+	return n / ORC_JOINT_DECISION_FLOATS;
+}
 void orc_set_joint_order(world* w, u32 type, const u32* order, u32 n) { if (type < 6) w->jointOrder[type].assign(order, order + n); }
 u32 orc_read_slot_counts(world* w, u8* out) { memcpy(out, w->slotCounts.data(), w->slotCounts.size()); return (u32)w->slotCounts.size(); }
 
