@@ -1,0 +1,558 @@
+// C-ABI of include/mi_physics.h, part 2: the world's life cycle, body state in and out, the step, statistics, device pointers,
+// multi-GPU slabs and the mi_debug_* inspection calls.  (What a world is made of is added in api_scene.hip; mi_snapshot_* and
+// mi_world_restore are in snapshot.hip.)
+#include "api.h"
+#include "ray_tests.h"
+#include <cstring>
+#include <cmath>
+#include <algorithm>
+
+extern "C" {
+
+mi_world* mi_world_create(const mi_world_desc* desc)
+{
+	g_createError.clear();
+	int count = 0;
+	if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) { g_createError = "no HIP device available (this library has no CPU fallback)"; return nullptr; }
+	int dev = desc ? desc->device : -1;
+	if (dev < 0) { if (hipGetDevice(&dev) != hipSuccess) dev = 0; }
+	if (dev >= count) { g_createError = "device ordinal out of range"; return nullptr; }
+	mi_world* world = new mi_world(dev);
+	if (world->w.lastError) { g_createError = world->w.lastErrorText; delete world; return nullptr; }
+	if (desc)
+	{
+		if (desc->reserveBodies) world->w.bodies.reserve(desc->reserveBodies);
+		if (desc->reserveColliders) world->w.colliders.reserve(desc->reserveColliders);
+		if (desc->reservePairs) ensurePairBuffers(world->w, desc->reservePairs);
+	}
+	return world;
+}
+void mi_world_destroy(mi_world* world) { delete world; }
+const char* mi_last_error(mi_world* world) { return world ? world->w.lastErrorText.c_str() : g_createError.c_str(); }
+
+// A setter that finds live state on the device while bodies / colliders were added since the last step cannot write to the device
+// (the buffers are about to be rebuilt) and must not write to the host mirror only (upload() would pull the device state over it):
+// pull the state now and let the host mirror be authoritative until upload().
+static void makeHostAuthoritative(World* w) { if (w->stateOnDevice && w->topologyDirty) { w->downloadState(); w->stateOnDevice = false; } }
+
+// Entity deletion (scene.deleteEntity -> the rigid body, its colliders and its constraints go away; collision_broad.cpp:42-75
+// removes the colliders from the sweep).  Body and collider indices are add-order positions and stay valid: the body is switched
+// off (no AABBs, no integration — the mechanism of the spatial slabs), its joints are deleted.
+int mi_delete_body(mi_world* world, uint32_t body)
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	if (body >= W->bodies.size()) return MI_ERR_INVALID_ARGUMENT;
+	W->resolvePendingFlow();
+	makeHostAuthoritative(W);
+	int e = mi_delete_all_constraints_from_body(world, body);
+	if (e) return e;
+	{ World::HBody& hb = W->bodies[body]; hb.removed = true; hb.invMass = 0.f; for (int i = 0; i < 3; ++i) { hb.v[i] = 0.f; hb.w[i] = 0.f; } }
+	if (W->stateOnDevice && !W->topologyDirty && body < W->nb)
+	{
+		uint8_t zero = 0;
+		float4 still[2] = { make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f) }; // gone: no velocity, no mass
+		MI_CHECK(hipMemcpyAsync(W->vel.p + 2 * body, still, sizeof(still), hipMemcpyHostToDevice, W->stream));
+		MI_CHECK(hipMemcpyAsync(W->simMask.p + body, &zero, 1, hipMemcpyHostToDevice, W->stream));
+		W->activeDirty = true;
+		MI_CHECK(hipMemcpyAsync(W->aliveMask.p + body, &zero, 1, hipMemcpyHostToDevice, W->stream));
+		MI_CHECK(hipStreamSynchronize(W->stream));
+	}
+	return W->lastError;
+}
+
+// ---- testPhysicsInteraction (physics.h:404, physics.cpp:556-628): ray vs every collider of every rigid body, in the body's frame;
+// the closest hit gets force = direction * strength at the hit point.  Host code, like the reference's (an editor interaction); the
+// ray tests live in ray_tests.h, shared with the batched kernel of mi_test_physics_interaction_batch (k_interact.hip).
+// Tables of the batched ray test: every body's colliders (CSR over HBody::colliders) and the hull triangles as indices into hullVerts
+// (the vertex pool upload() builds, in the same order).
+void World::buildInteractTables()
+{
+	std::vector<u32> start(1, 0u), list;
+	for (const HBody& b : bodies) { list.insert(list.end(), b.colliders.begin(), b.colliders.end()); start.push_back((u32)list.size()); }
+	std::vector<uint4> tris; std::vector<uint2> range;
+	u32 firstVertex = 0;
+	for (const HHull& g : hulls)
+	{
+		range.push_back(make_uint2((u32)tris.size(), (u32)(g.triangles.size() / 3)));
+		for (size_t f = 0; f + 2 < g.triangles.size(); f += 3) tris.push_back(make_uint4(firstVertex + g.triangles[f], firstVertex + g.triangles[f + 1], firstVertex + g.triangles[f + 2], 0u));
+		firstVertex += (u32)(g.vertices.size() / 3);
+	}
+	bodyColStart.ensure(start.size(), stream); bodyColList.ensure(std::max<size_t>(list.size(), 1), stream);
+	hullTris.ensure(std::max<size_t>(tris.size(), 1), stream); hullTriRange.ensure(std::max<size_t>(range.size(), 1), stream);
+	MI_CHECK(hipMemcpyAsync(bodyColStart.p, start.data(), sizeof(u32) * start.size(), hipMemcpyHostToDevice, stream));
+	if (!list.empty()) MI_CHECK(hipMemcpyAsync(bodyColList.p, list.data(), sizeof(u32) * list.size(), hipMemcpyHostToDevice, stream));
+	if (!tris.empty()) MI_CHECK(hipMemcpyAsync(hullTris.p, tris.data(), sizeof(uint4) * tris.size(), hipMemcpyHostToDevice, stream));
+	if (!range.empty()) MI_CHECK(hipMemcpyAsync(hullTriRange.p, range.data(), sizeof(uint2) * range.size(), hipMemcpyHostToDevice, stream));
+	MI_CHECK(hipStreamSynchronize(stream));
+	interactTablesValid = true;
+}
+
+struct HostHulls
+{
+	const std::vector<World::HHull>& hulls;
+	u32 numTriangles(u32 g) const { return (u32)(hulls[g].triangles.size() / 3); }
+	V3 vertex(u32 g, u32 f, u32 k) const { const World::HHull& h = hulls[g]; const float* p = &h.vertices[3 * h.triangles[3 * f + k]]; return v3(p[0], p[1], p[2]); }
+};
+
+int mi_test_physics_interaction(mi_world* world, const float origin[3], const float direction[3], float strength)
+{
+	CHECK_WORLD(0);
+	W->upload();
+	if (W->stateOnDevice) W->downloadState(); // physics_transform1 of every body
+	HRay r{ v3(origin[0], origin[1], origin[2]), v3(direction[0], direction[1], direction[2]) };
+	float minT = MI_FLT_MAX; int minBody = -1; V3 force = v3s(0.f), torque = v3s(0.f);
+	const HostHulls hulls{ W->hulls };
+	for (const World::HCollider& c : W->colliders)
+	{
+		if (c.body == MI_STATIC_BODY || W->bodies[c.body].removed) continue;
+		const World::HBody& rb = W->bodies[c.body];
+		Q4 rot = q4(rb.rot[0], rb.rot[1], rb.rot[2], rb.rot[3]); V3 pos = v3(rb.pos[0], rb.pos[1], rb.pos[2]);
+		HRay lr; float t;
+		bool hit = rayBodyCollider(r, rot, pos, c.type, c.shape, hulls, lr, t);
+		if (hit && t < minT)
+		{
+			minT = t; minBody = (int)c.body;
+			interactionPush(r, lr, t, rot, pos, v3(rb.localCOG[0], rb.localCOG[1], rb.localCOG[2]), strength, force, torque);
+		}
+	}
+	if (minBody < 0) return 0;
+	float f[3] = { force.x, force.y, force.z }, tq[3] = { torque.x, torque.y, torque.z };
+	if (mi_apply_force_torque(world, (uint32_t)minBody, f, tq)) return 0;
+	return 1 + minBody; // the body that was pushed, plus one
+}
+
+int mi_apply_force_torque(mi_world* world, uint32_t body, const float f[3], const float t[3])
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	W->resolvePendingFlow();
+	if (body >= W->bodies.size()) return MI_ERR_INVALID_ARGUMENT;
+	makeHostAuthoritative(W);
+	if (W->stateOnDevice && !W->topologyDirty && body < W->nb)
+	{
+		float4 cur[2];
+		MI_CHECK(hipMemcpyAsync(cur, W->force.p + 2 * body, sizeof(cur), hipMemcpyDeviceToHost, W->stream)); MI_CHECK(hipStreamSynchronize(W->stream));
+		cur[0].x += f[0]; cur[0].y += f[1]; cur[0].z += f[2]; cur[1].x += t[0]; cur[1].y += t[1]; cur[1].z += t[2];
+		MI_CHECK(hipMemcpyAsync(W->force.p + 2 * body, cur, sizeof(cur), hipMemcpyHostToDevice, W->stream)); MI_CHECK(hipStreamSynchronize(W->stream));
+	}
+	else { World::HBody& b = W->bodies[body]; for (int i = 0; i < 3; ++i) { b.force[i] += f[i]; b.torque[i] += t[i]; } }
+	return W->lastError;
+}
+int mi_set_velocity(mi_world* world, uint32_t body, const float lin[3], const float ang[3])
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	W->resolvePendingFlow();
+	if (body >= W->bodies.size()) return MI_ERR_INVALID_ARGUMENT;
+	makeHostAuthoritative(W);
+	World::HBody& b = W->bodies[body];
+	if (W->stateOnDevice && !W->topologyDirty && body < W->nb)
+	{
+		float4 v[2] = { make_float4(lin[0], lin[1], lin[2], b.invMass), make_float4(ang[0], ang[1], ang[2], 0.f) };
+		MI_CHECK(hipMemcpyAsync(W->vel.p + 2 * body, v, sizeof(v), hipMemcpyHostToDevice, W->stream)); MI_CHECK(hipStreamSynchronize(W->stream));
+	}
+	memcpy(b.v, lin, 12); memcpy(b.w, ang, 12);
+	return W->lastError;
+}
+int mi_set_transform(mi_world* world, uint32_t body, const float pos[3], const float rot[4])
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	W->resolvePendingFlow();
+	if (body >= W->bodies.size()) return MI_ERR_INVALID_ARGUMENT;
+	makeHostAuthoritative(W);
+	if (W->stateOnDevice && !W->topologyDirty && body < W->nb)
+	{
+		float4 p[2] = { make_float4(pos[0], pos[1], pos[2], 0.f), make_float4(rot[0], rot[1], rot[2], rot[3]) };
+		MI_CHECK(hipMemcpyAsync(W->pose.p + 2 * body, p, sizeof(p), hipMemcpyHostToDevice, W->stream));
+		MI_CHECK(hipMemcpyAsync(W->pose0.p + 2 * body, p, sizeof(p), hipMemcpyHostToDevice, W->stream));
+		MI_CHECK(hipMemcpyAsync(W->poseLerp.p + 2 * body, p, sizeof(p), hipMemcpyHostToDevice, W->stream)); MI_CHECK(hipStreamSynchronize(W->stream));
+	}
+	memcpy(W->bodies[body].pos, pos, 12); memcpy(W->bodies[body].rot, rot, 16);
+	return W->lastError;
+}
+
+int mi_write_transforms(mi_world* world, const float* in7, uint32_t n)
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	W->resolvePendingFlow();
+	W->upload();
+	n = std::min<u32>(n, W->nb);
+	if (!n) return W->lastError;
+	std::vector<float4> h(2 * (size_t)n);
+	for (u32 i = 0; i < n; ++i)
+	{
+		const float* s = in7 + 7 * (size_t)i;
+		h[2 * i] = make_float4(s[0], s[1], s[2], 0.f); h[2 * i + 1] = make_float4(s[3], s[4], s[5], s[6]);
+	}
+	MI_CHECK(hipMemcpyAsync(W->pose.p, h.data(), sizeof(float4) * h.size(), hipMemcpyHostToDevice, W->stream));
+	MI_CHECK(hipMemcpyAsync(W->pose0.p, h.data(), sizeof(float4) * h.size(), hipMemcpyHostToDevice, W->stream));
+	MI_CHECK(hipMemcpyAsync(W->poseLerp.p, h.data(), sizeof(float4) * h.size(), hipMemcpyHostToDevice, W->stream));
+	MI_CHECK(hipStreamSynchronize(W->stream));
+	return W->lastError;
+}
+int mi_write_velocities(mi_world* world, const float* in6, uint32_t n)
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	W->resolvePendingFlow();
+	W->upload();
+	n = std::min<u32>(n, W->nb);
+	if (!n) return W->lastError;
+	std::vector<float4> h(2 * (size_t)n);
+	for (u32 i = 0; i < n; ++i)
+	{
+		const float* s = in6 + 6 * (size_t)i;
+		h[2 * i] = make_float4(s[0], s[1], s[2], W->bodies[i].invMass); h[2 * i + 1] = make_float4(s[3], s[4], s[5], 0.f);
+	}
+	MI_CHECK(hipMemcpyAsync(W->vel.p, h.data(), sizeof(float4) * h.size(), hipMemcpyHostToDevice, W->stream));
+	MI_CHECK(hipStreamSynchronize(W->stream));
+	return W->lastError;
+}
+
+int mi_step(mi_world* world, float* timer, const mi_physics_settings* settings, float dt)
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	if (!timer || !settings) return MI_ERR_INVALID_ARGUMENT;
+	return W->step(timer, settings, dt);
+}
+int mi_step_internal(mi_world* world, float dt, uint32_t iterations)
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	int e = W->stepInternal(dt, iterations);
+	if (!e && W->nb) MI_CHECK(hipMemcpyAsync(W->poseLerp.p, W->pose.p, sizeof(float4) * 2 * W->nb, hipMemcpyDeviceToDevice, W->stream));
+	return e ? e : W->lastError;
+}
+int mi_synchronize(mi_world* world) { CHECK_WORLD(MI_ERR_INVALID_ARGUMENT); MI_CHECK(hipStreamSynchronize(W->stream)); return W->resolvePendingFlow(); }
+
+int mi_read_transforms(mi_world* world, uint32_t which, float* out7, uint32_t n)
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	W->resolvePendingFlow();
+	W->upload();
+	n = std::min<u32>(n, W->nb);
+	if (!n) return W->lastError;
+	std::vector<float4> h(2 * (size_t)n);
+	const float4* src = which == 0 ? W->poseLerp.p : (which == 1 ? W->pose.p : W->pose0.p);
+	MI_CHECK(hipMemcpyAsync(h.data(), src, sizeof(float4) * h.size(), hipMemcpyDeviceToHost, W->stream)); MI_CHECK(hipStreamSynchronize(W->stream));
+	for (u32 i = 0; i < n; ++i)
+	{
+		float* o = out7 + 7 * (size_t)i;
+		o[0] = h[2 * i].x; o[1] = h[2 * i].y; o[2] = h[2 * i].z; o[3] = h[2 * i + 1].x; o[4] = h[2 * i + 1].y; o[5] = h[2 * i + 1].z; o[6] = h[2 * i + 1].w;
+	}
+	return W->lastError;
+}
+int mi_read_velocities(mi_world* world, float* out6, uint32_t n)
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	W->resolvePendingFlow();
+	W->upload();
+	n = std::min<u32>(n, W->nb);
+	if (!n) return W->lastError;
+	std::vector<float4> h(2 * (size_t)n);
+	MI_CHECK(hipMemcpyAsync(h.data(), W->vel.p, sizeof(float4) * h.size(), hipMemcpyDeviceToHost, W->stream)); MI_CHECK(hipStreamSynchronize(W->stream));
+	for (u32 i = 0; i < n; ++i)
+	{
+		float* o = out6 + 6 * (size_t)i;
+		o[0] = h[2 * i].x; o[1] = h[2 * i].y; o[2] = h[2 * i].z; o[3] = h[2 * i + 1].x; o[4] = h[2 * i + 1].y; o[5] = h[2 * i + 1].z;
+	}
+	return W->lastError;
+}
+int mi_read_mass_properties(mi_world* world, float* out13, uint32_t n)
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	n = std::min<u32>(n, (u32)W->bodies.size());
+	for (u32 i = 0; i < n; ++i)
+	{
+		const World::HBody& b = W->bodies[i]; float* o = out13 + 13 * (size_t)i;
+		memcpy(o, b.localCOG, 12); o[3] = b.invMass; memcpy(o + 4, b.invInertia, 36);
+	}
+	return MI_OK;
+}
+int mi_get_stats(mi_world* world, mi_stats* out)
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	W->refreshCounters();     // counts of the last step (one small read-back if the step did not do it itself)
+	W->harvestTiming();
+	mi_stats& st = W->stats;
+	if (W->accTimed)
+	{
+		double n = W->accTimed;
+		st.msCollidersBroad = (float)(W->accMs[0] / n); st.msNarrow = (float)(W->accMs[1] / n); st.msSolverSetup = (float)(W->accMs[2] / n); st.msSolve = (float)(W->accMs[3] / n); st.msIntegrate = (float)(W->accMs[4] / n);
+		st.msTotal = st.msCollidersBroad + st.msNarrow + st.msSolverSetup + st.msSolve + st.msIntegrate;
+		for (double& a : W->accMs) a = 0; W->accTimed = 0;
+	}
+	st.avgSteps = W->sumSteps;
+	double n = W->sumSteps ? W->sumSteps : 1;
+	st.avgContacts = (float)(W->sumContacts / n); st.avgCollisions = (float)(W->sumManifolds / n); st.avgColors = (float)(W->sumColors / n);
+	st.avgBroadphaseOverlaps = (float)(W->sumPairs / n); st.avgFlowProbes = (float)(W->sumProbes / n);
+	W->sumContacts = W->sumManifolds = W->sumColors = W->sumPairs = W->sumProbes = 0; W->sumSteps = 0;
+	*out = st;
+	return W->lastError;
+}
+int mi_enable_validation(mi_world* world, int enable) { CHECK_WORLD(MI_ERR_INVALID_ARGUMENT); W->validate = enable != 0; return MI_OK; }
+int mi_enable_stage_timing(mi_world* world, int enable) { CHECK_WORLD(MI_ERR_INVALID_ARGUMENT); if (!enable) W->harvestTiming(); W->timeStages = enable != 0; return MI_OK; }
+uint32_t mi_num_bodies(mi_world* world) { CHECK_WORLD(0); return (u32)W->bodies.size(); }
+uint32_t mi_num_colliders(mi_world* world) { CHECK_WORLD(0); return (u32)W->colliders.size(); }
+
+int mi_device_pointers(mi_world* world, void** pose, void** vel, void** stream)
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	W->resolvePendingFlow();
+	W->upload();
+	if (pose) *pose = W->pose.p; if (vel) *vel = W->vel.p; if (stream) *stream = (void*)W->stream;
+	return W->lastError;
+}
+
+int mi_device_state(mi_world* world, struct mi_device_state* out)
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	if (!out) return MI_ERR_INVALID_ARGUMENT;
+	W->resolvePendingFlow();
+	W->upload();
+	out->pose = W->pose.p; out->pose0 = W->pose0.p; out->poseLerp = W->poseLerp.p; out->vel = W->vel.p; out->force = W->force.p;
+	out->stream = (void*)W->stream; out->numBodies = W->nb; out->reserved = 0;
+	return W->lastError;
+}
+
+int mi_joint_device_pods(mi_world* world, uint32_t type, void** dPods, uint32_t* outSlotOfId, uint32_t numIds, uint32_t* outGeneration)
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	if (type >= MI_JOINT_TYPES) return MI_ERR_INVALID_ARGUMENT;
+	W->resolvePendingFlow();
+	W->upload(); W->uploadJoints();
+	if (W->lastError) return W->lastError;
+	W->jointPodsOnDevice = true;
+	const JointSet& js = W->joints[type];
+	if (dPods) *dPods = js.order.empty() ? nullptr : js.dPods.p;
+	if (outSlotOfId)
+	{
+		for (u32 i = 0; i < numIds; ++i) outSlotOfId[i] = 0xFFFFFFFFu;
+		for (u32 slot = 0; slot < (u32)js.order.size(); ++slot) if (js.order[slot] < numIds) outSlotOfId[js.order[slot]] = slot;
+	}
+	if (outGeneration) *outGeneration = W->jointGeneration;
+	return MI_OK;
+}
+
+int mi_test_physics_interaction_batch(mi_world* world, uint32_t numRays, uint32_t firstBody, uint32_t bodiesPerRay, const float* dRays, int32_t* dOutBody)
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	W->resolvePendingFlow();
+	W->upload();
+	if (!numRays) return W->lastError;
+	if (!dRays || !dOutBody || (uint64_t)firstBody + (uint64_t)numRays * bodiesPerRay > W->nb)
+	{
+		W->fail(MI_ERR_INVALID_ARGUMENT, "mi_test_physics_interaction_batch: body range outside the world");
+		return MI_ERR_INVALID_ARGUMENT;
+	}
+	if (!W->interactTablesValid) W->buildInteractTables();
+	launch_interaction_batch(*W, numRays, firstBody, bodiesPerRay, dRays, dOutBody);
+	return W->lastError;
+}
+
+// ---- multi-GPU slabs: state hand-over in device memory (directx-renderer-kurth_amd/parallel.py drives the halo exchange) ----
+int mi_state_to_device_buffers(mi_world* world, void* dPose, void* dVel)
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	W->resolvePendingFlow();
+	W->upload();
+	if (!W->nb) return W->lastError;
+	MI_CHECK(hipMemcpyAsync(dPose, W->pose.p, sizeof(float4) * 2 * W->nb, hipMemcpyDeviceToDevice, W->stream));
+	MI_CHECK(hipMemcpyAsync(dVel, W->vel.p, sizeof(float4) * 2 * W->nb, hipMemcpyDeviceToDevice, W->stream));
+	MI_CHECK(hipStreamSynchronize(W->stream));
+	return W->lastError;
+}
+int mi_state_from_device_buffers(mi_world* world, const void* dPose, const void* dVel, const uint8_t* dMask)
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	W->resolvePendingFlow();
+	W->upload();
+	if (!W->nb) return W->lastError;
+	if (dPose) MI_CHECK(hipMemcpyAsync(W->pose.p, dPose, sizeof(float4) * 2 * W->nb, hipMemcpyDeviceToDevice, W->stream));
+	if (dVel) MI_CHECK(hipMemcpyAsync(W->vel.p, dVel, sizeof(float4) * 2 * W->nb, hipMemcpyDeviceToDevice, W->stream));
+	if (dMask)
+	{
+		MI_CHECK(hipMemcpyAsync(W->simMask.p, dMask, W->nb, hipMemcpyDeviceToDevice, W->stream));
+		launch_and_mask(*W); // deleted bodies stay off whatever the caller's mask says
+	}
+	return W->lastError;
+}
+
+// ---- spatial slab halo (device side; the exchange of the messages is the caller's: RCCL send/recv on the world's stream) ----
+int mi_slab_configure(mi_world* world, uint32_t rank, uint32_t size, uint32_t axis, float lo, float hi, float margin)
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	if (!size || rank >= size || axis > 2 || !(lo < hi) || !(margin >= 0.f)) { W->fail(MI_ERR_INVALID_ARGUMENT, "mi_slab_configure: bad slab"); return W->lastError; }
+	W->resolvePendingFlow();
+	W->upload();
+	if (W->lastError) return W->lastError;
+	W->slabRank = rank; W->slabSize = size; W->slabAxis = axis; W->slabLo = lo; W->slabHi = hi; W->slabMargin = margin; W->slabStamp = 0;
+	W->slabCode.ensure((size_t)W->nb + 1, W->stream); W->slabFresh.ensure((size_t)W->nb + 1, W->stream);
+	if (W->lastError) return W->lastError;
+	launch_slab_classify(*W);
+	W->clusterSortDue = true;
+	return W->lastError;
+}
+uint64_t mi_slab_message_bytes(uint32_t capacity) { return 16ull + 72ull * capacity; }
+int mi_slab_pack(mi_world* world, void* dMessageLeft, void* dMessageRight, uint32_t capacity)
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	if (!W->slabSize || W->topologyDirty || W->slabCode.cap < (size_t)W->nb) { W->fail(MI_ERR_INVALID_ARGUMENT, "mi_slab_pack: configure the slab after the last add call"); return W->lastError; }
+	// (a give-up of the previous step's cluster sweep is settled first: the message must carry that step's real result)
+	W->resolvePendingFlow();
+	W->slabStamp++;
+	launch_slab_pack(*W, dMessageLeft, dMessageRight, capacity);
+	return W->lastError;
+}
+int mi_slab_unpack(mi_world* world, const void* dMessageLeft, const void* dMessageRight, uint32_t capacity)
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	if (!W->slabSize || W->topologyDirty) { W->fail(MI_ERR_INVALID_ARGUMENT, "mi_slab_unpack: configure the slab after the last add call"); return W->lastError; }
+	launch_slab_unpack(*W, dMessageLeft, dMessageRight, capacity);
+	return W->lastError;
+}
+int mi_slab_read_codes(mi_world* world, uint8_t* outCodes, uint32_t n)
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	if (!W->slabSize) return MI_ERR_INVALID_ARGUMENT;
+	n = std::min<u32>(n, W->nb);
+	MI_CHECK(hipMemcpyAsync(outCodes, W->slabCode.p, n, hipMemcpyDeviceToHost, W->stream));
+	MI_CHECK(hipStreamSynchronize(W->stream));
+	return W->lastError;
+}
+
+// ---- inspection ----
+static void d2h(World* w, void* dst, const void* src, size_t bytes)
+{
+	w->resolvePendingFlow();
+	w->refreshCounters();
+	if (!bytes) return;
+	MI_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, w->stream)); MI_CHECK(hipStreamSynchronize(w->stream));
+}
+uint32_t mi_debug_num_pairs(mi_world* world) { CHECK_WORLD(0); W->refreshCounters(); return W->hCounters[CTR_NUM_PAIRS]; }
+int mi_debug_read_pairs(mi_world* world, uint32_t* out) { CHECK_WORLD(MI_ERR_INVALID_ARGUMENT); W->refreshCounters(); d2h(W, out, W->pairs.p, sizeof(uint2) * W->hCounters[CTR_NUM_PAIRS]); return W->lastError; }
+int mi_debug_read_world_colliders(mi_world* world, void* outColliders64, float* outAabbs6)
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	u32 n = W->nc;
+	std::vector<ColliderRec> c(n); std::vector<float4> mn(n), mx(n);
+	d2h(W, c.data(), W->colWorld.p, sizeof(ColliderRec) * n); d2h(W, mn.data(), W->aabbMin.p, sizeof(float4) * n); d2h(W, mx.data(), W->aabbMax.p, sizeof(float4) * n);
+	struct Out { float shape[10]; float restitution, friction, density; u32 type, objectType, objectIndex; };
+	Out* o = (Out*)outColliders64;
+	for (u32 i = 0; i < n; ++i)
+	{
+		const float* f = (const float*)&c[i];
+		memcpy(o[i].shape, f, 40); o[i].restitution = f[10]; o[i].friction = f[11]; o[i].density = f[14];
+		o[i].type = mi_f2u(f[12]); o[i].objectIndex = mi_f2u(f[13]); o[i].objectType = (o[i].objectIndex < W->nb) ? 0u : 1u;
+		float* a = outAabbs6 + 6 * (size_t)i;
+		a[0] = mn[i].x; a[1] = mn[i].y; a[2] = mn[i].z; a[3] = mx[i].x; a[4] = mx[i].y; a[5] = mx[i].z;
+	}
+	return W->lastError;
+}
+uint32_t mi_debug_num_manifold_slots(mi_world* world) { CHECK_WORLD(0); W->refreshCounters(); return (W->hCounters[CTR_NUM_PAIRS] || W->terrainChunksPerDim) ? W->hCounters[CTR_NUM_VALID] : 0; }
+int mi_debug_read_manifolds(mi_world* world, uint32_t* outPairs2, uint32_t* outCounts, void* outContacts4x32, uint32_t* outBodyPairs2)
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	u32 n = mi_debug_num_manifold_slots(world);
+	if (!n) return MI_OK;
+	std::vector<ManifoldRec> m(n); std::vector<u64> packed(n);
+	d2h(W, m.data(), W->manifolds.p, sizeof(ManifoldRec) * n); d2h(W, packed.data(), W->pairsSorted.p, sizeof(u64) * n);
+	struct Contact { float point[3], depth, normal[3]; u32 fr; };
+	Contact* oc = (Contact*)outContacts4x32;
+	for (u32 i = 0; i < n; ++i)
+	{
+		outPairs2[2 * i] = (u32)packed[i]; outPairs2[2 * i + 1] = (u32)(packed[i] >> 32);
+		outCounts[i] = m[i].ids.z; outBodyPairs2[2 * i] = m[i].ids.x; outBodyPairs2[2 * i + 1] = m[i].ids.y;
+		for (u32 k = 0; k < 4; ++k)
+		{
+			Contact& c = oc[4 * (size_t)i + k];
+			c.point[0] = m[i].p[k].x; c.point[1] = m[i].p[k].y; c.point[2] = m[i].p[k].z; c.depth = m[i].p[k].w;
+			c.normal[0] = m[i].nf.x; c.normal[1] = m[i].nf.y; c.normal[2] = m[i].nf.z; c.fr = mi_f2u(m[i].nf.w);
+		}
+	}
+	return W->lastError;
+}
+// out[0] = sorting axis the last step oriented its equal-type pairs by, out[1] = the axis the next step will use (collision_broad.cpp:443-444)
+int mi_debug_sorting_axis(mi_world* world, uint32_t out[2])
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	u32 words[2] = { 0, 0 };
+	d2h(W, words, W->dCounters.p + CTR_SAP_AXIS, sizeof(words));
+	const u32 k = W->stats.numInternalSteps;
+	out[0] = k ? words[(k - 1u) & 1u] : 0u; out[1] = words[k & 1u];
+	return W->lastError;
+}
+int mi_debug_narrow_limits(mi_world* world, uint32_t out[8])
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	u32 words[5] = { 0, 0, 0, 0, 0 };
+	d2h(W, words, W->dCounters.p + CTR_NARROW_LIMITS, sizeof(words));
+	for (u32 i = 0; i < 8; ++i) out[i] = i < 5 ? words[i] : 0u;
+	return W->lastError;
+}
+uint32_t mi_debug_num_colors(mi_world* world) { CHECK_WORLD(0); return MI_MAX_COLORS + 1; }
+int mi_debug_read_schedule(mi_world* world, uint32_t* outManifoldSlots, uint32_t* outColorStart)
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	W->refreshCounters();
+	u32 n = (W->hCounters[CTR_NUM_PAIRS] || W->terrainChunksPerDim) ? W->hCounters[CTR_NUM_MANIFOLDS] : 0;
+	std::vector<uint4> ids(n);
+	d2h(W, ids.data(), W->rowIds.p, sizeof(uint4) * n); // rowIds[s].w = manifold slot executed at schedule position s
+	for (u32 s = 0; s < n; ++s) outManifoldSlots[s] = ids[s].w;
+	if (W->last.cluster)
+	{
+		// The cluster sweep's order is (phase, task, local colour): there is no global colour table.  Report as many evenly sized
+		// "colours" as the largest local colouring has, so that callers who count colours see that number.
+		u32 nc = std::max(1u, W->hCounters[CTR_NUM_COLORS]);
+		for (u32 c = 0; c <= MI_MAX_COLORS + 1; ++c) outColorStart[c] = (c < nc) ? (u32)(((u64)n * c) / nc) : n;
+	}
+	else for (u32 c = 0; c <= MI_MAX_COLORS + 1; ++c) outColorStart[c] = W->hCounters[CTR_KEY_START + 4 * c];
+	return W->lastError;
+}
+int mi_debug_read_joint_order(mi_world* world, uint32_t type, uint32_t* out)
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	if (type >= MI_JOINT_TYPES) return MI_ERR_INVALID_ARGUMENT;
+	W->uploadJoints();
+	memcpy(out, W->joints[type].order.data(), sizeof(u32) * W->joints[type].order.size());
+	return MI_OK;
+}
+int mi_debug_read_joint_update(mi_world* world, uint32_t type, float* out, uint32_t capacityFloats, uint32_t* outPath)
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	if (type >= MI_JOINT_TYPES || (!out && capacityFloats)) return MI_ERR_INVALID_ARGUMENT;
+	W->uploadJoints();
+	size_t n = std::min<size_t>(capacityFloats, W->joints[type].order.size() * MI_JOINT_UPDATE_FLOATS[type]);
+	d2h(W, out, W->joints[type].dUpdate.p, sizeof(float) * n); // (resolves a pending cluster sweep first: a give-up redoes the step with the launch sweep)
+	if (outPath) *outPath = W->last.jointPath;
+	return W->lastError;
+}
+int mi_debug_read_body_state(mi_world* world, float* outCog4, float* outInvInertia12, uint32_t n)
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	n = std::min<u32>(n, W->nb + 1);
+	d2h(W, outCog4, W->cog.p, sizeof(float4) * n); d2h(W, outInvInertia12, W->invIw.p, sizeof(float4) * 3 * n);
+	return W->lastError;
+}
+/* Replay facility: on != 0 makes every following step solve its contacts in the REFERENCE's own order (its greedy 8-wide batch
+ * scheduler over the contacts in emission order, constraints.cpp:51-184, batches executed one after the other) instead of the
+ * device's schedule.  One workgroup sweeps everything: for parity tests on small worlds, not for speed. */
+int mi_debug_set_replay(mi_world* world, int on)
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	W->resolvePendingFlow();
+	W->replayReferenceOrder = on != 0;
+	W->forceFullColoring = true;
+	return MI_OK;
+}
+uint32_t mi_debug_num_replay_batches(mi_world* world) { CHECK_WORLD(0); return W->replayBatches; }
+int mi_debug_read_replay_batches(mi_world* world, uint32_t* outEntries) { CHECK_WORLD(MI_ERR_INVALID_ARGUMENT); if (!W->replayHost.empty()) memcpy(outEntries, W->replayHost.data(), sizeof(u32) * W->replayHost.size()); return MI_OK; }
+/* Developer timeline of the cluster sweep: enable (allocates 16 rows of 32 stamps per workgroup of the solve launch), step, then read
+ * numSlots rows of 32 u64 (k_cl_solve documents the rows; wall-clock stamps are 10 ns ticks). */
+int mi_debug_flow_trace(mi_world* world, int enable, unsigned long long* out, uint32_t numSlots)
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	const size_t rows = (size_t)CL_MAX_TASKS * 16u;
+	if (enable && !W->flowTrace.p) { W->flowTrace.ensure(rows * 32, W->stream); if (!W->flowTrace.p) return W->lastError; MI_CHECK(hipMemsetAsync(W->flowTrace.p, 0, sizeof(u64) * rows * 32, W->stream)); }
+	if (out && W->flowTrace.p) d2h(W, out, W->flowTrace.p, sizeof(u64) * 32 * std::min<size_t>(numSlots, rows));
+	if (!enable) W->flowTrace.release();
+	return W->lastError;
+}
+
+} // extern "C"

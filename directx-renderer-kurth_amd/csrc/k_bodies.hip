@@ -313,10 +313,10 @@ void launch_restore_velocities(World& w)
 	hipLaunchKernelGGL(k_restore_velocities, dim3(std::max(1u, active_grid(w.estActiveBodies + 1, w.nb + 1))), dim3(256), 0, w.stream, w.nb, w.dCounters.p, w.actBodies.p, w.velBackup.p, w.vel.p);
 }
 
-void launch_integrate_forces(World& w, float dt)
+void launch_integrate_forces(World& w, float dt, bool backupVelocities)
 {
 	hipLaunchKernelGGL(k_integrate_forces, dim3(std::max(1u, active_grid(w.estActiveBodies + 1, w.nb + 1))), dim3(256), 0, w.stream, w.nb, dt, w.dCounters.p, w.actBodies.p, w.pose.p, w.bprops.p, w.force.p,
-		w.vel.p, w.cog.p, w.invIw.p, w.bodyMask.p, w.claim.p, w.backupVelocities ? w.velBackup.p : nullptr);
+		w.vel.p, w.cog.p, w.invIw.p, w.bodyMask.p, w.claim.p, backupVelocities ? w.velBackup.p : nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -157,3 +157,93 @@ void launch_cloth(World& w, float dt)
 		hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cloth_simulate<false>), dim3(numLarge), dim3(CLOTH_BLOCK), 0, w.stream, descs, w.clothList.p + w.numSmallCloths, w.clothPlanes.p,
 			(size_t)w.clothStride, w.clothAB.p, w.clothRestIms.p, w.clothTemp.p, w.globalForce[0], w.globalForce[1], w.globalForce[2], w.clothIterations[0], w.clothIterations[1], w.clothIterations[2], dt);
 }
+
+// ---- host side: the particle state and the descriptors between World::HCloth and the device (cloth.cpp:198-204, 331-347) ----
+static void clothRecalculateProperties(World::HCloth& c) // cloth.cpp:331-347
+{
+	u32 numParticles = c.gridX * c.gridY;
+	float invMassPerParticle = numParticles / c.totalMass;
+	for (float& invMass : c.invMass) invMass = (invMass != 0.f) ? invMassPerParticle : 0.f;
+	c.stiffness = clampf(c.stiffness, 0.01f, 1.f);
+	float invStiffness = 1.f / c.stiffness;
+	for (auto& k : c.constraints) k.inverseMassSum = (c.invMass[k.a] + c.invMass[k.b]) * invStiffness;
+}
+void World::downloadCloths()
+{
+	if (!clothStateOnDevice || cloths.empty()) return;
+	resolvePendingFlow();
+	std::vector<float> planes((size_t)9 * clothStride);
+	MI_CHECK(hipMemcpyAsync(planes.data(), clothPlanes.p, sizeof(float) * planes.size(), hipMemcpyDeviceToHost, stream));
+	MI_CHECK(hipStreamSynchronize(stream));
+	size_t first = 0;
+	for (HCloth& c : cloths)
+	{
+		size_t n = (size_t)c.gridX * c.gridY;
+		for (size_t i = 0; i < n; ++i)
+			for (int k = 0; k < 3; ++k)
+			{
+				c.pos[3 * i + k] = planes[(size_t)k * clothStride + first + i];
+				c.vel[3 * i + k] = planes[(size_t)(3 + k) * clothStride + first + i];
+				c.prev[3 * i + k] = planes[(size_t)(6 + k) * clothStride + first + i];
+			}
+		first += n;
+	}
+	clothStateOnDevice = false;
+}
+void World::uploadCloths()
+{
+	for (HCloth& c : cloths)
+		if (c.totalMass != c.oldTotalMass || c.stiffness != c.oldStiffness) { clothRecalculateProperties(c); c.oldTotalMass = c.totalMass; c.oldStiffness = c.stiffness; clothsDirty = true; } // cloth.cpp:198-204
+	if (!clothsDirty) return;
+	downloadCloths();
+	size_t totalParticles = 0, totalConstraints = 0;
+	for (const HCloth& c : cloths) { totalParticles += (size_t)c.gridX * c.gridY; totalConstraints += c.constraints.size(); }
+	clothStride = (u32)totalParticles;
+	std::vector<float> planes((size_t)10 * clothStride);
+	std::vector<uint2> ab(totalConstraints); std::vector<float2> rk(totalConstraints);
+	std::vector<ClothDesc> descs(cloths.size());
+	std::vector<u32> small, large;
+	size_t firstP = 0, firstC = 0; maxSmallClothParticles = 0;
+	for (size_t ci = 0; ci < cloths.size(); ++ci)
+	{
+		const HCloth& c = cloths[ci];
+		size_t n = (size_t)c.gridX * c.gridY;
+		for (size_t i = 0; i < n; ++i)
+		{
+			for (int k = 0; k < 3; ++k)
+			{
+				planes[(size_t)k * clothStride + firstP + i] = c.pos[3 * i + k];
+				planes[(size_t)(3 + k) * clothStride + firstP + i] = c.vel[3 * i + k];
+				planes[(size_t)(6 + k) * clothStride + firstP + i] = c.prev[3 * i + k];
+			}
+			planes[(size_t)9 * clothStride + firstP + i] = c.invMass[i];
+		}
+		ClothDesc& d = descs[ci];
+		d.firstParticle = (u32)firstP; d.numParticles = (u32)n; d.gridX = c.gridX; d.gridY = c.gridY; d.firstConstraint = (u32)firstC;
+		d.gravityFactor = c.gravityFactor; d.damping = c.damping;
+		u32 color = 0; d.colorStart[0] = 0;
+		for (size_t k = 0; k < c.constraints.size(); ++k)
+		{
+			const HClothConstraint& e = c.constraints[k];
+			while (color < e.color) d.colorStart[++color] = (u32)k;
+			ab[firstC + k] = make_uint2(e.a, e.b); rk[firstC + k] = make_float2(e.restDistance, e.inverseMassSum);
+		}
+		while (color < 12) d.colorStart[++color] = (u32)c.constraints.size();
+		if (n <= cloth_lds_particle_limit()) { small.push_back((u32)ci); maxSmallClothParticles = std::max(maxSmallClothParticles, (u32)n); } else large.push_back((u32)ci);
+		firstP += n; firstC += c.constraints.size();
+	}
+	numSmallCloths = (u32)small.size();
+	small.insert(small.end(), large.begin(), large.end());
+	clothPlanes.ensure(planes.size(), stream); clothAB.ensure(std::max<size_t>(totalConstraints, 1), stream); clothRestIms.ensure(std::max<size_t>(totalConstraints, 1), stream);
+	clothTemp.ensure(std::max<size_t>(totalConstraints, 1), stream); clothDescs.ensure(sizeof(ClothDesc) * descs.size(), stream); clothList.ensure(small.size(), stream);
+	MI_CHECK(hipMemcpyAsync(clothPlanes.p, planes.data(), sizeof(float) * planes.size(), hipMemcpyHostToDevice, stream));
+	if (totalConstraints)
+	{
+		MI_CHECK(hipMemcpyAsync(clothAB.p, ab.data(), sizeof(uint2) * ab.size(), hipMemcpyHostToDevice, stream));
+		MI_CHECK(hipMemcpyAsync(clothRestIms.p, rk.data(), sizeof(float2) * rk.size(), hipMemcpyHostToDevice, stream));
+	}
+	MI_CHECK(hipMemcpyAsync(clothDescs.p, descs.data(), sizeof(ClothDesc) * descs.size(), hipMemcpyHostToDevice, stream));
+	MI_CHECK(hipMemcpyAsync(clothList.p, small.data(), sizeof(u32) * small.size(), hipMemcpyHostToDevice, stream));
+	MI_CHECK(hipStreamSynchronize(stream));
+	clothsDirty = false; clothStateOnDevice = false; // both copies are equal until the next launch
+}

@@ -1,6 +1,7 @@
 // Force fields, trigger events, collision begin/end events (row N2 of SURVEY §8f) — reference physics.cpp:759-787, 952-1178.
 // None of this is launched for a world without force fields / triggers / enabled collision events.
 #include "events.h"
+#include <cstdlib>
 
 // ---------------------------------------------------------------------------------------------------------------
 // Force fields -> force accumulators, before the force integration (physics.cpp:963-967 localized, :1273 global).
@@ -123,4 +124,90 @@ void launch_collision_events(World& w, u32 numPairs)
 		hipLaunchKernelGGL(k_collision_begin, dim3((numPairs + 255) / 256), dim3(256), 0, w.stream, w.dCounters.p, (const u64*)w.pairsSorted.p, w.manifolds.p, w.vel.p, w.cog.p, w.nb, v, sinkOf(w), w.collisionBeginEvents ? 1u : 0u);
 	hipLaunchKernelGGL(HIP_KERNEL_NAME(k_scan_previous_set<true>), dim3((w.collisionSetSize + 255) / 256), dim3(256), 0, w.stream, v, sinkOf(w), w.colWorld.p, w.nb, w.collisionEndEvents ? 1u : 0u);
 	w.collisionCur ^= 1u;
+}
+
+// ---- force fields / events: host side ------------------------------------------------------------------------------
+static V3 fieldForceWorld(const World::HField& f) // physics.cpp:767-771
+{
+	V3 force = v3(f.force[0], f.force[1], f.force[2]);
+	return f.hasTransform ? (q4(f.rot[0], f.rot[1], f.rot[2], f.rot[3]) * force) : force;
+}
+void World::uploadFields()
+{
+	if (!fieldsDirty) return;
+	fieldsDirty = false;
+	std::vector<float4> hf(std::max<size_t>(fields.size(), 1), make_float4(0.f, 0.f, 0.f, 0.f));
+	V3 sum = v3s(0.f); anyGlobalForce = false; bool anyLocal = false;
+	for (size_t i = fields.size(); i-- > 0;) // getForceFieldStates (physics.cpp:759-787): EnTT walks newest first
+	{
+		V3 f = fieldForceWorld(fields[i]);
+		if (fields[i].numColliders) { hf[i] = make_float4(f.x, f.y, f.z, 0.f); anyLocal = true; }
+		else { sum = sum + f; anyGlobalForce = true; }
+	}
+	globalForce[0] = sum.x; globalForce[1] = sum.y; globalForce[2] = sum.z;
+	u32 words = anyLocal ? ((u32)fields.size() + 31u) / 32u : 0u;
+	fieldForce.ensure(hf.size(), stream);
+	MI_CHECK(hipMemcpyAsync(fieldForce.p, hf.data(), sizeof(float4) * hf.size(), hipMemcpyHostToDevice, stream));
+	size_t maskWords = std::max<size_t>((size_t)words * ((size_t)nb + 1), 1);
+	if (words != fieldWords || maskWords > fieldMask.cap)
+	{
+		fieldWords = words;
+		fieldMask.ensure(maskWords, stream);
+		MI_CHECK(hipMemsetAsync(fieldMask.p, 0, sizeof(u32) * maskWords, stream)); // bits are set by k_zone_overlap and cleared by k_apply_fields
+	}
+	MI_CHECK(hipStreamSynchronize(stream)); // `hf` goes out of scope
+}
+
+// Gives both tables of a pair set `newSize` slots; the previous step's keys (tables[cur ^ 1]) move over.
+static void resizePairSet(World& w, DevBuf<u64>* tables, u32& size, u32 cur, u32 newSize, std::vector<u64>* seed = nullptr)
+{
+	const u32 shift = 64u - (u32)__builtin_ctz(newSize);
+	std::vector<u64> image(newSize, ~0ull);
+	if (seed)
+	{
+		for (u64 key : *seed) { u32 h = pairSetHash(key, shift); while (image[h] != ~0ull) h = (h + 1) & (newSize - 1); image[h] = key; }
+		seed->clear();
+	}
+	if (size)
+	{
+		std::vector<u64> old(size);
+		MI_CHECK(hipMemcpyAsync(old.data(), tables[cur ^ 1].p, sizeof(u64) * size, hipMemcpyDeviceToHost, w.stream));
+		MI_CHECK(hipStreamSynchronize(w.stream));
+		for (u64 key : old)
+		{
+			if (key == ~0ull) continue;
+			u32 h = pairSetHash(key, shift);
+			while (image[h] != ~0ull) h = (h + 1) & (newSize - 1);
+			image[h] = key;
+		}
+	}
+	tables[0].ensure(newSize, w.stream); tables[1].ensure(newSize, w.stream);
+	MI_CHECK(hipMemsetAsync(tables[cur].p, 0xFF, sizeof(u64) * newSize, w.stream));
+	MI_CHECK(hipMemcpyAsync(tables[cur ^ 1].p, image.data(), sizeof(u64) * newSize, hipMemcpyHostToDevice, w.stream));
+	MI_CHECK(hipStreamSynchronize(w.stream));
+	size = newSize;
+}
+void World::ensureEventBuffers(u32 numPairs)
+{
+	bool collisions = collisionBeginEvents || collisionEndEvents;
+	if (triggers.empty() && !collisions && fields.empty()) return;
+	if (!fields.empty()) uploadFields(); // the narrowphase's overlap kernel needs the per-body field bits
+	if (!eventRing.p)
+	{
+		if (const char* e = getenv("MI_EVENT_CAPACITY")) eventCap = std::max(16, atoi(e));
+		eventRing.ensure((size_t)eventCap * sizeof(mi_event), stream);
+	}
+	if (!triggers.empty())
+	{
+		u32 want = std::max(4096u, nextPow2(4u * std::max(nb, 1u)));
+		if (hCounters[CTR_EVENT_OVERFLOW] & 2u) want = std::max(want, triggerSetSize * 4u); // a table was full last step
+		want = std::max(want, nextPow2(4u * (u32)restoredTriggerKeys.size()));
+		if (want > triggerSetSize) resizePairSet(*this, triggerSet, triggerSetSize, triggerCur, want, &restoredTriggerKeys);
+	}
+	if (collisions)
+	{
+		u32 want = std::max(4096u, nextPow2(2u * std::max(numPairs, lastNumManifolds * 2u)));
+		want = std::max(want, nextPow2(4u * (u32)restoredCollisionKeys.size()));
+		if (want > collisionSetSize) resizePairSet(*this, collisionSet, collisionSetSize, collisionCur, want, &restoredCollisionKeys);
+	}
 }

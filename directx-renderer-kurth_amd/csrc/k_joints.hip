@@ -1,7 +1,7 @@
 // Joint constraints on the GPU: distance, ball, fixed, hinge, cone-twist, slider — init and sequential-impulse solve, following the
 // SCALAR formulations of the reference (constraints.cpp:189-264, 460-528, 736-823, 1079-1307, 1782-2070, 2638-2846), whose results
 // the 8-wide variants reproduce up to their polynomial trig / rsqrt approximations (SURVEY finding 3).
-// Joints change rarely, so they are greedily coloured on the host when the joint set changes (world.hip) and stored colour-sorted;
+// Joints change rarely, so they are greedily coloured on the host when the joint set changes (World::uploadJoints) and stored colour-sorted;
 // each colour of each type is one launch, one lane per joint.  Per-joint scratch is an AoS record in HBM (joint counts are small:
 // config 4 has 3 328 joints); body state is the same 32-B velocity record + 48-B world inverse inertia the contact path uses.
 #include "world.h"

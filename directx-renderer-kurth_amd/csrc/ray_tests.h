@@ -1,5 +1,5 @@
 // testPhysicsInteraction's ray tests (bounding_volumes.cpp:197-394, 677-705; pointInTriangle: math.cpp:1273-1290) and the push
-// it applies (physics.cpp:556-628), written once for the host entry point mi_test_physics_interaction (world.hip) and the batched
+// it applies (physics.cpp:556-628), written once for the host entry point mi_test_physics_interaction (api.hip) and the batched
 // kernel of mi_test_physics_interaction_batch (k_interact.hip).  Both translation units are compiled with -ffp-contract=off, so the
 // same ray against the same pose gives the same bits on either side.
 #pragma once

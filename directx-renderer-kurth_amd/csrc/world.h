@@ -54,9 +54,12 @@ struct JointSet
 	std::vector<u32> order;               // sorted slot -> joint id
 	std::vector<u32> colorStart;          // size numColors+1
 	u32 count() const { return (u32)a.size(); }
+	u32 numColors() const { return colorStart.empty() ? 0u : (u32)colorStart.size() - 1u; } // = kernels per solver iteration
 };
 
-// Device-side step counters (u32 words of World::dCounters), copied to pinned host memory twice per step.
+// Device-side step counters (u32 words of World::dCounters), copied to pinned host memory twice per step.  The offsets are part of
+// the snapshot / inspection contract (and of the compiled kernels): a new entry takes a free word, nothing moves.  CTR_LAYOUT below
+// holds every entry's extent and is checked at compile time.
 enum
 {
 	CTR_NUM_PAIRS = 0,      // broadphase overlaps
@@ -73,12 +76,18 @@ enum
 	CTR_PAIR_OVERFLOW = 11, // some collider has more broadphase partners than its slab holds
 	CTR_FIRST_INACTIVE = 12,// sorted position of the first collider whose body is simulated by another GPU
 	CTR_FLOW_STATUS = 13,   // cluster sweep: non-zero = the launch could not run or a lane gave up waiting (result invalid): the host redoes the step
+	CTR_FLOW_PROBES = 14,   // always 0: no kernel counts probes any more; the word stays because mi_stats.flowProbes reports it (ABI)
 	CTR_EPA_COUNT_HULL = 15,// GJK hits among the hull pairs (their EPA work list grows from the end of epaList)
-	CTR_FLOW_PROBES = 14,   // unused (kept: the statistics layout has the word)
 	CTR_BUCKET_START = 16,  // 65 words: first slot of narrowphase bucket key b (tA*6+tB); [64] unused
 	CTR_KEY_START = 96,     // (MI_MAX_COLORS+1)*4 + 1 words: first schedule slot of key colour*4 + (4-count); last = numManifolds
 	CTR_COLOR_BARRIER = 360,// 4 words: grid barrier of the fused colouring kernel (arrivals, 3 x manifolds left)
 	CTR_SAP_AXIS = 368,     // 2 words: the reference sweep's sorting axis (collision_broad.cpp:443-444) for internal step k at [k & 1]: written by step k - 1 from its AABB centres, read by k_classify
+	CTR_CL_SCRATCH = 371,   // cluster sweep: append cursor of the global row scratch (contacts that fit neither registers nor LDS), reset before every launch
+	CTR_CL_LEFT = 372,      // 5 words: cluster build: manifolds left over by the curve phases (cursor of the list the component phase works on); statistics of the component phase: tasks, total weight, manifolds whose ends disagree, weight of the largest component sent to the rest task
+	CTR_ACTIVE_BODIES = 377, // simulated bodies / their colliders + the static ones (lengths of the active lists, k_active_scan); more of the latter than the broadphase was launched for
+	CTR_ACTIVE_COLS = 378,
+	CTR_ACTIVE_OVERFLOW = 379,
+	CTR_CELL_SIZE_USED = 380, // float bits: the cell size the current sorted order was built with (CTR_CELL_SIZE is reset for the next step's atomicMax before the last pair kernel runs)
 	CTR_EVENT_COUNT = 416,  // append cursor of the event ring (trigger enter/leave, collision begin/end), reset by mi_drain_events
 	CTR_EVENT_OVERFLOW = 417,// bit 0: the event ring was full, events were dropped; bit 1: a pair-set table was full
 	CTR_TERRAIN_BASE = 418, // first manifold slot of the terrain contacts (= number of pair manifold slots)
@@ -88,17 +97,22 @@ enum
 	CTR_CL_SHARED = 430,    // statistics: bodies handed between tasks (summed over tasks)
 	CTR_CL_PHASE_COUNT = 431,// 5 words: statistics: manifolds per phase
 	CTR_CL_BBOX = 436,      // 6 words: min xyz, max xyz of the simulated bodies' centres of gravity (order-preserving integer encoding)
-	CTR_CL_LEFT = 372,      // 5 words: cluster build: manifolds left over by the curve phases (cursor of the list the component phase works on); statistics of the component phase: tasks, total weight, manifolds whose ends disagree, weight of the largest component sent to the rest task
-	CTR_ACTIVE_BODIES = 377, // simulated bodies / their colliders + the static ones (lengths of the active lists, k_active_scan); more of the latter than the broadphase was launched for
-	CTR_ACTIVE_COLS = 378,
-	CTR_ACTIVE_OVERFLOW = 379,
-	CTR_CELL_SIZE_USED = 380, // float bits: the cell size the current sorted order was built with (CTR_CELL_SIZE is reset for the next step's atomicMax before the last pair kernel runs)
-	CTR_CL_SCRATCH = 371,   // cluster sweep: append cursor of the global row scratch (contacts that fit neither registers nor LDS), reset before every launch
+	CTR_CL_REMAIN = 442,    // 6 words: manifolds still unassigned when partition phase p starts ([0] unused: all active ones)
 	CTR_VALIDATE = 448,     // 2 words: non-finite values found by the debug guard (MI_PHYSICS_VALIDATE=1), first offender (stage << 28 | index)
 	CTR_NARROW_LIMITS = 450,// 5 words: high-water marks of the GJK / EPA caps since the world was created (k_gjk, k_epa): GJK iterations, EPA triangles, edges, border edges; EPA runs that left through an out-of-memory exit (mi_debug_narrow_limits)
-	CTR_CL_REMAIN = 442,    // 6 words: manifolds still unassigned when partition phase p starts ([0] unused: all active ones)
 	CTR_WORDS = 512,
 };
+struct CtrRange { u32 first, words; };
+static constexpr CtrRange CTR_LAYOUT[] = // every entry of the enum, ascending
+{
+	{ CTR_NUM_PAIRS, 1 }, { CTR_NUM_VALID, 1 }, { CTR_NUM_MANIFOLDS, 1 }, { CTR_EPA_COUNT, 1 }, { CTR_NUM_COLORS, 1 }, { CTR_FIRST_LARGE, 1 }, { CTR_LAST_ROUND, 1 }, { CTR_OVERFLOW, 1 },
+	{ CTR_CELL_SIZE, 1 }, { CTR_NUM_ACTIVE, 1 }, { CTR_NUM_CONTACTS, 1 }, { CTR_PAIR_OVERFLOW, 1 }, { CTR_FIRST_INACTIVE, 1 }, { CTR_FLOW_STATUS, 1 }, { CTR_FLOW_PROBES, 1 }, { CTR_EPA_COUNT_HULL, 1 },
+	{ CTR_BUCKET_START, 65 }, { CTR_KEY_START, (MI_MAX_COLORS + 1) * 4 + 1 }, { CTR_COLOR_BARRIER, 4 }, { CTR_SAP_AXIS, 2 }, { CTR_CL_SCRATCH, 1 }, { CTR_CL_LEFT, 5 },
+	{ CTR_ACTIVE_BODIES, 1 }, { CTR_ACTIVE_COLS, 1 }, { CTR_ACTIVE_OVERFLOW, 1 }, { CTR_CELL_SIZE_USED, 1 }, { CTR_EVENT_COUNT, 1 }, { CTR_EVENT_OVERFLOW, 1 }, { CTR_TERRAIN_BASE, 1 }, { CTR_TERRAIN_OVERFLOW, 1 },
+	{ CTR_CL_NUM_TASKS, 5 }, { CTR_CL_STATUS, 1 }, { CTR_CL_SHARED, 1 }, { CTR_CL_PHASE_COUNT, 5 }, { CTR_CL_BBOX, 6 }, { CTR_CL_REMAIN, 6 }, { CTR_VALIDATE, 2 }, { CTR_NARROW_LIMITS, 5 },
+};
+constexpr bool ctrLayoutDisjoint() { u32 end = 0; for (const CtrRange& r : CTR_LAYOUT) { if (r.first < end) return false; end = r.first + r.words; } return end <= CTR_WORDS; }
+static_assert(ctrLayoutDisjoint(), "CTR_*: an entry reaches into the next one (or past CTR_WORDS), or CTR_LAYOUT is not in ascending order");
 // Cluster sweep (k_cluster.hip): up to CL_MAX_PARTS partition phases + the rest phase; task key = phase * CL_MAX_TASKS + task.
 #define MI_REPLAY_WIDTH 8u // lanes of the reference's SIMD batches (constraints.cpp: CONSTRAINT_SIMD_WIDTH with AVX)
 #define CL_MAX_PARTS 4u
@@ -109,6 +123,22 @@ enum
 #define CL_MAX_JOINT_CLASSES 64u   // (type, colour) classes of joints the cluster sweep can run
 #define CL_TASK_MAX_JOINTS 512u    // joints per task (one lane each)
 #define MI_NUM_SCHEDULE_KEYS ((MI_MAX_COLORS + 1) * 4)
+
+// What the host knows about the last internal step.  The step after it is launched before the host has seen how it ended, so this
+// is what that step (and every entry point that synchronises in between) settles, counts or redoes it from.  Written as a whole
+// by World::stepInternal once the step's solve is enqueued; afterwards only `unsettled` and `counted` are ticked off, and a
+// recovery (World::recoverFlow) corrects `cluster` and `jointPath` to what finally solved the step.
+struct StepRecord
+{
+	u32 numPairs = 0, truePairs = 0;   // bound on its manifold slots (pair slots + room for the terrain contacts) / its broadphase overlaps
+	bool slabOverflow = false;         // its CTR_PAIR_OVERFLOW
+	u32 axis = 0;                      // its sorting axis (CTR_SAP_AXIS of its parity): its narrowphase is run again with it before a redo
+	float dt = 0.f; u32 iters = 0;     // what a redo of its solve + integration needs
+	bool cluster = false;              // solved by the cluster sweep (its pre-solve velocities are in velBackup)
+	bool unsettled = false;            // ... which is not yet known to have completed (CTR_FLOW_STATUS not looked at)
+	u32 jointPath = MI_JOINT_PATH_NONE;// where it solved its joints (mi_debug_read_joint_update)
+	bool counted = true;               // its counts are in the running sums (nothing to count before the first step)
+};
 
 struct World
 {
@@ -127,9 +157,6 @@ struct World
 	std::vector<uint16_t> hTerrainHeights; std::vector<u32> hTerrainValid;
 	DevBuf<uint16_t> terrainHeights; DevBuf<u32> terrainValid, terrainCounts, terrainOffsets;
 	u32 terrainSlotCap() const { return terrainChunksPerDim ? std::max(terrainMinSlots, terrainSlotsPerCollider * (u32)colliders.size()) : 0u; }
-	u32 prevTruePairs = 0;                // broadphase overlaps of the last step (prevNumPairs counts the terrain slots too)
-	bool prevSlabOverflow = false;        // CTR_PAIR_OVERFLOW of the last step
-	u32 stepAxis = 0;                     // sorting axis of the last step (CTR_SAP_AXIS of its parity): the narrowphase of a recovered step is run again with it
 	hipEvent_t countersEvent = nullptr;   // behind the step's asynchronous read of the counters
 	// cloth_component (cloth.h:5-60): parameters + host mirror of the particle state (authoritative until the first step; refreshed by downloadCloths)
 	struct HClothConstraint { u32 a, b; float restDistance, inverseMassSum; u32 color; };
@@ -153,6 +180,8 @@ struct World
 	struct HHull { std::vector<float> vertices; std::vector<u32> triangles; float aabbMin[3], aabbMax[3]; }; // bounding_hull_geometry (bounding_volumes.h:208-218)
 	std::vector<HHull> hulls;
 	JointSet joints[MI_JOINT_TYPES];
+	u32 numJointKernels() const { u32 n = 0; for (const JointSet& js : joints) n += js.numColors(); return n; }      // launches of one joint iteration
+	u32 numSortedJoints() const { u32 n = 0; for (const JointSet& js : joints) n += (u32)js.order.size(); return n; } // live joints (as of the last uploadJoints)
 	bool topologyDirty = true;   // bodies/colliders added since last upload
 	bool jointsDirty = true;
 	bool stateOnDevice = false;  // device holds the authoritative pose/velocity
@@ -191,8 +220,6 @@ struct World
 	bool replayReferenceOrder = false; DevBuf<u32> replayEntries; std::vector<u32> replayHost; u32 replayBatches = 0;
 	u32 scheduleReferenceBatches(const std::vector<uint4>& ids, u32 numPositions);
 	bool useCluster = true;               // MI_PHYSICS_NO_CLUSTER=1: launch-per-colour sweep only
-	bool lastStepCluster = false, backupVelocities = false;
-	u32 lastJointPath = 3;                // where the last step solved its joints (MI_JOINT_PATH_*, mi_debug_read_joint_update)
 	u32 clusterBlocksLimit = 0, clusterFailStreak = 0, clusterTaskWeight = 64u * 1000u, clusterTaskWeightLater = 64u * 500u; // MI_CLUSTER_BLOCKS / _TASK / _TASK_LATER
 	bool clusterSortDue = true; u32 clusterSortAge = 0, clusterSortBodies = 0; // body order along the curves: refreshed every few steps
 	u32 clusterLdsBytes = 0, clusterBlocks = 0, clusterCooldown = 0;
@@ -213,7 +240,7 @@ struct World
 	// Safety net of the persistent kernels: if one gives up waiting (only possible when the GPU is shared with another persistent
 	// kernel), the step's velocity integration is skipped on the device and the host redoes solve + integration with the launch
 	// sweep from the saved pre-solve velocities, at the next point where it synchronises anyway.
-	DevBuf<float4> velBackup; bool flowPending = false; float pendingDt = 0.f; u32 pendingIters = 0, flowTestAbortStep = ~0u;
+	DevBuf<float4> velBackup; u32 flowTestAbortStep = ~0u;
 	void recoverFlow(); int resolvePendingFlow();
 	// force fields, triggers, events
 	DevBuf<float4> fieldForce;            // per field: world-space force (localized fields only; global ones are summed on the host into globalForce)
@@ -236,6 +263,7 @@ struct World
 	bool forceFullColoring = true;
 	u32 lastNumManifolds = 0;    // sizes the colouring-round launches of the next step
 	mi_stats stats = {};
+	StepRecord last;
 	// Stage timing: HIP events of the last STAGE_RING timed steps, read back without stalling every step (mi_get_stats harvests them)
 	static const u32 STAGE_RING = 32;
 	std::vector<hipEvent_t> stageEvents;  // STAGE_RING x 6
@@ -243,7 +271,7 @@ struct World
 	bool timeStages = false;
 	void harvestTiming();
 	// Counts of the steps since the last mi_get_stats (the host learns a step's counts at its next synchronisation)
-	double sumContacts = 0, sumManifolds = 0, sumColors = 0, sumPairs = 0, sumProbes = 0; u32 sumSteps = 0, countedStep = 0, prevNumPairs = 0;
+	double sumContacts = 0, sumManifolds = 0, sumColors = 0, sumPairs = 0, sumProbes = 0; u32 sumSteps = 0;
 	void countPreviousStep(); void refreshCounters();
 	u32 jointVersion = 0;                 // bumped by every upload of the joints
 	// Device-written joint PODs (mi_joint_device_pods): once a caller has the device array, JointSet::dPods is authoritative and
@@ -267,6 +295,11 @@ struct World
 	int step(float* timer, const mi_physics_settings* s, float dt);
 };
 
+extern thread_local World* g_currentWorld;                 // the world MI_CHECK reports a HIP error to: set by every entry point (world.hip)
+static inline u32 nextPow2(u32 v) { u32 p = 1; while (p < v) p <<= 1; return p; }
+void recalculateProperties(World& w, World::HBody& rb);    // mass, centre of gravity and inertia of a body from its colliders (world.hip)
+void ensurePairBuffers(World& w, size_t numPairs);         // every buffer sized by the pair count (step.hip)
+
 // ---- launchers (one per stage; each defined next to its kernels) --------------------------------------------------
 void launch_active_lists(World& w);                        // (re)builds the lists of simulated bodies / colliders if the simulate mask may have changed
 void launch_restore_velocities(World& w);                  // velocities of the simulated bodies <- velBackup
@@ -276,7 +309,7 @@ void launch_broadphase_count(World& w);                    // grid build + pair 
 void launch_broadphase_write(World& w, u32 numPairs, bool slabOverflow);       // slabOverflow: some collider has more partners than its slab holds (CTR_PAIR_OVERFLOW)
 void launch_narrowphase(World& w, u32 numPairs, u32 stepParity); // numPairs may exceed the device's pair count (a launch sized before the host knows it); stepParity: the internal step's k & 1 (its sorting-axis word)
 void launch_zone_overlap(World& w, u32 numPairs);           // force-field / trigger overlap tests on the classified pairs (once per step)
-void launch_integrate_forces(World& w, float dt);
+void launch_integrate_forces(World& w, float dt, bool backupVelocities); // backupVelocities: keep the pre-solve velocities in velBackup (a cluster step)
 void launch_heightmap(World& w, u32 numPairs, u32 slotCap);  // terrain contacts appended after the pair manifolds (physics.cpp:1236-1249)
 void launch_cloth(World& w, float dt);                      // cloth_component::applyWindForce + simulate for every cloth (physics.cpp:1354-1358)
 u32 cloth_lds_particle_limit();

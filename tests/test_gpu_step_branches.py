@@ -58,7 +58,7 @@ def _set_mask(g, o, mask):
 def test_active_list_growth_follows_the_oracle(mi, oracle, grow_to):
     """c3_small (3 001 colliders) simulated in full, then only a compact block of 350 bodies for 3 steps, then `grow_to` bodies
     around the same block again (None: all).  In the step after the switch the active collider list is longer than the last known
-    length + 12 % + 2 048, so the step repeats its broadphase with the right bound (world.hip: CTR_ACTIVE_OVERFLOW) — from the
+    length + 12 % + 2 048, so the step repeats its broadphase with the right bound (step.hip: CTR_ACTIVE_OVERFLOW) — from the
     rebuilt cell size and bucket sizes; every step follows the masked oracle exactly."""
     from directx_renderer_kurth_amd import scenes
     scene = scenes.by_name("c3_small")
