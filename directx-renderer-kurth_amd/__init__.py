@@ -98,7 +98,9 @@ LOCOMOTION_SYMBOLS = ["getPhysicsStateSize", "getPhysicsActionSize", "getPhysics
                       "resetPhysicsBatch", "updatePhysicsBatch", "updatePhysicsBatchDevice", "resetPhysicsBatchEnvs", "observePhysicsBatch",
                       "getPhysicsBatchWorld", "getPhysicsBatchStream", "getPhysicsBatchPushes",
                       "setPhysicsPolicy", "inferPhysicsPolicy", "updatePhysicsPolicy", "inferPhysicsBatchDevice", "updatePhysicsBatchPolicy",
-                      "updatePhysicsBatchPolicyDevice", "rolloutPhysicsBatchDevice"]
+                      "updatePhysicsBatchPolicyDevice", "rolloutPhysicsBatchDevice",
+                      "setPhysicsValueNetwork", "inferPhysicsValue", "inferPhysicsBatchValueDevice", "setPhysicsActionStd", "samplePhysicsBatchNoiseDevice",
+                      "samplePhysicsNoise", "samplePhysicsNoiseUniforms", "getPhysicsBatchNoiseCounter", "collectPhysicsBatchDevice", "gaePhysicsBatchDevice"]
 _HIPCC = "/opt/rocm/bin/hipcc"
 
 
@@ -542,8 +544,11 @@ class _BorrowedWorld(World):
 
 POLICY_NAMES = ("mlp_extractor.policy_net.0.weight", "mlp_extractor.policy_net.0.bias", "mlp_extractor.policy_net.2.weight",
                 "mlp_extractor.policy_net.2.bias", "action_net.weight", "action_net.bias")
+VALUE_NAMES = ("mlp_extractor.value_net.0.weight", "mlp_extractor.value_net.0.bias", "mlp_extractor.value_net.2.weight",
+               "mlp_extractor.value_net.2.bias", "value_net.weight", "value_net.bias")
 _locomotion_lib = None
 _policy_hidden = 0  # H of the policy the library holds (it holds one, for the single environment and the batch)
+_value_hidden = 0   # Hv of the critic it holds
 
 
 def _load_locomotion():
@@ -554,23 +559,28 @@ def _load_locomotion():
         lib.setPhysicsSeed.argtypes = [C.c_ulonglong]
         lib.getPhysicsBatchWorld.restype = C.c_void_p
         lib.getPhysicsBatchStream.restype = C.c_void_p
+        lib.getPhysicsBatchNoiseCounter.restype = C.c_ulonglong
+        lib.samplePhysicsNoise.argtypes = [C.c_ulonglong, C.c_uint32, C.c_ulonglong, C.c_void_p]
+        lib.samplePhysicsBatchNoiseDevice.argtypes = [C.c_ulonglong, C.c_uint32, C.c_void_p]
+        lib.gaePhysicsBatchDevice.argtypes = [C.c_uint32, C.c_uint32, C.c_float, C.c_float] + [C.c_void_p] * 6
         _locomotion_lib = lib
     return _locomotion_lib
 
 
-def _policy_arrays(args):
+def _policy_arrays(args, names=POLICY_NAMES, outputs=27):
     """The six arrays W1 [H, 66], b1 [H], W2 [H, H], b2 [H], W3 [27, H], b3 [27] as contiguous float32, shapes checked; `args` is the
-    six of them, or one mapping with the stable-baselines names (POLICY_NAMES) whose values are arrays or tensors."""
+    six of them, or one mapping with the stable-baselines names (POLICY_NAMES) whose values are arrays or tensors.  With VALUE_NAMES
+    and outputs=1: the critic's."""
     if len(args) == 1 and hasattr(args[0], "keys"):
-        args = [args[0][k] for k in POLICY_NAMES]
+        args = [args[0][k] for k in names]
     if len(args) != 6:
-        raise ValueError("a policy is six arrays: w1, b1, w2, b2, w3, b3")
+        raise ValueError("a network is six arrays: w1, b1, w2, b2, w3, b3")
     arrays = [np.ascontiguousarray(a.detach().cpu().numpy() if hasattr(a, "detach") else a, dtype=np.float32) for a in args]
     h = arrays[1].size
-    shapes = [(h, 66), (h,), (h, h), (h,), (27, h), (27,)]
+    shapes = [(h, 66), (h,), (h, h), (h,), (outputs, h), (outputs,)]
     for a, shape in zip(arrays, shapes):
         if a.shape != shape:
-            raise ValueError("policy array of shape %s where %s is expected" % (a.shape, shape))
+            raise ValueError("network array of shape %s where %s is expected" % (a.shape, shape))
     return h, arrays
 
 
@@ -593,6 +603,49 @@ def infer_policy(state, hidden=False):
     if code:
         raise PhysicsError("inferPhysicsPolicy failed (%d)" % code)
     return (action, ab[:_policy_hidden], ab[_policy_hidden:]) if hidden else action
+
+
+def set_value_network(*args):
+    """setPhysicsValueNetwork: the critic 66 -> Hv -> Hv -> 1 (tanh) of training: six arrays w1 [Hv, 66], b1, w2 [Hv, Hv], b2, w3 [1, Hv],
+    b3 [1], or one mapping with the stable-baselines names (VALUE_NAMES)."""
+    global _value_hidden
+    h, arrays = _policy_arrays(args, VALUE_NAMES, 1)
+    code = _load_locomotion().setPhysicsValueNetwork(C.c_uint32(h), *[_p(a) for a in arrays])
+    if code:
+        raise PhysicsError("setPhysicsValueNetwork failed (%d)" % code)
+    _value_hidden = h
+
+
+def infer_value(state, hidden=False):
+    """inferPhysicsValue: the critic on one state [66], on the host.  Returns the value, with hidden also (tanh(z1), tanh(z2))."""
+    state = np.ascontiguousarray(state, np.float32).reshape(66)
+    value = np.zeros(1, np.float32)
+    ab = np.zeros(2 * max(_value_hidden, 1), np.float32)
+    code = _load_locomotion().inferPhysicsValue(_p(state), _p(value), _p(ab) if hidden else None)
+    if code:
+        raise PhysicsError("inferPhysicsValue failed (%d)" % code)
+    return (value[0], ab[:_value_hidden], ab[_value_hidden:]) if hidden else value[0]
+
+
+def set_log_std(log_std):
+    """setPhysicsActionStd: the Gaussian's per-action log-scale [27] (a scalar is broadcast); the library receives it together with
+    std = float32(exp(float64(log_std))) and evaluates neither."""
+    if hasattr(log_std, "detach"):
+        log_std = log_std.detach().cpu().numpy()
+    log_std = np.ascontiguousarray(np.broadcast_to(np.asarray(log_std, np.float32), (27,)))
+    std = np.exp(log_std.astype(np.float64)).astype(np.float32)
+    code = _load_locomotion().setPhysicsActionStd(_p(std), _p(log_std))
+    if code:
+        raise PhysicsError("setPhysicsActionStd failed (%d)" % code)
+
+
+def sample_noise(seed, env, update):
+    """samplePhysicsNoise: the exploration noise [27] of environment `env` at update counter `update` under `seed`, on the host."""
+    out = np.zeros(27, np.float32)
+    code = _load_locomotion().samplePhysicsNoise(C.c_ulonglong(seed), C.c_uint32(env), C.c_ulonglong(update), _p(out))
+    if code:
+        raise PhysicsError("samplePhysicsNoise failed (%d)" % code)
+    return out
 
 
 def update_policy():
@@ -692,6 +745,91 @@ class LocomotionBatch:
             torch.cuda.synchronize(dev)
             out = tuple(t.cpu().numpy() for t in out)
         return out if hidden else out[0]
+
+    # ---- training data (k_loco_sample, k_loco_value, k_loco_gae) ----
+    def set_value_network(self, *args):
+        """The critic: six arrays w1 [Hv, 66], b1, w2 [Hv, Hv], b2, w3 [1, Hv], b3 [1], or one mapping with the stable-baselines names
+        (VALUE_NAMES).  Hv is independent of the policy's H; the library keeps it across reset()."""
+        set_value_network(*args)
+
+    def set_log_std(self, log_std):
+        """The log of the per-action scale of the Gaussian that collect() samples from ([27], or a scalar)."""
+        set_log_std(log_std)
+
+    @property
+    def value_hidden(self):
+        return _value_hidden
+
+    @property
+    def noise_counter(self):
+        """Collecting updates since reset(): the update counter the next collect() starts at."""
+        return int(self.lib.getPhysicsBatchNoiseCounter())
+
+    def _device(self):
+        import torch
+        return torch.device("cuda", torch.cuda.current_device())
+
+    def values(self, states, hidden=False):
+        """The critic on `states` [count, 66], like act(): numpy in, numpy out; ROCm tensor in, tensors out.  Returns the values [count];
+        with hidden=True (values, a [count, Hv], b [count, Hv])."""
+        import torch
+        if not self.value_hidden:
+            raise PhysicsError("values: no value network set")
+        on_device = hasattr(states, "is_cuda") and states.is_cuda
+        s = states.detach() if on_device else torch.from_numpy(np.ascontiguousarray(states, np.float32)).cuda()
+        s = s.to(torch.float32).contiguous().reshape(-1, self.state_size)
+        count, dev, hv = s.shape[0], s.device, self.value_hidden
+        values = torch.empty(count, dtype=torch.float32, device=dev)
+        ab = torch.empty((count, 2 * hv), dtype=torch.float32, device=dev) if hidden else None
+        code = self._on_stream(dev, [t for t in (s, values, ab) if t is not None], lambda: self.lib.inferPhysicsBatchValueDevice(
+            C.c_uint32(count), C.c_void_p(s.data_ptr()), C.c_void_p(values.data_ptr()), C.c_void_p(ab.data_ptr()) if hidden else None))
+        self._check(code, "inferPhysicsBatchValueDevice")
+        out = (values, ab[:, :hv], ab[:, hv:]) if hidden else (values,)
+        if not on_device:
+            torch.cuda.synchronize(dev)
+            out = tuple(t.cpu().numpy() for t in out)
+        return out if hidden else out[0]
+
+    def noise(self, first_update, num_updates):
+        """The exploration noise of update counters first_update .. first_update + num_updates - 1 as a ROCm tensor [num_updates, n, 27]:
+        what collect() draws there.  A function of (seed, environment, counter, action index) alone; moves no state."""
+        import torch
+        dev = self._device()
+        eps = torch.empty((num_updates, self.n, self.action_size), dtype=torch.float32, device=dev)
+        code = self._on_stream(dev, (eps,), lambda: self.lib.samplePhysicsBatchNoiseDevice(C.c_ulonglong(first_update), C.c_uint32(num_updates), C.c_void_p(eps.data_ptr())))
+        self._check(code, "samplePhysicsBatchNoiseDevice")
+        return eps
+
+    def collect(self, steps, clip=True):
+        """`steps` closed-loop updates with actions sampled around the policy's output, enqueued back to back with the device-side reset
+        of the fallen.  Returns a dict of ROCm tensors; row t: obs [steps, n, 66] the states the networks saw (after a fall the reset
+        state), actions [steps, n, 27] = mu + std * eps (unclipped), eps, log_probs [steps, n], values [steps, n] = V(obs), rewards and
+        dones (int32) after the update; last_values [n] = V of the states after the last update.  With clip the environment receives the
+        action clamped to the action ranges, as stable-baselines clips to the environment's Box."""
+        import torch
+        dev = self._device()
+        new = lambda *shape, dtype=torch.float32: torch.empty(shape, dtype=dtype, device=dev)
+        out = dict(obs=new(steps, self.n, self.state_size), actions=new(steps, self.n, self.action_size), eps=new(steps, self.n, self.action_size),
+                   log_probs=new(steps, self.n), values=new(steps, self.n), rewards=new(steps, self.n), dones=new(steps, self.n, dtype=torch.int32),
+                   last_values=new(self.n))
+        code = self._on_stream(dev, tuple(out.values()), lambda: self.lib.collectPhysicsBatchDevice(
+            C.c_uint32(steps), C.c_int(1 if clip else 0), *[C.c_void_p(t.data_ptr()) for t in out.values()]))
+        self._check(code, "collectPhysicsBatchDevice")
+        return out
+
+    def gae(self, rewards, values, dones, last_values, gamma=0.99, lam=0.95):
+        """Generalised advantage estimation on [steps, n] ROCm tensors (dones int32), on the device.  Returns (advantages, returns).
+        Episodes end by falling only: a done row bootstraps nothing."""
+        import torch
+        r = rewards.detach().to(torch.float32).contiguous(); v = values.detach().to(torch.float32).contiguous()
+        d = dones.detach().to(torch.int32).contiguous(); last = last_values.detach().to(torch.float32).contiguous()
+        steps, n = r.shape
+        assert v.shape == d.shape == (steps, n) and last.shape == (n,)
+        advantages = torch.empty_like(r); returns = torch.empty_like(r)
+        code = self._on_stream(r.device, (r, v, d, last, advantages, returns), lambda: self.lib.gaePhysicsBatchDevice(
+            C.c_uint32(steps), C.c_uint32(n), C.c_float(gamma), C.c_float(lam), *[C.c_void_p(t.data_ptr()) for t in (r, v, d, last, advantages, returns)]))
+        self._check(code, "gaePhysicsBatchDevice")
+        return advantages, returns
 
     def step_policy(self, device=False):
         """One closed-loop update: the policy on the current states, smoothing, motors, push, step.  Returns (states, rewards, fallen) as

@@ -13,6 +13,11 @@
 // launches as one driven by given actions.  dStates always holds the state of every environment as it is now (what
 // observePhysicsBatch returns): every entry point that moves the environments refreshes it.  rolloutPhysicsBatchDevice enqueues
 // whole trajectories, with the fallen environments reset from their flags on the device.
+//
+// Training data (learning/learn_locomotion.py:71-107, PPO) is collected the same way: collectPhysicsBatchDevice runs the rollout's
+// updates with k_loco_sample in place of k_loco_policy, which adds the critic, the exploration noise (locomotion_policy.h:
+// noiseSample), the sampled action, its log-probability and the clamp to the action ranges in the same launch.  The advantages of
+// gaePhysicsBatchDevice come from one lane per environment walking the rows backwards.  The gradient step is not here.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <vector>
@@ -46,6 +51,11 @@ namespace
 		float* dActions = nullptr; float* dStates = nullptr; float* dRewards = nullptr; int32_t* dFallen = nullptr; uint32_t* dIds = nullptr;
 		float* dPolicy = nullptr;     // the policy, transposed to [in][out]: W1T, b1, W2T, b2, W3T, b3 back to back
 		uint32_t hidden = 0;          // 0: no policy uploaded
+		float* dValueNet = nullptr;   // the critic, transposed like the policy: W1T, b1, W2T, b2, W3T (= w3), b3
+		uint32_t valueHidden = 0;     // 0: no critic uploaded
+		float* dScales = nullptr;     // 4 x 27: std, logStd, actionMin, actionMax
+		bool stdSet = false, rangesSet = false;
+		uint64_t noiseCounter = 0;    // collecting updates since resetPhysicsBatch
 		void* pods[2] = { nullptr, nullptr }; // cone-twist, hinge
 		uint32_t generation[2] = { ~0u, ~0u };
 	};
@@ -57,7 +67,7 @@ namespace
 	{
 		if (!b) return;
 		if (b->stream) (void)hipStreamSynchronize(b->stream);
-		void* bufs[] = { b->dInit, b->dSmoothed, b->dRng, b->dRays, b->dPushes, b->dSlots, b->dActions, b->dStates, b->dRewards, b->dFallen, b->dIds, b->dPolicy };
+		void* bufs[] = { b->dInit, b->dSmoothed, b->dRng, b->dRays, b->dPushes, b->dSlots, b->dActions, b->dStates, b->dRewards, b->dFallen, b->dIds, b->dPolicy, b->dValueNet, b->dScales };
 		for (void* p : bufs) if (p) (void)hipFree(p);
 		if (b->world) mi_world_destroy(b->world);
 		delete b;
@@ -167,6 +177,154 @@ namespace
 		}
 	}
 	static_assert(POLICY_TILE * NUM_MOTOR_JOINTS <= 64 && ACTION_SIZE <= 64, "one wave covers the tile's joints and actions");
+
+	struct network { const float* w1; const float* b1; const float* w2; const float* b2; const float* w3; const float* b3; };
+	__device__ network networkOf(const float* __restrict__ p, uint32_t hidden, uint32_t outputs)
+	{
+		network n;
+		n.w1 = p; n.b1 = n.w1 + (size_t)STATE_SIZE * hidden;
+		n.w2 = n.b1 + hidden; n.b2 = n.w2 + (size_t)hidden * hidden;
+		n.w3 = n.b2 + hidden; n.b3 = n.w3 + (size_t)hidden * outputs;
+		return n;
+	}
+
+	// The tile's states into LDS as [in][tile]; rows past count read as zeros.  copy (may be null) receives the rows as they were read.
+	__device__ void loadTile(float4* input, const float* __restrict__ states, float* __restrict__ copy, uint32_t first, uint32_t count)
+	{
+		for (uint32_t i = threadIdx.x; i < POLICY_TILE * STATE_SIZE; i += blockDim.x)
+		{
+			const uint32_t r = i / STATE_SIZE, x = i % STATE_SIZE;
+			const float v = first + r < count ? states[(size_t)STATE_SIZE * (first + r) + x] : 0.f;
+			((float*)input)[POLICY_TILE * x + r] = v;
+			if (copy && first + r < count) copy[(size_t)STATE_SIZE * (first + r) + x] = v;
+		}
+	}
+
+	// Kernel V: the critic alone, 66 -> Hv -> Hv -> 1, for a tile of POLICY_TILE rows per workgroup.  blockDim.x >= max(hidden, 64), a
+	// multiple of 64.  hiddenOut (count x 2Hv) may be null.
+	__global__ void __launch_bounds__(POLICY_MAX_HIDDEN) k_loco_value(uint32_t count, uint32_t hidden, const float* __restrict__ states, const float* __restrict__ valueNet,
+		float* __restrict__ valuesOut, float* __restrict__ hiddenOut)
+	{
+		__shared__ float4 input[STATE_SIZE], hiddenA[POLICY_MAX_HIDDEN], hiddenB[POLICY_MAX_HIDDEN];
+		const uint32_t first = blockIdx.x * POLICY_TILE, t = threadIdx.x;
+		const network v = networkOf(valueNet, hidden, 1);
+		loadTile(input, states, nullptr, first, count);
+		__syncthreads();
+		const float4 a = policyLayer(v.w1, v.b1, STATE_SIZE, hidden, input, t, true);
+		if (t < hidden) hiddenA[t] = a;
+		__syncthreads();
+		const float4 b = policyLayer(v.w2, v.b2, hidden, hidden, hiddenA, t, true);
+		if (t < hidden) hiddenB[t] = b;
+		__syncthreads();
+		const float4 out = policyLayer(v.w3, v.b3, hidden, 1, hiddenB, t, false);
+		const float av[POLICY_TILE] = { a.x, a.y, a.z, a.w }, bv[POLICY_TILE] = { b.x, b.y, b.z, b.w }, ov[POLICY_TILE] = { out.x, out.y, out.z, out.w };
+		#pragma unroll
+		for (uint32_t r = 0; r < POLICY_TILE; ++r)
+		{
+			const uint32_t e = first + r;
+			if (e >= count) continue;
+			if (hiddenOut && t < hidden) { hiddenOut[(size_t)2 * hidden * e + t] = av[r]; hiddenOut[(size_t)2 * hidden * e + hidden + t] = bv[r]; }
+			if (t == 0) valuesOut[e] = ov[r];
+		}
+	}
+
+	// Kernel S: the collecting update of a tile of POLICY_TILE environments, everything before the push in one launch: the actor and
+	// the critic on the current states (layer by layer side by side, both pairs of hidden vectors in LDS), the noise, the sample
+	// a = mu + std * eps, its log-probability, the clamp to the action ranges (clip != 0), smoothAction and the motor PODs.
+	// blockDim.x >= max(hidden, valueHidden, 64), a multiple of 64.  Row outputs: obs (the states as read), actions (unclipped), eps
+	// (may be null), logProbs, values.  The last layers run on different waves where there are two: actor on lanes 0..26, critic on
+	// lane 64 (lane 32 in a one-wave block).
+	__global__ void __launch_bounds__(POLICY_MAX_HIDDEN) k_loco_sample(uint32_t count, uint32_t hidden, uint32_t valueHidden, int clip, uint64_t seed, uint64_t update,
+		const float* __restrict__ states, const float* __restrict__ policy, const float* __restrict__ valueNet, const float* __restrict__ scales,
+		float* __restrict__ obsOut, float* __restrict__ actionsOut, float* __restrict__ epsOut, float* __restrict__ logProbsOut, float* __restrict__ valuesOut,
+		float* __restrict__ smoothedAll, const uint32_t* __restrict__ slots, uint8_t* conePods, uint8_t* hingePods)
+	{
+		__shared__ float4 input[STATE_SIZE], hiddenA[POLICY_MAX_HIDDEN], hiddenB[POLICY_MAX_HIDDEN], valueA[POLICY_MAX_HIDDEN], valueB[POLICY_MAX_HIDDEN];
+		__shared__ float smoothed[POLICY_TILE][ACTION_SIZE], eps[POLICY_TILE][ACTION_SIZE];
+		const uint32_t first = blockIdx.x * POLICY_TILE, t = threadIdx.x;
+		const network p = networkOf(policy, hidden, ACTION_SIZE), v = networkOf(valueNet, valueHidden, 1);
+		loadTile(input, states, obsOut, first, count);
+		for (uint32_t i = t; i < POLICY_TILE * ACTION_SIZE; i += blockDim.x)
+		{
+			const uint32_t r = i / ACTION_SIZE, j = i % ACTION_SIZE;
+			eps[r][j] = first + r < count ? noiseSample(seed, first + r, update, j) : 0.f;
+		}
+		__syncthreads();
+		const float4 a = policyLayer(p.w1, p.b1, STATE_SIZE, hidden, input, t, true);
+		const float4 va = policyLayer(v.w1, v.b1, STATE_SIZE, valueHidden, input, t, true);
+		if (t < hidden) hiddenA[t] = a;
+		if (t < valueHidden) valueA[t] = va;
+		__syncthreads();
+		const float4 b = policyLayer(p.w2, p.b2, hidden, hidden, hiddenA, t, true);
+		const float4 vb = policyLayer(v.w2, v.b2, valueHidden, valueHidden, valueA, t, true);
+		if (t < hidden) hiddenB[t] = b;
+		if (t < valueHidden) valueB[t] = vb;
+		__syncthreads();
+		const uint32_t valueLane = blockDim.x > 64 ? 64 : 32;
+		const float4 out = policyLayer(p.w3, p.b3, hidden, ACTION_SIZE, hiddenB, t, false);
+		const float4 value = policyLayer(v.w3, v.b3, valueHidden, 1, valueB, t - valueLane, false); // t < valueLane wraps: no unit
+		const float ov[POLICY_TILE] = { out.x, out.y, out.z, out.w }, vv[POLICY_TILE] = { value.x, value.y, value.z, value.w };
+		#pragma unroll
+		for (uint32_t r = 0; r < POLICY_TILE; ++r)
+		{
+			const uint32_t e = first + r;
+			if (e >= count) continue;
+			if (t == valueLane) valuesOut[e] = vv[r];
+			if (t < ACTION_SIZE)
+			{
+				const float noise = eps[r][t];
+				const float scaled = scales[t] * noise;
+				const float sample = ov[r] + scaled;
+				actionsOut[(size_t)ACTION_SIZE * e + t] = sample;
+				if (epsOut) epsOut[(size_t)ACTION_SIZE * e + t] = noise;
+				const float applied = clip ? clampf(sample, scales[2 * ACTION_SIZE + t], scales[3 * ACTION_SIZE + t]) : sample;
+				const float s = lerpf(smoothedAll[(size_t)ACTION_SIZE * e + t], applied, 0.1f); // smoothAction, one element per lane
+				smoothedAll[(size_t)ACTION_SIZE * e + t] = s; smoothed[r][t] = s;
+			}
+		}
+		__syncthreads();
+		const uint32_t r = t / NUM_MOTOR_JOINTS, j = t % NUM_MOTOR_JOINTS, e = first + r;
+		if (r < POLICY_TILE && e < count) // writeMotors, one joint per lane
+		{
+			if (j < NUM_CONE_TWIST) setConeTwistMotors(*(cone_twist_pod*)(conePods + (size_t)slots[NUM_MOTOR_JOINTS * e + j] * sizeof(cone_twist_pod)), smoothed[r], j);
+			else setHingeMotors(*(hinge_pod*)(hingePods + (size_t)slots[NUM_MOTOR_JOINTS * e + j] * sizeof(hinge_pod)), smoothed[r], j - NUM_CONE_TWIST);
+		}
+		const uint32_t q = t - POLICY_TILE * NUM_MOTOR_JOINTS; // the log-probabilities on the lanes after the joints'
+		if (q < POLICY_TILE && first + q < count) logProbsOut[first + q] = noiseLogProb(eps[q], scales + ACTION_SIZE);
+	}
+	static_assert(POLICY_TILE * NUM_MOTOR_JOINTS + POLICY_TILE <= 64, "one wave covers the tile's joints and log-probabilities");
+
+	// Generalised advantage estimation, one lane per environment walking its column of [steps][n] backwards (the lanes run along n:
+	// every load is one coalesced line).  All float32, in this order: delta = (r + (gamma * next) * nd) - V;
+	// A = delta + ((gamma * lambda) * nd) * A_next;  return = A + V, with nd = done ? 0 : 1 and next = V[t + 1], or last[e] in the last row.
+	__global__ void __launch_bounds__(64) k_loco_gae(uint32_t steps, uint32_t n, float gamma, float lambda, const float* __restrict__ rewards, const float* __restrict__ values,
+		const int32_t* __restrict__ dones, const float* __restrict__ lastValues, float* __restrict__ advantages, float* __restrict__ returns)
+	{
+		const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+		if (e >= n) return;
+		const float gl = gamma * lambda;
+		float next = lastValues[e], advantage = 0.f;
+		for (uint32_t t = steps; t-- > 0;)
+		{
+			const size_t i = (size_t)n * t + e;
+			const float nd = dones[i] ? 0.f : 1.f, value = values[i];
+			const float discounted = gamma * next;
+			const float delta = (rewards[i] + discounted * nd) - value;
+			const float carry = gl * nd;
+			advantage = delta + carry * advantage;
+			advantages[i] = advantage; returns[i] = advantage + value;
+			next = value;
+		}
+	}
+
+	// The noise alone: out[u][e][j] = noiseSample(seed, e, firstUpdate + u, j).
+	__global__ void __launch_bounds__(256) k_loco_noise(uint64_t seed, uint64_t firstUpdate, uint32_t n, size_t total, float* __restrict__ out)
+	{
+		const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+		if (i >= total) return;
+		const uint32_t j = (uint32_t)(i % ACTION_SIZE), e = (uint32_t)(i / ACTION_SIZE % n);
+		out[i] = noiseSample(seed, e, firstUpdate + i / ((size_t)ACTION_SIZE * n), j);
+	}
 
 	// Kernel B: the random push of updatePhysics (:322-330), drawn in its order, as a ray for mi_test_physics_interaction_batch.
 	__global__ void __launch_bounds__(64) k_loco_push_rays(uint32_t n, uint64_t* __restrict__ rngAll, const float4* __restrict__ poseLerp, float4* __restrict__ rays)
@@ -311,14 +469,81 @@ namespace
 		return 0;
 	}
 
+	// The critic of setPhysicsValueNetwork, transposed the same way.
+	int uploadValueNetwork(batch& b)
+	{
+		locomotion_policy p;
+		if (!locomotionValueNetwork(&p)) return 0;
+		const uint32_t h = p.hidden;
+		std::vector<float> t(valueFloats(h));
+		float* q = t.data();
+		auto transposed = [&](const float* w, uint32_t outputs, uint32_t inputs) { for (uint32_t x = 0; x < inputs; ++x) for (uint32_t y = 0; y < outputs; ++y) *q++ = w[(size_t)y * inputs + x]; };
+		auto plain = [&](const float* v, uint32_t count) { memcpy(q, v, sizeof(float) * count); q += count; };
+		transposed(p.w1, h, STATE_SIZE); plain(p.b1, h); transposed(p.w2, h, h); plain(p.b2, h); transposed(p.w3, 1, h); plain(p.b3, 1);
+		if (!ok(hipStreamSynchronize(b.stream), "value network")) return MI_ERR_HIP; // nothing in flight reads the old one
+		if (b.dValueNet) (void)hipFree(b.dValueNet);
+		b.dValueNet = nullptr; b.valueHidden = 0;
+		if (!ok(hipMalloc(&b.dValueNet, sizeof(float) * t.size()), "alloc")) return MI_ERR_HIP;
+		if (!ok(hipMemcpyAsync(b.dValueNet, t.data(), sizeof(float) * t.size(), hipMemcpyHostToDevice, b.stream), "value network") || !ok(hipStreamSynchronize(b.stream), "value network")) return MI_ERR_HIP;
+		b.valueHidden = h;
+		return 0;
+	}
+
+	// std and logStd of setPhysicsActionStd into the first half of dScales.
+	int uploadActionStd(batch& b)
+	{
+		const float* scales = locomotionActionStd();
+		if (!scales) return 0;
+		if (!ok(hipMemcpyAsync(b.dScales, scales, sizeof(float) * 2 * ACTION_SIZE, hipMemcpyHostToDevice, b.stream), "std") || !ok(hipStreamSynchronize(b.stream), "std")) return MI_ERR_HIP;
+		b.stdSet = true;
+		return 0;
+	}
+
+	// The action ranges of getPhysicsRanges into the second half of dScales, once per batch; they are those of any ragdoll, read from one
+	// in a world of its own so that the batch's world is not touched.
+	int uploadRanges(batch& b)
+	{
+		if (b.rangesSet) return 0;
+		static bool known = false;
+		static float ranges[2 * ACTION_SIZE];
+		if (!known)
+		{
+			mi_world_desc d = { -1, 0, 0, 0 };
+			mi_world* w = mi_world_create(&d);
+			if (!w) return MI_ERR_NO_DEVICE;
+			ragdoll r = createRagdoll(w, v3(0.f, 0.f, 0.f), 0.f);
+			fillRanges(w, r, ranges, ranges + ACTION_SIZE);
+			mi_world_destroy(w);
+			known = true;
+		}
+		if (!ok(hipMemcpyAsync(b.dScales + 2 * ACTION_SIZE, ranges, sizeof(ranges), hipMemcpyHostToDevice, b.stream), "ranges") || !ok(hipStreamSynchronize(b.stream), "ranges")) return MI_ERR_HIP;
+		b.rangesSet = true;
+		return 0;
+	}
+
+	dim3 networkBlock(uint32_t hidden) { return dim3(64 * ((hidden + 63) / 64)); }
+
+	int launchValue(batch& b, uint32_t count, const float* dStatesIn, float* dValuesOut, float* dHiddenOut)
+	{
+		hipLaunchKernelGGL(k_loco_value, dim3((count + POLICY_TILE - 1) / POLICY_TILE), networkBlock(b.valueHidden), 0, b.stream, count, b.valueHidden, dStatesIn, (const float*)b.dValueNet, dValuesOut, dHiddenOut);
+		return ok(hipGetLastError(), "value kernel") ? 0 : MI_ERR_HIP;
+	}
+
 	// One update of every environment, all on the world's stream, writing the three outputs (device pointers; dStates may be null, the
 	// batch's current-state buffer receives the states in any case).  With dActions: applyAction of these.  Without: the policy on the
 	// current states, its raw outputs to dActionsOut (may be null).
+	int launchAfterAction(batch& b, float* dStates, float* dRewards, int32_t* dFallen);
 	int launchUpdate(batch& b, const float* dActions, float* dActionsOut, float* dStates, float* dRewards, int32_t* dFallen)
 	{
 		if (int e = refreshPods(b)) return e;
 		if (dActions) hipLaunchKernelGGL(k_loco_actions, blocks(b.n), dim3(64), 0, b.stream, b.n, dActions, b.dSmoothed, b.dSlots, (uint8_t*)b.pods[0], (uint8_t*)b.pods[1]);
 		else if (int e = launchPolicy(b, true, b.n, b.dStates, dActionsOut, nullptr)) return e;
+		return launchAfterAction(b, dStates, dRewards, dFallen);
+	}
+
+	// The rest of an update once the motors are written: push, step, gather.
+	int launchAfterAction(batch& b, float* dStates, float* dRewards, int32_t* dFallen)
+	{
 		hipLaunchKernelGGL(k_loco_push_rays, blocks(b.n), dim3(64), 0, b.stream, b.n, b.dRng, (const float4*)b.ds.poseLerp, (float4*)b.dRays);
 		if (!ok(hipGetLastError(), "action / push kernels")) return MI_ERR_HIP;
 		if (int e = mi_test_physics_interaction_batch(b.world, b.n, 0, NUM_BODY_PARTS, b.dRays, b.dPushes)) return e;
@@ -391,7 +616,7 @@ extern "C"
 			&& ok(hipMalloc(&b->dPushes, sizeof(int32_t) * n), "alloc") && ok(hipMalloc(&b->dSlots, sizeof(uint32_t) * NUM_MOTOR_JOINTS * n), "alloc")
 			&& ok(hipMalloc(&b->dActions, sizeof(float) * ACTION_SIZE * n), "alloc") && ok(hipMalloc(&b->dStates, sizeof(float) * STATE_SIZE * n), "alloc")
 			&& ok(hipMalloc(&b->dRewards, sizeof(float) * n), "alloc") && ok(hipMalloc(&b->dFallen, sizeof(int32_t) * n), "alloc")
-			&& ok(hipMalloc(&b->dIds, sizeof(uint32_t) * n), "alloc");
+			&& ok(hipMalloc(&b->dIds, sizeof(uint32_t) * n), "alloc") && ok(hipMalloc(&b->dScales, sizeof(float) * 4 * ACTION_SIZE), "alloc");
 		good = good && ok(hipMemcpyAsync(b->dInit, init.data(), sizeof(env_init) * n, hipMemcpyHostToDevice, b->stream), "init")
 			&& ok(hipMemcpyAsync(b->dRng, rng.data(), sizeof(uint64_t) * n, hipMemcpyHostToDevice, b->stream), "rng")
 			&& ok(hipMemcpyAsync(b->dIds, ids.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, b->stream), "ids")
@@ -401,6 +626,8 @@ extern "C"
 		int e = launchReset(*b, b->dIds, nullptr, numEnvs);
 		if (!e) e = launchGather(*b, nullptr, nullptr, numEnvs, b->dStates, b->dRewards, b->dFallen);
 		if (!e) e = uploadPolicy(*b);
+		if (!e) e = uploadValueNetwork(*b);
+		if (!e) e = uploadActionStd(*b);
 		if (!e) e = copyOut(*b, outStates, nullptr, nullptr);
 		return e;
 	}
@@ -520,6 +747,73 @@ extern "C"
 		}
 		return 0;
 	}
+
+	// The critic alone on count rows of dStates (device, count x 66) into dValues (count), on the world's stream; dHidden (may be NULL,
+	// count x 2Hv) receives tanh(z1), tanh(z2) of every row.  Touches no environment.
+	int inferPhysicsBatchValueDevice(uint32_t count, const float* dStates, float* dValues, float* dHidden)
+	{
+		if (!B || !B->valueHidden) return MI_ERR_INVALID_STATE;
+		if (!count || !dStates || !dValues) return MI_ERR_INVALID_ARGUMENT;
+		return launchValue(*B, count, dStates, dValues, dHidden);
+	}
+
+	// The exploration noise of updates firstUpdate .. firstUpdate + numUpdates - 1 of every environment into dEps [numUpdates][n][27], on
+	// the world's stream: what collectPhysicsBatchDevice draws at those counters.  Moves neither the counter nor any random state.
+	int samplePhysicsBatchNoiseDevice(unsigned long long firstUpdate, uint32_t numUpdates, float* dEps)
+	{
+		if (!B) return MI_ERR_INVALID_STATE;
+		if (!numUpdates || !dEps) return MI_ERR_INVALID_ARGUMENT;
+		const size_t total = (size_t)numUpdates * B->n * ACTION_SIZE;
+		hipLaunchKernelGGL(k_loco_noise, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, B->stream, (uint64_t)locomotionSeed(), (uint64_t)firstUpdate, B->n, total, dEps);
+		return ok(hipGetLastError(), "noise kernel") ? 0 : MI_ERR_HIP;
+	}
+
+	// Collecting updates since resetPhysicsBatch: the counter the next collectPhysicsBatchDevice starts at (0 without a batch).
+	unsigned long long getPhysicsBatchNoiseCounter(void) { return B ? B->noiseCounter : 0; }
+
+	// `steps` closed-loop updates with sampled actions, enqueued back to back, always with the device-side reset of the fallen.  Row t:
+	// dObs [steps][n][66] the states the networks saw at update t (after a fall: the reset state); dActions [steps][n][27] the sample
+	// a = mu + std * eps, unclipped; dEps [steps][n][27] (may be NULL) the noise; dLogProbs [steps][n] log N(a; mu, std); dValues
+	// [steps][n] the critic on dObs[t]; dRewards, dDones [steps][n] reward and fallen after the update.  The environment receives a,
+	// with clip != 0 a clamped to the action ranges of getPhysicsRanges.  dLastValues [n]: the critic on the states after the last
+	// update's reset.  Needs a policy, a critic and a std.
+	int collectPhysicsBatchDevice(uint32_t steps, int clip, float* dObs, float* dActions, float* dEps, float* dLogProbs, float* dValues, float* dRewards, int32_t* dDones, float* dLastValues)
+	{
+		if (!B || !B->hidden || !B->valueHidden || !B->stdSet) return MI_ERR_INVALID_STATE;
+		if (!steps || !dObs || !dActions || !dLogProbs || !dValues || !dRewards || !dDones || !dLastValues) return MI_ERR_INVALID_ARGUMENT;
+		batch& b = *B;
+		if (int e = uploadRanges(b)) return e;
+		const size_t n = b.n;
+		const uint64_t seed = locomotionSeed();
+		const dim3 grid((b.n + POLICY_TILE - 1) / POLICY_TILE), block = networkBlock(b.hidden > b.valueHidden ? b.hidden : b.valueHidden);
+		for (uint32_t t = 0; t < steps; ++t)
+		{
+			int32_t* fallen = dDones + n * t;
+			if (int e = refreshPods(b)) return e;
+			hipLaunchKernelGGL(k_loco_sample, grid, block, 0, b.stream, b.n, b.hidden, b.valueHidden, clip, seed, b.noiseCounter, (const float*)b.dStates, (const float*)b.dPolicy,
+				(const float*)b.dValueNet, (const float*)b.dScales, dObs + STATE_SIZE * n * t, dActions + ACTION_SIZE * n * t, dEps ? dEps + ACTION_SIZE * n * t : nullptr,
+				dLogProbs + n * t, dValues + n * t, b.dSmoothed, (const uint32_t*)b.dSlots, (uint8_t*)b.pods[0], (uint8_t*)b.pods[1]);
+			if (!ok(hipGetLastError(), "sample kernel")) return MI_ERR_HIP;
+			++b.noiseCounter;
+			if (int e = launchAfterAction(b, nullptr, dRewards + n * t, fallen)) return e;
+			if (int e = launchReset(b, nullptr, fallen, b.n)) return e;
+			if (int e = launchGather(b, nullptr, fallen, b.n, b.dStates, b.dRewards, b.dFallen)) return e;
+		}
+		return launchValue(b, b.n, b.dStates, dLastValues, nullptr);
+	}
+
+	// Generalised advantage estimation over [steps][n] device buffers (k_loco_gae), on the batch's stream.  Episodes end by falling only:
+	// a done row bootstraps nothing, every other row bootstraps from the next value (the last row from dLastValues).
+	int gaePhysicsBatchDevice(uint32_t steps, uint32_t n, float gamma, float lambda, const float* dRewards, const float* dValues, const int32_t* dDones, const float* dLastValues,
+		float* dAdvantages, float* dReturns)
+	{
+		if (!B) return MI_ERR_INVALID_STATE;
+		if (!steps || !n || !dRewards || !dValues || !dDones || !dLastValues || !dAdvantages || !dReturns) return MI_ERR_INVALID_ARGUMENT;
+		hipLaunchKernelGGL(k_loco_gae, blocks(n), dim3(64), 0, B->stream, steps, n, gamma, lambda, dRewards, dValues, dDones, dLastValues, dAdvantages, dReturns);
+		return ok(hipGetLastError(), "gae kernel") ? 0 : MI_ERR_HIP;
+	}
 }
 
 int locomotionBatchPolicyChanged() { return B ? uploadPolicy(*B) : 0; }
+int locomotionBatchValueChanged() { return B ? uploadValueNetwork(*B) : 0; }
+int locomotionBatchStdChanged() { return B ? uploadActionStd(*B) : 0; }

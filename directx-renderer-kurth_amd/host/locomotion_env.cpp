@@ -10,6 +10,8 @@
 // fixed) so that runs are reproducible.  resetPhysics also fills outState (the reference leaves it untouched).
 // The controller half (learned_locomotion::update, :44-68) is here too: setPhysicsPolicy keeps a network (locomotion_policy.h),
 // inferPhysicsPolicy runs it on one state, updatePhysicsPolicy drives the single environment from it.
+// For training (learning/learn_locomotion.py) the file also keeps a critic and the Gaussian's scales (setPhysicsValueNetwork,
+// inferPhysicsValue, setPhysicsActionStd) and states the exploration noise on the host (samplePhysicsNoise); the batch collects with them.
 // Everything physical happens in libmi_physics.so on the GPU; this file is host logic only, like the reference's.
 //
 // Build: directx_renderer_kurth_amd.build_locomotion() compiles this file with g++ and locomotion_batch.hip (the batched environments)
@@ -77,6 +79,11 @@ namespace
 	// The policy of setPhysicsPolicy: one block of policyFloats(hidden) floats, the six arrays back to back.
 	uint32_t policyHidden = 0;
 	std::vector<float> policyData;
+	// The critic of setPhysicsValueNetwork, in the same way (w3 is [1][Hv], b3 one float), and the scales of setPhysicsActionStd.
+	uint32_t valueHidden = 0;
+	std::vector<float> valueData;
+	bool actionStdSet = false;
+	float actionStd[2 * ACTION_SIZE] = {}; // std[27], logStd[27]
 
 	// updatePhysics after its applyAction (:469-489): push draw, step, state, reward, fallen.
 	int stepAfterAction(float* outState, float* outReward)
@@ -115,6 +122,20 @@ bool locomotionPolicy(locomotion_policy* out)
 	out->w3 = p; p += (size_t)ACTION_SIZE * h; out->b3 = p;
 	return true;
 }
+
+bool locomotionValueNetwork(locomotion_policy* out)
+{
+	if (!valueHidden) return false;
+	const uint32_t h = valueHidden;
+	const float* p = valueData.data();
+	out->hidden = h;
+	out->w1 = p; p += (size_t)h * STATE_SIZE; out->b1 = p; p += h;
+	out->w2 = p; p += (size_t)h * h; out->b2 = p; p += h;
+	out->w3 = p; p += h; out->b3 = p;
+	return true;
+}
+
+const float* locomotionActionStd() { return actionStdSet ? actionStd : nullptr; }
 
 extern "C"
 {
@@ -197,5 +218,56 @@ extern "C"
 		inferPolicy(p, state, ab, ab + p.hidden, action);
 		env->applyAction(action);
 		return stepAfterAction(outState, outReward);
+	}
+
+	// The critic of training, 66 -> Hv -> Hv -> 1 with tanh on the hidden layers: w1 [Hv][66], b1, w2 [Hv][Hv], b2, w3 [1][Hv], b3 [1].
+	// Independent of the policy's H; kept and uploaded like the policy.  A bad argument leaves the previous one active.
+	int setPhysicsValueNetwork(uint32_t hidden, const float* w1, const float* b1, const float* w2, const float* b2, const float* w3, const float* b3)
+	{
+		if (!hidden || hidden > POLICY_MAX_HIDDEN || !w1 || !b1 || !w2 || !b2 || !w3 || !b3) return MI_ERR_INVALID_ARGUMENT;
+		std::vector<float> data(valueFloats(hidden));
+		float* p = data.data();
+		auto put = [&](const float* from, size_t count) { memcpy(p, from, sizeof(float) * count); p += count; };
+		put(w1, (size_t)hidden * STATE_SIZE); put(b1, hidden); put(w2, (size_t)hidden * hidden); put(b2, hidden); put(w3, hidden); put(b3, 1);
+		valueData.swap(data);
+		valueHidden = hidden;
+		return locomotionBatchValueChanged();
+	}
+
+	// The critic on one state, on the host.  hidden (2 x Hv floats, may be NULL) receives tanh(z1), tanh(z2).
+	int inferPhysicsValue(const float* state, float* outValue, float* hidden)
+	{
+		locomotion_policy p;
+		if (!locomotionValueNetwork(&p)) return MI_ERR_INVALID_STATE;
+		if (!state || !outValue) return MI_ERR_INVALID_ARGUMENT;
+		float ab[2 * POLICY_MAX_HIDDEN];
+		inferValue(p, state, ab, ab + p.hidden, outValue);
+		if (hidden) memcpy(hidden, ab, sizeof(float) * 2 * p.hidden);
+		return MI_OK;
+	}
+
+	// The scale of the Gaussian around the policy's output, per action, and its logarithm: both given, so that the library evaluates
+	// neither exp nor log of them.  Zeros are legal (the sample is then the mean).
+	int setPhysicsActionStd(const float* std, const float* logStd)
+	{
+		if (!std || !logStd) return MI_ERR_INVALID_ARGUMENT;
+		memcpy(actionStd, std, sizeof(float) * ACTION_SIZE); memcpy(actionStd + ACTION_SIZE, logStd, sizeof(float) * ACTION_SIZE);
+		actionStdSet = true;
+		return locomotionBatchStdChanged();
+	}
+
+	// The exploration noise of environment env at update counter `update` under `seed` (locomotion_policy.h: noiseSample), on the host:
+	// out[27].  samplePhysicsNoiseUniforms gives the two uniforms behind every sample, which are exact: the integer stage made visible.
+	int samplePhysicsNoise(unsigned long long seed, uint32_t env, unsigned long long update, float* out)
+	{
+		if (!out) return MI_ERR_INVALID_ARGUMENT;
+		for (uint32_t j = 0; j < ACTION_SIZE; ++j) out[j] = noiseSample(seed, env, update, j);
+		return MI_OK;
+	}
+	int samplePhysicsNoiseUniforms(unsigned long long seed, uint32_t env, unsigned long long update, float* outU1, float* outU2)
+	{
+		if (!outU1 || !outU2) return MI_ERR_INVALID_ARGUMENT;
+		for (uint32_t j = 0; j < ACTION_SIZE; ++j) noiseUniforms(seed, env, update, j, outU1 + j, outU2 + j);
+		return MI_OK;
 	}
 }
