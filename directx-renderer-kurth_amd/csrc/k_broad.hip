@@ -97,23 +97,42 @@ __global__ void __launch_bounds__(256) k_cell_rank(u32* __restrict__ counters, u
 }
 
 // Overlapping partners of the collider at sorted position t.  Every pair is produced exactly once, as (A = this collider,
-// B = partner): partners in the 13 "forward" neighbour cells, partners sorted before t in the own cell, and every large collider.
-// SIXTEEN lanes work on one collider: lane g < 14 visits neighbour cell 13 + g, lane 14 the list of large colliders (a large
-// collider itself: lane 0 tests the large colliders before it).  Each lane counts its hits, a 16-lane prefix sum places them —
-// cell after cell, candidate after candidate, exactly the order one lane visiting everything would produce — and a second visit
-// writes them.  (One lane per collider left 6 waves per CU chasing 14 dependent hash -> range -> AABB chains each: 150 us at 100k.)
+// B = partner): partners sorted before t in the own cell, partners in the 13 "forward" neighbour cells, and every large collider
+// (a large collider itself: the large colliders before it).
+// SIXTEEN lanes work on one collider, and they share its candidates EVENLY.  Lane g first finds range g of the visiting order —
+// g < 14: the bucket of neighbour cell 13 + g (own cell first, cut at t; then the forward half in offset order), g == 14: the list
+// of large colliders — with what a candidate of it must match (the cell's tag: buckets are shared by the cells that hash alike; the
+// large list: nothing).  A 16-lane prefix sum over the range lengths strings the ranges together into one candidate sequence of
+// length T, and a table in LDS (per range: where it ends in the sequence, sorted position minus sequence position, tag) lets any
+// lane find the candidate at any sequence position.  Lane l then walks the contiguous slice [l * ceil(T / 16), (l + 1) * ceil(T / 16)),
+// which may begin in the middle of one cell and end in another, four boxes per turn.  Slices are in sequence order and lanes in
+// slice order, so the 16-lane prefix sum over the lanes' hit counts places every hit exactly where one lane visiting everything
+// would place it: the pair list does not depend on how the sequence is cut.
+// (A wave takes as long as its longest lane's chain of dependent turns.  One lane per RANGE made that the own cell's lane, up to 28
+// candidates = 7 turns, while most other lanes had an empty or short cell: see DESIGN.md section 4 for the figures.  One lane per
+// collider left 6 waves per CU chasing 14 dependent hash -> range -> AABB chains each: 150 us at 100k.)
+// A forward cell that cannot hold a partner gets length 0 before its range is even loaded: a box filed under a cell whose offset is
+// +1 on some axis has its min corner in that cell, so cellCoord(its min) = own coordinate + 1 there; cellCoord is monotonic, so if
+// cellCoord(own max) on that axis is still the own coordinate, own max < its min and the box test fails for every candidate of
+// that cell.  (The comparison is between two results of cellCoord, clamp included, never against a separately rounded boundary.)
 // MODE_SLAB  : the first PAIR_SLAB partners go to a per-collider slab, the full count to pairCount.
 // MODE_WRITE : ONLY the colliders with more than PAIR_SLAB partners (the slab pass sets CTR_PAIR_OVERFLOW) repeat the visit,
 //              writing directly at pairOffset[t]; same order, so the pair list is identical.  Everybody else is packed from the slabs.
 #define PAIR_SLAB 32
 #define PAIR_LANES 16
+#define PAIR_NO_TAG 0xFFFFFFFFu // (a cell tag has 30 bits)
 enum { MODE_SLAB = 0, MODE_WRITE = 1 };
+MI_DEV uint2 pairRange(const uint4* ranges, u32 r) { return make_uint2(ranges[r].x, ranges[r].y); }
+// (the record at a sorted position, addressed with a 32-bit byte offset from the uniform base: one address register per box in flight; 2^27 colliders)
+MI_DEV const float4* pairBox(const float4* __restrict__ sBox, u32 u) { return (const float4*)((const char*)sBox + u * 32u); }
 template <int MODE>
 __global__ void __launch_bounds__(256) k_pairs(u32 nc, u32 hashMask, const float4* __restrict__ sBox, const uint2* __restrict__ cellRange, u32* __restrict__ counters,
 	u32* __restrict__ pairCount, const u32* __restrict__ pairOffset, uint2* __restrict__ out, u32 pairCap)
 {
+	__shared__ uint4 sRange[256 / PAIR_LANES][PAIR_LANES]; // per group and range: {end in the candidate sequence, sorted position - sequence position, tag, -}
 	u32 gid = blockIdx.x * blockDim.x + threadIdx.x;
 	u32 t = gid / PAIR_LANES, g = gid % PAIR_LANES;
+	const uint4* __restrict__ ranges = sRange[threadIdx.x / PAIR_LANES];
 	bool valid = t < nc;                                   // nc = the launch's bound on the sorted positions (>= the active colliders, or the host repeats the broadphase)
 	u32 nEnd = min(counters[CTR_FIRST_INACTIVE], min(nc, counters[CTR_ACTIVE_COLS])); // colliders behind this position have empty AABBs
 	u32 firstLarge = min(counters[CTR_FIRST_LARGE], nEnd);
@@ -121,54 +140,77 @@ __global__ void __launch_bounds__(256) k_pairs(u32 nc, u32 hashMask, const float
 	if (MODE == MODE_WRITE) live = live && pairCount[t] > PAIR_SLAB; // everybody else is complete in its slab
 	float4 amin = make_float4(0.f, 0.f, 0.f, 0.f), amax = amin;
 	u32 me = 0;
-	// this lane's candidate range [s, e) and what a candidate must match
-	u32 s = 0, e = 0; u32 ntag = 0; bool checkKey = false;
+	// range g of this collider: sorted positions [s, s + len) and what a candidate must match
+	u32 s = 0, len = 0, ntag = PAIR_NO_TAG;
 	if (live)
 	{
 		amin = sBox[2 * t]; amax = sBox[2 * t + 1];
 		me = __float_as_uint(amin.w);
-		if (t >= firstLarge) { if (g == 0) { s = firstLarge; e = t; } }
-		else if (g == 14) { s = firstLarge; e = nEnd; }
+		if (t >= firstLarge) { if (g == 0) { s = firstLarge; len = t - firstLarge; } }
+		else if (g == 14) { s = firstLarge; len = nEnd - firstLarge; }
 		else if (g < 14)
 		{
 			const float invCell = 1.f / (fmaxf(__uint_as_float(counters[CTR_CELL_SIZE_USED]), 1e-3f) * 1.001f); // (as k_cell_rank computes it)
 			i32 ix = cellCoord(amin.x, invCell), iy = cellCoord(amin.y, invCell), iz = cellCoord(amin.z, invCell);
 			i32 o = 13 + (i32)g; // offsets (dz,dy,dx) >= (0,0,0) in lexicographic order: own cell first, then the forward half
 			i32 dz = o / 9 - 1, dy = (o / 3) % 3 - 1, dx = o % 3 - 1;
-			ntag = cellTag(ix + dx, iy + dy, iz + dz);
-			u32 h = hashCell(packCell(ix + dx, iy + dy, iz + dz), hashMask);
-			uint2 range = cellRange[h];
-			if (range.x != EMPTY_CELL)
+			bool reach = true; // (exact cull of the forward cells, see above)
+			if (dx > 0 && cellCoord(amax.x, invCell) == ix) reach = false; // my box ends before that cell begins
+			if (dy > 0 && cellCoord(amax.y, invCell) == iy) reach = false;
+			if (dz > 0 && cellCoord(amax.z, invCell) == iz) reach = false;
+			if (reach)
 			{
-				s = range.x; e = range.y;
-				if (g == 0) e = min(e, t); // own cell: only partners sorted before me
-				checkKey = true;           // other cells may share the hash bucket
+				ntag = cellTag(ix + dx, iy + dy, iz + dz);
+				u32 h = hashCell(packCell(ix + dx, iy + dy, iz + dz), hashMask);
+				uint2 range = cellRange[h];
+				if (range.x != EMPTY_CELL) { s = range.x; const u32 e = g == 0 ? min(range.y, t) : range.y; len = e > s ? e - s : 0u; } // own cell: only partners sorted before me
 			}
 		}
 	}
+	// the ranges strung together (the groups of a wave are aligned to 16 lanes)
+	u32 end = len;
+	for (u32 d = 1; d < PAIR_LANES; d <<= 1) { u32 v = __shfl_up(end, d, PAIR_LANES); if (g >= d) end += v; }
+	sRange[threadIdx.x / PAIR_LANES][g] = make_uint4(end, s - (end - len), ntag, 0u);
+	__syncthreads();
+	// this lane's slice [lo, hi) of the sequence, and the range it begins in = the number of ranges that end at or before lo
+	const u32 T = ranges[PAIR_LANES - 1].x;
+	const u32 chunk = (T + PAIR_LANES - 1u) / PAIR_LANES;
+	const u32 lo = min(g * chunk, T), hi = min(lo + chunk, T);
+	u32 r0 = 0;
+#pragma unroll
+	for (u32 k = 0; k < PAIR_LANES - 1u; ++k) r0 += ranges[k].x <= lo ? 1u : 0u;
 	u32 n = 0;
 	u32 hit0 = 0, hit1 = 0, hit2 = 0, hit3 = 0; // the first four partners of this lane stay in registers: the write pass then needs no second visit
-	// (four candidates per turn, their boxes requested together — eight cost more in registers than they save: a wave's time is the longest lane's chain of dependent loads —
-	// 78 load instructions per wave, 82 % of its cycles parked on them, when every candidate waited for the one before it)
-	for (u32 u = s; u < e; u += 4u)
+	// (four candidates per turn, their boxes requested together — eight cost more in registers than they save: a wave's time is the longest lane's chain of dependent loads)
+	if (lo < hi)
 	{
-		float4 bmin[4], bmax[4];
-#pragma unroll
-		for (u32 k = 0; k < 4u; ++k) if (u + k < e) { bmin[k] = sBox[2 * (u + k)]; bmax[k] = sBox[2 * (u + k) + 1]; }
-#pragma unroll
-		for (u32 k = 0; k < 4u; ++k)
+		u32 r = r0; uint2 cur = pairRange(ranges, r);
+		for (u32 p = lo; p < hi; p += 4u)
 		{
-			if (u + k >= e) continue;
-			if (checkKey && __float_as_uint(bmax[k].w) != ntag) continue;
-			if (aabbOverlap(amin, amax, bmin[k], bmax[k]))
+			float4 bmin[4], bmax[4]; u32 from = 0; // (the range each of the four came from, four bits each: its tag is looked up when the box is there)
+#pragma unroll
+			for (u32 k = 0; k < 4u; ++k) if (p + k < hi)
 			{
-				u32 partner = __float_as_uint(bmin[k].w);
-				if (n == 0) hit0 = partner; else if (n == 1) hit1 = partner; else if (n == 2) hit2 = partner; else if (n == 3) hit3 = partner;
-				++n;
+				while (p + k >= cur.x) cur = pairRange(ranges, ++r); // (p + k < T = the last range's end: r stays below 16)
+				const float4* box = pairBox(sBox, cur.y + p + k);
+				from |= r << (4u * k); bmin[k] = box[0]; bmax[k] = box[1];
+			}
+#pragma unroll
+			for (u32 k = 0; k < 4u; ++k)
+			{
+				if (p + k >= hi) continue;
+				const u32 want = ranges[(from >> (4u * k)) & 15u].z;
+				if (want != PAIR_NO_TAG && __float_as_uint(bmax[k].w) != want) continue;
+				if (aabbOverlap(amin, amax, bmin[k], bmax[k]))
+				{
+					u32 partner = __float_as_uint(bmin[k].w);
+					if (n == 0) hit0 = partner; else if (n == 1) hit1 = partner; else if (n == 2) hit2 = partner; else if (n == 3) hit3 = partner;
+					++n;
+				}
 			}
 		}
 	}
-	// exclusive prefix over the 16 lanes of the group (the groups of a wave are aligned to 16 lanes)
+	// exclusive prefix over the 16 lanes of the group
 	u32 incl = n;
 	for (u32 d = 1; d < PAIR_LANES; d <<= 1) { u32 v = __shfl_up(incl, d, PAIR_LANES); if (g >= d) incl += v; }
 	u32 total = __shfl(incl, PAIR_LANES - 1, PAIR_LANES);
@@ -186,10 +228,15 @@ __global__ void __launch_bounds__(256) k_pairs(u32 nc, u32 hashMask, const float
 		}
 		return;
 	}
-	for (u32 u = s; u < e; ++u)
+	// more than four hits in the slice: a second visit of it
+	u32 r = r0; uint2 cur = pairRange(ranges, r);
+	for (u32 p = lo; p < hi; ++p)
 	{
-		float4 bmin = sBox[2 * u], bmax = sBox[2 * u + 1];
-		if (checkKey && __float_as_uint(bmax.w) != ntag) continue;
+		while (p >= cur.x) cur = pairRange(ranges, ++r);
+		const float4* box = pairBox(sBox, cur.y + p);
+		float4 bmin = box[0], bmax = box[1];
+		const u32 want = ranges[r].z;
+		if (want != PAIR_NO_TAG && __float_as_uint(bmax.w) != want) continue;
 		if (!aabbOverlap(amin, amax, bmin, bmax)) continue;
 		if (pos < room && (MODE == MODE_SLAB || base + pos < pairCap)) out[base + pos] = make_uint2(me, __float_as_uint(bmin.w));
 		++pos;
