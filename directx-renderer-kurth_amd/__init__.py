@@ -100,23 +100,28 @@ LOCOMOTION_SYMBOLS = ["getPhysicsStateSize", "getPhysicsActionSize", "getPhysics
                       "setPhysicsPolicy", "inferPhysicsPolicy", "updatePhysicsPolicy", "inferPhysicsBatchDevice", "updatePhysicsBatchPolicy",
                       "updatePhysicsBatchPolicyDevice", "rolloutPhysicsBatchDevice",
                       "setPhysicsValueNetwork", "inferPhysicsValue", "inferPhysicsBatchValueDevice", "setPhysicsActionStd", "samplePhysicsBatchNoiseDevice",
-                      "samplePhysicsNoise", "samplePhysicsNoiseUniforms", "getPhysicsBatchNoiseCounter", "collectPhysicsBatchDevice", "gaePhysicsBatchDevice"]
+                      "samplePhysicsNoise", "samplePhysicsNoiseUniforms", "getPhysicsBatchNoiseCounter", "collectPhysicsBatchDevice", "gaePhysicsBatchDevice",
+                      "beginPhysicsBatchTraining", "endPhysicsBatchTraining", "updatePhysicsBatchPPODevice", "gradientsPhysicsBatchPPODevice",
+                      "readPhysicsBatchPolicy", "readPhysicsBatchValueNetwork", "readPhysicsBatchLogStd"]
 _HIPCC = "/opt/rocm/bin/hipcc"
 
 
 def build_locomotion():
     """libmi_locomotion.so: the reference's ragdoll RL environment (learned_locomotion.cpp:395-489) as host C++ over the C-ABI (g++),
-    plus the batched environments of host/locomotion_batch.hip (hipcc, gfx950, strict fp32 like libmi_physics.so)."""
+    plus the batched environments of host/locomotion_batch.hip and the PPO gradient step of host/locomotion_update.hip (hipcc, gfx950,
+    strict fp32 like libmi_physics.so)."""
     host = os.path.join(_HERE, "host")
     include = "-I" + os.path.join(os.path.dirname(_HERE), "include")
-    cpp, hip = os.path.join(host, "locomotion_env.cpp"), os.path.join(host, "locomotion_batch.hip")
-    deps = [cpp, hip, os.path.join(host, "locomotion_shared.h"), os.path.join(host, "locomotion_policy.h"), os.path.join(os.path.dirname(_HERE), "include", "mi_physics.h"), _LIB_PATH]
+    cpp, hips = os.path.join(host, "locomotion_env.cpp"), [os.path.join(host, "locomotion_batch.hip"), os.path.join(host, "locomotion_update.hip")]
+    headers = [os.path.join(host, h) for h in ("locomotion_shared.h", "locomotion_policy.h", "locomotion_layers.h", "locomotion_update.h")]
+    deps = [cpp] + hips + headers + [os.path.join(os.path.dirname(_HERE), "include", "mi_physics.h"), _LIB_PATH]
     if os.path.exists(LOCOMOTION_LIB_PATH) and os.path.getmtime(LOCOMOTION_LIB_PATH) >= max(os.path.getmtime(p) for p in deps):
         return LOCOMOTION_LIB_PATH
-    cpp_o, hip_o = os.path.join(host, "locomotion_env.o"), os.path.join(host, "locomotion_batch.o")
+    cpp_o, hip_os = os.path.join(host, "locomotion_env.o"), [h[:-len(".hip")] + ".o" for h in hips]
     subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-ffp-contract=off", "-Wall", include, "-c", cpp, "-o", cpp_o])
-    subprocess.check_call([_HIPCC, "-std=c++17", "-O3", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", "-Wall", include, "-c", hip, "-o", hip_o])
-    subprocess.check_call([_HIPCC, "-shared", "-fPIC", "--offload-arch=gfx950", cpp_o, hip_o, "-L" + _HERE, "-lmi_physics", "-Wl,-rpath,$ORIGIN",
+    for hip, hip_o in zip(hips, hip_os):
+        subprocess.check_call([_HIPCC, "-std=c++17", "-O3", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", "-Wall", include, "-c", hip, "-o", hip_o])
+    subprocess.check_call([_HIPCC, "-shared", "-fPIC", "--offload-arch=gfx950", cpp_o] + hip_os + ["-L" + _HERE, "-lmi_physics", "-Wl,-rpath,$ORIGIN",
                            "-o", LOCOMOTION_LIB_PATH])
     return LOCOMOTION_LIB_PATH
 
@@ -563,6 +568,9 @@ def _load_locomotion():
         lib.samplePhysicsNoise.argtypes = [C.c_ulonglong, C.c_uint32, C.c_ulonglong, C.c_void_p]
         lib.samplePhysicsBatchNoiseDevice.argtypes = [C.c_ulonglong, C.c_uint32, C.c_void_p]
         lib.gaePhysicsBatchDevice.argtypes = [C.c_uint32, C.c_uint32, C.c_float, C.c_float] + [C.c_void_p] * 6
+        lib.beginPhysicsBatchTraining.argtypes = [C.c_float] * 4
+        lib.updatePhysicsBatchPPODevice.argtypes = [C.c_uint32] + [C.c_void_p] * 5 + [C.c_uint32, C.c_void_p, C.c_uint32] + [C.c_float] * 4 + [C.c_int, C.c_void_p]
+        lib.gradientsPhysicsBatchPPODevice.argtypes = [C.c_uint32] + [C.c_void_p] * 5 + [C.c_uint32, C.c_void_p] + [C.c_float] * 3 + [C.c_int] + [C.c_void_p] * 3
         _locomotion_lib = lib
     return _locomotion_lib
 
@@ -655,6 +663,23 @@ def update_policy():
     if code < 0:
         raise PhysicsError("updatePhysicsPolicy failed (%d)" % code)
     return state, reward.value, bool(code)
+
+
+def _network_floats(hidden, outputs):
+    return hidden * 66 + hidden + hidden * hidden + hidden + outputs * hidden + outputs
+
+
+def _split_flat(flat, hidden, value_hidden):
+    """A tensor in the flat parameter order of host/locomotion_update.h (the device's [in][out] layouts: actor, critic, log_std) as a
+    dict under the stable-baselines names, weights transposed back to [out, in]."""
+    out, at = {}, 0
+    for names, h, outputs in ((POLICY_NAMES, hidden, 27), (VALUE_NAMES, value_hidden, 1)):
+        for name, (inputs, units) in zip(names[0::2], ((66, h), (h, h), (h, outputs))):
+            out[name] = flat[at:at + inputs * units].reshape(inputs, units).t().contiguous(); at += inputs * units
+            out[name.replace("weight", "bias")] = flat[at:at + units].clone(); at += units
+    out["log_std"] = flat[at:at + 27].clone()
+    assert at + 27 == flat.numel()
+    return out
 
 
 class LocomotionBatch:
@@ -830,6 +855,80 @@ class LocomotionBatch:
             C.c_uint32(steps), C.c_uint32(n), C.c_float(gamma), C.c_float(lam), *[C.c_void_p(t.data_ptr()) for t in (r, v, d, last, advantages, returns)]))
         self._check(code, "gaePhysicsBatchDevice")
         return advantages, returns
+
+    # ---- the gradient step (host/locomotion_update.hip) ----
+    def begin_training(self, lr=2.5e-5, betas=(0.9, 0.999), eps=1e-5):
+        """Opens a training session: torch.optim.Adam(lr, betas, eps) with zeroed moments over the networks and log_std as they are on the
+        device.  From here on the device holds the master copy of the parameters (parameters() reads it); set_policy, set_value_network,
+        set_log_std and reset() end the session."""
+        self._check(self.lib.beginPhysicsBatchTraining(lr, betas[0], betas[1], eps), "beginPhysicsBatchTraining")
+
+    def end_training(self):
+        """Drops the optimiser state; the parameters stay as they are on the device."""
+        self._check(self.lib.endPhysicsBatchTraining(), "endPhysicsBatchTraining")
+
+    def _rows(self, obs, actions, old_log_probs, advantages, returns):
+        import torch
+        t = [x.detach().to(torch.float32).contiguous() for x in (obs, actions, old_log_probs, advantages, returns)]
+        rows = t[2].numel()
+        t = [t[0].reshape(rows, self.state_size), t[1].reshape(rows, self.action_size)] + [x.reshape(rows) for x in t[2:]]
+        if not all(x.is_cuda for x in t):
+            raise ValueError("the rows of the gradient step are ROCm tensors")
+        return rows, t
+
+    def _indices(self, order, rows):
+        """Row indices as an int32 ROCm tensor; a host tensor or array is checked against `rows` before it is uploaded."""
+        import torch
+        order = order if hasattr(order, "is_cuda") else torch.as_tensor(np.asarray(order))
+        if not order.is_cuda and order.numel() and (int(order.min()) < 0 or int(order.max()) >= rows):
+            raise ValueError("row index outside [0, %d)" % rows)
+        return order.to(device=self._device(), dtype=torch.int32).contiguous()
+
+    def ppo_update(self, obs, actions, old_log_probs, advantages, returns, order, batch_size=128, clip_range=0.1, vf_coef=0.5, ent_coef=0.0,
+                   max_grad_norm=0.5, normalize_advantage=True):
+        """PPO's epochs on the device, enqueued without a host synchronisation: `order` [epochs, rows] holds one permutation of the rows per
+        epoch, each cut into minibatches of batch_size (the last one short); every minibatch is one optimiser step (training.ppo_loss,
+        clip_grad_norm_, Adam) on the device's parameters.  Returns a ROCm tensor [epochs * minibatches, 5]: per step loss, policy loss,
+        value loss, clip fraction and the gradient's norm before clipping."""
+        import torch
+        rows, t = self._rows(obs, actions, old_log_probs, advantages, returns)
+        order = self._indices(order, rows).reshape(-1, rows)
+        epochs = order.shape[0]
+        stats = torch.empty((epochs * ((rows + batch_size - 1) // batch_size), 5), dtype=torch.float32, device=order.device)
+        code = self._on_stream(order.device, t + [order, stats], lambda: self.lib.updatePhysicsBatchPPODevice(
+            rows, *[x.data_ptr() for x in t], epochs, order.data_ptr(), batch_size, clip_range, vf_coef, ent_coef, max_grad_norm, 1 if normalize_advantage else 0, stats.data_ptr()))
+        self._check(code, "updatePhysicsBatchPPODevice")
+        return stats
+
+    def ppo_gradients(self, obs, actions, old_log_probs, advantages, returns, indices=None, clip_range=0.1, vf_coef=0.5, ent_coef=0.0, normalize_advantage=True):
+        """The unclipped gradient of training.ppo_loss on one minibatch (the rows `indices`, all rows if None) with the parameters as they
+        are, moving nothing.  Returns (gradients, ratios [count], stats [4]): gradients under the names of parameters(), in their shapes;
+        stats = loss, policy loss, value loss, clip fraction."""
+        import torch
+        rows, t = self._rows(obs, actions, old_log_probs, advantages, returns)
+        idx = None if indices is None else self._indices(indices, rows).reshape(-1)
+        count, dev = rows if idx is None else idx.numel(), t[0].device
+        h, hv = self.hidden, self.value_hidden
+        flat = torch.empty(_network_floats(h, 27) + _network_floats(hv, 1) + 27, dtype=torch.float32, device=dev)
+        ratios = torch.empty(count, dtype=torch.float32, device=dev); stats = torch.empty(4, dtype=torch.float32, device=dev)
+        code = self._on_stream(dev, t + [flat, ratios, stats] + ([] if idx is None else [idx]), lambda: self.lib.gradientsPhysicsBatchPPODevice(
+            rows, *[x.data_ptr() for x in t], count, None if idx is None else idx.data_ptr(), clip_range, vf_coef, ent_coef, 1 if normalize_advantage else 0,
+            flat.data_ptr(), ratios.data_ptr(), stats.data_ptr()))
+        self._check(code, "gradientsPhysicsBatchPPODevice")
+        return _split_flat(flat, h, hv), ratios, stats
+
+    def parameters(self):
+        """The parameters as they are on the device now, as float32 numpy arrays under the stable-baselines names of
+        training.ActorCritic.state_dict(): POLICY_NAMES, VALUE_NAMES and "log_std", in the [out, in] shapes set_policy takes."""
+        h, hv = self.hidden, self.value_hidden
+        out = {}
+        for names, hidden, outputs, call in ((POLICY_NAMES, h, 27, self.lib.readPhysicsBatchPolicy), (VALUE_NAMES, hv, 1, self.lib.readPhysicsBatchValueNetwork)):
+            arrays = [np.zeros(shape, np.float32) for shape in ((hidden, 66), (hidden,), (hidden, hidden), (hidden,), (outputs, hidden), (outputs,))]
+            self._check(call(*[_p(a) for a in arrays]), "readPhysicsBatch network")
+            out.update(zip(names, arrays))
+        out["log_std"] = np.zeros(27, np.float32)
+        self._check(self.lib.readPhysicsBatchLogStd(None, _p(out["log_std"])), "readPhysicsBatchLogStd")
+        return out
 
     def step_policy(self, device=False):
         """One closed-loop update: the policy on the current states, smoothing, motors, push, step.  Returns (states, rewards, fallen) as

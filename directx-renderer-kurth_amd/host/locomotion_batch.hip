@@ -17,18 +17,22 @@
 // Training data (learning/learn_locomotion.py:71-107, PPO) is collected the same way: collectPhysicsBatchDevice runs the rollout's
 // updates with k_loco_sample in place of k_loco_policy, which adds the critic, the exploration noise (locomotion_policy.h:
 // noiseSample), the sampled action, its log-probability and the clamp to the action ranges in the same launch.  The advantages of
-// gaePhysicsBatchDevice come from one lane per environment walking the rows backwards.  The gradient step is not here.
+// gaePhysicsBatchDevice come from one lane per environment walking the rows backwards.
+//
+// The gradient step on that data is locomotion_update.hip's; its entry points are here (beginPhysicsBatchTraining ..
+// readPhysicsBatchLogStd).  dPolicy, dValueNet and dScales are the master copy of the parameters while a training session is open: Adam
+// writes them in place, and the kernels above read what it wrote.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <vector>
 
-#include "locomotion_policy.h"
+#include "locomotion_layers.h"
+#include "locomotion_update.h"
 
 namespace
 {
 	constexpr uint32_t NUM_MOTOR_JOINTS = NUM_CONE_TWIST + NUM_HINGE;
 	constexpr float GRID_PITCH = 8.f;
-	constexpr uint32_t POLICY_TILE = 4; // environments per workgroup of k_loco_policy, all four in the registers of every lane
 
 	// Per environment, fixed at resetPhysicsBatch: the spawn pose of every part (pose layout of the world: {pos, 0}, {quat}) and the
 	// training targets of resetTraining.
@@ -57,6 +61,14 @@ namespace
 		bool stdSet = false, rangesSet = false;
 		uint64_t noiseCounter = 0;    // collecting updates since resetPhysicsBatch
 		void* pods[2] = { nullptr, nullptr }; // cone-twist, hinge
+		// the training session of beginPhysicsBatchTraining: Adam's m, then v, in the flat parameter order of locomotion_update.h
+		bool training = false;
+		float lr = 0.f, beta1 = 0.f, beta2 = 0.f, adamEps = 0.f;
+		uint64_t adamStep = 0;
+		float* dMoments = nullptr;
+		// scratch of the gradient step, grown on demand: the slab, the gradient, the blocks' sums of squares, the groups' statistics
+		float* dSlab = nullptr; float* dGradient = nullptr; float* dPartial = nullptr; float* dGroupStats = nullptr;
+		size_t slabFloats = 0, gradientFloats = 0;
 		uint32_t generation[2] = { ~0u, ~0u };
 	};
 	batch* B = nullptr;
@@ -67,7 +79,7 @@ namespace
 	{
 		if (!b) return;
 		if (b->stream) (void)hipStreamSynchronize(b->stream);
-		void* bufs[] = { b->dInit, b->dSmoothed, b->dRng, b->dRays, b->dPushes, b->dSlots, b->dActions, b->dStates, b->dRewards, b->dFallen, b->dIds, b->dPolicy, b->dValueNet, b->dScales };
+		void* bufs[] = { b->dInit, b->dSmoothed, b->dRng, b->dRays, b->dPushes, b->dSlots, b->dActions, b->dStates, b->dRewards, b->dFallen, b->dIds, b->dPolicy, b->dValueNet, b->dScales, b->dMoments, b->dSlab, b->dGradient, b->dPartial, b->dGroupStats };
 		for (void* p : bufs) if (p) (void)hipFree(p);
 		if (b->world) mi_world_destroy(b->world);
 		delete b;
@@ -100,27 +112,6 @@ namespace
 		for (int i = 0; i < ACTION_SIZE; ++i) smoothedAll[ACTION_SIZE * e + i] = smoothed[i];
 		writeMotors(e, smoothed, slots, conePods, hingePods);
 	}
-
-	// One layer of applyLayer for POLICY_TILE environments: lane = output unit, weights transposed to [in][out] (one coalesced line per
-	// input), the tile's inputs in LDS as [in][tile] (one broadcast read per input).  Per unit and environment the products are added
-	// in ascending input order, product rounded, then added (-ffp-contract=off), then the bias: the sums of applyLayer, bit for bit.
-	__device__ float4 policyLayer(const float* __restrict__ weightsT, const float* __restrict__ bias, uint32_t inputSize, uint32_t outputSize, const float4* from, uint32_t unit, bool activation)
-	{
-		float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
-		if (unit >= outputSize) return sum;
-		#pragma unroll 8
-		for (uint32_t x = 0; x < inputSize; ++x)
-		{
-			const float w = weightsT[(size_t)x * outputSize + unit];
-			const float4 f = from[x];
-			sum.x += w * f.x; sum.y += w * f.y; sum.z += w * f.z; sum.w += w * f.w;
-		}
-		const float b = bias[unit];
-		sum.x += b; sum.y += b; sum.z += b; sum.w += b;
-		if (activation) { sum.x = tanhf(sum.x); sum.y = tanhf(sum.y); sum.z = tanhf(sum.z); sum.w = tanhf(sum.w); }
-		return sum;
-	}
-	static_assert(POLICY_TILE == 4, "policyLayer carries the tile as one float4");
 
 	// Kernel P: learned_locomotion::update for a tile of POLICY_TILE environments per workgroup: states -> three layers -> raw action;
 	// with APPLY also smoothAction and the motor PODs, i.e. everything k_loco_actions does.  blockDim.x >= max(hidden, 64), a multiple
@@ -177,16 +168,6 @@ namespace
 		}
 	}
 	static_assert(POLICY_TILE * NUM_MOTOR_JOINTS <= 64 && ACTION_SIZE <= 64, "one wave covers the tile's joints and actions");
-
-	struct network { const float* w1; const float* b1; const float* w2; const float* b2; const float* w3; const float* b3; };
-	__device__ network networkOf(const float* __restrict__ p, uint32_t hidden, uint32_t outputs)
-	{
-		network n;
-		n.w1 = p; n.b1 = n.w1 + (size_t)STATE_SIZE * hidden;
-		n.w2 = n.b1 + hidden; n.b2 = n.w2 + (size_t)hidden * hidden;
-		n.w3 = n.b2 + hidden; n.b3 = n.w3 + (size_t)hidden * outputs;
-		return n;
-	}
 
 	// The tile's states into LDS as [in][tile]; rows past count read as zeros.  copy (may be null) receives the rows as they were read.
 	__device__ void loadTile(float4* input, const float* __restrict__ states, float* __restrict__ copy, uint32_t first, uint32_t count)
@@ -553,6 +534,57 @@ namespace
 		return launchGather(b, nullptr, nullptr, b.n, dStates, dRewards, dFallen);
 	}
 
+	// Ends the training session, if one is open: the optimiser state goes, the parameters stay as they are.
+	int endTraining(batch& b)
+	{
+		if (!b.training) return 0;
+		b.training = false; b.adamStep = 0;
+		if (!ok(hipStreamSynchronize(b.stream), "end training")) return MI_ERR_HIP;
+		if (b.dMoments) (void)hipFree(b.dMoments);
+		b.dMoments = nullptr;
+		return 0;
+	}
+
+	ppo_parameters parametersOf(batch& b) { return { b.dPolicy, b.dValueNet, b.dScales, b.hidden, b.valueHidden }; }
+	ppo_scratch scratchOf(batch& b) { return { b.dSlab, b.dPartial, b.dGroupStats }; }
+
+	// The scratch of the gradient step for minibatches of up to `count` rows with the networks as they are.
+	int ensureScratch(batch& b, uint32_t count)
+	{
+		const size_t total = ppoTotal(b.hidden, b.valueHidden), slab = total * ppoGroups(count);
+		if (slab <= b.slabFloats && total <= b.gradientFloats) return 0;
+		if (!ok(hipStreamSynchronize(b.stream), "scratch")) return MI_ERR_HIP; // nothing in flight uses the old buffers
+		if (slab > b.slabFloats)
+		{
+			if (b.dSlab) (void)hipFree(b.dSlab);
+			b.dSlab = nullptr; b.slabFloats = 0;
+			if (!ok(hipMalloc(&b.dSlab, sizeof(float) * slab), "alloc")) return MI_ERR_HIP;
+			b.slabFloats = slab;
+		}
+		if (total > b.gradientFloats)
+		{
+			for (float** p : { &b.dGradient, &b.dPartial, &b.dGroupStats }) { if (*p) (void)hipFree(*p); *p = nullptr; }
+			b.gradientFloats = 0;
+			if (!ok(hipMalloc(&b.dGradient, sizeof(float) * total), "alloc") || !ok(hipMalloc(&b.dPartial, sizeof(float) * ppoBlocks(total)), "alloc")
+				|| !ok(hipMalloc(&b.dGroupStats, sizeof(float) * PPO_MAX_GROUPS * PPO_GROUP_STATS), "alloc")) return MI_ERR_HIP;
+			b.gradientFloats = total;
+		}
+		return 0;
+	}
+
+	// A network of the master copy back into the [out][in] arrays the setters take (host pointers).
+	int readNetwork(batch& b, const float* dNetwork, uint32_t h, uint32_t outputs, float* w1, float* b1, float* w2, float* b2, float* w3, float* b3)
+	{
+		const size_t floats = (size_t)h * STATE_SIZE + h + (size_t)h * h + h + (size_t)outputs * h + outputs;
+		std::vector<float> t(floats);
+		if (!ok(hipMemcpyAsync(t.data(), dNetwork, sizeof(float) * floats, hipMemcpyDeviceToHost, b.stream), "read network") || !ok(hipStreamSynchronize(b.stream), "read network")) return MI_ERR_HIP;
+		const float* q = t.data();
+		auto transposed = [&](float* w, uint32_t outs, uint32_t inputs) { for (uint32_t x = 0; x < inputs; ++x) for (uint32_t y = 0; y < outs; ++y) w[(size_t)y * inputs + x] = *q++; };
+		auto plain = [&](float* v, uint32_t count) { memcpy(v, q, sizeof(float) * count); q += count; };
+		transposed(w1, h, STATE_SIZE); plain(b1, h); transposed(w2, h, h); plain(b2, h); transposed(w3, outputs, h); plain(b3, outputs);
+		return 0;
+	}
+
 	int copyOut(batch& b, float* outStates, float* outRewards, int32_t* outFallen)
 	{
 		if (outStates && !ok(hipMemcpyAsync(outStates, b.dStates, sizeof(float) * STATE_SIZE * b.n, hipMemcpyDeviceToHost, b.stream), "states")) return MI_ERR_HIP;
@@ -812,8 +844,101 @@ extern "C"
 		hipLaunchKernelGGL(k_loco_gae, blocks(n), dim3(64), 0, B->stream, steps, n, gamma, lambda, dRewards, dValues, dDones, dLastValues, dAdvantages, dReturns);
 		return ok(hipGetLastError(), "gae kernel") ? 0 : MI_ERR_HIP;
 	}
+
+	// Opens a training session on the batch's networks: Adam (torch.optim.Adam: lr, betas, eps) with m, v and the step count at zero.
+	// From here on the device buffers the kernels read are the master copy of the parameters: updatePhysicsBatchPPODevice moves them in
+	// place, readPhysicsBatch* return them, and the library's host copies (what the setters received) fall behind.  setPhysicsPolicy,
+	// setPhysicsValueNetwork and setPhysicsActionStd end the session and drop the optimiser state; so does resetPhysicsBatch, which
+	// builds a new batch from the host copies.  Needs a policy, a critic and a std.
+	int beginPhysicsBatchTraining(float lr, float beta1, float beta2, float adamEps)
+	{
+		if (!B || !B->hidden || !B->valueHidden || !B->stdSet) return MI_ERR_INVALID_STATE;
+		if (!(lr >= 0.f) || !(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f) || !(adamEps >= 0.f)) return MI_ERR_INVALID_ARGUMENT;
+		batch& b = *B;
+		if (int e = endTraining(b)) return e;
+		const size_t total = ppoTotal(b.hidden, b.valueHidden);
+		if (!ok(hipMalloc(&b.dMoments, sizeof(float) * 2 * total), "alloc")) return MI_ERR_HIP;
+		if (!ok(hipMemsetAsync(b.dMoments, 0, sizeof(float) * 2 * total, b.stream), "moments")) return MI_ERR_HIP;
+		b.lr = lr; b.beta1 = beta1; b.beta2 = beta2; b.adamEps = adamEps; b.adamStep = 0; b.training = true;
+		return 0;
+	}
+
+	int endPhysicsBatchTraining(void) { return B ? endTraining(*B) : MI_ERR_INVALID_STATE; }
+
+	// PPO's epochs over `rows` collected rows (device buffers: dObs [rows][66], dActions [rows][27], dOldLogProbs, dAdvantages, dReturns
+	// [rows]), enqueued on the world's stream, three launches per minibatch, no host synchronisation.  dOrder [epochs][rows] (uint32 row
+	// indices, one permutation per epoch; an index >= rows reads the last row) is cut into ceil(rows / batchSize) minibatches per epoch,
+	// the last one short.  Each minibatch is one optimiser step of training.py's loop: ppo_loss (clipRange, vfCoef, entCoef, advantages
+	// normalised per minibatch of more than one row with normalizeAdvantage), clip_grad_norm_(maxGradNorm), Adam.  dStats (may be NULL)
+	// [epochs * minibatches][5] receives per step {loss, policy loss, value loss, clip fraction, gradient norm before clipping}.
+	int updatePhysicsBatchPPODevice(uint32_t rows, const float* dObs, const float* dActions, const float* dOldLogProbs, const float* dAdvantages, const float* dReturns,
+		uint32_t epochs, const uint32_t* dOrder, uint32_t batchSize, float clipRange, float vfCoef, float entCoef, float maxGradNorm, int normalizeAdvantage, float* dStats)
+	{
+		if (!B || !B->training) return MI_ERR_INVALID_STATE;
+		if (!rows || !epochs || !batchSize || !dObs || !dActions || !dOldLogProbs || !dAdvantages || !dReturns || !dOrder) return MI_ERR_INVALID_ARGUMENT;
+		batch& b = *B;
+		if (int e = ensureScratch(b, batchSize < rows ? batchSize : rows)) return e;
+		const ppo_parameters p = parametersOf(b);
+		const ppo_scratch scratch = scratchOf(b);
+		const ppo_rows data = { rows, dObs, dActions, dOldLogProbs, dAdvantages, dReturns };
+		const ppo_loss loss = { clipRange, vfCoef, entCoef, normalizeAdvantage };
+		const size_t total = ppoTotal(b.hidden, b.valueHidden);
+		for (uint32_t epoch = 0; epoch < epochs; ++epoch)
+			for (uint32_t start = 0; start < rows; start += batchSize)
+			{
+				const uint32_t count = rows - start < batchSize ? rows - start : batchSize;
+				float* stats = dStats; if (dStats) dStats += PPO_STATS;
+				if (int e = ppoGradients(b.stream, p, data, dOrder + (size_t)rows * epoch + start, count, loss, scratch, b.dGradient, nullptr, stats)) return e;
+				const double t = (double)++b.adamStep;
+				const ppo_adam adam = { b.beta1, b.beta2, b.adamEps, (float)((double)b.lr / (1.0 - pow((double)b.beta1, t))), (float)sqrt(1.0 - pow((double)b.beta2, t)), maxGradNorm };
+				if (int e = ppoAdam(b.stream, p, scratch, b.dGradient, b.dMoments, b.dMoments + total, adam, stats)) return e;
+			}
+		return 0;
+	}
+
+	// The parity facility of the gradient step: the unclipped gradient of ppo_loss on one minibatch, dIndices [count] (uint32 rows of the
+	// buffers; NULL: rows 0 .. count-1), into dGradient in the flat parameter order of locomotion_update.h (the device's [in][out]
+	// layouts: actor, critic, logStd), the per-row ratio exp(logp - old) into dRatios [count] (may be NULL), and {loss, policy loss, value
+	// loss, clip fraction} into dStats [4] (may be NULL).  Touches neither the parameters nor the optimiser state; needs no session.
+	int gradientsPhysicsBatchPPODevice(uint32_t rows, const float* dObs, const float* dActions, const float* dOldLogProbs, const float* dAdvantages, const float* dReturns,
+		uint32_t count, const uint32_t* dIndices, float clipRange, float vfCoef, float entCoef, int normalizeAdvantage, float* dGradient, float* dRatios, float* dStats)
+	{
+		if (!B || !B->hidden || !B->valueHidden || !B->stdSet) return MI_ERR_INVALID_STATE;
+		if (!rows || !count || (!dIndices && count > rows) || !dObs || !dActions || !dOldLogProbs || !dAdvantages || !dReturns || !dGradient) return MI_ERR_INVALID_ARGUMENT;
+		batch& b = *B;
+		if (int e = ensureScratch(b, count)) return e;
+		const ppo_rows data = { rows, dObs, dActions, dOldLogProbs, dAdvantages, dReturns };
+		const ppo_loss loss = { clipRange, vfCoef, entCoef, normalizeAdvantage };
+		return ppoGradients(b.stream, parametersOf(b), data, dIndices, count, loss, scratchOf(b), dGradient, dRatios, dStats);
+	}
+
+	// The parameters as they are on the device, after everything enqueued so far, in the layouts the setters take (host pointers).
+	int readPhysicsBatchPolicy(float* w1, float* b1, float* w2, float* b2, float* w3, float* b3)
+	{
+		if (!B || !B->hidden) return MI_ERR_INVALID_STATE;
+		if (!w1 || !b1 || !w2 || !b2 || !w3 || !b3) return MI_ERR_INVALID_ARGUMENT;
+		return readNetwork(*B, B->dPolicy, B->hidden, ACTION_SIZE, w1, b1, w2, b2, w3, b3);
+	}
+	int readPhysicsBatchValueNetwork(float* w1, float* b1, float* w2, float* b2, float* w3, float* b3)
+	{
+		if (!B || !B->valueHidden) return MI_ERR_INVALID_STATE;
+		if (!w1 || !b1 || !w2 || !b2 || !w3 || !b3) return MI_ERR_INVALID_ARGUMENT;
+		return readNetwork(*B, B->dValueNet, B->valueHidden, 1, w1, b1, w2, b2, w3, b3);
+	}
+	// std [27] (may be NULL) and logStd [27].
+	int readPhysicsBatchLogStd(float* std, float* logStd)
+	{
+		if (!B || !B->stdSet) return MI_ERR_INVALID_STATE;
+		if (!logStd) return MI_ERR_INVALID_ARGUMENT;
+		float scales[2 * ACTION_SIZE];
+		if (!ok(hipMemcpyAsync(scales, B->dScales, sizeof(scales), hipMemcpyDeviceToHost, B->stream), "read std") || !ok(hipStreamSynchronize(B->stream), "read std")) return MI_ERR_HIP;
+		if (std) memcpy(std, scales, sizeof(float) * ACTION_SIZE);
+		memcpy(logStd, scales + ACTION_SIZE, sizeof(float) * ACTION_SIZE);
+		return 0;
+	}
 }
 
-int locomotionBatchPolicyChanged() { return B ? uploadPolicy(*B) : 0; }
-int locomotionBatchValueChanged() { return B ? uploadValueNetwork(*B) : 0; }
-int locomotionBatchStdChanged() { return B ? uploadActionStd(*B) : 0; }
+// A new network or std from the host replaces the master copy: an open training session ends with it.
+int locomotionBatchPolicyChanged() { if (!B) return 0; if (int e = endTraining(*B)) return e; return uploadPolicy(*B); }
+int locomotionBatchValueChanged() { if (!B) return 0; if (int e = endTraining(*B)) return e; return uploadValueNetwork(*B); }
+int locomotionBatchStdChanged() { if (!B) return 0; if (int e = endTraining(*B)) return e; return uploadActionStd(*B); }

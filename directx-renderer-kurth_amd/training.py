@@ -1,7 +1,9 @@
 """PPO for the ragdoll locomotion controller, as the reference trains it (learning/learn_locomotion.py:71-107: stable-baselines PPO,
 pi=[128,128], vf=[128,128], tanh, clip_range 0.1, n_epochs 10, batch_size 128, lr 2.5e-5, action layer initialised U(-0.01, 0.01)),
 split where the work is: the rollouts, the sampled actions, their log-probabilities, the values and the advantages come from the device
-kernels of LocomotionBatch.collect() and .gae(); the gradient step is PyTorch's.  stable-baselines is not needed.
+kernels of LocomotionBatch.collect() and .gae(); the gradient step is PyTorch's by default, and with device_update=True the device's
+(LocomotionBatch.ppo_update: the same loss, clipping and Adam in three launches per minibatch, the parameters staying on the device).
+stable-baselines is not needed.
 
 The torch modules carry stable-baselines' parameter names, so ActorCritic.state_dict() is what LocomotionBatch.set_policy() and
 .set_value_network() take."""
@@ -72,10 +74,12 @@ def ppo_loss(log_probs, old_log_probs, advantages, values, returns, entropy, cli
 
 
 class PPOTrainer:
-    """PPO over a LocomotionBatch.  iterate(steps) collects steps x n transitions on the device and runs the epochs of minibatches."""
+    """PPO over a LocomotionBatch.  iterate(steps) collects steps x n transitions on the device and runs the epochs of minibatches.
+    With device_update the epochs run on the device too: the module's parameters go to the device once, before the first iteration, the
+    device's copy is the one that learns, and pull() brings it back into trainer.model when it is wanted."""
 
     def __init__(self, batch, hidden=128, value_hidden=128, clip_range=0.1, n_epochs=10, batch_size=128, lr=2.5e-5, gamma=0.99, gae_lambda=0.95,
-                 vf_coef=0.5, ent_coef=0.0, max_grad_norm=0.5, normalize_advantage=True, clip_actions=True, seed=0):
+                 vf_coef=0.5, ent_coef=0.0, max_grad_norm=0.5, normalize_advantage=True, clip_actions=True, seed=0, device_update=False):
         self.batch = batch
         self.device = torch.device("cuda", torch.cuda.current_device())
         self.generator = torch.Generator(device="cpu").manual_seed(seed)
@@ -87,6 +91,7 @@ class PPOTrainer:
         self.clip_range, self.n_epochs, self.batch_size = clip_range, n_epochs, batch_size
         self.gamma, self.gae_lambda, self.vf_coef, self.ent_coef, self.max_grad_norm = gamma, gae_lambda, vf_coef, ent_coef, max_grad_norm
         self.normalize_advantage, self.clip_actions = normalize_advantage, clip_actions
+        self.lr, self.adam_eps, self.device_update, self._session = lr, 1e-5, device_update, False
 
     def sync(self):
         """The module's weights and log_std to the library (and so to the batch's device copies)."""
@@ -97,6 +102,8 @@ class PPOTrainer:
 
     def iterate(self, steps):
         """One PPO iteration: sync, collect, gae, epochs.  Returns statistics as a dict of floats."""
+        if self.device_update:
+            return self._iterate_device(steps)
         self.sync()
         data = self.batch.collect(steps, clip=self.clip_actions)
         advantages, returns = self.batch.gae(data["rewards"], data["values"], data["dones"], data["last_values"], self.gamma, self.gae_lambda)
@@ -131,3 +138,25 @@ class PPOTrainer:
         stats.update(loss=losses[-1][0], policy_loss=sum(l[1] for l in losses) / len(losses), value_loss=sum(l[2] for l in losses) / len(losses),
                      clip_fraction=sum(l[3] for l in losses) / len(losses), first_loss=losses[0][0])
         return stats
+
+    def _iterate_device(self, steps):
+        """iterate() with the epochs on the device: the same permutations from the same generator, one ppo_update, one read of its statistics."""
+        if not self._session:
+            self.sync()
+            self.batch.begin_training(lr=self.lr, eps=self.adam_eps)
+            self._session = True
+        data = self.batch.collect(steps, clip=self.clip_actions)
+        advantages, returns = self.batch.gae(data["rewards"], data["values"], data["dones"], data["last_values"], self.gamma, self.gae_lambda)
+        rows = steps * self.batch.n
+        order = torch.stack([torch.randperm(rows, generator=self.generator) for _ in range(self.n_epochs)])
+        steps_stats = self.batch.ppo_update(data["obs"], data["actions"], data["log_probs"], advantages, returns, order, self.batch_size, self.clip_range,
+                                            self.vf_coef, self.ent_coef, self.max_grad_norm, self.normalize_advantage)
+        s = steps_stats.cpu().double()   # the one read of the update
+        stats = dict(mean_reward=float(data["rewards"].mean()), falls=int(data["dones"].sum()), rows=rows)
+        stats.update(loss=float(s[-1, 0]), policy_loss=float(s[:, 1].mean()), value_loss=float(s[:, 2].mean()), clip_fraction=float(s[:, 3].mean()),
+                     first_loss=float(s[0, 0]), grad_norm=float(s[:, 4].mean()))
+        return stats
+
+    def pull(self):
+        """The device's parameters into trainer.model (device_update: the module is not refreshed per step)."""
+        self.model.load_state_dict({k: torch.from_numpy(v) for k, v in self.batch.parameters().items()})
