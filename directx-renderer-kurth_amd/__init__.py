@@ -43,6 +43,12 @@ class Settings(C.Structure):
             setattr(self, k, v)
 
 
+class DeviceState(C.Structure):
+    """struct mi_device_state (include/mi_physics.h): the world's device buffers and its stream"""
+    _fields_ = [("pose", C.c_void_p), ("pose0", C.c_void_p), ("poseLerp", C.c_void_p), ("vel", C.c_void_p), ("force", C.c_void_p), ("stream", C.c_void_p),
+                ("numBodies", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class WorldDesc(C.Structure):
     _fields_ = [("device", C.c_int32), ("reserveBodies", C.c_uint32), ("reserveColliders", C.c_uint32), ("reservePairs", C.c_uint32)]
 
@@ -78,7 +84,7 @@ EXPORTED_SYMBOLS = [
     "mi_set_transform", "mi_write_transforms", "mi_write_velocities", "mi_step", "mi_step_internal", "mi_synchronize", "mi_read_transforms", "mi_read_velocities", "mi_read_mass_properties",
     "mi_get_stats", "mi_enable_validation", "mi_enable_stage_timing", "mi_num_bodies", "mi_num_colliders", "mi_device_pointers", "mi_state_to_device_buffers", "mi_state_from_device_buffers", "mi_slab_configure", "mi_slab_message_bytes", "mi_slab_pack", "mi_slab_unpack", "mi_slab_read_codes", "mi_debug_num_pairs", "mi_debug_read_pairs", "mi_debug_sorting_axis", "mi_debug_narrow_limits",
     "mi_debug_read_world_colliders", "mi_debug_num_manifold_slots", "mi_debug_read_manifolds", "mi_debug_num_colors", "mi_debug_read_schedule",
-    "mi_debug_read_joint_order", "mi_debug_read_joint_update", "mi_debug_read_body_state", "mi_debug_flow_trace",
+    "mi_debug_read_joint_order", "mi_debug_read_joint_update", "mi_debug_read_body_state", "mi_debug_read_accumulators", "mi_debug_flow_trace",
     "mi_debug_set_replay", "mi_debug_num_replay_batches", "mi_debug_read_replay_batches",
     "mi_device_state", "mi_joint_device_pods", "mi_test_physics_interaction_batch",
 ]
@@ -364,6 +370,42 @@ class World:
         """testPhysicsInteraction(scene, ray, strength) — reference physics.h:404.  Returns the pushed body's index or None."""
         r = self.lib.mi_test_physics_interaction(self.w, _f(origin), _f(direction), C.c_float(strength))
         return r - 1 if r > 0 else None
+
+    def device_state(self):
+        """mi_device_state: the device addresses of pose, pose0, poseLerp, vel, force and the world's stream, after an upload."""
+        ds = DeviceState()
+        self._check(self.lib.mi_device_state(self.w, C.byref(ds)))
+        return ds
+
+    def _interaction_batch(self, rays, first_body, bodies_per_ray, fill, extra):
+        """(status code, int32 results [n + extra], every entry `fill` before the launch) of mi_test_physics_interaction_batch"""
+        import torch
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+        n = len(rays)
+        dev = torch.device("cuda", torch.cuda.current_device())
+        ext = torch.cuda.ExternalStream(self.device_state().stream or 0, device=dev)
+        with torch.cuda.stream(ext):
+            d_rays = torch.from_numpy(rays).to(dev) if n else torch.zeros((1, 8), dtype=torch.float32, device=dev)
+            d_out = torch.full((n + extra,), fill, dtype=torch.int32, device=dev)
+            code = self.lib.mi_test_physics_interaction_batch(self.w, C.c_uint32(n), C.c_uint32(first_body), C.c_uint32(bodies_per_ray),
+                                                              C.c_void_p(d_rays.data_ptr()), C.c_void_p(d_out.data_ptr()))
+            ext.synchronize()
+            out = d_out.cpu().numpy()
+        return code, out
+
+    def test_physics_interaction_batch(self, rays, first_body, bodies_per_ray, fill=0, extra=0):
+        """mi_test_physics_interaction_batch: test_physics_interaction for rays [n, 8] = origin, strength, direction, enabled, ray i against
+        the bodies first_body + i * bodies_per_ray ... only, as one kernel on the world's stream (import torch before the first World).
+        Returns int32 [n + extra]: 1 + the pushed body or 0 per ray; the buffer holds `fill` before the launch."""
+        code, out = self._interaction_batch(rays, first_body, bodies_per_ray, fill, extra)
+        self._check(code)
+        return out
+
+    def accumulators(self):
+        """Force and torque accumulators of every body [n, 6]: the pushes the next step will apply and clear."""
+        out = np.zeros((self.num_bodies, 6), np.float32)
+        self._check(self.lib.mi_debug_read_accumulators(self.w, _p(out), C.c_uint32(len(out))))
+        return out
 
     def apply_force_torque(self, body, force, torque=(0, 0, 0)):
         self._check(self.lib.mi_apply_force_torque(self.w, body, _f(force), _f(torque)))

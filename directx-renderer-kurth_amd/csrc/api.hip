@@ -530,6 +530,23 @@ int mi_debug_read_body_state(mi_world* world, float* outCog4, float* outInvInert
 	d2h(W, outCog4, W->cog.p, sizeof(float4) * n); d2h(W, outInvInertia12, W->invIw.p, sizeof(float4) * 3 * n);
 	return W->lastError;
 }
+// force / torque accumulators of the first n bodies, 6 floats each: what mi_test_physics_interaction, its batched form, mi_apply_force_torque
+// and the force fields have added since the last step cleared them (pushes still held on the host are uploaded first)
+int mi_debug_read_accumulators(mi_world* world, float* outForceTorque6, uint32_t n)
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	W->resolvePendingFlow();
+	W->upload();
+	n = std::min<u32>(n, W->nb);
+	std::vector<float4> f(2 * (size_t)n);
+	d2h(W, f.data(), W->force.p, sizeof(float4) * f.size());
+	for (u32 i = 0; i < n; ++i)
+	{
+		float* o = outForceTorque6 + 6 * (size_t)i;
+		o[0] = f[2 * i].x; o[1] = f[2 * i].y; o[2] = f[2 * i].z; o[3] = f[2 * i + 1].x; o[4] = f[2 * i + 1].y; o[5] = f[2 * i + 1].z;
+	}
+	return W->lastError;
+}
 /* Replay facility: on != 0 makes every following step solve its contacts in the REFERENCE's own order (its greedy 8-wide batch
  * scheduler over the contacts in emission order, constraints.cpp:51-184, batches executed one after the other) instead of the
  * device's schedule.  One workgroup sweeps everything: for parity tests on small worlds, not for speed. */

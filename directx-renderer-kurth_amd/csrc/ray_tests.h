@@ -13,16 +13,20 @@ MI_DEV bool rayPlane(const HRay& r, V3 normal, float d, float& outT)
 	outT = -(dot(r.origin, normal) + d) / ndotd;
 	return true;
 }
+// the reference's own min / max (pch.h:57-67), not fminf / fmaxf: they differ in which operand a NaN replaces, and 0 * inf is a NaN here
+// whenever the origin lies on a slab plane of an axis the ray does not move along
+MI_DEV float refMin(float a, float b) { return (a < b) ? a : b; }
+MI_DEV float refMax(float a, float b) { return (a < b) ? b : a; }
 MI_DEV bool rayAABB(const HRay& r, V3 lo, V3 hi, float& outT)
 {
 	V3 invDir = v3(1.f / r.direction.x, 1.f / r.direction.y, 1.f / r.direction.z);
 	float tx1 = (lo.x - r.origin.x) * invDir.x, tx2 = (hi.x - r.origin.x) * invDir.x;
-	outT = fminf(tx1, tx2);
-	float tmax = fmaxf(tx1, tx2);
+	outT = refMin(tx1, tx2);
+	float tmax = refMax(tx1, tx2);
 	float ty1 = (lo.y - r.origin.y) * invDir.y, ty2 = (hi.y - r.origin.y) * invDir.y;
-	outT = fmaxf(outT, fminf(ty1, ty2)); tmax = fminf(tmax, fmaxf(ty1, ty2));
+	outT = refMax(outT, refMin(ty1, ty2)); tmax = refMin(tmax, refMax(ty1, ty2));
 	float tz1 = (lo.z - r.origin.z) * invDir.z, tz2 = (hi.z - r.origin.z) * invDir.z;
-	outT = fmaxf(outT, fminf(tz1, tz2)); tmax = fminf(tmax, fmaxf(tz1, tz2));
+	outT = refMax(outT, refMin(tz1, tz2)); tmax = refMin(tmax, refMax(tz1, tz2));
 	return tmax >= outT && outT > 0.f;
 }
 MI_DEV bool raySphere(const HRay& r, V3 center, float radius, float& outT)
@@ -71,10 +75,13 @@ MI_DEV bool rayCylinder(const HRay& r, V3 pa, V3 pb, float radius, float& outT)
 MI_DEV bool rayCapsule(const HRay& r, V3 pa, V3 pb, float radius, float& outT)
 {
 	outT = MI_FLT_MAX;
-	float t; bool result = false;
+	// t starts at 0: the reference declares it unwritten (bounding_volumes.cpp:366), and intersectCylinder reads it at :357 when the origin
+	// is radially inside and no cap disk is taken (:346-355); on the device that is a register nobody wrote.  0 is what rayBodyCollider
+	// hands the cylinder collider (physics.cpp:577).
+	float t = 0.f; bool result = false;
 	if (rayCylinder(r, pa, pb, radius, t)) { outT = t; result = true; }
-	if (raySphere(r, pa, radius, t)) { outT = fminf(outT, t); result = true; }
-	if (raySphere(r, pb, radius, t)) { outT = fminf(outT, t); result = true; }
+	if (raySphere(r, pa, radius, t)) { outT = refMin(outT, t); result = true; }
+	if (raySphere(r, pb, radius, t)) { outT = refMin(outT, t); result = true; }
 	return result;
 }
 MI_DEV bool pointInTriangleH(V3 point, V3 a, V3 b, V3 c)

@@ -306,6 +306,7 @@ int mi_debug_read_joint_order(mi_world* w, uint32_t type, uint32_t* outJointIds)
 enum { MI_JOINT_PATH_LAUNCH_SWEEP = 0, MI_JOINT_PATH_CLUSTER = 1, MI_JOINT_PATH_INTERLEAVED = 2, MI_JOINT_PATH_NONE = 3 };
 int mi_debug_read_joint_update(mi_world* w, uint32_t type, float* out, uint32_t capacityFloats, uint32_t* outPath);
 int mi_debug_read_body_state(mi_world* w, float* outCog4, float* outInvInertia12, uint32_t nPlusOne); /* rbGlobal: {cog.xyz, invMass}, 3 x float4 columns */
+int mi_debug_read_accumulators(mi_world* w, float* outForceTorque6, uint32_t n); /* force.xyz, torque.xyz of the first n bodies: the pushes waiting for the next step */
 /* Replay of the reference's own Gauss-Seidel order (SURVEY section 7 / 8c "replay mode"): on != 0 makes the following steps run the reference's
  * greedy 8-wide batch scheduler (scheduleConstraintsSIMD, constraints.cpp:51-184) over the step's contacts in emission order and sweep
  * the batches one after the other (constraints.cpp:3618-3709) instead of the device's own schedule.  A parity facility (one workgroup

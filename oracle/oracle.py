@@ -76,6 +76,7 @@ def _lib(avx2=False):
             getattr(lib, name).restype = C.c_uint32
         lib.orc_heightmap_height_at.restype = C.c_float
         lib.orc_poly_trig.restype = C.c_float
+        lib.orc_last_interaction_distance.restype = C.c_float
         _libs[key] = lib
     return _libs[key]
 
@@ -253,6 +254,16 @@ class OracleWorld:
     def test_physics_interaction(self, origin, direction, strength=1000.0):
         r = self.lib.orc_test_physics_interaction(self.w, _f(origin), _f(direction), C.c_float(strength))
         return r - 1 if r > 0 else None
+
+    def last_interaction_distance(self):
+        """The distance t of the closest hit of this world's last test_physics_interaction (the push does not depend on it)."""
+        return float(self.lib.orc_last_interaction_distance(self.w))
+
+    def accumulators(self):
+        """forceAccumulator, torqueAccumulator of every body [n, 6]: what the next step will apply and clear."""
+        out = np.zeros((self.num_bodies, 6), np.float32)
+        self.lib.orc_read_accumulators(self.w, _p(out))
+        return out
 
     def apply_force_torque(self, body, force, torque=(0, 0, 0)):
         assert self.lib.orc_apply_force_torque(self.w, body, _f(force), _f(torque)) == 0

@@ -67,6 +67,7 @@ enum solver_mode : u32 { solver_scalar = 0, solver_wide8 = 1, solver_custom_orde
 static const u32 ORC_JOINT_DECISION_FLOATS = 24;
 struct world
 {
+	float lastInteractionT = FLT_MAX; // distance of the closest hit of the last orc_test_physics_interaction (FLT_MAX: nothing was hit)
 	std::vector<body> bodies;
 	std::vector<collider> colliders;
 	std::vector<bounding_hull_geometry> hullGeometries; // boundingHullGeometries (physics.cpp:47), per world instead of global
@@ -1368,16 +1369,20 @@ static bool intersectPlane(const ray& r, vec3 normal, float d, float& outT)
 	outT = -(dot(r.origin, normal) + d) / ndotd;
 	return true;
 }
+// the reference's own min / max (pch.h:57-67), not std::min / std::max: they differ in which operand a NaN replaces, and 0 * inf is a NaN
+// here whenever the origin lies on a slab plane of an axis the ray does not move along
+static inline float refMin(float a, float b) { return (a < b) ? a : b; }
+static inline float refMax(float a, float b) { return (a < b) ? b : a; }
 static bool intersectAABB(const ray& r, const bounding_box& a, float& outT)
 {
 	vec3 invDir = vec3(1.f / r.direction.x, 1.f / r.direction.y, 1.f / r.direction.z);
 	float tx1 = (a.minCorner.x - r.origin.x) * invDir.x, tx2 = (a.maxCorner.x - r.origin.x) * invDir.x;
-	outT = std::min(tx1, tx2);
-	float tmax = std::max(tx1, tx2);
+	outT = refMin(tx1, tx2);
+	float tmax = refMax(tx1, tx2);
 	float ty1 = (a.minCorner.y - r.origin.y) * invDir.y, ty2 = (a.maxCorner.y - r.origin.y) * invDir.y;
-	outT = std::max(outT, std::min(ty1, ty2)); tmax = std::min(tmax, std::max(ty1, ty2));
+	outT = refMax(outT, refMin(ty1, ty2)); tmax = refMin(tmax, refMax(ty1, ty2));
 	float tz1 = (a.minCorner.z - r.origin.z) * invDir.z, tz2 = (a.maxCorner.z - r.origin.z) * invDir.z;
-	outT = std::max(outT, std::min(tz1, tz2)); tmax = std::min(tmax, std::max(tz1, tz2));
+	outT = refMax(outT, refMin(tz1, tz2)); tmax = refMin(tmax, refMax(tz1, tz2));
 	return tmax >= outT && outT > 0.f;
 }
 static bool intersectSphere(const ray& r, vec3 center, float radius, float& outT)
@@ -1430,10 +1435,12 @@ static bool intersectCylinder(const ray& r, const bounding_cylinder& cylinder, f
 static bool intersectCapsule(const ray& r, const bounding_capsule& capsule, float& outT)
 {
 	outT = FLT_MAX;
-	float t; bool result = false;
+	// t starts at 0: the reference declares it unwritten (bounding_volumes.cpp:366), and intersectCylinder reads it at :357 when the origin
+	// is radially inside and no cap disk is taken (:346-355).  0 is what testPhysicsInteraction hands the cylinder collider (physics.cpp:577).
+	float t = 0.f; bool result = false;
 	if (intersectCylinder(r, bounding_cylinder{ capsule.positionA, capsule.positionB, capsule.radius }, t)) { outT = t; result = true; }
-	if (intersectSphere(r, capsule.positionA, capsule.radius, t)) { outT = std::min(outT, t); result = true; }
-	if (intersectSphere(r, capsule.positionB, capsule.radius, t)) { outT = std::min(outT, t); result = true; }
+	if (intersectSphere(r, capsule.positionA, capsule.radius, t)) { outT = refMin(outT, t); result = true; }
+	if (intersectSphere(r, capsule.positionB, capsule.radius, t)) { outT = refMin(outT, t); result = true; }
 	return result;
 }
 static bool pointInTriangle(vec3 point, vec3 triA, vec3 triB, vec3 triC)
@@ -1457,6 +1464,9 @@ static bool intersectTriangle(const ray& r, vec3 a, vec3 b, vec3 c, float& outT)
 	vec3 q = r.origin + outT * r.direction;
 	return outT >= 0.f && pointInTriangle(q, a, b, c);
 }
+// the distance of the closest hit of this world's last orc_test_physics_interaction (FLT_MAX: nothing was hit).  The push does not show it: the
+// force is along the ray, so the torque is the same wherever along the ray it is applied.
+float orc_last_interaction_distance(world* w) { return w->lastInteractionT; }
 // returns 1 + the index of the pushed body, 0 if nothing was hit
 u32 orc_test_physics_interaction(world* w, const float* origin, const float* direction, float strength)
 {
@@ -1508,6 +1518,7 @@ u32 orc_test_physics_interaction(world* w, const float* origin, const float* dir
 			torque = cross(globalHit - cogPosition, force);
 		}
 	}
+	w->lastInteractionT = minT;
 	if (minRB < 0) { return 0; }
 	w->bodies[minRB].torqueAccumulator += torque;
 	w->bodies[minRB].forceAccumulator += force;
@@ -1616,6 +1627,16 @@ void orc_read_velocities(world* w, float* out6)
 	}
 }
 // localCOG(3) invMass(1) invInertia(9, column-major like the reference's mat3)
+// forceAccumulator / torqueAccumulator of every body (what testPhysicsInteraction and the force fields add to until the next step clears them)
+void orc_read_accumulators(world* w, float* out6)
+{
+	for (size_t i = 0; i < w->bodies.size(); ++i)
+	{
+		float* o = out6 + 6 * i; const body& b = w->bodies[i];
+		o[0] = b.forceAccumulator.x; o[1] = b.forceAccumulator.y; o[2] = b.forceAccumulator.z;
+		o[3] = b.torqueAccumulator.x; o[4] = b.torqueAccumulator.y; o[5] = b.torqueAccumulator.z;
+	}
+}
 void orc_read_mass_properties(world* w, float* out13)
 {
 	for (size_t i = 0; i < w->bodies.size(); ++i)
