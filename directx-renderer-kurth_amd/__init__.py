@@ -49,6 +49,16 @@ class DeviceState(C.Structure):
                 ("numBodies", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class RayHit(C.Structure):
+    """struct mi_ray_hit (include/mi_physics.h): one record of mi_raycast_batch, 32 bytes"""
+    _fields_ = [("t", C.c_float), ("collider", C.c_uint32), ("body", C.c_uint32), ("hit", C.c_uint32), ("point", C.c_float * 3), ("reserved", C.c_float)]
+
+
+RAY_HIT_DTYPE = np.dtype([("t", "<f4"), ("collider", "<u4"), ("body", "<u4"), ("hit", "<u4"), ("point", "<f4", 3), ("reserved", "<f4")])
+RAY_STATIC, RAY_BRUTE_FORCE = 1, 2
+STATIC_BODY = 0xFFFFFFFF   # mi_ray_hit.body of a collider without a rigid body (MI_STATIC_BODY)
+
+
 class WorldDesc(C.Structure):
     _fields_ = [("device", C.c_int32), ("reserveBodies", C.c_uint32), ("reserveColliders", C.c_uint32), ("reservePairs", C.c_uint32)]
 
@@ -86,7 +96,7 @@ EXPORTED_SYMBOLS = [
     "mi_debug_read_world_colliders", "mi_debug_num_manifold_slots", "mi_debug_read_manifolds", "mi_debug_num_colors", "mi_debug_read_schedule",
     "mi_debug_read_joint_order", "mi_debug_read_joint_update", "mi_debug_read_body_state", "mi_debug_read_accumulators", "mi_debug_flow_trace",
     "mi_debug_set_replay", "mi_debug_num_replay_batches", "mi_debug_read_replay_batches",
-    "mi_device_state", "mi_joint_device_pods", "mi_test_physics_interaction_batch",
+    "mi_device_state", "mi_joint_device_pods", "mi_test_physics_interaction_batch", "mi_raycast_batch", "mi_raycast_host",
 ]
 
 
@@ -401,6 +411,45 @@ class World:
         self._check(code)
         return out
 
+    def raycast(self, rays, static=True, brute_force=False):
+        """mi_raycast_batch: rays [n, 8] = origin, maxT, direction, enabled, each against every candidate collider of the world (with
+        `static` also the colliders of entities without a rigid body); nothing is pushed.  brute_force: every ray against every
+        candidate, no tree (same answers).
+        numpy rays are copied to the device and the hits back: returns (t [n], collider [n], body [n], hit [n], point [n, 3]); body is
+        STATIC_BODY for a static collider, everything 0 for a miss.
+        A torch tensor on the device (float32, contiguous) is used in place: returns one float32 tensor [n, 8] of mi_ray_hit records
+        (columns 1..3 hold the bits of collider, body, hit: view them with .view(torch.int32)), enqueued on the world's stream with no
+        synchronisation."""
+        import torch
+        flags = (RAY_STATIC if static else 0) | (RAY_BRUTE_FORCE if brute_force else 0)
+        if isinstance(rays, torch.Tensor):
+            if not rays.is_cuda or rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous():
+                raise ValueError("raycast: a device tensor must be float32, contiguous and [n, 8]")
+            ext = torch.cuda.ExternalStream(self.device_state().stream or 0, device=rays.device)
+            ext.wait_stream(torch.cuda.current_stream(rays.device))   # the rays were written on the caller's stream
+            with torch.cuda.stream(ext):
+                out = torch.empty((rays.shape[0], 8), dtype=torch.float32, device=rays.device)
+                self._check(self.lib.mi_raycast_batch(self.w, C.c_uint32(rays.shape[0]), C.c_void_p(rays.data_ptr()), C.c_uint32(flags), C.c_void_p(out.data_ptr())))
+            rays.record_stream(ext)
+            torch.cuda.current_stream(rays.device).wait_stream(ext)   # stream order, not a host synchronisation
+            return out
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+        n = len(rays)
+        hits = np.zeros(n, RAY_HIT_DTYPE)
+        if n:
+            dev = torch.device("cuda", torch.cuda.current_device())
+            ext = torch.cuda.ExternalStream(self.device_state().stream or 0, device=dev)
+            with torch.cuda.stream(ext):
+                d_rays = torch.from_numpy(rays).to(dev)
+                d_out = torch.empty((n, 8), dtype=torch.float32, device=dev)
+                code = self.lib.mi_raycast_batch(self.w, C.c_uint32(n), C.c_void_p(d_rays.data_ptr()), C.c_uint32(flags), C.c_void_p(d_out.data_ptr()))
+                ext.synchronize()
+                self._check(code)
+                hits = d_out.cpu().numpy().view(RAY_HIT_DTYPE).reshape(n)
+        else:
+            self._check(self.lib.mi_raycast_batch(self.w, C.c_uint32(0), None, C.c_uint32(flags), None))
+        return hits["t"].copy(), hits["collider"].copy(), hits["body"].copy(), hits["hit"].copy(), hits["point"].copy()
+
     def accumulators(self):
         """Force and torque accumulators of every body [n, 6]: the pushes the next step will apply and clear."""
         out = np.zeros((self.num_bodies, 6), np.float32)
@@ -409,6 +458,10 @@ class World:
 
     def apply_force_torque(self, body, force, torque=(0, 0, 0)):
         self._check(self.lib.mi_apply_force_torque(self.w, body, _f(force), _f(torque)))
+
+    def set_transform(self, body, pos, rot=(0, 0, 0, 1)):
+        """mi_set_transform: one body's pose (physics_transform0 / 1 and the interpolated one alike)."""
+        self._check(self.lib.mi_set_transform(self.w, C.c_uint32(body), _f(pos), _f(rot)))
 
     def set_velocity(self, body, lin, ang=(0, 0, 0)):
         self._check(self.lib.mi_set_velocity(self.w, body, _f(lin), _f(ang)))

@@ -346,6 +346,34 @@ int mi_test_physics_interaction_batch(mi_world* world, uint32_t numRays, uint32_
 	return W->lastError;
 }
 
+int mi_raycast_batch(mi_world* world, uint32_t numRays, const float* dRays, uint32_t flags, mi_ray_hit* dOutHits)
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	W->resolvePendingFlow();
+	W->upload();
+	if (!numRays) return W->lastError;
+	if (!dRays || !dOutHits) return MI_ERR_INVALID_ARGUMENT;
+	if (!W->interactTablesValid) W->buildInteractTables();
+	if (W->lastError) return W->lastError;
+	launch_raycast(*W, numRays, dRays, flags, dOutHits);
+	return W->lastError;
+}
+
+int mi_raycast_host(mi_world* world, uint32_t numRays, const float* rays, uint32_t flags, mi_ray_hit* outHits)
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	if (!numRays) return mi_raycast_batch(world, 0, nullptr, flags, nullptr);
+	if (!rays || !outHits) return MI_ERR_INVALID_ARGUMENT;
+	W->rcHostRays.ensure(2 * (size_t)numRays, W->stream); W->rcHostHits.ensure(2 * (size_t)numRays, W->stream);
+	if (W->lastError) return W->lastError;
+	MI_CHECK(hipMemcpyAsync(W->rcHostRays.p, rays, 32 * (size_t)numRays, hipMemcpyHostToDevice, W->stream));
+	int e = mi_raycast_batch(world, numRays, (const float*)W->rcHostRays.p, flags, (mi_ray_hit*)W->rcHostHits.p);
+	if (e) return e;
+	MI_CHECK(hipMemcpyAsync(outHits, W->rcHostHits.p, 32 * (size_t)numRays, hipMemcpyDeviceToHost, W->stream));
+	MI_CHECK(hipStreamSynchronize(W->stream));
+	return W->lastError;
+}
+
 // ---- multi-GPU slabs: state hand-over in device memory (directx-renderer-kurth_amd/parallel.py drives the halo exchange) ----
 int mi_state_to_device_buffers(mi_world* world, void* dPose, void* dVel)
 {

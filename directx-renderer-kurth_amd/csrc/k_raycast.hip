@@ -1,0 +1,350 @@
+// mi_raycast_batch: many rays, each against every candidate collider of the world, closest hit with its point (DESIGN.md,
+// "Whole-world ray casts").  A structure of its own, rebuilt at every call from the current poses and kept in buffers nothing else
+// uses (World::rc*): the step's AABBs, world colliders, sorted boxes, cell tables and counters belong to a step that may still be in
+// flight and are neither read nor written here.
+//   k_rc_leaves   candidate flag + padded world AABB per collider; count, bounds of the box centres, largest box diagonal
+//   k_rc_keys     30-bit Morton key of every candidate's box centre (non-candidates: bit 30, so they sort behind the candidates)
+//   (radix sort)  prim_sort_pairs_u32, 31 bits
+//   k_rc_tree     internal nodes after Karras (2012), equal keys separated by their sorted position
+//   k_rc_fit      node boxes bottom-up: the second child to arrive at a node merges and goes on
+//   k_raycast     one lane per ray: near child first, fixed stack in LDS; with MI_RAY_BRUTE_FORCE the same body walks all colliders
+// A hit is decided by rayBodyCollider (ray_tests.h) on the collider's LOCAL record and pose alone, as in k_interaction_batch; the
+// boxes only say which colliders need not be asked.
+#include "world.h"
+#include "ray_tests.h"
+
+void prim_sort_pairs_u32(World& w, const u32* kin, u32* kout, const u32* vin, u32* vout, u32 n, u32 bits);
+
+struct RcHulls
+{
+	const float4* verts; const uint4* tris; const uint2* range;
+	MI_DEV u32 numTriangles(u32 g) const { return range[g].y; }
+	MI_DEV V3 vertex(u32 g, u32 f, u32 k) const { uint4 t = tris[range[g].x + f]; return v3f4(verts[k == 0 ? t.x : (k == 1 ? t.y : t.z)]); }
+};
+
+// ---- header words of World::rcCount (zeroed before every build; every accumulated word has 0 as its neutral element) ----
+enum
+{
+	RC_N = 0,        // candidates
+	RC_NEG_MIN = 1,  // 3 words: max of rcOrdered(-centre): the lower bound of the box centres
+	RC_MAX = 4,      // 3 words: max of rcOrdered(centre)
+	RC_DIAG = 7,     // float bits: largest diagonal of a padded leaf box
+	RC_ABS = 8,      // float bits: largest |coordinate| of a padded leaf box
+	RC_HEADER = 16,  // the arrival counters of the internal nodes follow
+};
+#define RC_LEAF 0x80000000u
+#define RC_NO_PARENT 0xFFFFFFFFu
+#define RC_NOT_A_CANDIDATE (1u << 30)
+#define RC_KEY_BITS 30
+// Depth of the tree = length of the longest chain of internal nodes.  Going down, the length of the common prefix of a node's range
+// grows strictly; the prefix is counted over the 30 key bits and then, for equal keys, over the 32 bits of the sorted position.  The
+// root's range has a prefix of >= 0 key bits and a node with two different leaves one of <= 61, so a chain has <= 62 nodes, and
+// the stack, which holds one pending sibling per node of the chain, <= 62 entries.
+#define RC_STACK 64
+static_assert(RC_KEY_BITS + 32 <= RC_STACK, "k_raycast's stack holds one entry per level of the tree: key bits + position bits");
+
+// Leaf pad, per axis: RC_PAD_ULPS ulps of (largest |coordinate| of the box + its diagonal) + RC_PAD_FLOOR.  Slack of the slab test:
+// RC_SLACK_ULPS ulps of (|origin| + largest |coordinate| of the scene) in space, RC_SLACK_REL of the distance in t.  DESIGN.md derives them.
+#define RC_EPS 1.1920929e-7f
+#define RC_PAD_ULPS 8.f
+#define RC_PAD_FLOOR 1e-5f
+#define RC_SLACK_ULPS 16.f
+#define RC_SLACK_REL (1.f / 256.f)
+
+MI_DEV u32 rcOrdered(float f) { u32 u = mi_f2u(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); } // order-preserving, never 0 for a finite f
+MI_DEV float rcUnordered(u32 u) { return mi_u2f((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u); }
+MI_DEV void rcGrow(V3& mn, V3& mx, V3 p) { mn = vmin(mn, p); mx = vmax(mx, p); }
+MI_DEV void rcCorners(V3 lo, V3 hi, Q4 rot, V3 tr, V3& mn, V3& mx)
+{
+	mn = v3s(MI_FLT_MAX); mx = v3s(-MI_FLT_MAX);
+	for (u32 k = 0; k < 8; ++k) rcGrow(mn, mx, rot * v3((k & 1) ? hi.x : lo.x, (k & 2) ? hi.y : lo.y, (k & 4) ? hi.z : lo.z) + tr);
+}
+// World AABB of a local collider at (rot, pos), unpadded.  A cylinder gets its capsule's box.
+MI_DEV void rcWorldBox(const ColliderRec& c, Q4 rot, V3 pos, const float4* __restrict__ hullInfo, V3& mn, V3& mx)
+{
+	switch (colType(c))
+	{
+		case MI_SPHERE: { V3 ce = rot * v3(c.a.x, c.a.y, c.a.z) + pos; mn = ce - v3s(c.a.w); mx = ce + v3s(c.a.w); } break;
+		case MI_CAPSULE: case MI_CYLINDER:
+		{
+			V3 a = rot * v3(c.a.x, c.a.y, c.a.z) + pos, b = rot * v3(c.a.w, c.b.x, c.b.y) + pos;
+			mn = vmin(a, b) - v3s(c.b.z); mx = vmax(a, b) + v3s(c.b.z);
+		} break;
+		case MI_AABB: rcCorners(v3(c.a.x, c.a.y, c.a.z), v3(c.a.w, c.b.x, c.b.y), rot, pos, mn, mx); break;
+		case MI_OBB: { V3 ra = v3(c.b.w, c.c.x, c.c.y); rcCorners(-ra, ra, rot * q4f4(c.a), rot * v3(c.b.x, c.b.y, c.b.z) + pos, mn, mx); } break;
+		case MI_HULL:
+		{
+			const u32 g = (u32)c.b.w;
+			rcCorners(v3f4(hullInfo[2 * g]), v3f4(hullInfo[2 * g + 1]), rot * q4f4(c.a), rot * v3(c.b.x, c.b.y, c.b.z) + pos, mn, mx);
+		} break;
+		default: mn = pos; mx = pos; break;
+	}
+}
+
+// Collider c: is it a candidate, and if so its padded box; acc = what the header accumulates (negMin xyz, max xyz, diagonal, |coordinate|).
+MI_DEV bool rcLeaf(u32 c, u32 nb, u32 withStatic, const ColliderRec* __restrict__ cols, const float4* __restrict__ pose, const float4* __restrict__ colStaticPose,
+	const uint8_t* __restrict__ alive, const uint8_t* __restrict__ simMask, const float4* __restrict__ hullInfo, float4* __restrict__ leafBox, u32* acc)
+{
+	const ColliderRec rec = cols[c];
+	const u32 body = colBody(rec), zone = mi_f2u(rec.d.w) & 0xFFu;
+	const bool candidate = zone == 0u && (body < nb ? (alive[body] && simMask[body]) : withStatic != 0u);
+	V3 mn = v3s(0.f), mx = v3s(0.f);
+	if (candidate)
+	{
+		const float4* P = (body < nb) ? (pose + 2 * body) : (colStaticPose + 2 * c);
+		rcWorldBox(rec, q4f4(P[1]), v3f4(P[0]), hullInfo, mn, mx);
+		const float diag = length(mx - mn);
+		const V3 pad = (vmax(vabs(mn), vabs(mx)) + v3s(diag)) * (RC_PAD_ULPS * RC_EPS) + v3s(RC_PAD_FLOOR);
+		mn = mn - pad; mx = mx + pad;
+		const V3 ce = (mn + mx) * 0.5f, am = vmax(vabs(mn), vabs(mx));
+		const u32 v[8] = { rcOrdered(-ce.x), rcOrdered(-ce.y), rcOrdered(-ce.z), rcOrdered(ce.x), rcOrdered(ce.y), rcOrdered(ce.z),
+			mi_f2u(length(mx - mn)), mi_f2u(fmaxf(fmaxf(am.x, am.y), am.z)) }; // (non-negative floats order like their bits)
+		for (int k = 0; k < 8; ++k) acc[k] = acc[k] > v[k] ? acc[k] : v[k];
+	}
+	leafBox[2 * c] = make_float4(mn.x, mn.y, mn.z, candidate ? 1.f : 0.f);
+	leafBox[2 * c + 1] = make_float4(mx.x, mx.y, mx.z, 0.f);
+	return candidate;
+}
+__global__ void __launch_bounds__(256) k_rc_leaves(u32 nc, u32 nb, u32 withStatic, const ColliderRec* __restrict__ cols, const float4* __restrict__ pose, const float4* __restrict__ colStaticPose,
+	const uint8_t* __restrict__ alive, const uint8_t* __restrict__ simMask, const float4* __restrict__ hullInfo, float4* __restrict__ leafBox, u32* __restrict__ hdr)
+{
+	u32 count = 0, acc[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+	for (u32 c = blockIdx.x * blockDim.x + threadIdx.x; c < nc; c += gridDim.x * blockDim.x)
+		count += rcLeaf(c, nb, withStatic, cols, pose, colStaticPose, alive, simMask, hullInfo, leafBox, acc) ? 1u : 0u;
+	// one atomic per word and workgroup (same-address atomics serialise)
+	__shared__ u32 sAcc[4][9];
+	for (int o = 32; o > 0; o >>= 1) { count += __shfl_xor(count, o); for (int k = 0; k < 8; ++k) acc[k] = max(acc[k], (u32)__shfl_xor(acc[k], o)); }
+	if ((threadIdx.x & 63) == 0) { for (int k = 0; k < 8; ++k) sAcc[threadIdx.x >> 6][k] = acc[k]; sAcc[threadIdx.x >> 6][8] = count; }
+	__syncthreads();
+	if (threadIdx.x < 8) { const u32 m = max(max(sAcc[0][threadIdx.x], sAcc[1][threadIdx.x]), max(sAcc[2][threadIdx.x], sAcc[3][threadIdx.x])); if (m) atomicMax(&hdr[RC_NEG_MIN + threadIdx.x], m); }
+	if (threadIdx.x == 8) { const u32 s = sAcc[0][8] + sAcc[1][8] + sAcc[2][8] + sAcc[3][8]; if (s) atomicAdd(&hdr[RC_N], s); }
+}
+
+MI_DEV u32 rcSpread(u32 v) { v = (v * 0x00010001u) & 0xFF0000FFu; v = (v * 0x00000101u) & 0x0F00F00Fu; v = (v * 0x00000011u) & 0xC30C30C3u; v = (v * 0x00000005u) & 0x49249249u; return v; }
+// (an extent of 0 on an axis — centres coplanar, collinear or all the same — gives cell 0 on it: nothing is divided)
+MI_DEV u32 rcCell(float v, float lo, float hi) { const float e = hi - lo; return e > 0.f ? min(1023u, (u32)fmaxf((v - lo) * (1024.f / e), 0.f)) : 0u; }
+
+MI_DEV u32 rcKey(u32 c, const float4* __restrict__ leafBox, const u32* __restrict__ hdr)
+{
+	const float4 mn = leafBox[2 * c], mx = leafBox[2 * c + 1];
+	if (mn.w == 0.f) return RC_NOT_A_CANDIDATE;
+	const V3 lo = v3(-rcUnordered(hdr[RC_NEG_MIN]), -rcUnordered(hdr[RC_NEG_MIN + 1]), -rcUnordered(hdr[RC_NEG_MIN + 2]));
+	const V3 hi = v3(rcUnordered(hdr[RC_MAX]), rcUnordered(hdr[RC_MAX + 1]), rcUnordered(hdr[RC_MAX + 2]));
+	return (rcSpread(rcCell((mn.x + mx.x) * 0.5f, lo.x, hi.x)) << 2) | (rcSpread(rcCell((mn.y + mx.y) * 0.5f, lo.y, hi.y)) << 1) | rcSpread(rcCell((mn.z + mx.z) * 0.5f, lo.z, hi.z));
+}
+__global__ void __launch_bounds__(256) k_rc_keys(u32 nc, const float4* __restrict__ leafBox, const u32* __restrict__ hdr, u32* __restrict__ keys, u32* __restrict__ vals)
+{
+	const u32 c = blockIdx.x * blockDim.x + threadIdx.x;
+	if (c >= nc) return;
+	keys[c] = rcKey(c, leafBox, hdr); vals[c] = c;
+}
+
+// One internal node: 64 bytes = the boxes of its two children {min xyz, max xyz} x 2 (written by k_rc_fit), their ids (a leaf: RC_LEAF |
+// collider index) and two unused words.  Node 0 is the root.
+#define RC_NODE_WORDS 16u
+// Common prefix of the sorted keys i and j (Karras 2012, section 4): -1 outside the list; equal keys go on with their positions.
+MI_DEV int rcDelta(const u32* __restrict__ keys, int n, int i, int j)
+{
+	if (j < 0 || j >= n) return -1;
+	const u32 a = keys[i], b = keys[j];
+	return a != b ? __builtin_clz(a ^ b) : 32 + __builtin_clz((u32)i ^ (u32)j);
+}
+MI_DEV void rcTreeNode(int i, int n, const u32* __restrict__ keys, const u32* __restrict__ vals, u32* __restrict__ nodes, u32* __restrict__ parentInt, u32* __restrict__ parentLeaf)
+{
+	const int d = rcDelta(keys, n, i, i + 1) > rcDelta(keys, n, i, i - 1) ? 1 : -1;
+	const int dMin = rcDelta(keys, n, i, i - d);
+	int lMax = 2;
+	while (rcDelta(keys, n, i, i + lMax * d) > dMin) lMax <<= 1;
+	int l = 0;
+	for (int t = lMax >> 1; t > 0; t >>= 1) if (rcDelta(keys, n, i, i + (l + t) * d) > dMin) l += t;
+	const int j = i + l * d, dNode = rcDelta(keys, n, i, j);
+	int s = 0;
+	for (int t = (l + 1) >> 1; ; t = (t + 1) >> 1) { if (rcDelta(keys, n, i, i + (s + t) * d) > dNode) s += t; if (t <= 1) break; }
+	const int split = i + s * d + min(d, 0), first = min(i, j), last = max(i, j);
+	const bool leafL = first == split, leafR = last == split + 1;
+	nodes[RC_NODE_WORDS * (u32)i + 12] = leafL ? (RC_LEAF | vals[split]) : (u32)split;
+	nodes[RC_NODE_WORDS * (u32)i + 13] = leafR ? (RC_LEAF | vals[split + 1]) : (u32)(split + 1);
+	(leafL ? parentLeaf : parentInt)[split] = (u32)i << 1;
+	(leafR ? parentLeaf : parentInt)[split + 1] = ((u32)i << 1) | 1u;
+	if (i == 0) parentInt[0] = RC_NO_PARENT;
+}
+__global__ void __launch_bounds__(256) k_rc_tree(const u32* __restrict__ hdr, const u32* __restrict__ keys, const u32* __restrict__ vals, u32* __restrict__ nodes, u32* __restrict__ parentInt, u32* __restrict__ parentLeaf)
+{
+	const int n = (int)hdr[RC_N], i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+	if (i < n - 1) rcTreeNode(i, n, keys, vals, nodes, parentInt, parentLeaf); // (n < 2: no internal node)
+}
+
+// One lane per leaf climbs towards the root.  At every node it writes the box it carries into its slot of the node's record; the first
+// child to arrive stops there, the second reads its sibling's box, merges and climbs on.  The box is published by a fence before the
+// arrival counter's atomic and picked up behind a fence after it.  The root's own box is the scene's: nobody needs it.
+MI_DEV void rcFitLeaf(u32 j, const u32* __restrict__ vals, const float4* __restrict__ leafBox, const u32* __restrict__ parentInt, const u32* __restrict__ parentLeaf, float* nodes, u32* arrivals)
+{
+	const u32 c = vals[j];
+	V3 mn = v3f4(leafBox[2 * c]), mx = v3f4(leafBox[2 * c + 1]);
+	u32 up = parentLeaf[j];
+	for (u32 level = 0; level < RC_STACK && up != RC_NO_PARENT; ++level)
+	{
+		const u32 p = up >> 1, side = up & 1u;
+		float* mine = nodes + RC_NODE_WORDS * p + 6u * side;
+		mine[0] = mn.x; mine[1] = mn.y; mine[2] = mn.z; mine[3] = mx.x; mine[4] = mx.y; mine[5] = mx.z;
+#if defined(__HIP_DEVICE_COMPILE__)
+		__threadfence();
+		if (atomicAdd(&arrivals[p], 1u) == 0u) return;
+		__threadfence();
+#else
+		if (arrivals[p]++ == 0u) return; // (host build of this function: one leaf after the other)
+#endif
+		const float* other = nodes + RC_NODE_WORDS * p + 6u * (side ^ 1u);
+		mn = vmin(mn, v3(other[0], other[1], other[2])); mx = vmax(mx, v3(other[3], other[4], other[5]));
+		up = parentInt[p];
+	}
+}
+__global__ void __launch_bounds__(256) k_rc_fit(const u32* __restrict__ hdr, const u32* __restrict__ vals, const float4* __restrict__ leafBox, const u32* __restrict__ parentInt, const u32* __restrict__ parentLeaf,
+	float* nodes, u32* arrivals)
+{
+	const u32 n = hdr[RC_N], j = blockIdx.x * blockDim.x + threadIdx.x;
+	if (n >= 2u && j < n) rcFitLeaf(j, vals, leafBox, parentInt, parentLeaf, nodes, arrivals);
+}
+
+struct RcRay
+{
+	HRay r; float maxT;
+	V3 inv; bool par[3];        // 1 / direction; axes the ray does not move along are tested by containment
+	float space, absT, relT;    // slack of the slab test: in space, in t, and the share of the largest leaf in the relative part
+};
+// May the ray hit something in this padded box at a distance in [0, tmax]?  Conservative: the interval is widened by the slack, a box
+// entered exactly at tmax is visited (a lower collider index may win the tie), and a comparison with a NaN visits.  tEnter orders the visit.
+MI_DEV bool rcBoxTest(const RcRay& q, const float* b, float tmax, float& tEnter)
+{
+	float tE = -MI_FLT_MAX, tX = MI_FLT_MAX; bool outside = false;
+	const float o[3] = { q.r.origin.x, q.r.origin.y, q.r.origin.z }, inv[3] = { q.inv.x, q.inv.y, q.inv.z };
+	#pragma unroll
+	for (u32 a = 0; a < 3; ++a)
+	{
+		if (q.par[a]) outside = outside || o[a] < b[a] - q.space || o[a] > b[3 + a] + q.space;
+		else { const float t1 = (b[a] - o[a]) * inv[a], t2 = (b[3 + a] - o[a]) * inv[a]; tE = fmaxf(tE, fminf(t1, t2)); tX = fminf(tX, fmaxf(t1, t2)); }
+	}
+	const float lo = tE - q.absT - RC_SLACK_REL * (fmaxf(tE, 0.f) + q.relT), hi = tX + q.absT + RC_SLACK_REL * (fabsf(tX) + q.relT);
+	tEnter = tE;
+	return !(outside || lo > tmax || hi < 0.f || lo > hi);
+}
+
+struct RcBest { float t; u32 col, body; V3 point; }; // t starts at MI_FLT_MAX like the reference's minDistance: a test that reports FLT_MAX or +inf (a box whose slab interval is poisoned, rule R2a) has not hit
+MI_DEV void rcTestCollider(u32 c, const RcRay& q, u32 nb, const float4* __restrict__ pose, const float4* __restrict__ colStaticPose, const ColliderRec* __restrict__ cols, const RcHulls& hulls, RcBest& best)
+{
+	const ColliderRec rec = cols[c];
+	const u32 body = colBody(rec);
+	const float4* P = (body < nb) ? (pose + 2 * body) : (colStaticPose + 2 * c);
+	const Q4 rot = q4f4(P[1]); const V3 pos = v3f4(P[0]);
+	const float s[10] = { rec.a.x, rec.a.y, rec.a.z, rec.a.w, rec.b.x, rec.b.y, rec.b.z, rec.b.w, rec.c.x, rec.c.y };
+	HRay lr; float t;
+	if (rayBodyCollider(q.r, rot, pos, colType(rec), s, hulls, lr, t) && t >= 0.f && t <= q.maxT && (t < best.t || (best.col != 0xFFFFFFFFu && t == best.t && c < best.col)))
+	{
+		best.t = t; best.col = c; best.body = body < nb ? body : MI_STATIC_BODY;
+		best.point = rot * (lr.origin + t * lr.direction) + pos; // interactionPush's globalHit
+	}
+}
+
+// The slack of the slab test for this ray (RcRay::inv ... relT); scene = largest |coordinate|, diag = largest diagonal of the leaf boxes.
+MI_DEV void rcPrepareRay(RcRay& q, float scene, float diag)
+{
+	const V3 ad = vabs(q.r.direction), ao = vabs(q.r.origin);
+	const float dMax = fmaxf(fmaxf(ad.x, ad.y), ad.z);
+	q.par[0] = !(ad.x > 1e-12f * dMax); q.par[1] = !(ad.y > 1e-12f * dMax); q.par[2] = !(ad.z > 1e-12f * dMax);
+	q.inv = v3(q.par[0] ? 0.f : 1.f / q.r.direction.x, q.par[1] ? 0.f : 1.f / q.r.direction.y, q.par[2] ? 0.f : 1.f / q.r.direction.z);
+	q.space = RC_SLACK_ULPS * RC_EPS * (fmaxf(fmaxf(ao.x, ao.y), ao.z) + scene);
+	q.absT = q.space * fmaxf(fmaxf(fabsf(q.inv.x), fabsf(q.inv.y)), fabsf(q.inv.z));
+	q.relT = diag / length(q.r.direction);
+}
+// Closest hit among the n >= 1 candidates of the tree.  stack[k * stride]: the caller's RC_STACK entries.
+MI_DEV void rcTraverse(const RcRay& q, u32 n, const float4* __restrict__ nodes, const u32* __restrict__ vals, u32* stack, u32 stride, u32 nb, const float4* __restrict__ pose,
+	const float4* __restrict__ colStaticPose, const ColliderRec* __restrict__ cols, const RcHulls& hulls, RcBest& best)
+{
+	u32 node = n == 1u ? (RC_LEAF | vals[0]) : 0u, sp = 0u;
+	for (;;)
+	{
+		if (node & RC_LEAF) rcTestCollider(node & ~RC_LEAF, q, nb, pose, colStaticPose, cols, hulls, best);
+		else
+		{
+			const float4 w0 = nodes[4 * node], w1 = nodes[4 * node + 1], w2 = nodes[4 * node + 2], w3 = nodes[4 * node + 3];
+			const float bl[6] = { w0.x, w0.y, w0.z, w0.w, w1.x, w1.y }, br[6] = { w1.z, w1.w, w2.x, w2.y, w2.z, w2.w };
+			const u32 idL = mi_f2u(w3.x), idR = mi_f2u(w3.y);
+			const float tmax = fminf(q.maxT, best.t);
+			float tL, tR;
+			const bool hitL = rcBoxTest(q, bl, tmax, tL), hitR = rcBoxTest(q, br, tmax, tR);
+			if (hitL && hitR)
+			{
+				const bool leftFirst = tL <= tR;
+				if (sp < RC_STACK) stack[stride * sp++] = leftFirst ? idR : idL; // (sp < RC_STACK always: see RC_STACK)
+				node = leftFirst ? idL : idR;
+				continue;
+			}
+			if (hitL || hitR) { node = hitL ? idL : idR; continue; }
+		}
+		if (sp == 0u) break;
+		node = stack[stride * --sp];
+	}
+}
+
+template <bool BRUTE>
+__global__ void __launch_bounds__(64) k_raycast(u32 numRays, const float4* __restrict__ rays, float4* __restrict__ out, u32 nb, u32 nc, const float4* __restrict__ pose, const float4* __restrict__ colStaticPose,
+	const ColliderRec* __restrict__ cols, RcHulls hulls, const u32* __restrict__ hdr, const float4* __restrict__ nodes, const u32* __restrict__ vals, const float4* __restrict__ leafBox)
+{
+	__shared__ u32 stack[BRUTE ? 1 : RC_STACK][64]; // [level][lane]: a wave's access is one row, conflict-free
+	const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= numRays) return;
+	const float4 r0 = rays[2 * i], r1 = rays[2 * i + 1];
+	RcBest best; best.t = MI_FLT_MAX; best.col = 0xFFFFFFFFu; best.body = 0u; best.point = v3s(0.f);
+	RcRay q; q.r = HRay{ v3(r0.x, r0.y, r0.z), v3(r1.x, r1.y, r1.z) }; q.maxT = r0.w;
+	const u32 n = hdr[RC_N];
+	if (r1.w != 0.f && n != 0u)
+	{
+		if (BRUTE)
+		{
+			for (u32 c = 0; c < nc; ++c) if (leafBox[2 * c].w != 0.f) rcTestCollider(c, q, nb, pose, colStaticPose, cols, hulls, best);
+		}
+		else
+		{
+			rcPrepareRay(q, mi_u2f(hdr[RC_ABS]), mi_u2f(hdr[RC_DIAG]));
+			rcTraverse(q, n, nodes, vals, &stack[0][threadIdx.x], 64u, nb, pose, colStaticPose, cols, hulls, best);
+		}
+	}
+	const bool hit = best.col != 0xFFFFFFFFu;
+	out[2 * i] = hit ? make_float4(best.t, mi_u2f(best.col), mi_u2f(best.body), mi_u2f(1u)) : make_float4(0.f, 0.f, 0.f, 0.f);
+	out[2 * i + 1] = hit ? make_float4(best.point.x, best.point.y, best.point.z, 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+void launch_raycast(World& w, u32 numRays, const float* dRays, u32 flags, mi_ray_hit* dOutHits)
+{
+	const bool withStatic = (flags & MI_RAY_STATIC) != 0, brute = (flags & MI_RAY_BRUTE_FORCE) != 0;
+	// what the host knows of the candidates (a slab's simulate mask can only take some away): none = every ray misses, nothing is built
+	u32 hostCandidates = 0;
+	for (const World::HCollider& c : w.colliders) if (c.zoneType == 0u && (c.body == MI_STATIC_BODY ? withStatic : !w.bodies[c.body].removed)) hostCandidates++;
+	if (!hostCandidates || !w.nc) { MI_CHECK(hipMemsetAsync(dOutHits, 0, sizeof(mi_ray_hit) * (size_t)numRays, w.stream)); return; }
+	const u32 nc = w.nc;
+	w.rcLeafBox.ensure(2 * (size_t)nc, w.stream); w.rcCount.ensure(RC_HEADER + (size_t)nc, w.stream);
+	w.rcKeys.ensure(nc, w.stream); w.rcKeysSorted.ensure(nc, w.stream); w.rcVals.ensure(nc, w.stream); w.rcValsSorted.ensure(nc, w.stream);
+	w.rcNodes.ensure(4 * (size_t)nc, w.stream); w.rcParentInt.ensure(nc, w.stream); w.rcParentLeaf.ensure(nc, w.stream);
+	if (w.lastError) return;
+	const RcHulls hulls{ w.hullVerts.p, w.hullTris.p, w.hullTriRange.p };
+	const u32 blocks = (nc + 255u) / 256u;
+	MI_CHECK(hipMemsetAsync(w.rcCount.p, 0, sizeof(u32) * (brute ? (size_t)RC_HEADER : RC_HEADER + (size_t)nc), w.stream));
+	hipLaunchKernelGGL(k_rc_leaves, dim3(std::min(blocks, 256u)), dim3(256), 0, w.stream, nc, w.nb, withStatic ? 1u : 0u, w.colLocal.p, w.pose.p, w.colStaticPose.p,
+		w.aliveMask.p, w.simMask.p, w.hullInfo.p, w.rcLeafBox.p, w.rcCount.p);
+	if (brute)
+	{
+		hipLaunchKernelGGL(k_raycast<true>, dim3((numRays + 63) / 64), dim3(64), 0, w.stream, numRays, (const float4*)dRays, (float4*)dOutHits, w.nb, nc, w.pose.p, w.colStaticPose.p,
+			w.colLocal.p, hulls, w.rcCount.p, (const float4*)w.rcNodes.p, w.rcValsSorted.p, w.rcLeafBox.p);
+		return;
+	}
+	hipLaunchKernelGGL(k_rc_keys, dim3(blocks), dim3(256), 0, w.stream, nc, w.rcLeafBox.p, w.rcCount.p, w.rcKeys.p, w.rcVals.p);
+	prim_sort_pairs_u32(w, w.rcKeys.p, w.rcKeysSorted.p, w.rcVals.p, w.rcValsSorted.p, nc, RC_KEY_BITS + 1);
+	if (hostCandidates > 1u)
+	{
+		const u32 treeBlocks = (hostCandidates + 255u) / 256u; // (the device's count is at most the host's)
+		hipLaunchKernelGGL(k_rc_tree, dim3(treeBlocks), dim3(256), 0, w.stream, w.rcCount.p, w.rcKeysSorted.p, w.rcValsSorted.p, (u32*)w.rcNodes.p, w.rcParentInt.p, w.rcParentLeaf.p);
+		hipLaunchKernelGGL(k_rc_fit, dim3(treeBlocks), dim3(256), 0, w.stream, w.rcCount.p, w.rcValsSorted.p, w.rcLeafBox.p, w.rcParentInt.p, w.rcParentLeaf.p, (float*)w.rcNodes.p, w.rcCount.p + RC_HEADER);
+	}
+	hipLaunchKernelGGL(k_raycast<false>, dim3((numRays + 63) / 64), dim3(64), 0, w.stream, numRays, (const float4*)dRays, (float4*)dOutHits, w.nb, nc, w.pose.p, w.colStaticPose.p,
+		w.colLocal.p, hulls, w.rcCount.p, (const float4*)w.rcNodes.p, w.rcValsSorted.p, w.rcLeafBox.p);
+}

@@ -284,6 +284,11 @@ struct World
 	// mi_test_physics_interaction_batch: colliders of every body (CSR), hull triangles as global vertex indices; rebuilt after upload()
 	DevBuf<u32> bodyColStart, bodyColList; DevBuf<uint4> hullTris; DevBuf<uint2> hullTriRange; bool interactTablesValid = false;
 	void buildInteractTables();
+	// mi_raycast_batch (k_raycast.hip): rebuilt at every call, read and written by nothing else.  Per collider: candidate flag + padded
+	// world AABB; header words + arrival counter per internal node; Morton keys and collider indices, before and after the sort; the
+	// internal nodes (64 bytes each: both children's boxes and ids); the parent of every internal node and of every sorted leaf
+	DevBuf<float4> rcHostRays, rcHostHits; // staging of mi_raycast_host
+	DevBuf<float4> rcLeafBox, rcNodes; DevBuf<u32> rcCount, rcKeys, rcKeysSorted, rcVals, rcValsSorted, rcParentInt, rcParentLeaf;
 
 	World(int dev);
 	~World();
@@ -335,6 +340,7 @@ void launch_slab_unpack(World& w, const void* left, const void* right, u32 capac
 void launch_validate(World& w, u32 stage, u32 numPairs); // stage 0: world colliders + AABBs, 1: contacts, 2: body update records, 3: poses + velocities after the step
 void launch_copy_pose0(World& w);
 void launch_interaction_batch(World& w, u32 numRays, u32 firstBody, u32 bodiesPerRay, const float* dRays, int32_t* dOutBody); // k_interact.hip
+void launch_raycast(World& w, u32 numRays, const float* dRays, u32 flags, mi_ray_hit* dOutHits); // k_raycast.hip
 void launch_lerp_pose(World& w, float t);
 void csort_pairs_u32(World& w, const u32* keys, u32* keysOut, const u32* vals, u32* valsOut, u32 n, u32 numBuckets); // stable, keys < numBuckets <= 272
 void csort_pairs_u64(World& w, const u32* keys, u32* keysOut, const u64* vals, u64* valsOut, u32 n, u32 numBuckets);

@@ -77,6 +77,12 @@ int main()
 		settings.collisionEndCallback = [&](const collision_end_event&) { ++ends; };
 		for (int frame = 0; frame < 120; ++frame) physicsStep(scene, arena, timer, settings, 1.f / 60.f);
 
+		{	// a pick straight down onto the platform's top face (y = 0), away from everything that moves: a static collider, 10 below the origin
+			ray_hit hit;
+			if (!castRay(scene, ray{ vec3(20.f, 10.f, 20.f), vec3(0.f, -1.f, 0.f) }, 100.f, hit)) std::abort();
+			if (hit.body != MI_STATIC_BODY || !(hit.distance > 9.999f && hit.distance < 10.001f) || castRay(scene, ray{ vec3(20.f, 10.f, 20.f), vec3(0.f, -1.f, 0.f) }, 5.f, hit)) std::abort();
+			std::printf("ray %.6f %.6f %.6f %.6f\n", hit.distance, hit.point.x, hit.point.y, hit.point.z);
+		}
 		for (auto& e : boxes) { auto t = e.transform(); std::printf("box %.6f %.6f %.6f %.6f %.6f %.6f %.6f\n", t.position.x, t.position.y, t.position.z, t.rotation.x, t.rotation.y, t.rotation.z, t.rotation.w); }
 		std::printf("events %d %d %d %d\n", enters, leaves, begins, ends);
 		{ auto p = banner.clothPositions(); vec3 c = p.back(); std::printf("cloth %.6f %.6f %.6f\n", c.x, c.y, c.z); }

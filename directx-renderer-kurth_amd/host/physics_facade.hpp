@@ -419,6 +419,20 @@ namespace mi
 	// void testPhysicsInteraction(game_scene&, ray, float strength = 1000.f), physics.h:404
 	inline void testPhysicsInteraction(game_scene& scene, ray r, float strength = 1000.f) { scene.flushStaticColliders(); mi_test_physics_interaction(scene.world, &r.origin.x, &r.direction.x, strength); }
 
+	// A ray cast against the whole scene (rigid bodies and static colliders; no counterpart in the reference's physics.h): the closest
+	// hit within maxDistance, in units of the direction's length, or false.  Nothing is pushed.  One ray through mi_raycast_batch.
+	struct ray_hit { float distance = 0.f; vec3 point; uint32_t collider = 0, body = MI_STATIC_BODY; }; // body: MI_STATIC_BODY for an entity without a rigid body
+	inline bool castRay(game_scene& scene, ray r, float maxDistance, ray_hit& out)
+	{
+		scene.flushStaticColliders();
+		const float in[8] = { r.origin.x, r.origin.y, r.origin.z, maxDistance, r.direction.x, r.direction.y, r.direction.z, 1.f };
+		mi_ray_hit h{};
+		scene.check(mi_raycast_host(scene.world, 1u, in, MI_RAY_STATIC, &h), "castRay");
+		if (!h.hit) return false;
+		out.distance = h.t; out.point = vec3(h.point[0], h.point[1], h.point[2]); out.collider = h.collider; out.body = h.body;
+		return true;
+	}
+
 	// ---- void physicsStep(game_scene&, memory_arena&, float& timer, const physics_settings&, float dt), physics.h:405
 	inline void physicsStep(game_scene& scene, memory_arena& /*arena*/, float& timer, const physics_settings& settings, float dt)
 	{

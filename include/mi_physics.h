@@ -252,6 +252,31 @@ int mi_joint_device_pods(mi_world* w, uint32_t type, void** dPods, uint32_t* out
  * and torque of mi_test_physics_interaction, added to the accumulators.  dOutBody[i] (device) = 1 + the pushed body, or 0. */
 int mi_test_physics_interaction_batch(mi_world* w, uint32_t numRays, uint32_t firstBody, uint32_t bodiesPerRay, const float* dRays, int32_t* dOutBody);
 
+/* Ray casts against the whole world: numRays rays, each against every candidate collider, as one call on the world's stream with no
+ * host synchronisation.  Nothing is pushed and no accumulator is written.  dRays (device): 8 floats per ray {origin.xyz, maxT,
+ * direction.xyz, enabled}; maxT is the largest accepted distance (+INFINITY allowed), enabled == 0 switches the ray off.  The
+ * direction need not be a unit vector: t is in units of its length, as in the reference (whose sphere test, and with it a capsule's
+ * ends, is geometric for unit directions only).
+ * Candidates: the colliders of rigid bodies that are alive and, in a slab run, simulated here; with MI_RAY_STATIC also the colliders
+ * of entities without a rigid body.  Force-field and trigger colliders are never candidates; the heightmap and cloth are not either
+ * (the reference's ray test knows neither).
+ * Hit rule: a candidate's test is testPhysicsInteraction's test of that collider, in the collider's own frame.  It is a hit if
+ * 0 <= t <= maxT; the smallest t wins, and of equal t the lowest collider index.  This is where the cast deviates from
+ * testPhysicsInteraction: that function also accepts the negative distances its cylinder and capsule tests report for a cap disk
+ * behind the origin; a ray cast reports no hit behind the ray.
+ * dOutHits[i] (device): hit = 1, t, the collider, its body (MI_STATIC_BODY for a static collider) and the world hit point
+ * rot * (local origin + t * local direction) + pos, bit for bit the point mi_test_physics_interaction pushes at; all zero for a miss
+ * or a switched-off ray.  Hit normals are not reported.
+ * The acceleration structure (a BVH over the candidates) is rebuilt from the current poses at every call, in buffers of its own: poses
+ * written through mi_device_state are seen, and the step's buffers are not touched.  MI_RAY_BRUTE_FORCE tests every ray against every
+ * candidate instead (same answers; a yardstick, and cheaper for a handful of colliders). */
+enum { MI_RAY_STATIC = 1, MI_RAY_BRUTE_FORCE = 2 };
+typedef struct mi_ray_hit { float t; uint32_t collider, body, hit; float point[3]; float reserved; } mi_ray_hit; /* 32 bytes */
+int mi_raycast_batch(mi_world* w, uint32_t numRays, const float* dRays, uint32_t flags, mi_ray_hit* dOutHits);
+/* The same cast for callers without device memory of their own (a single pick: the C++ facade's castRay): rays and hits in HOST memory,
+ * copied through staging buffers of the world around one mi_raycast_batch; returns after the hits have arrived. */
+int mi_raycast_host(mi_world* w, uint32_t numRays, const float* rays, uint32_t flags, mi_ray_hit* outHits);
+
 /* Spatial-slab runs (one world per GPU holding ALL bodies, each simulating its slab + ghosts): copy the whole pose / velocity arrays
  * (layout as mi_device_pointers) to / from caller-owned DEVICE buffers, and set the per-body simulate mask (1 byte per body, device
  * memory; 0 = body lives on another GPU: no AABB, no integration).  The halo exchange itself (RCCL send/recv of boundary bodies) is

@@ -1,0 +1,102 @@
+"""Developer tool (not part of bench.py): what a whole-world ray cast costs on the C2 scene (10 k spheres) and the C3 generator at 100 k.
+
+    python tests/raycast_bench.py [c2] [c3] [--settle STEPS] [--repeats N] [--host-rays 64]
+
+Per scene and ray count (4 096 and 65 536 rays, origins above the pile, half pointing down, half sideways and down): time of one
+mi_raycast_batch call through the tree and with MI_RAY_BRUTE_FORCE (HIP events around the call on the world's stream, median of
+repeated calls after a warm-up), the part of the tree call that is the build (a call with one ray: leaves, keys, sort, tree, fit), and
+rays per second.  For comparison the only whole-world path before this entry point: mi_test_physics_interaction, one host call per
+ray (state read back, host loop over every collider), timed over --host-rays rays."""
+import argparse
+import ctypes
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import directx_renderer_kurth_amd as mi  # noqa: E402
+from directx_renderer_kurth_amd import scenes  # noqa: E402
+
+
+def make_rays(n, lo, hi, top, seed=99):
+    rng = np.random.default_rng(seed)
+    rays = np.zeros((n, 8), np.float32)
+    rays[:, 0] = rng.uniform(lo[0], hi[0], n)
+    rays[:, 1] = top + rng.uniform(1.0, 5.0, n)
+    rays[:, 2] = rng.uniform(lo[1], hi[1], n)
+    d = np.zeros((n, 3))
+    d[:, 1] = -1.0
+    side = np.arange(n) % 2 == 1
+    d[side, 0] = rng.normal(size=side.sum())
+    d[side, 2] = rng.normal(size=side.sum())
+    d[side, 1] = -rng.uniform(0.05, 0.5, side.sum())
+    rays[:, 4:7] = d / np.linalg.norm(d, axis=1, keepdims=True)
+    rays[:, 3] = np.inf
+    rays[:, 7] = 1.0
+    return rays
+
+
+def time_calls(w, stream, d_rays, d_out, n, flags, repeats, warmup=3):
+    ms = []
+    for k in range(warmup + repeats):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(stream)
+        code = w.lib.mi_raycast_batch(w.w, ctypes.c_uint32(n), ctypes.c_void_p(d_rays.data_ptr()), ctypes.c_uint32(flags), ctypes.c_void_p(d_out.data_ptr()))
+        b.record(stream)
+        b.synchronize()
+        assert code == 0, code
+        if k >= warmup:
+            ms.append(a.elapsed_time(b))
+    return float(np.median(ms)), float(np.min(ms)), float(np.max(ms))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("scenes", nargs="*", default=["c2", "c3"])
+    ap.add_argument("--settle", type=int, default=120)
+    ap.add_argument("--repeats", type=int, default=15)
+    ap.add_argument("--brute-repeats", type=int, default=3)
+    ap.add_argument("--host-rays", type=int, default=64)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("raycast_bench: no GPU; there is nothing to measure on a CPU")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    for name in args.scenes:
+        s = scenes.c2_spheres() if name == "c2" else scenes.c3_mixed(100000)
+        w = s.instantiate(mi.World())
+        for _ in range(args.settle):
+            w.step_internal(s.dt)
+        w.synchronize()
+        tr = w.transforms()
+        lo, hi, top = tr[:, [0, 2]].min(axis=0), tr[:, [0, 2]].max(axis=0), float(tr[:, 1].max())
+        stream = torch.cuda.ExternalStream(w.device_state().stream or 0, device=dev)
+        print("%s: %d bodies, %d colliders, pile x/z [%.1f, %.1f] x [%.1f, %.1f], top %.1f" % (name, w.num_bodies, w.num_colliders, lo[0], hi[0], lo[1], hi[1], top), flush=True)
+        for n in (4096, 65536):
+            rays = make_rays(n, lo, hi, top)
+            with torch.cuda.stream(stream):
+                d_rays = torch.from_numpy(rays).to(dev)
+                d_tree, d_brute = torch.zeros((n, 8), dtype=torch.float32, device=dev), torch.zeros((n, 8), dtype=torch.float32, device=dev)
+                stream.synchronize()
+                build = time_calls(w, stream, d_rays, d_tree, 1, mi.RAY_STATIC, args.repeats)
+                tree = time_calls(w, stream, d_rays, d_tree, n, mi.RAY_STATIC, args.repeats)
+                brute = time_calls(w, stream, d_rays, d_brute, n, mi.RAY_STATIC | mi.RAY_BRUTE_FORCE, args.brute_repeats, warmup=1)
+                stream.synchronize()
+                same = bool(torch.equal(d_tree.view(torch.int32), d_brute.view(torch.int32)))
+                hits = int(d_tree.view(torch.int32)[:, 3].sum().item())
+            print("  %6d rays: tree %.3f ms/call [%.3f, %.3f] (build alone %.3f ms, traversal %.3f ms) = %.3g rays/s; brute force %.3f ms/call [%.3f, %.3f] = %.3g rays/s; "
+                  "%d hits, records identical: %s" % (n, tree[0], tree[1], tree[2], build[0], tree[0] - build[0], n / (tree[0] * 1e-3), brute[0], brute[1], brute[2], n / (brute[0] * 1e-3), hits, same), flush=True)
+        # the host path, one call per ray; its pushes are taken back so that the world stays what it was
+        rays = make_rays(args.host_rays, lo, hi, top, seed=7)
+        t0 = time.perf_counter()
+        pushed = [w.test_physics_interaction(r[0:3], r[4:7], 1.0) for r in rays]
+        w.synchronize()
+        dt = time.perf_counter() - t0
+        print("  host mi_test_physics_interaction: %d rays in %.3f s = %.3g rays/s (%d pushed)" % (len(rays), dt, len(rays) / dt, sum(p is not None for p in pushed)), flush=True)
+        w.close()
+
+
+if __name__ == "__main__":
+    main()
