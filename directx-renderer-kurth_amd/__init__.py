@@ -93,7 +93,7 @@ EXPORTED_SYMBOLS = [
     "mi_test_physics_interaction", "mi_apply_force_torque", "mi_set_velocity",
     "mi_set_transform", "mi_write_transforms", "mi_write_velocities", "mi_step", "mi_step_internal", "mi_synchronize", "mi_read_transforms", "mi_read_velocities", "mi_read_mass_properties",
     "mi_get_stats", "mi_enable_validation", "mi_enable_stage_timing", "mi_num_bodies", "mi_num_colliders", "mi_device_pointers", "mi_state_to_device_buffers", "mi_state_from_device_buffers", "mi_slab_configure", "mi_slab_message_bytes", "mi_slab_pack", "mi_slab_unpack", "mi_slab_read_codes", "mi_debug_num_pairs", "mi_debug_read_pairs", "mi_debug_sorting_axis", "mi_debug_narrow_limits",
-    "mi_debug_read_world_colliders", "mi_debug_num_manifold_slots", "mi_debug_read_manifolds", "mi_debug_num_colors", "mi_debug_read_schedule",
+    "mi_debug_read_world_colliders", "mi_debug_num_manifold_slots", "mi_debug_read_manifolds", "mi_debug_num_colors", "mi_debug_read_schedule", "mi_debug_read_contact_impulses",
     "mi_debug_read_joint_order", "mi_debug_read_joint_update", "mi_debug_read_body_state", "mi_debug_read_accumulators", "mi_debug_flow_trace",
     "mi_debug_set_replay", "mi_debug_num_replay_batches", "mi_debug_read_replay_batches",
     "mi_device_state", "mi_joint_device_pods", "mi_test_physics_interaction_batch", "mi_raycast_batch", "mi_raycast_host",
@@ -593,6 +593,13 @@ class World:
         slots = np.zeros(max(n, 1), np.uint32)
         self._check(self.lib.mi_debug_read_schedule(self.w, _p(slots), _p(cs)))
         return slots[:int(cs[65])], cs
+
+    def contact_impulses(self):
+        """Accumulated (normal, tangent) impulses of the last step's contacts [positions, 4, 2], by position in schedule()'s order."""
+        n = len(self.schedule()[0])
+        out = np.zeros((max(n, 1), 4, 2), np.float32)
+        self._check(self.lib.mi_debug_read_contact_impulses(self.w, _p(out)))
+        return out[:n]
 
     def joint_order(self, ctype, n):
         out = np.zeros(max(n, 1), np.uint32)

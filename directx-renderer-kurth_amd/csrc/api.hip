@@ -533,6 +533,27 @@ int mi_debug_read_schedule(mi_world* world, uint32_t* outManifoldSlots, uint32_t
 	else for (u32 c = 0; c <= MI_MAX_COLORS + 1; ++c) outColorStart[c] = W->hCounters[CTR_KEY_START + 4 * c];
 	return W->lastError;
 }
+// The accumulated impulses of the last step's contacts, by schedule position (mi_debug_read_schedule) and contact: {normal, tangent}.
+// Every sweep leaves them in rowLambda (k * rowCap + position); this copies them out.  Contacts a manifold does not have read 0.
+int mi_debug_read_contact_impulses(mi_world* world, float* outImpulses4x2)
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	W->refreshCounters();
+	u32 n = (W->hCounters[CTR_NUM_PAIRS] || W->terrainChunksPerDim) ? W->hCounters[CTR_NUM_MANIFOLDS] : 0;
+	if (!n) return MI_OK;
+	if (!outImpulses4x2 || n > W->rowCap) return MI_ERR_INVALID_ARGUMENT;
+	std::vector<uint4> ids(n); std::vector<float2> lam((size_t)MI_MAX_CONTACTS_PER_MANIFOLD * n);
+	d2h(W, ids.data(), W->rowIds.p, sizeof(uint4) * n);
+	for (u32 k = 0; k < MI_MAX_CONTACTS_PER_MANIFOLD; ++k) d2h(W, lam.data() + (size_t)k * n, W->rowLambda.p + (size_t)k * W->rowCap, sizeof(float2) * n);
+	for (u32 s = 0; s < n; ++s)
+		for (u32 k = 0; k < MI_MAX_CONTACTS_PER_MANIFOLD; ++k)
+		{
+			const bool has = k < ids[s].z;
+			float* o = outImpulses4x2 + 2 * ((size_t)MI_MAX_CONTACTS_PER_MANIFOLD * s + k);
+			o[0] = has ? lam[(size_t)k * n + s].x : 0.f; o[1] = has ? lam[(size_t)k * n + s].y : 0.f;
+		}
+	return W->lastError;
+}
 int mi_debug_read_joint_order(mi_world* world, uint32_t type, uint32_t* out)
 {
 	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);

@@ -322,6 +322,9 @@ int mi_debug_read_manifolds(mi_world* w, uint32_t* outPairs2, uint32_t* outCount
 /* Gauss-Seidel schedule of the contact solve: manifold slots in execution order + colour boundaries. */
 uint32_t mi_debug_num_colors(mi_world* w);
 int mi_debug_read_schedule(mi_world* w, uint32_t* outManifoldSlots, uint32_t* outColorStart /* numColors+1 */);
+/* Accumulated impulses of the last step's contacts: per schedule position (the order of mi_debug_read_schedule) 4 contacts x {normal, tangent}
+ * impulse, 8 floats; contacts a manifold does not have read 0.  A copy of what the sweep left behind: it costs the step nothing. */
+int mi_debug_read_contact_impulses(mi_world* w, float* outImpulses4x2PerPosition);
 int mi_debug_read_joint_order(mi_world* w, uint32_t type, uint32_t* outJointIds);
 /* The joint update records of the last step (what k_*_init wrote and the solve accumulated its impulses into): numJoints(type) records in
  * joint ORDER (mi_debug_read_joint_order), each MI_JOINT_UPDATE_FLOATS = {20, 20, 36, 56, 80, 72}[type] floats long (layouts: the comments of

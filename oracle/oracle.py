@@ -72,7 +72,7 @@ def _lib(avx2=False):
                      "orc_add_slider_constraint_global", "orc_num_bodies", "orc_num_colliders", "orc_num_pairs", "orc_num_contacts",
                      "orc_num_collisions", "orc_sorting_axis_used", "orc_sorting_axis_next", "orc_num_contact_slots",
                      "orc_narrowphase_ordered", "orc_schedule", "orc_read_slot_counts", "orc_add_hull_geometry", "orc_test_physics_interaction",
-                     "orc_terrain_slot_mismatch", "orc_terrain_contacts", "orc_add_cloth", "orc_cloth_num_particles", "orc_cloth_num_constraints", "orc_add_force_field", "orc_add_trigger", "orc_add_force_field_collider", "orc_add_trigger_collider", "orc_drain_events"):
+                     "orc_terrain_slot_mismatch", "orc_read_contact_impulses", "orc_terrain_contacts", "orc_add_cloth", "orc_cloth_num_particles", "orc_cloth_num_constraints", "orc_add_force_field", "orc_add_trigger", "orc_add_force_field_collider", "orc_add_trigger_collider", "orc_drain_events"):
             getattr(lib, name).restype = C.c_uint32
         lib.orc_heightmap_height_at.restype = C.c_float
         lib.orc_poly_trig.restype = C.c_float
@@ -295,7 +295,7 @@ class OracleWorld:
         self.lib.orc_set_follow(self.w, _p(pairs), C.c_uint32(len(pairs)), _p(order), C.c_uint32(len(order)))
 
     def set_row_form(self, on=True):
-        """Custom-order contact solves in the device's row form (default) or with the reference formula."""
+        """Custom-order and replay-order contact solves in the device's row form (default) or with the reference formula."""
         self.lib.orc_set_row_form(self.w, int(on))
 
     def set_scalar_row_form(self, on=True):
@@ -391,6 +391,12 @@ class OracleWorld:
         c = np.zeros(n, CONTACT_DTYPE); bp = np.zeros((n, 2), np.uint32); ci = np.zeros(n, np.uint32)
         self.lib.orc_read_contacts(self.w, _p(c), _p(bp), _p(ci))
         return c, bp, ci
+
+    def contact_impulses(self):
+        """(normal, tangent) impulses the last step accumulated [numContacts, 2], parallel to contacts() (scalar, follow and replay solvers)."""
+        out = np.zeros((max(1, self.lib.orc_num_contacts(self.w)), 2), np.float32)
+        n = self.lib.orc_read_contact_impulses(self.w, _p(out))
+        return out[:n]
 
     def collisions(self):
         n = self.lib.orc_num_collisions(self.w)

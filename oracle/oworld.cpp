@@ -949,7 +949,9 @@ static void physicsStepInternal(world& w, u32 iterations, u32 mode, float dt)
 					u32 ci = slot.indices[l];
 					bool padding = false; // (empty lanes duplicate lane 0: the SIMD code solves it again with identical operands)
 					for (u32 m = 0; m < l; ++m) if (slot.indices[m] == ci) padding = true;
-					if (!padding && ci < numContacts) solveCollisionConstraintRowForm(w.contactConstraints[ci], w.contacts[ci], w.contactBodyPairs[ci], rbs);
+					if (padding || ci >= numContacts) continue;
+					if (w.rowForm) solveCollisionConstraintRowForm(w.contactConstraints[ci], w.contacts[ci], w.contactBodyPairs[ci], rbs);
+					else solveCollisionConstraint(w.contactConstraints[ci], w.contacts[ci], w.contactBodyPairs[ci], rbs); // (set_row_form(false): the reference formula in the batch order)
 				}
 		}
 		else if (mode == solver_custom_order)
@@ -1592,6 +1594,12 @@ u32 orc_read_joint_decisions(world* w, u32 type, float* out, u32 capacityFloats)
 	return n / ORC_JOINT_DECISION_FLOATS;
 }
 void orc_set_joint_order(world* w, u32 type, const u32* order, u32 n) { if (type < 6) w->jointOrder[type].assign(order, order + n); }
+// {impulseInNormalDir, impulseInTangentDir} of the last step's contacts in contact order (orc_read_contacts); the 8-wide solver keeps none
+u32 orc_read_contact_impulses(world* w, float* out2)
+{
+	for (size_t i = 0; i < w->contactConstraints.size(); ++i) { out2[2 * i] = w->contactConstraints[i].impulseInNormalDir; out2[2 * i + 1] = w->contactConstraints[i].impulseInTangentDir; }
+	return (u32)w->contactConstraints.size();
+}
 u32 orc_read_slot_counts(world* w, u8* out) { memcpy(out, w->slotCounts.data(), w->slotCounts.size()); return (u32)w->slotCounts.size(); }
 
 u32 orc_num_bodies(world* w) { return (u32)w->bodies.size(); }
