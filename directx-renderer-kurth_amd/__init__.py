@@ -873,7 +873,7 @@ class LocomotionBatch:
             out = tuple(t.cpu().numpy() for t in out)
         return out if hidden else out[0]
 
-    # ---- training data (k_loco_sample, k_loco_value, k_loco_gae) ----
+    # ---- training data (k_loco_sample, k_loco_policy<1, false>, k_loco_gae) ----
     def set_value_network(self, *args):
         """The critic: six arrays w1 [Hv, 66], b1, w2 [Hv, Hv], b2, w3 [1, Hv], b3 [1], or one mapping with the stable-baselines names
         (VALUE_NAMES).  Hv is independent of the policy's H; the library keeps it across reset()."""

@@ -8,19 +8,20 @@
 // xorshift64 (seed ^ e * 0x9E3779B97F4A7C15; env 0 draws what the single environment draws), the same step settings, the same
 // state and reward formulas (locomotion_shared.h), read from the interpolated pose as the single environment reads it.
 //
-// The controller (learned_locomotion::update, locomotion_policy.h) closes the loop on the device: k_loco_policy reads the current
-// states, runs the network, smooths and writes the motors, in place of k_loco_actions, so an update driven by the policy has the same
-// launches as one driven by given actions.  dStates always holds the state of every environment as it is now (what
+// The controller (learned_locomotion::update, locomotion_policy.h) closes the loop on the device: k_loco_policy<27, true> reads the
+// current states, runs the network (locomotion_layers.h), smooths and writes the motors, in place of k_loco_actions, so an update driven
+// by the policy has the same launches as one driven by given actions.  The same kernel without the motors is the inference of either
+// network: k_loco_policy<27, false> the policy's, k_loco_policy<1, false> the critic's.  dStates always holds the state of every environment as it is now (what
 // observePhysicsBatch returns): every entry point that moves the environments refreshes it.  rolloutPhysicsBatchDevice enqueues
 // whole trajectories, with the fallen environments reset from their flags on the device.
 //
 // Training data (learning/learn_locomotion.py:71-107, PPO) is collected the same way: collectPhysicsBatchDevice runs the rollout's
-// updates with k_loco_sample in place of k_loco_policy, which adds the critic, the exploration noise (locomotion_policy.h:
+// updates with k_loco_sample in place of k_loco_policy<27, true>, which adds the critic, the exploration noise (locomotion_policy.h:
 // noiseSample), the sampled action, its log-probability and the clamp to the action ranges in the same launch.  The advantages of
 // gaePhysicsBatchDevice come from one lane per environment walking the rows backwards.
 //
 // The gradient step on that data is locomotion_update.hip's; its entry points are here (beginPhysicsBatchTraining ..
-// readPhysicsBatchLogStd).  dPolicy, dValueNet and dScales are the master copy of the parameters while a training session is open: Adam
+// readPhysicsBatchLogStd).  policy.data, critic.data and dScales are the master copy of the parameters while a training session is open: Adam
 // writes them in place, and the kernels above read what it wrote.
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -38,6 +39,9 @@ namespace
 	// training targets of resetTraining.
 	struct env_init { float4 spawn[2 * NUM_BODY_PARTS]; training train; };
 
+	// A network on the device: locomotion_policy.h's six arrays, the weights transposed to [in][out], in one block.
+	struct device_network { uint32_t outputs; float* data = nullptr; uint32_t hidden = 0; }; // hidden 0: none uploaded
+
 	struct batch
 	{
 		mi_world* world = nullptr;
@@ -53,10 +57,7 @@ namespace
 		int32_t* dPushes = nullptr;   // n: 1 + pushed body, or 0
 		uint32_t* dSlots = nullptr;   // n x 13: POD slot of each env's 7 cone-twist, then 6 hinge joints
 		float* dActions = nullptr; float* dStates = nullptr; float* dRewards = nullptr; int32_t* dFallen = nullptr; uint32_t* dIds = nullptr;
-		float* dPolicy = nullptr;     // the policy, transposed to [in][out]: W1T, b1, W2T, b2, W3T, b3 back to back
-		uint32_t hidden = 0;          // 0: no policy uploaded
-		float* dValueNet = nullptr;   // the critic, transposed like the policy: W1T, b1, W2T, b2, W3T (= w3), b3
-		uint32_t valueHidden = 0;     // 0: no critic uploaded
+		device_network policy = { ACTION_SIZE }, critic = { 1 };
 		float* dScales = nullptr;     // 4 x 27: std, logStd, actionMin, actionMax
 		bool stdSet = false, rangesSet = false;
 		uint64_t noiseCounter = 0;    // collecting updates since resetPhysicsBatch
@@ -79,7 +80,7 @@ namespace
 	{
 		if (!b) return;
 		if (b->stream) (void)hipStreamSynchronize(b->stream);
-		void* bufs[] = { b->dInit, b->dSmoothed, b->dRng, b->dRays, b->dPushes, b->dSlots, b->dActions, b->dStates, b->dRewards, b->dFallen, b->dIds, b->dPolicy, b->dValueNet, b->dScales, b->dMoments, b->dSlab, b->dGradient, b->dPartial, b->dGroupStats };
+		void* bufs[] = { b->dInit, b->dSmoothed, b->dRng, b->dRays, b->dPushes, b->dSlots, b->dActions, b->dStates, b->dRewards, b->dFallen, b->dIds, b->policy.data, b->critic.data, b->dScales, b->dMoments, b->dSlab, b->dGradient, b->dPartial, b->dGroupStats };
 		for (void* p : bufs) if (p) (void)hipFree(p);
 		if (b->world) mi_world_destroy(b->world);
 		delete b;
@@ -95,10 +96,17 @@ namespace
 		}
 	}
 
+	// The motor targets of joint j of environment e (cone-twist joints first, then the hinges) from its smoothed action, into its POD.
+	__device__ void writeMotor(uint32_t e, uint32_t j, const float* smoothed, const uint32_t* __restrict__ slots, uint8_t* conePods, uint8_t* hingePods)
+	{
+		const size_t slot = slots[NUM_MOTOR_JOINTS * e + j];
+		if (j < NUM_CONE_TWIST) setConeTwistMotors(*(cone_twist_pod*)(conePods + slot * sizeof(cone_twist_pod)), smoothed, j);
+		else setHingeMotors(*(hinge_pod*)(hingePods + slot * sizeof(hinge_pod)), smoothed, j - NUM_CONE_TWIST);
+	}
+
 	__device__ void writeMotors(uint32_t e, const float* smoothed, const uint32_t* __restrict__ slots, uint8_t* conePods, uint8_t* hingePods)
 	{
-		for (int i = 0; i < NUM_CONE_TWIST; ++i) setConeTwistMotors(*(cone_twist_pod*)(conePods + (size_t)slots[NUM_MOTOR_JOINTS * e + i] * sizeof(cone_twist_pod)), smoothed, i);
-		for (int i = 0; i < NUM_HINGE; ++i) setHingeMotors(*(hinge_pod*)(hingePods + (size_t)slots[NUM_MOTOR_JOINTS * e + NUM_CONE_TWIST + i] * sizeof(hinge_pod)), smoothed, i);
+		for (uint32_t j = 0; j < NUM_MOTOR_JOINTS; ++j) writeMotor(e, j, smoothed, slots, conePods, hingePods);
 	}
 
 	// Kernel A: applyAction for every environment.
@@ -113,108 +121,61 @@ namespace
 		writeMotors(e, smoothed, slots, conePods, hingePods);
 	}
 
-	// Kernel P: learned_locomotion::update for a tile of POLICY_TILE environments per workgroup: states -> three layers -> raw action;
-	// with APPLY also smoothAction and the motor PODs, i.e. everything k_loco_actions does.  blockDim.x >= max(hidden, 64), a multiple
-	// of 64.  actionsOut (count x 27, raw network outputs) and hiddenOut (count x 2H: tanh(z1), tanh(z2)) may be null.
-	template <bool APPLY>
-	__global__ void __launch_bounds__(POLICY_MAX_HIDDEN) k_loco_policy(uint32_t count, uint32_t hidden, const float* __restrict__ states, const float* __restrict__ policy,
-		float* __restrict__ actionsOut, float* __restrict__ hiddenOut, float* __restrict__ smoothedAll, const uint32_t* __restrict__ slots, uint8_t* conePods, uint8_t* hingePods)
+	// applyAction for a tile, by one wave: smoothAction of `applied` (this lane's action element of every tile row, lanes 0 .. 26), one
+	// element per lane, through `smoothed` in LDS; barrier; then one joint per lane writes its POD.
+	__device__ __forceinline__ void smoothAndDrive(const float (&applied)[POLICY_TILE], float (*smoothed)[ACTION_SIZE], uint32_t first, uint32_t count,
+		float* __restrict__ smoothedAll, const uint32_t* __restrict__ slots, uint8_t* conePods, uint8_t* hingePods)
 	{
+		const uint32_t t = threadIdx.x;
+		if (t < ACTION_SIZE)
+		{
+			#pragma unroll
+			for (uint32_t r = 0; r < POLICY_TILE; ++r)
+			{
+				const uint32_t e = first + r;
+				if (e >= count) continue;
+				const float s = lerpf(smoothedAll[(size_t)ACTION_SIZE * e + t], applied[r], 0.1f);
+				smoothedAll[(size_t)ACTION_SIZE * e + t] = s; smoothed[r][t] = s;
+			}
+		}
+		__syncthreads();
+		const uint32_t r = t / NUM_MOTOR_JOINTS, j = t % NUM_MOTOR_JOINTS, e = first + r;
+		if (r < POLICY_TILE && e < count) writeMotor(e, j, smoothed[r], slots, conePods, hingePods);
+	}
+	static_assert(POLICY_TILE * NUM_MOTOR_JOINTS <= 64 && ACTION_SIZE <= 64, "one wave covers the tile's joints and actions");
+	static_assert(POLICY_TILE * NUM_MOTOR_JOINTS + POLICY_TILE <= 64, "one wave covers the tile's joints and log-probabilities");
+
+	// Kernel P: one network, 66 -> hidden -> hidden -> OUTPUTS, on a tile of POLICY_TILE rows per workgroup.  <27, true> is
+	// learned_locomotion::update: the policy on the environments' states, then smoothAction and the motor PODs, i.e. everything
+	// k_loco_actions does.  <27, false> and <1, false> are the policy and the critic alone on any rows.  blockDim.x >= max(hidden, 64), a
+	// multiple of 64.  out (count x OUTPUTS, raw network outputs) and hiddenOut (count x 2 hidden: tanh(z1), tanh(z2)) may be null.
+	template <uint32_t OUTPUTS, bool APPLY>
+	__global__ void __launch_bounds__(POLICY_MAX_HIDDEN) k_loco_policy(uint32_t count, uint32_t hidden, const float* __restrict__ states, const float* __restrict__ net,
+		float* __restrict__ out, float* __restrict__ hiddenOut, float* __restrict__ smoothedAll, const uint32_t* __restrict__ slots, uint8_t* conePods, uint8_t* hingePods)
+	{
+		static_assert(!APPLY || OUTPUTS == ACTION_SIZE, "only the policy drives the motors");
 		__shared__ float4 input[STATE_SIZE], hiddenA[POLICY_MAX_HIDDEN], hiddenB[POLICY_MAX_HIDDEN];
 		__shared__ float smoothed[POLICY_TILE][ACTION_SIZE];
 		const uint32_t first = blockIdx.x * POLICY_TILE, t = threadIdx.x;
-		const float* w1 = policy; const float* b1 = w1 + (size_t)STATE_SIZE * hidden;
-		const float* w2 = b1 + hidden; const float* b2 = w2 + (size_t)hidden * hidden;
-		const float* w3 = b2 + hidden; const float* b3 = w3 + (size_t)hidden * ACTION_SIZE;
-		for (uint32_t i = t; i < POLICY_TILE * STATE_SIZE; i += blockDim.x)
-		{
-			const uint32_t r = i / STATE_SIZE, x = i % STATE_SIZE;
-			((float*)input)[POLICY_TILE * x + r] = first + r < count ? states[(size_t)STATE_SIZE * (first + r) + x] : 0.f;
-		}
-		__syncthreads();
-		const float4 a = policyLayer(w1, b1, STATE_SIZE, hidden, input, t, true);
-		if (t < hidden) hiddenA[t] = a;
-		__syncthreads();
-		const float4 b = policyLayer(w2, b2, hidden, hidden, hiddenA, t, true);
-		if (t < hidden) hiddenB[t] = b;
-		__syncthreads();
-		const float4 out = policyLayer(w3, b3, hidden, ACTION_SIZE, hiddenB, t, false);
-		const float av[POLICY_TILE] = { a.x, a.y, a.z, a.w }, bv[POLICY_TILE] = { b.x, b.y, b.z, b.w }, ov[POLICY_TILE] = { out.x, out.y, out.z, out.w };
-		#pragma unroll
-		for (uint32_t r = 0; r < POLICY_TILE; ++r)
-		{
-			const uint32_t e = first + r;
-			if (e >= count) continue;
-			if (hiddenOut && t < hidden) { hiddenOut[(size_t)2 * hidden * e + t] = av[r]; hiddenOut[(size_t)2 * hidden * e + hidden + t] = bv[r]; }
-			if (t < ACTION_SIZE)
-			{
-				if (actionsOut) actionsOut[(size_t)ACTION_SIZE * e + t] = ov[r];
-				if (APPLY) // smoothAction, one element per lane
-				{
-					const float s = lerpf(smoothedAll[(size_t)ACTION_SIZE * e + t], ov[r], 0.1f);
-					smoothedAll[(size_t)ACTION_SIZE * e + t] = s; smoothed[r][t] = s;
-				}
-			}
-		}
-		if (APPLY) // writeMotors, one joint per lane
-		{
-			__syncthreads();
-			const uint32_t r = t / NUM_MOTOR_JOINTS, j = t % NUM_MOTOR_JOINTS, e = first + r;
-			if (r < POLICY_TILE && e < count)
-			{
-				if (j < NUM_CONE_TWIST) setConeTwistMotors(*(cone_twist_pod*)(conePods + (size_t)slots[NUM_MOTOR_JOINTS * e + j] * sizeof(cone_twist_pod)), smoothed[r], j);
-				else setHingeMotors(*(hinge_pod*)(hingePods + (size_t)slots[NUM_MOTOR_JOINTS * e + j] * sizeof(hinge_pod)), smoothed[r], j - NUM_CONE_TWIST);
-			}
-		}
-	}
-	static_assert(POLICY_TILE * NUM_MOTOR_JOINTS <= 64 && ACTION_SIZE <= 64, "one wave covers the tile's joints and actions");
-
-	// The tile's states into LDS as [in][tile]; rows past count read as zeros.  copy (may be null) receives the rows as they were read.
-	__device__ void loadTile(float4* input, const float* __restrict__ states, float* __restrict__ copy, uint32_t first, uint32_t count)
-	{
-		for (uint32_t i = threadIdx.x; i < POLICY_TILE * STATE_SIZE; i += blockDim.x)
-		{
-			const uint32_t r = i / STATE_SIZE, x = i % STATE_SIZE;
-			const float v = first + r < count ? states[(size_t)STATE_SIZE * (first + r) + x] : 0.f;
-			((float*)input)[POLICY_TILE * x + r] = v;
-			if (copy && first + r < count) copy[(size_t)STATE_SIZE * (first + r) + x] = v;
-		}
-	}
-
-	// Kernel V: the critic alone, 66 -> Hv -> Hv -> 1, for a tile of POLICY_TILE rows per workgroup.  blockDim.x >= max(hidden, 64), a
-	// multiple of 64.  hiddenOut (count x 2Hv) may be null.
-	__global__ void __launch_bounds__(POLICY_MAX_HIDDEN) k_loco_value(uint32_t count, uint32_t hidden, const float* __restrict__ states, const float* __restrict__ valueNet,
-		float* __restrict__ valuesOut, float* __restrict__ hiddenOut)
-	{
-		__shared__ float4 input[STATE_SIZE], hiddenA[POLICY_MAX_HIDDEN], hiddenB[POLICY_MAX_HIDDEN];
-		const uint32_t first = blockIdx.x * POLICY_TILE, t = threadIdx.x;
-		const network v = networkOf(valueNet, hidden, 1);
 		loadTile(input, states, nullptr, first, count);
 		__syncthreads();
-		const float4 a = policyLayer(v.w1, v.b1, STATE_SIZE, hidden, input, t, true);
-		if (t < hidden) hiddenA[t] = a;
-		__syncthreads();
-		const float4 b = policyLayer(v.w2, v.b2, hidden, hidden, hiddenA, t, true);
-		if (t < hidden) hiddenB[t] = b;
-		__syncthreads();
-		const float4 out = policyLayer(v.w3, v.b3, hidden, 1, hiddenB, t, false);
-		const float av[POLICY_TILE] = { a.x, a.y, a.z, a.w }, bv[POLICY_TILE] = { b.x, b.y, b.z, b.w }, ov[POLICY_TILE] = { out.x, out.y, out.z, out.w };
+		const forward_one f = forwardNetwork(networkOf(net, hidden, OUTPUTS), input, hiddenA, hiddenB);
+		const float av[POLICY_TILE] = { f.a.x, f.a.y, f.a.z, f.a.w }, bv[POLICY_TILE] = { f.b.x, f.b.y, f.b.z, f.b.w }, ov[POLICY_TILE] = { f.out.x, f.out.y, f.out.z, f.out.w };
 		#pragma unroll
 		for (uint32_t r = 0; r < POLICY_TILE; ++r)
 		{
 			const uint32_t e = first + r;
 			if (e >= count) continue;
 			if (hiddenOut && t < hidden) { hiddenOut[(size_t)2 * hidden * e + t] = av[r]; hiddenOut[(size_t)2 * hidden * e + hidden + t] = bv[r]; }
-			if (t == 0) valuesOut[e] = ov[r];
+			if (out && t < OUTPUTS) out[(size_t)OUTPUTS * e + t] = ov[r];
 		}
+		if (APPLY) smoothAndDrive(ov, smoothed, first, count, smoothedAll, slots, conePods, hingePods);
 	}
 
 	// Kernel S: the collecting update of a tile of POLICY_TILE environments, everything before the push in one launch: the actor and
-	// the critic on the current states (layer by layer side by side, both pairs of hidden vectors in LDS), the noise, the sample
-	// a = mu + std * eps, its log-probability, the clamp to the action ranges (clip != 0), smoothAction and the motor PODs.
-	// blockDim.x >= max(hidden, valueHidden, 64), a multiple of 64.  Row outputs: obs (the states as read), actions (unclipped), eps
-	// (may be null), logProbs, values.  The last layers run on different waves where there are two: actor on lanes 0..26, critic on
-	// lane 64 (lane 32 in a one-wave block).
+	// the critic on the current states (forwardActorCritic), the noise, the sample a = mu + std * eps, its log-probability, the clamp to
+	// the action ranges (clip != 0), smoothAction and the motor PODs.  blockDim.x >= max(hidden, valueHidden, 64), a multiple of 64.
+	// Row outputs: obs (the states as read), actions (unclipped), eps (may be null), logProbs, values.
 	__global__ void __launch_bounds__(POLICY_MAX_HIDDEN) k_loco_sample(uint32_t count, uint32_t hidden, uint32_t valueHidden, int clip, uint64_t seed, uint64_t update,
 		const float* __restrict__ states, const float* __restrict__ policy, const float* __restrict__ valueNet, const float* __restrict__ scales,
 		float* __restrict__ obsOut, float* __restrict__ actionsOut, float* __restrict__ epsOut, float* __restrict__ logProbsOut, float* __restrict__ valuesOut,
@@ -223,7 +184,6 @@ namespace
 		__shared__ float4 input[STATE_SIZE], hiddenA[POLICY_MAX_HIDDEN], hiddenB[POLICY_MAX_HIDDEN], valueA[POLICY_MAX_HIDDEN], valueB[POLICY_MAX_HIDDEN];
 		__shared__ float smoothed[POLICY_TILE][ACTION_SIZE], eps[POLICY_TILE][ACTION_SIZE];
 		const uint32_t first = blockIdx.x * POLICY_TILE, t = threadIdx.x;
-		const network p = networkOf(policy, hidden, ACTION_SIZE), v = networkOf(valueNet, valueHidden, 1);
 		loadTile(input, states, obsOut, first, count);
 		for (uint32_t i = t; i < POLICY_TILE * ACTION_SIZE; i += blockDim.x)
 		{
@@ -231,26 +191,15 @@ namespace
 			eps[r][j] = first + r < count ? noiseSample(seed, first + r, update, j) : 0.f;
 		}
 		__syncthreads();
-		const float4 a = policyLayer(p.w1, p.b1, STATE_SIZE, hidden, input, t, true);
-		const float4 va = policyLayer(v.w1, v.b1, STATE_SIZE, valueHidden, input, t, true);
-		if (t < hidden) hiddenA[t] = a;
-		if (t < valueHidden) valueA[t] = va;
-		__syncthreads();
-		const float4 b = policyLayer(p.w2, p.b2, hidden, hidden, hiddenA, t, true);
-		const float4 vb = policyLayer(v.w2, v.b2, valueHidden, valueHidden, valueA, t, true);
-		if (t < hidden) hiddenB[t] = b;
-		if (t < valueHidden) valueB[t] = vb;
-		__syncthreads();
-		const uint32_t valueLane = blockDim.x > 64 ? 64 : 32;
-		const float4 out = policyLayer(p.w3, p.b3, hidden, ACTION_SIZE, hiddenB, t, false);
-		const float4 value = policyLayer(v.w3, v.b3, valueHidden, 1, valueB, t - valueLane, false); // t < valueLane wraps: no unit
-		const float ov[POLICY_TILE] = { out.x, out.y, out.z, out.w }, vv[POLICY_TILE] = { value.x, value.y, value.z, value.w };
+		const forward_pair f = forwardActorCritic(networkOf(policy, hidden, ACTION_SIZE), networkOf(valueNet, valueHidden, 1), input, hiddenA, hiddenB, valueA, valueB);
+		const float ov[POLICY_TILE] = { f.out.x, f.out.y, f.out.z, f.out.w }, vv[POLICY_TILE] = { f.value.x, f.value.y, f.value.z, f.value.w };
+		float applied[POLICY_TILE] = {};
 		#pragma unroll
 		for (uint32_t r = 0; r < POLICY_TILE; ++r)
 		{
 			const uint32_t e = first + r;
 			if (e >= count) continue;
-			if (t == valueLane) valuesOut[e] = vv[r];
+			if (t == criticLane()) valuesOut[e] = vv[r];
 			if (t < ACTION_SIZE)
 			{
 				const float noise = eps[r][t];
@@ -258,22 +207,13 @@ namespace
 				const float sample = ov[r] + scaled;
 				actionsOut[(size_t)ACTION_SIZE * e + t] = sample;
 				if (epsOut) epsOut[(size_t)ACTION_SIZE * e + t] = noise;
-				const float applied = clip ? clampf(sample, scales[2 * ACTION_SIZE + t], scales[3 * ACTION_SIZE + t]) : sample;
-				const float s = lerpf(smoothedAll[(size_t)ACTION_SIZE * e + t], applied, 0.1f); // smoothAction, one element per lane
-				smoothedAll[(size_t)ACTION_SIZE * e + t] = s; smoothed[r][t] = s;
+				applied[r] = clip ? clampf(sample, scales[2 * ACTION_SIZE + t], scales[3 * ACTION_SIZE + t]) : sample;
 			}
 		}
-		__syncthreads();
-		const uint32_t r = t / NUM_MOTOR_JOINTS, j = t % NUM_MOTOR_JOINTS, e = first + r;
-		if (r < POLICY_TILE && e < count) // writeMotors, one joint per lane
-		{
-			if (j < NUM_CONE_TWIST) setConeTwistMotors(*(cone_twist_pod*)(conePods + (size_t)slots[NUM_MOTOR_JOINTS * e + j] * sizeof(cone_twist_pod)), smoothed[r], j);
-			else setHingeMotors(*(hinge_pod*)(hingePods + (size_t)slots[NUM_MOTOR_JOINTS * e + j] * sizeof(hinge_pod)), smoothed[r], j - NUM_CONE_TWIST);
-		}
+		smoothAndDrive(applied, smoothed, first, count, smoothedAll, slots, conePods, hingePods);
 		const uint32_t q = t - POLICY_TILE * NUM_MOTOR_JOINTS; // the log-probabilities on the lanes after the joints'
 		if (q < POLICY_TILE && first + q < count) logProbsOut[first + q] = noiseLogProb(eps[q], scales + ACTION_SIZE);
 	}
-	static_assert(POLICY_TILE * NUM_MOTOR_JOINTS + POLICY_TILE <= 64, "one wave covers the tile's joints and log-probabilities");
 
 	// Generalised advantage estimation, one lane per environment walking its column of [steps][n] backwards (the lanes run along n:
 	// every load is one coalesced line).  All float32, in this order: delta = (r + (gamma * next) * nd) - V;
@@ -421,52 +361,41 @@ namespace
 		return ok(hipGetLastError(), "gather kernel") ? 0 : MI_ERR_HIP;
 	}
 
-	// The network on count rows of dStatesIn, on the world's stream.  With apply: rows are the environments, smoothed and motors written.
-	int launchPolicy(batch& b, bool apply, uint32_t count, const float* dStatesIn, float* dActionsOut, float* dHiddenOut)
+	dim3 networkBlock(uint32_t hidden) { return dim3(64 * ((hidden + 63) / 64)); }
+
+	// A network on count rows of dStatesIn, on the world's stream.  With apply (the policy only): rows are the environments, smoothed and
+	// motors written.
+	int launchNetwork(batch& b, const device_network& net, bool apply, uint32_t count, const float* dStatesIn, float* dOut, float* dHiddenOut)
 	{
-		const dim3 grid((count + POLICY_TILE - 1) / POLICY_TILE), block(64 * ((b.hidden + 63) / 64));
-		if (apply) hipLaunchKernelGGL(k_loco_policy<true>, grid, block, 0, b.stream, count, b.hidden, dStatesIn, (const float*)b.dPolicy, dActionsOut, dHiddenOut, b.dSmoothed, (const uint32_t*)b.dSlots, (uint8_t*)b.pods[0], (uint8_t*)b.pods[1]);
-		else hipLaunchKernelGGL(k_loco_policy<false>, grid, block, 0, b.stream, count, b.hidden, dStatesIn, (const float*)b.dPolicy, dActionsOut, dHiddenOut, (float*)nullptr, (const uint32_t*)nullptr, (uint8_t*)nullptr, (uint8_t*)nullptr);
-		return ok(hipGetLastError(), "policy kernel") ? 0 : MI_ERR_HIP;
+		const auto kernel = net.outputs == 1 ? k_loco_policy<1, false> : apply ? k_loco_policy<ACTION_SIZE, true> : k_loco_policy<ACTION_SIZE, false>;
+		hipLaunchKernelGGL(kernel, dim3((count + POLICY_TILE - 1) / POLICY_TILE), networkBlock(net.hidden), 0, b.stream, count, net.hidden, dStatesIn, (const float*)net.data, dOut, dHiddenOut,
+			apply ? b.dSmoothed : nullptr, apply ? (const uint32_t*)b.dSlots : nullptr, apply ? (uint8_t*)b.pods[0] : nullptr, apply ? (uint8_t*)b.pods[1] : nullptr);
+		return ok(hipGetLastError(), "network kernel") ? 0 : MI_ERR_HIP;
 	}
 
-	// The policy of setPhysicsPolicy, transposed to [in][out] once, here.
-	int uploadPolicy(batch& b)
+	// Replaces *p by a new buffer of `floats` floats; *p stays null, and *recorded (may be null) 0, where that fails.  The caller has made
+	// sure that nothing in flight uses the old one.
+	int reallocate(float** p, size_t floats, size_t* recorded = nullptr)
 	{
-		locomotion_policy p;
-		if (!locomotionPolicy(&p)) return 0;
-		const uint32_t h = p.hidden;
-		std::vector<float> t(policyFloats(h));
-		float* q = t.data();
-		auto transposed = [&](const float* w, uint32_t outputs, uint32_t inputs) { for (uint32_t x = 0; x < inputs; ++x) for (uint32_t y = 0; y < outputs; ++y) *q++ = w[(size_t)y * inputs + x]; };
-		auto plain = [&](const float* v, uint32_t count) { memcpy(q, v, sizeof(float) * count); q += count; };
-		transposed(p.w1, h, STATE_SIZE); plain(p.b1, h); transposed(p.w2, h, h); plain(p.b2, h); transposed(p.w3, ACTION_SIZE, h); plain(p.b3, ACTION_SIZE);
-		if (!ok(hipStreamSynchronize(b.stream), "policy")) return MI_ERR_HIP; // nothing in flight reads the old one
-		if (b.dPolicy) (void)hipFree(b.dPolicy);
-		b.dPolicy = nullptr; b.hidden = 0;
-		if (!ok(hipMalloc(&b.dPolicy, sizeof(float) * t.size()), "alloc")) return MI_ERR_HIP;
-		if (!ok(hipMemcpyAsync(b.dPolicy, t.data(), sizeof(float) * t.size(), hipMemcpyHostToDevice, b.stream), "policy") || !ok(hipStreamSynchronize(b.stream), "policy")) return MI_ERR_HIP;
-		b.hidden = h;
+		if (*p) (void)hipFree(*p);
+		*p = nullptr; if (recorded) *recorded = 0;
+		if (!ok(hipMalloc(p, sizeof(float) * floats), "alloc")) return MI_ERR_HIP;
+		if (recorded) *recorded = floats;
 		return 0;
 	}
 
-	// The critic of setPhysicsValueNetwork, transposed the same way.
-	int uploadValueNetwork(batch& b)
+	// The network that the host keeps for `net` (setPhysicsPolicy or setPhysicsValueNetwork), if any, transposed to [in][out] once, here.
+	int uploadNetwork(batch& b, device_network& net)
 	{
 		locomotion_policy p;
-		if (!locomotionValueNetwork(&p)) return 0;
-		const uint32_t h = p.hidden;
-		std::vector<float> t(valueFloats(h));
-		float* q = t.data();
-		auto transposed = [&](const float* w, uint32_t outputs, uint32_t inputs) { for (uint32_t x = 0; x < inputs; ++x) for (uint32_t y = 0; y < outputs; ++y) *q++ = w[(size_t)y * inputs + x]; };
-		auto plain = [&](const float* v, uint32_t count) { memcpy(q, v, sizeof(float) * count); q += count; };
-		transposed(p.w1, h, STATE_SIZE); plain(p.b1, h); transposed(p.w2, h, h); plain(p.b2, h); transposed(p.w3, 1, h); plain(p.b3, 1);
-		if (!ok(hipStreamSynchronize(b.stream), "value network")) return MI_ERR_HIP; // nothing in flight reads the old one
-		if (b.dValueNet) (void)hipFree(b.dValueNet);
-		b.dValueNet = nullptr; b.valueHidden = 0;
-		if (!ok(hipMalloc(&b.dValueNet, sizeof(float) * t.size()), "alloc")) return MI_ERR_HIP;
-		if (!ok(hipMemcpyAsync(b.dValueNet, t.data(), sizeof(float) * t.size(), hipMemcpyHostToDevice, b.stream), "value network") || !ok(hipStreamSynchronize(b.stream), "value network")) return MI_ERR_HIP;
-		b.valueHidden = h;
+		if (!locomotionNetwork(net.outputs, &p)) return 0;
+		std::vector<float> t(networkFloats(p.hidden, p.outputs));
+		copyNetwork(p, networkOf(t.data(), p.hidden, p.outputs), NETWORK_TO_DEVICE);
+		if (!ok(hipStreamSynchronize(b.stream), "network")) return MI_ERR_HIP; // nothing in flight reads the old one
+		net.hidden = 0;
+		if (int e = reallocate(&net.data, t.size())) return e;
+		if (!ok(hipMemcpyAsync(net.data, t.data(), sizeof(float) * t.size(), hipMemcpyHostToDevice, b.stream), "network") || !ok(hipStreamSynchronize(b.stream), "network")) return MI_ERR_HIP;
+		net.hidden = p.hidden;
 		return 0;
 	}
 
@@ -502,14 +431,6 @@ namespace
 		return 0;
 	}
 
-	dim3 networkBlock(uint32_t hidden) { return dim3(64 * ((hidden + 63) / 64)); }
-
-	int launchValue(batch& b, uint32_t count, const float* dStatesIn, float* dValuesOut, float* dHiddenOut)
-	{
-		hipLaunchKernelGGL(k_loco_value, dim3((count + POLICY_TILE - 1) / POLICY_TILE), networkBlock(b.valueHidden), 0, b.stream, count, b.valueHidden, dStatesIn, (const float*)b.dValueNet, dValuesOut, dHiddenOut);
-		return ok(hipGetLastError(), "value kernel") ? 0 : MI_ERR_HIP;
-	}
-
 	// One update of every environment, all on the world's stream, writing the three outputs (device pointers; dStates may be null, the
 	// batch's current-state buffer receives the states in any case).  With dActions: applyAction of these.  Without: the policy on the
 	// current states, its raw outputs to dActionsOut (may be null).
@@ -518,7 +439,7 @@ namespace
 	{
 		if (int e = refreshPods(b)) return e;
 		if (dActions) hipLaunchKernelGGL(k_loco_actions, blocks(b.n), dim3(64), 0, b.stream, b.n, dActions, b.dSmoothed, b.dSlots, (uint8_t*)b.pods[0], (uint8_t*)b.pods[1]);
-		else if (int e = launchPolicy(b, true, b.n, b.dStates, dActionsOut, nullptr)) return e;
+		else if (int e = launchNetwork(b, b.policy, true, b.n, b.dStates, dActionsOut, nullptr)) return e;
 		return launchAfterAction(b, dStates, dRewards, dFallen);
 	}
 
@@ -545,43 +466,31 @@ namespace
 		return 0;
 	}
 
-	ppo_parameters parametersOf(batch& b) { return { b.dPolicy, b.dValueNet, b.dScales, b.hidden, b.valueHidden }; }
+	ppo_parameters parametersOf(batch& b) { return { b.policy.data, b.critic.data, b.dScales, b.policy.hidden, b.critic.hidden }; }
 	ppo_scratch scratchOf(batch& b) { return { b.dSlab, b.dPartial, b.dGroupStats }; }
 
 	// The scratch of the gradient step for minibatches of up to `count` rows with the networks as they are.
 	int ensureScratch(batch& b, uint32_t count)
 	{
-		const size_t total = ppoTotal(b.hidden, b.valueHidden), slab = total * ppoGroups(count);
+		const size_t total = ppoTotal(b.policy.hidden, b.critic.hidden), slab = total * ppoGroups(count);
 		if (slab <= b.slabFloats && total <= b.gradientFloats) return 0;
 		if (!ok(hipStreamSynchronize(b.stream), "scratch")) return MI_ERR_HIP; // nothing in flight uses the old buffers
-		if (slab > b.slabFloats)
-		{
-			if (b.dSlab) (void)hipFree(b.dSlab);
-			b.dSlab = nullptr; b.slabFloats = 0;
-			if (!ok(hipMalloc(&b.dSlab, sizeof(float) * slab), "alloc")) return MI_ERR_HIP;
-			b.slabFloats = slab;
-		}
+		if (slab > b.slabFloats && reallocate(&b.dSlab, slab, &b.slabFloats)) return MI_ERR_HIP;
 		if (total > b.gradientFloats)
 		{
-			for (float** p : { &b.dGradient, &b.dPartial, &b.dGroupStats }) { if (*p) (void)hipFree(*p); *p = nullptr; }
 			b.gradientFloats = 0;
-			if (!ok(hipMalloc(&b.dGradient, sizeof(float) * total), "alloc") || !ok(hipMalloc(&b.dPartial, sizeof(float) * ppoBlocks(total)), "alloc")
-				|| !ok(hipMalloc(&b.dGroupStats, sizeof(float) * PPO_MAX_GROUPS * PPO_GROUP_STATS), "alloc")) return MI_ERR_HIP;
+			if (reallocate(&b.dGradient, total) || reallocate(&b.dPartial, ppoBlocks(total)) || reallocate(&b.dGroupStats, PPO_MAX_GROUPS * PPO_GROUP_STATS)) return MI_ERR_HIP;
 			b.gradientFloats = total;
 		}
 		return 0;
 	}
 
 	// A network of the master copy back into the [out][in] arrays the setters take (host pointers).
-	int readNetwork(batch& b, const float* dNetwork, uint32_t h, uint32_t outputs, float* w1, float* b1, float* w2, float* b2, float* w3, float* b3)
+	int readNetwork(batch& b, const device_network& net, float* w1, float* b1, float* w2, float* b2, float* w3, float* b3)
 	{
-		const size_t floats = (size_t)h * STATE_SIZE + h + (size_t)h * h + h + (size_t)outputs * h + outputs;
-		std::vector<float> t(floats);
-		if (!ok(hipMemcpyAsync(t.data(), dNetwork, sizeof(float) * floats, hipMemcpyDeviceToHost, b.stream), "read network") || !ok(hipStreamSynchronize(b.stream), "read network")) return MI_ERR_HIP;
-		const float* q = t.data();
-		auto transposed = [&](float* w, uint32_t outs, uint32_t inputs) { for (uint32_t x = 0; x < inputs; ++x) for (uint32_t y = 0; y < outs; ++y) w[(size_t)y * inputs + x] = *q++; };
-		auto plain = [&](float* v, uint32_t count) { memcpy(v, q, sizeof(float) * count); q += count; };
-		transposed(w1, h, STATE_SIZE); plain(b1, h); transposed(w2, h, h); plain(b2, h); transposed(w3, outputs, h); plain(b3, outputs);
+		std::vector<float> t(networkFloats(net.hidden, net.outputs));
+		if (!ok(hipMemcpyAsync(t.data(), net.data, sizeof(float) * t.size(), hipMemcpyDeviceToHost, b.stream), "read network") || !ok(hipStreamSynchronize(b.stream), "read network")) return MI_ERR_HIP;
+		copyNetwork(networkOf((const float*)t.data(), net.hidden, net.outputs), { net.hidden, net.outputs, { w1, w2, w3 }, { b1, b2, b3 } }, NETWORK_TO_HOST);
 		return 0;
 	}
 
@@ -591,6 +500,17 @@ namespace
 		if (outRewards && !ok(hipMemcpyAsync(outRewards, b.dRewards, sizeof(float) * b.n, hipMemcpyDeviceToHost, b.stream), "rewards")) return MI_ERR_HIP;
 		if (outFallen && !ok(hipMemcpyAsync(outFallen, b.dFallen, sizeof(int32_t) * b.n, hipMemcpyDeviceToHost, b.stream), "fallen")) return MI_ERR_HIP;
 		return ok(hipStreamSynchronize(b.stream), "copy out") ? 0 : MI_ERR_HIP;
+	}
+
+	// The tail of an update from the host: copyOut, then the number of fallen environments (negative: an error code).
+	int copyOutFallen(batch& b, float* outStates, float* outRewards, int32_t* outFallen)
+	{
+		std::vector<int32_t> fallen(b.n);
+		if (int e = copyOut(b, outStates, outRewards, fallen.data())) return -e;
+		int count = 0;
+		for (uint32_t i = 0; i < b.n; ++i) count += fallen[i] != 0;
+		if (outFallen) memcpy(outFallen, fallen.data(), sizeof(int32_t) * b.n);
+		return count;
 	}
 }
 
@@ -657,8 +577,8 @@ extern "C"
 		B = b;
 		int e = launchReset(*b, b->dIds, nullptr, numEnvs);
 		if (!e) e = launchGather(*b, nullptr, nullptr, numEnvs, b->dStates, b->dRewards, b->dFallen);
-		if (!e) e = uploadPolicy(*b);
-		if (!e) e = uploadValueNetwork(*b);
+		if (!e) e = uploadNetwork(*b, b->policy);
+		if (!e) e = uploadNetwork(*b, b->critic);
 		if (!e) e = uploadActionStd(*b);
 		if (!e) e = copyOut(*b, outStates, nullptr, nullptr);
 		return e;
@@ -672,12 +592,7 @@ extern "C"
 		batch& b = *B;
 		if (!ok(hipMemcpyAsync(b.dActions, actions, sizeof(float) * ACTION_SIZE * b.n, hipMemcpyHostToDevice, b.stream), "actions")) return -MI_ERR_HIP;
 		if (int e = launchUpdate(b, b.dActions, nullptr, b.dStates, b.dRewards, b.dFallen)) return -e;
-		std::vector<int32_t> fallen(b.n);
-		if (int e = copyOut(b, outStates, outRewards, fallen.data())) return -e;
-		int count = 0;
-		for (uint32_t i = 0; i < b.n; ++i) count += fallen[i] != 0;
-		if (outFallen) memcpy(outFallen, fallen.data(), sizeof(int32_t) * b.n);
-		return count;
+		return copyOutFallen(b, outStates, outRewards, outFallen);
 	}
 
 	// The same from device buffers, enqueued on the world's stream (getPhysicsBatchStream) without a host synchronisation.
@@ -732,30 +647,25 @@ extern "C"
 	// NULL, count x 2H) receives tanh(z1), tanh(z2) of every row: a parity facility.  Touches no environment.
 	int inferPhysicsBatchDevice(uint32_t count, const float* dStates, float* dActions, float* dHidden)
 	{
-		if (!B || !B->hidden) return MI_ERR_INVALID_STATE;
+		if (!B || !B->policy.hidden) return MI_ERR_INVALID_STATE;
 		if (!count || !dStates || !dActions) return MI_ERR_INVALID_ARGUMENT;
-		return launchPolicy(*B, false, count, dStates, dActions, dHidden);
+		return launchNetwork(*B, B->policy, false, count, dStates, dActions, dHidden);
 	}
 
 	// One closed-loop update of every environment, host buffers out (any may be NULL).  Returns what updatePhysicsBatch returns.
 	int updatePhysicsBatchPolicy(float* outStates, float* outRewards, int32_t* outFallen)
 	{
-		if (!B || !B->hidden) return -MI_ERR_INVALID_STATE;
+		if (!B || !B->policy.hidden) return -MI_ERR_INVALID_STATE;
 		batch& b = *B;
 		if (int e = launchUpdate(b, nullptr, nullptr, b.dStates, b.dRewards, b.dFallen)) return -e;
-		std::vector<int32_t> fallen(b.n);
-		if (int e = copyOut(b, outStates, outRewards, fallen.data())) return -e;
-		int count = 0;
-		for (uint32_t i = 0; i < b.n; ++i) count += fallen[i] != 0;
-		if (outFallen) memcpy(outFallen, fallen.data(), sizeof(int32_t) * b.n);
-		return count;
+		return copyOutFallen(b, outStates, outRewards, outFallen);
 	}
 
 	// The same into device buffers, enqueued on the world's stream without a host synchronisation; dActions (may be NULL, n x 27)
 	// receives the raw, unsmoothed network outputs.
 	int updatePhysicsBatchPolicyDevice(float* dStates, float* dRewards, int32_t* dFallen, float* dActions)
 	{
-		if (!B || !B->hidden || !dStates || !dRewards || !dFallen) return MI_ERR_INVALID_STATE;
+		if (!B || !B->policy.hidden || !dStates || !dRewards || !dFallen) return MI_ERR_INVALID_STATE;
 		return launchUpdate(*B, nullptr, dActions, dStates, dRewards, dFallen);
 	}
 
@@ -766,7 +676,7 @@ extern "C"
 	// terminal state, and the policy's next input is the reset state.  No host synchronisation beyond those of mi_step.
 	int rolloutPhysicsBatchDevice(uint32_t steps, int autoReset, float* dStates, float* dActions, float* dRewards, int32_t* dFallen)
 	{
-		if (!B || !B->hidden || !dRewards || !dFallen) return MI_ERR_INVALID_STATE;
+		if (!B || !B->policy.hidden || !dRewards || !dFallen) return MI_ERR_INVALID_STATE;
 		batch& b = *B;
 		const size_t n = b.n;
 		for (uint32_t t = 0; t < steps; ++t)
@@ -784,9 +694,9 @@ extern "C"
 	// count x 2Hv) receives tanh(z1), tanh(z2) of every row.  Touches no environment.
 	int inferPhysicsBatchValueDevice(uint32_t count, const float* dStates, float* dValues, float* dHidden)
 	{
-		if (!B || !B->valueHidden) return MI_ERR_INVALID_STATE;
+		if (!B || !B->critic.hidden) return MI_ERR_INVALID_STATE;
 		if (!count || !dStates || !dValues) return MI_ERR_INVALID_ARGUMENT;
-		return launchValue(*B, count, dStates, dValues, dHidden);
+		return launchNetwork(*B, B->critic, false, count, dStates, dValues, dHidden);
 	}
 
 	// The exploration noise of updates firstUpdate .. firstUpdate + numUpdates - 1 of every environment into dEps [numUpdates][n][27], on
@@ -811,19 +721,19 @@ extern "C"
 	// update's reset.  Needs a policy, a critic and a std.
 	int collectPhysicsBatchDevice(uint32_t steps, int clip, float* dObs, float* dActions, float* dEps, float* dLogProbs, float* dValues, float* dRewards, int32_t* dDones, float* dLastValues)
 	{
-		if (!B || !B->hidden || !B->valueHidden || !B->stdSet) return MI_ERR_INVALID_STATE;
+		if (!B || !B->policy.hidden || !B->critic.hidden || !B->stdSet) return MI_ERR_INVALID_STATE;
 		if (!steps || !dObs || !dActions || !dLogProbs || !dValues || !dRewards || !dDones || !dLastValues) return MI_ERR_INVALID_ARGUMENT;
 		batch& b = *B;
 		if (int e = uploadRanges(b)) return e;
 		const size_t n = b.n;
 		const uint64_t seed = locomotionSeed();
-		const dim3 grid((b.n + POLICY_TILE - 1) / POLICY_TILE), block = networkBlock(b.hidden > b.valueHidden ? b.hidden : b.valueHidden);
+		const dim3 grid((b.n + POLICY_TILE - 1) / POLICY_TILE), block = networkBlock(b.policy.hidden > b.critic.hidden ? b.policy.hidden : b.critic.hidden);
 		for (uint32_t t = 0; t < steps; ++t)
 		{
 			int32_t* fallen = dDones + n * t;
 			if (int e = refreshPods(b)) return e;
-			hipLaunchKernelGGL(k_loco_sample, grid, block, 0, b.stream, b.n, b.hidden, b.valueHidden, clip, seed, b.noiseCounter, (const float*)b.dStates, (const float*)b.dPolicy,
-				(const float*)b.dValueNet, (const float*)b.dScales, dObs + STATE_SIZE * n * t, dActions + ACTION_SIZE * n * t, dEps ? dEps + ACTION_SIZE * n * t : nullptr,
+			hipLaunchKernelGGL(k_loco_sample, grid, block, 0, b.stream, b.n, b.policy.hidden, b.critic.hidden, clip, seed, b.noiseCounter, (const float*)b.dStates, (const float*)b.policy.data,
+				(const float*)b.critic.data, (const float*)b.dScales, dObs + STATE_SIZE * n * t, dActions + ACTION_SIZE * n * t, dEps ? dEps + ACTION_SIZE * n * t : nullptr,
 				dLogProbs + n * t, dValues + n * t, b.dSmoothed, (const uint32_t*)b.dSlots, (uint8_t*)b.pods[0], (uint8_t*)b.pods[1]);
 			if (!ok(hipGetLastError(), "sample kernel")) return MI_ERR_HIP;
 			++b.noiseCounter;
@@ -831,7 +741,7 @@ extern "C"
 			if (int e = launchReset(b, nullptr, fallen, b.n)) return e;
 			if (int e = launchGather(b, nullptr, fallen, b.n, b.dStates, b.dRewards, b.dFallen)) return e;
 		}
-		return launchValue(b, b.n, b.dStates, dLastValues, nullptr);
+		return launchNetwork(b, b.critic, false, b.n, b.dStates, dLastValues, nullptr);
 	}
 
 	// Generalised advantage estimation over [steps][n] device buffers (k_loco_gae), on the batch's stream.  Episodes end by falling only:
@@ -852,12 +762,12 @@ extern "C"
 	// builds a new batch from the host copies.  Needs a policy, a critic and a std.
 	int beginPhysicsBatchTraining(float lr, float beta1, float beta2, float adamEps)
 	{
-		if (!B || !B->hidden || !B->valueHidden || !B->stdSet) return MI_ERR_INVALID_STATE;
+		if (!B || !B->policy.hidden || !B->critic.hidden || !B->stdSet) return MI_ERR_INVALID_STATE;
 		if (!(lr >= 0.f) || !(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f) || !(adamEps >= 0.f)) return MI_ERR_INVALID_ARGUMENT;
 		batch& b = *B;
 		if (int e = endTraining(b)) return e;
-		const size_t total = ppoTotal(b.hidden, b.valueHidden);
-		if (!ok(hipMalloc(&b.dMoments, sizeof(float) * 2 * total), "alloc")) return MI_ERR_HIP;
+		const size_t total = ppoTotal(b.policy.hidden, b.critic.hidden);
+		if (int e = reallocate(&b.dMoments, 2 * total)) return e;
 		if (!ok(hipMemsetAsync(b.dMoments, 0, sizeof(float) * 2 * total, b.stream), "moments")) return MI_ERR_HIP;
 		b.lr = lr; b.beta1 = beta1; b.beta2 = beta2; b.adamEps = adamEps; b.adamStep = 0; b.training = true;
 		return 0;
@@ -882,7 +792,7 @@ extern "C"
 		const ppo_scratch scratch = scratchOf(b);
 		const ppo_rows data = { rows, dObs, dActions, dOldLogProbs, dAdvantages, dReturns };
 		const ppo_loss loss = { clipRange, vfCoef, entCoef, normalizeAdvantage };
-		const size_t total = ppoTotal(b.hidden, b.valueHidden);
+		const size_t total = ppoTotal(b.policy.hidden, b.critic.hidden);
 		for (uint32_t epoch = 0; epoch < epochs; ++epoch)
 			for (uint32_t start = 0; start < rows; start += batchSize)
 			{
@@ -903,7 +813,7 @@ extern "C"
 	int gradientsPhysicsBatchPPODevice(uint32_t rows, const float* dObs, const float* dActions, const float* dOldLogProbs, const float* dAdvantages, const float* dReturns,
 		uint32_t count, const uint32_t* dIndices, float clipRange, float vfCoef, float entCoef, int normalizeAdvantage, float* dGradient, float* dRatios, float* dStats)
 	{
-		if (!B || !B->hidden || !B->valueHidden || !B->stdSet) return MI_ERR_INVALID_STATE;
+		if (!B || !B->policy.hidden || !B->critic.hidden || !B->stdSet) return MI_ERR_INVALID_STATE;
 		if (!rows || !count || (!dIndices && count > rows) || !dObs || !dActions || !dOldLogProbs || !dAdvantages || !dReturns || !dGradient) return MI_ERR_INVALID_ARGUMENT;
 		batch& b = *B;
 		if (int e = ensureScratch(b, count)) return e;
@@ -915,15 +825,15 @@ extern "C"
 	// The parameters as they are on the device, after everything enqueued so far, in the layouts the setters take (host pointers).
 	int readPhysicsBatchPolicy(float* w1, float* b1, float* w2, float* b2, float* w3, float* b3)
 	{
-		if (!B || !B->hidden) return MI_ERR_INVALID_STATE;
+		if (!B || !B->policy.hidden) return MI_ERR_INVALID_STATE;
 		if (!w1 || !b1 || !w2 || !b2 || !w3 || !b3) return MI_ERR_INVALID_ARGUMENT;
-		return readNetwork(*B, B->dPolicy, B->hidden, ACTION_SIZE, w1, b1, w2, b2, w3, b3);
+		return readNetwork(*B, B->policy, w1, b1, w2, b2, w3, b3);
 	}
 	int readPhysicsBatchValueNetwork(float* w1, float* b1, float* w2, float* b2, float* w3, float* b3)
 	{
-		if (!B || !B->valueHidden) return MI_ERR_INVALID_STATE;
+		if (!B || !B->critic.hidden) return MI_ERR_INVALID_STATE;
 		if (!w1 || !b1 || !w2 || !b2 || !w3 || !b3) return MI_ERR_INVALID_ARGUMENT;
-		return readNetwork(*B, B->dValueNet, B->valueHidden, 1, w1, b1, w2, b2, w3, b3);
+		return readNetwork(*B, B->critic, w1, b1, w2, b2, w3, b3);
 	}
 	// std [27] (may be NULL) and logStd [27].
 	int readPhysicsBatchLogStd(float* std, float* logStd)
@@ -939,6 +849,5 @@ extern "C"
 }
 
 // A new network or std from the host replaces the master copy: an open training session ends with it.
-int locomotionBatchPolicyChanged() { if (!B) return 0; if (int e = endTraining(*B)) return e; return uploadPolicy(*B); }
-int locomotionBatchValueChanged() { if (!B) return 0; if (int e = endTraining(*B)) return e; return uploadValueNetwork(*B); }
+int locomotionBatchNetworkChanged(uint32_t outputs) { if (!B) return 0; if (int e = endTraining(*B)) return e; return uploadNetwork(*B, outputs == 1 ? B->critic : B->policy); }
 int locomotionBatchStdChanged() { if (!B) return 0; if (int e = endTraining(*B)) return e; return uploadActionStd(*B); }

@@ -10,8 +10,9 @@
 // fixed) so that runs are reproducible.  resetPhysics also fills outState (the reference leaves it untouched).
 // The controller half (learned_locomotion::update, :44-68) is here too: setPhysicsPolicy keeps a network (locomotion_policy.h),
 // inferPhysicsPolicy runs it on one state, updatePhysicsPolicy drives the single environment from it.
-// For training (learning/learn_locomotion.py) the file also keeps a critic and the Gaussian's scales (setPhysicsValueNetwork,
-// inferPhysicsValue, setPhysicsActionStd) and states the exploration noise on the host (samplePhysicsNoise); the batch collects with them.
+// For training (learning/learn_locomotion.py) the file keeps a critic in the same record (setPhysicsValueNetwork, inferPhysicsValue)
+// and the Gaussian's scales (setPhysicsActionStd), and states the exploration noise on the host (samplePhysicsNoise); the batch
+// collects with them.
 // Everything physical happens in libmi_physics.so on the GPU; this file is host logic only, like the reference's.
 //
 // Build: directx_renderer_kurth_amd.build_locomotion() compiles this file with g++ and locomotion_batch.hip (the batched environments)
@@ -76,12 +77,39 @@ namespace
 	environment* env = nullptr;
 	uint64_t seed = 0x9E3779B97F4A7C15ull;
 
-	// The policy of setPhysicsPolicy: one block of policyFloats(hidden) floats, the six arrays back to back.
-	uint32_t policyHidden = 0;
-	std::vector<float> policyData;
-	// The critic of setPhysicsValueNetwork, in the same way (w3 is [1][Hv], b3 one float), and the scales of setPhysicsActionStd.
-	uint32_t valueHidden = 0;
-	std::vector<float> valueData;
+	// A network as a setter left it: one block of networkFloats(hidden, outputs) floats, the six arrays back to back.
+	struct stored_network
+	{
+		uint32_t outputs, hidden = 0; // hidden 0: none set
+		std::vector<float> data;
+
+		bool view(locomotion_policy* out) const { if (hidden) *out = networkOf(data.data(), hidden, outputs); return hidden != 0; }
+
+		// A bad argument returns MI_ERR_INVALID_ARGUMENT and leaves the previous network active.
+		int set(uint32_t h, const float* w1, const float* b1, const float* w2, const float* b2, const float* w3, const float* b3)
+		{
+			if (!h || h > POLICY_MAX_HIDDEN || !w1 || !b1 || !w2 || !b2 || !w3 || !b3) return MI_ERR_INVALID_ARGUMENT;
+			std::vector<float> packed(networkFloats(h, outputs));
+			copyNetwork({ h, outputs, { w1, w2, w3 }, { b1, b2, b3 } }, networkOf(packed.data(), h, outputs), NETWORK_PLAIN);
+			data.swap(packed);
+			hidden = h;
+			return locomotionBatchNetworkChanged(outputs);
+		}
+
+		// The network on one state, on the host.  ab (2 x hidden floats, may be NULL) receives tanh(z1), tanh(z2).
+		int infer(const float* state, float* out, float* ab) const
+		{
+			locomotion_policy p;
+			if (!view(&p)) return MI_ERR_INVALID_STATE;
+			if (!state || !out) return MI_ERR_INVALID_ARGUMENT;
+			float scratch[2 * POLICY_MAX_HIDDEN];
+			inferNetwork(p, state, scratch, scratch + p.hidden, out);
+			if (ab) memcpy(ab, scratch, sizeof(float) * 2 * p.hidden);
+			return MI_OK;
+		}
+	};
+	stored_network policy = { ACTION_SIZE }, critic = { 1 }; // setPhysicsPolicy's and setPhysicsValueNetwork's
+	// The scales of setPhysicsActionStd.
 	bool actionStdSet = false;
 	float actionStd[2 * ACTION_SIZE] = {}; // std[27], logStd[27]
 
@@ -111,29 +139,7 @@ namespace
 
 uint64_t locomotionSeed() { return seed; }
 
-bool locomotionPolicy(locomotion_policy* out)
-{
-	if (!policyHidden) return false;
-	const uint32_t h = policyHidden;
-	const float* p = policyData.data();
-	out->hidden = h;
-	out->w1 = p; p += (size_t)h * STATE_SIZE; out->b1 = p; p += h;
-	out->w2 = p; p += (size_t)h * h; out->b2 = p; p += h;
-	out->w3 = p; p += (size_t)ACTION_SIZE * h; out->b3 = p;
-	return true;
-}
-
-bool locomotionValueNetwork(locomotion_policy* out)
-{
-	if (!valueHidden) return false;
-	const uint32_t h = valueHidden;
-	const float* p = valueData.data();
-	out->hidden = h;
-	out->w1 = p; p += (size_t)h * STATE_SIZE; out->b1 = p; p += h;
-	out->w2 = p; p += (size_t)h * h; out->b2 = p; p += h;
-	out->w3 = p; p += h; out->b3 = p;
-	return true;
-}
+bool locomotionNetwork(uint32_t outputs, locomotion_policy* out) { return (outputs == 1 ? critic : policy).view(out); }
 
 const float* locomotionActionStd() { return actionStdSet ? actionStd : nullptr; }
 
@@ -184,26 +190,13 @@ extern "C"
 	// be called before or after either reset.  A bad argument returns MI_ERR_INVALID_ARGUMENT and leaves the previous policy active.
 	int setPhysicsPolicy(uint32_t hidden, const float* w1, const float* b1, const float* w2, const float* b2, const float* w3, const float* b3)
 	{
-		if (!hidden || hidden > POLICY_MAX_HIDDEN || !w1 || !b1 || !w2 || !b2 || !w3 || !b3) return MI_ERR_INVALID_ARGUMENT;
-		std::vector<float> data(policyFloats(hidden));
-		float* p = data.data();
-		auto put = [&](const float* from, size_t count) { memcpy(p, from, sizeof(float) * count); p += count; };
-		put(w1, (size_t)hidden * STATE_SIZE); put(b1, hidden); put(w2, (size_t)hidden * hidden); put(b2, hidden); put(w3, (size_t)ACTION_SIZE * hidden); put(b3, ACTION_SIZE);
-		policyData.swap(data);
-		policyHidden = hidden;
-		return locomotionBatchPolicyChanged();
+		return policy.set(hidden, w1, b1, w2, b2, w3, b3);
 	}
 
 	// The network on one state, on the host: needs no world and no GPU.  hidden (2 x H floats, may be NULL) receives tanh(z1), tanh(z2).
 	int inferPhysicsPolicy(const float* state, float* action, float* hidden)
 	{
-		locomotion_policy p;
-		if (!locomotionPolicy(&p)) return MI_ERR_INVALID_STATE;
-		if (!state || !action) return MI_ERR_INVALID_ARGUMENT;
-		float ab[2 * POLICY_MAX_HIDDEN];
-		inferPolicy(p, state, ab, ab + p.hidden, action);
-		if (hidden) memcpy(hidden, ab, sizeof(float) * 2 * p.hidden);
-		return MI_OK;
+		return policy.infer(state, action, hidden);
 	}
 
 	// learned_locomotion::update (:44-68) on the single environment: its state as it is -> network -> applyAction, then the rest of
@@ -211,11 +204,11 @@ extern "C"
 	int updatePhysicsPolicy(float* outState, float* outReward)
 	{
 		locomotion_policy p;
-		if (!locomotionPolicy(&p)) return -MI_ERR_INVALID_STATE;
+		if (!policy.view(&p)) return -MI_ERR_INVALID_STATE;
 		if (!env || !env->world) { if (outReward) *outReward = 0.f; return 1; }
 		float state[STATE_SIZE], action[ACTION_SIZE], ab[2 * POLICY_MAX_HIDDEN];
 		getState(env->view, env->train, env->lastSmoothedAction, state);
-		inferPolicy(p, state, ab, ab + p.hidden, action);
+		inferNetwork(p, state, ab, ab + p.hidden, action);
 		env->applyAction(action);
 		return stepAfterAction(outState, outReward);
 	}
@@ -224,26 +217,13 @@ extern "C"
 	// Independent of the policy's H; kept and uploaded like the policy.  A bad argument leaves the previous one active.
 	int setPhysicsValueNetwork(uint32_t hidden, const float* w1, const float* b1, const float* w2, const float* b2, const float* w3, const float* b3)
 	{
-		if (!hidden || hidden > POLICY_MAX_HIDDEN || !w1 || !b1 || !w2 || !b2 || !w3 || !b3) return MI_ERR_INVALID_ARGUMENT;
-		std::vector<float> data(valueFloats(hidden));
-		float* p = data.data();
-		auto put = [&](const float* from, size_t count) { memcpy(p, from, sizeof(float) * count); p += count; };
-		put(w1, (size_t)hidden * STATE_SIZE); put(b1, hidden); put(w2, (size_t)hidden * hidden); put(b2, hidden); put(w3, hidden); put(b3, 1);
-		valueData.swap(data);
-		valueHidden = hidden;
-		return locomotionBatchValueChanged();
+		return critic.set(hidden, w1, b1, w2, b2, w3, b3);
 	}
 
 	// The critic on one state, on the host.  hidden (2 x Hv floats, may be NULL) receives tanh(z1), tanh(z2).
 	int inferPhysicsValue(const float* state, float* outValue, float* hidden)
 	{
-		locomotion_policy p;
-		if (!locomotionValueNetwork(&p)) return MI_ERR_INVALID_STATE;
-		if (!state || !outValue) return MI_ERR_INVALID_ARGUMENT;
-		float ab[2 * POLICY_MAX_HIDDEN];
-		inferValue(p, state, ab, ab + p.hidden, outValue);
-		if (hidden) memcpy(hidden, ab, sizeof(float) * 2 * p.hidden);
-		return MI_OK;
+		return critic.infer(state, outValue, hidden);
 	}
 
 	// The scale of the Gaussian around the policy's output, per action, and its logarithm: both given, so that the library evaluates

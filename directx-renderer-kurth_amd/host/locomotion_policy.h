@@ -1,20 +1,66 @@
-// locomotion_policy.h — the learned controller's network (learned_locomotion.cpp:11-27, 44-68): a 66 -> H -> H -> 27 MLP, tanh after
-// the two hidden layers, none after the last.  A policy is six fp32 arrays in the layout of the reference's generated network.h,
-// which is torch's named_parameters order (learning/convert_model_to_c++.py:8-46):
-//     W1[H][66], b1[H], W2[H][H], b2[H], W3[27][H], b3[27]      row-major [out][in], one hidden size for both layers
+// locomotion_policy.h — the learned controller's networks (learned_locomotion.cpp:11-27, 44-68): the policy, a 66 -> H -> H -> 27 MLP,
+// tanh after the two hidden layers, none after the last, and the critic of training (learning/learn_locomotion.py:71-107,
+// vf=[128,128]), 66 -> Hv -> Hv -> 1 of the same form.  A network is six fp32 arrays in the layout of the reference's generated
+// network.h, which is torch's named_parameters order (learning/convert_model_to_c++.py:8-46):
+//     W1[H][66], b1[H], W2[H][H], b2[H], W3[outputs][H], b3[outputs]      row-major [out][in], one hidden size for both layers
 // The reference fixes HIDDEN_LAYER_SIZE at 128; any 1 <= H <= POLICY_MAX_HIDDEN is accepted.  Shared like locomotion_shared.h: the
-// single environment (g++) runs inferPolicy on the host, the batched one (hipcc) restates the same sums in k_loco_policy.
-// Also here, shared the same way: the critic of training, the exploration noise and the log-probability of a sampled action.
+// single environment (g++) runs inferNetwork on the host; the batched one (hipcc) keeps the same six arrays with every weight matrix
+// transposed to [in][out] and runs the same sums in locomotion_layers.h.  walkNetwork is the one statement of how the six arrays lie in
+// a block; sizes, pointer views, packing and both transpositions come from it.
+// Also here, shared the same way: the exploration noise and the log-probability of a sampled action.
 #pragma once
 #include "locomotion_shared.h"
 
-struct locomotion_policy { uint32_t hidden; const float* w1; const float* b1; const float* w2; const float* b2; const float* w3; const float* b3; };
+// Layer l of a network: weights w[l], bias b[l].  outputs is 27 (the policy) or 1 (the critic).
+template <class T> struct network_view { uint32_t hidden, outputs; T* w[3]; T* b[3]; };
+typedef network_view<const float> locomotion_policy;
 
 namespace
 {
 	enum { POLICY_MAX_HIDDEN = 256 };
 
-	LOCO_HD size_t policyFloats(uint32_t h) { return (size_t)h * STATE_SIZE + h + (size_t)h * h + h + (size_t)ACTION_SIZE * h + ACTION_SIZE; }
+	// The layout: layer l is inputs x units weights (in either orientation), then units biases; the three layers lie back to back.
+	// each(l, inputs, units, weightsAt, biasAt), the two offsets in floats from the start.  Returns the floats of the whole network.
+	template <class F> LOCO_HD size_t walkNetwork(uint32_t hidden, uint32_t outputs, F each)
+	{
+		size_t at = 0;
+		for (int l = 0; l < 3; ++l)
+		{
+			const uint32_t inputs = l ? hidden : STATE_SIZE, units = l < 2 ? hidden : outputs;
+			each(l, inputs, units, at, at + (size_t)inputs * units);
+			at += (size_t)inputs * units + units;
+		}
+		return at;
+	}
+
+	LOCO_HD size_t networkFloats(uint32_t hidden, uint32_t outputs) { return walkNetwork(hidden, outputs, [](int, uint32_t, uint32_t, size_t, size_t) {}); }
+	LOCO_HD size_t policyFloats(uint32_t h) { return networkFloats(h, ACTION_SIZE); }
+	LOCO_HD size_t valueFloats(uint32_t h) { return networkFloats(h, 1); }
+
+	// The six arrays of a network that lies in one block at p.
+	template <class T> LOCO_HD network_view<T> networkOf(T* p, uint32_t hidden, uint32_t outputs)
+	{
+		network_view<T> n = { hidden, outputs, {}, {} };
+		walkNetwork(hidden, outputs, [&](int l, uint32_t, uint32_t, size_t weightsAt, size_t biasAt) { n.w[l] = p + weightsAt; n.b[l] = p + biasAt; });
+		return n;
+	}
+
+	// Copies a network array by array.  NETWORK_PLAIN: as it is (packing the setters' six pointers into a block).  NETWORK_TO_DEVICE:
+	// `from` is [out][in] and `to` becomes [in][out], the upload.  NETWORK_TO_HOST: the way back, for readPhysicsBatch*.
+	enum network_copy { NETWORK_PLAIN, NETWORK_TO_DEVICE, NETWORK_TO_HOST };
+	inline void copyNetwork(const locomotion_policy& from, const network_view<float>& to, network_copy how)
+	{
+		walkNetwork(from.hidden, from.outputs, [&](int l, uint32_t inputs, uint32_t units, size_t, size_t)
+		{
+			if (how == NETWORK_PLAIN) memcpy(to.w[l], from.w[l], sizeof(float) * inputs * units);
+			else for (uint32_t x = 0; x < inputs; ++x) for (uint32_t y = 0; y < units; ++y)
+			{
+				const size_t host = (size_t)y * inputs + x, device = (size_t)x * units + y;
+				if (how == NETWORK_TO_DEVICE) to.w[l][device] = from.w[l][host]; else to.w[l][host] = from.w[l][device];
+			}
+			memcpy(to.b[l], from.b[l], sizeof(float) * units);
+		});
+	}
 
 	// applyLayer (:11-26): per output the products are added in ascending input order, each product rounded before it is added (both
 	// compilers run with -ffp-contract=off), then the bias, then tanh.
@@ -30,22 +76,13 @@ namespace
 		}
 	}
 
-	// learned_locomotion::update (:52-64) up to applyAction: state -> a -> b -> action; a and b hold `hidden` floats each.
-	LOCO_HD void inferPolicy(const locomotion_policy& p, const float* state, float* a, float* b, float* action)
+	// learned_locomotion::update (:52-64) up to applyAction, for either network in the [out][in] layout: state -> a -> b -> out; a and b
+	// hold `hidden` floats each, out `outputs`.
+	LOCO_HD void inferNetwork(const locomotion_policy& n, const float* state, float* a, float* b, float* out)
 	{
-		applyLayer(p.w1, p.b1, STATE_SIZE, p.hidden, state, a, true);
-		applyLayer(p.w2, p.b2, p.hidden, p.hidden, a, b, true);
-		applyLayer(p.w3, p.b3, p.hidden, ACTION_SIZE, b, action, false);
-	}
-
-	// The critic of training (learning/learn_locomotion.py:71-107, vf=[128,128]): 66 -> Hv -> Hv -> 1, tanh after the two hidden layers,
-	// carried in a locomotion_policy whose w3 is [1][Hv] and whose b3 is one float.
-	LOCO_HD size_t valueFloats(uint32_t h) { return (size_t)h * STATE_SIZE + h + (size_t)h * h + h + h + 1; }
-	LOCO_HD void inferValue(const locomotion_policy& p, const float* state, float* a, float* b, float* value)
-	{
-		applyLayer(p.w1, p.b1, STATE_SIZE, p.hidden, state, a, true);
-		applyLayer(p.w2, p.b2, p.hidden, p.hidden, a, b, true);
-		applyLayer(p.w3, p.b3, p.hidden, 1, b, value, false);
+		applyLayer(n.w[0], n.b[0], STATE_SIZE, n.hidden, state, a, true);
+		applyLayer(n.w[1], n.b[1], n.hidden, n.hidden, a, b, true);
+		applyLayer(n.w[2], n.b[2], n.hidden, n.outputs, b, out, false);
 	}
 
 	// The exploration noise of the sampled actions: a stateless function of (seed, environment, update counter, action index), so it
@@ -87,13 +124,11 @@ namespace
 	}
 }
 
-// The policy of setPhysicsPolicy (locomotion_env.cpp), for the batched environments: false while none is set.
-__attribute__((visibility("hidden"))) bool locomotionPolicy(locomotion_policy* out);
-// Uploads the current policy to the batch, if there is one (locomotion_batch.hip); called by setPhysicsPolicy.
-__attribute__((visibility("hidden"))) int locomotionBatchPolicyChanged();
-// The critic of setPhysicsValueNetwork and the scales of setPhysicsActionStd (std[27], then logStd[27]): false / null while none is set.
-__attribute__((visibility("hidden"))) bool locomotionValueNetwork(locomotion_policy* out);
+// The network of setPhysicsPolicy (outputs = 27) or setPhysicsValueNetwork (outputs = 1) as locomotion_env.cpp keeps it, for the
+// batched environments: false while none is set.
+__attribute__((visibility("hidden"))) bool locomotionNetwork(uint32_t outputs, locomotion_policy* out);
+// The scales of setPhysicsActionStd (std[27], then logStd[27]): null while none is set.
 __attribute__((visibility("hidden"))) const float* locomotionActionStd();
-// Upload them to the batch, if there is one; called by the two setters.
-__attribute__((visibility("hidden"))) int locomotionBatchValueChanged();
+// Upload them to the batch, if there is one (locomotion_batch.hip); called by the three setters.
+__attribute__((visibility("hidden"))) int locomotionBatchNetworkChanged(uint32_t outputs);
 __attribute__((visibility("hidden"))) int locomotionBatchStdChanged();

@@ -12,7 +12,7 @@
 
 enum { PPO_MAX_GROUPS = 128, PPO_STATS = 5, PPO_GROUP_STATS = 4, PPO_BLOCK = 256 };
 
-// The master copy: dPolicy, dValueNet and dScales (std [27], logStd [27], ...) of the batch.
+// The master copy: the two device networks and dScales (std [27], logStd [27], ...) of the batch.
 struct ppo_parameters { float* policy; float* valueNet; float* scales; uint32_t hidden, valueHidden; };
 // rows x {66, 27, 1, 1, 1} device buffers, as collect and gae leave them.
 struct ppo_rows { uint32_t rows; const float* obs; const float* actions; const float* oldLogProbs; const float* advantages; const float* returns; };

@@ -2,14 +2,14 @@
 // minibatch, all float32, no atomics, no host synchronisation.
 //
 //   k_loco_ppo_backward   a group (workgroup) takes tiles of POLICY_TILE minibatch rows: gathers them by index, runs the actor and the
-//                         critic forward with policyLayer (the sums collect ran), forms ppo_loss's per-row terms, backpropagates, and
+//                         critic forward with forwardActorCritic (what collect ran), forms ppo_loss's per-row terms, backpropagates, and
 //                         stores the tile's weight gradients to its own row of a slab [groups][parameters].  A group that takes more than
 //                         one tile (more than PPO_MAX_GROUPS tiles in the minibatch) adds them into its row in tile order.  Every group
 //                         recomputes the minibatch's advantage mean and std itself, in one fixed order.
 //   k_loco_ppo_reduce     one lane per parameter adds the slab's rows in ascending group order (+ the entropy term of logStd), and every
 //                         block stores the sum of the squares of its PPO_BLOCK gradients.
 //   k_loco_ppo_adam       every block adds those sums in one fixed order: the global norm; then clip_grad_norm_'s scale and
-//                         torch.optim.Adam's step on the master copy (dPolicy, dValueNet, dScales), and std = exp(logStd) beside it.
+//                         torch.optim.Adam's step on the master copy (the two networks and dScales), and std = exp(logStd) beside it.
 //
 // Every sum has one order that depends only on the shapes, so a step is bit-reproducible.  The tile's four rows are added as
 // fma(r3, fma(r2, fma(r1, r0))), the slab's rows one by one.
@@ -67,17 +67,17 @@ namespace
 	// The gradients of the two hidden layers of one network for the tile, into the group's slab row `g` (the network's part of it, in
 	// the network's own layout).  dz2 [hidden] is in LDS (`back`, written before a barrier) and, for this lane's unit, in `mine`; a1 is the
 	// first tanh vector, a1Mine this lane's entry of it.
-	__device__ void backHidden(const network& n, const float* base, uint32_t hidden, float* g, const float4* input, const float4* a1, float4 a1Mine, const float4* back, float4 mine, bool first)
+	__device__ void backHidden(const locomotion_policy& n, const float* base, uint32_t hidden, float* g, const float4* input, const float4* a1, float4 a1Mine, const float4* back, float4 mine, bool first)
 	{
 		const uint32_t t = threadIdx.x;
 		if (t >= hidden) return;
-		float* w2 = g + (n.w2 - base);
+		float* w2 = g + (n.w[1] - base);
 		for (uint32_t i = 0; i < hidden; ++i) put(w2 + (size_t)i * hidden + t, dot4(a1[i], mine), first);
-		put(g + (n.b2 - base) + t, sum4(mine), first);
-		const float4 dz1 = mul4(backLayer(n.w2 + (size_t)t * hidden, hidden, back), tanhSlope(a1Mine));
-		float* w1 = g + (n.w1 - base);
+		put(g + (n.b[1] - base) + t, sum4(mine), first);
+		const float4 dz1 = mul4(backLayer(n.w[1] + (size_t)t * hidden, hidden, back), tanhSlope(a1Mine));
+		float* w1 = g + (n.w[0] - base);
 		for (uint32_t x = 0; x < STATE_SIZE; ++x) put(w1 + (size_t)x * hidden + t, dot4(input[x], dz1), first);
-		put(g + (n.b1 - base) + t, sum4(dz1), first);
+		put(g + (n.b[0] - base) + t, sum4(dz1), first);
 	}
 
 	__global__ void __launch_bounds__(POLICY_MAX_HIDDEN) k_loco_ppo_backward(uint32_t count, uint32_t rows, const uint32_t* __restrict__ order,
@@ -91,7 +91,7 @@ namespace
 		__shared__ float invStd[ACTION_SIZE], sums[PPO_BLOCK + 1], rowStats[POLICY_TILE][3];
 		__shared__ uint32_t rowOf[POLICY_TILE];
 		const uint32_t t = threadIdx.x;
-		const network p = networkOf(policy, hidden, ACTION_SIZE), v = networkOf(valueNet, valueHidden, 1);
+		const locomotion_policy p = networkOf(policy, hidden, ACTION_SIZE), v = networkOf(valueNet, valueHidden, 1);
 		const float* logStd = scales + ACTION_SIZE;
 		auto rowAt = [&](uint32_t i) { const uint32_t r = order ? order[i] : i; return r < rows ? r : rows - 1; }; // a bad index reads the last row, never past it
 
@@ -117,31 +117,14 @@ namespace
 		{
 			const uint32_t firstRow = tile * POLICY_TILE;
 			__syncthreads(); // the previous tile's LDS is done with
-			for (uint32_t i = t; i < POLICY_TILE * STATE_SIZE; i += blockDim.x)
-			{
-				const uint32_t r = i / STATE_SIZE, x = i % STATE_SIZE;
-				((float*)input)[POLICY_TILE * x + r] = firstRow + r < count ? obs[(size_t)STATE_SIZE * rowAt(firstRow + r) + x] : 0.f;
-			}
+			loadTile(input, obs, nullptr, firstRow, count, rowAt);
 			if (t < POLICY_TILE) rowOf[t] = firstRow + t < count ? rowAt(firstRow + t) : ~0u;
 			__syncthreads();
-			// forward, as k_loco_sample runs it
-			const float4 a = policyLayer(p.w1, p.b1, STATE_SIZE, hidden, input, t, true);
-			const float4 va = policyLayer(v.w1, v.b1, STATE_SIZE, valueHidden, input, t, true);
-			if (t < hidden) hiddenA[t] = a;
-			if (t < valueHidden) valueA[t] = va;
-			__syncthreads();
-			const float4 b = policyLayer(p.w2, p.b2, hidden, hidden, hiddenA, t, true);
-			const float4 vb = policyLayer(v.w2, v.b2, valueHidden, valueHidden, valueA, t, true);
-			if (t < hidden) hiddenB[t] = b;
-			if (t < valueHidden) valueB[t] = vb;
-			__syncthreads();
-			const uint32_t valueLane = blockDim.x > 64 ? 64 : 32;
-			const float4 out = policyLayer(p.w3, p.b3, hidden, ACTION_SIZE, hiddenB, t, false);
-			const float4 value = policyLayer(v.w3, v.b3, valueHidden, 1, valueB, t - valueLane, false); // t < valueLane wraps: no unit
-			if (t == valueLane) valueOut = value;
+			const forward_pair f = forwardActorCritic(p, v, input, hiddenA, hiddenB, valueA, valueB);
+			if (t == criticLane()) valueOut = f.value;
 			if (t < ACTION_SIZE) // z = (action - mean) / std and noiseLogProb's term per action
 			{
-				const float mu[POLICY_TILE] = { out.x, out.y, out.z, out.w };
+				const float mu[POLICY_TILE] = { f.out.x, f.out.y, f.out.z, f.out.w };
 				float z[POLICY_TILE], term[POLICY_TILE];
 				#pragma unroll
 				for (uint32_t r = 0; r < POLICY_TILE; ++r)
@@ -188,20 +171,20 @@ namespace
 			}
 			__syncthreads();
 			// the last layers: the weights' gradients, and dz2 = (W3^T d) * (1 - b^2) into LDS
-			for (uint32_t e = t; e < hidden * ACTION_SIZE; e += blockDim.x) put(gPolicy + (p.w3 - policy) + e, dot4(hiddenB[e / ACTION_SIZE], dMean[e % ACTION_SIZE]), first);
-			if (t < ACTION_SIZE) put(gPolicy + (p.b3 - policy) + t, sum4(dMean[t]), first);
+			for (uint32_t e = t; e < hidden * ACTION_SIZE; e += blockDim.x) put(gPolicy + (p.w[2] - policy) + e, dot4(hiddenB[e / ACTION_SIZE], dMean[e % ACTION_SIZE]), first);
+			if (t < ACTION_SIZE) put(gPolicy + (p.b[2] - policy) + t, sum4(dMean[t]), first);
 			float4 dz2 = make_float4(0.f, 0.f, 0.f, 0.f), dvz2 = dz2;
-			if (t < hidden) { dz2 = mul4(backLayer(p.w3 + (size_t)t * ACTION_SIZE, ACTION_SIZE, dMean), tanhSlope(b)); back[t] = dz2; }
+			if (t < hidden) { dz2 = mul4(backLayer(p.w[2] + (size_t)t * ACTION_SIZE, ACTION_SIZE, dMean), tanhSlope(f.b)); back[t] = dz2; }
 			if (t < valueHidden)
 			{
-				put(gValue + (v.w3 - valueNet) + t, dot4(vb, dv), first);
-				const float w = v.w3[t];
-				dvz2 = mul4(make_float4(w * dv.x, w * dv.y, w * dv.z, w * dv.w), tanhSlope(vb)); valueBack[t] = dvz2;
+				put(gValue + (v.w[2] - valueNet) + t, dot4(f.vb, dv), first);
+				const float w = v.w[2][t];
+				dvz2 = mul4(make_float4(w * dv.x, w * dv.y, w * dv.z, w * dv.w), tanhSlope(f.vb)); valueBack[t] = dvz2;
 			}
-			if (t == 0) put(gValue + (v.b3 - valueNet), sum4(dv), first);
+			if (t == 0) put(gValue + (v.b[2] - valueNet), sum4(dv), first);
 			__syncthreads();
-			backHidden(p, policy, hidden, gPolicy, input, hiddenA, a, back, dz2, first);
-			backHidden(v, valueNet, valueHidden, gValue, input, valueA, va, valueBack, dvz2, first);
+			backHidden(p, policy, hidden, gPolicy, input, hiddenA, f.a, back, dz2, first);
+			backHidden(v, valueNet, valueHidden, gValue, input, valueA, f.va, valueBack, dvz2, first);
 		}
 		if (t < POLICY_TILE) { rowStats[t][0] = surrogate; rowStats[t][1] = valueError; rowStats[t][2] = clipped; }
 		__syncthreads();

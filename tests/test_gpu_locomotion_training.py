@@ -1,4 +1,4 @@
-"""Collecting PPO training data on the device (host/locomotion_batch.hip: k_loco_sample, k_loco_value, k_loco_noise, k_loco_gae) and
+"""Collecting PPO training data on the device (host/locomotion_batch.hip: k_loco_sample, k_loco_policy<1, false>, k_loco_noise, k_loco_gae) and
 the trainer over it (training.py).  Everything the device adds is pinned to something that existed before or to a restatement
 (training_util.py): the critic to applyLayer's sums like the policy; the noise to the integer hash bit for bit and to float64 Box-Muller
 at a measured tolerance; GAE to its float32 order bit for bit; collect() with std = 0 to rollout() bit for bit; collect() with noise to
