@@ -55,8 +55,21 @@ class RayHit(C.Structure):
 
 
 RAY_HIT_DTYPE = np.dtype([("t", "<f4"), ("collider", "<u4"), ("body", "<u4"), ("hit", "<u4"), ("point", "<f4", 3), ("reserved", "<f4")])
-RAY_STATIC, RAY_BRUTE_FORCE = 1, 2
+RAY_STATIC, RAY_BRUTE_FORCE, RAY_TERRAIN = 1, 2, 4
 STATIC_BODY = 0xFFFFFFFF   # mi_ray_hit.body of a collider without a rigid body (MI_STATIC_BODY)
+TERRAIN_COLLIDER = 0xFFFFFFFE   # mi_ray_hit.collider of a hit on the heightmap terrain (MI_TERRAIN_COLLIDER)
+
+
+def heightmap_triangle_id(chunks_per_dim, chunk_x, chunk_z, cell_x, cell_z, which):
+    """The uint32 triangle id a terrain hit carries in mi_ray_hit.reserved (include/mi_physics.h)"""
+    return (((chunk_z * chunks_per_dim + chunk_x) * 16384 + cell_z * 128 + cell_x) * 2 + which) & 0xFFFFFFFF
+
+
+def heightmap_triangle(triangle, chunks_per_dim):
+    """(chunkX, chunkZ, cellX, cellZ, which) of a triangle id: which = 0 is the cell's triangle (A, B, C), 1 is (C, B, D)"""
+    triangle = int(triangle)
+    which, cell, chunk = triangle & 1, (triangle >> 1) & 16383, triangle >> 15
+    return chunk % chunks_per_dim, chunk // chunks_per_dim, cell & 127, cell >> 7, which
 
 
 class WorldDesc(C.Structure):
@@ -290,6 +303,7 @@ class World:
     # ---- heightmap terrain (heightmap_collider.h:127-152) ----
     def set_heightmap(self, chunks_per_dim, chunk_size, material, min_corner, amplitude_scale):
         m = Material(*material)
+        self._terrain_chunks_per_dim = int(chunks_per_dim)
         self._check(self.lib.mi_set_heightmap(self.w, C.c_uint32(chunks_per_dim), C.c_float(chunk_size), C.byref(m), _f(min_corner), C.c_float(amplitude_scale)))
 
     def heightmap_set_chunk(self, x, z, heights):
@@ -301,6 +315,14 @@ class World:
 
     def heightmap_height_at(self, x, z):
         return float(self.lib.mi_heightmap_height_at(self.w, C.c_float(x), C.c_float(z)))
+
+    def heightmap_triangle(self, triangle, chunks_per_dim=None):
+        """(chunkX, chunkZ, cellX, cellZ, which) of the triangle id of a terrain hit (raycast(..., terrain=True)).  A restored world
+        does not know chunks_per_dim: pass it."""
+        cpd = chunks_per_dim if chunks_per_dim is not None else getattr(self, "_terrain_chunks_per_dim", None)
+        if not cpd:
+            raise ValueError("heightmap_triangle: no heightmap was set on this World object (pass chunks_per_dim)")
+        return heightmap_triangle(triangle, cpd)
 
     # ---- cloth (cloth.h:5-60; stepped after the rigid bodies, physics.cpp:1354-1358) ----
     def add_cloth(self, width, height, grid_x, grid_y, total_mass, stiffness=0.5, damping=0.3, gravity_factor=1.0):
@@ -411,17 +433,19 @@ class World:
         self._check(code)
         return out
 
-    def raycast(self, rays, static=True, brute_force=False):
+    def raycast(self, rays, static=True, brute_force=False, terrain=False):
         """mi_raycast_batch: rays [n, 8] = origin, maxT, direction, enabled, each against every candidate collider of the world (with
         `static` also the colliders of entities without a rigid body); nothing is pushed.  brute_force: every ray against every
-        candidate, no tree (same answers).
+        candidate, no tree (same answers).  terrain: the heightmap's triangles are candidates too (RAY_TERRAIN; nothing changes without a
+        heightmap): such a hit has collider TERRAIN_COLLIDER, body STATIC_BODY and a triangle id (heightmap_triangle).
         numpy rays are copied to the device and the hits back: returns (t [n], collider [n], body [n], hit [n], point [n, 3]); body is
-        STATIC_BODY for a static collider, everything 0 for a miss.
+        STATIC_BODY for a static collider, everything 0 for a miss.  With terrain=True a sixth array follows: triangle [n] uint32, 0 where
+        the hit is not on the terrain.
         A torch tensor on the device (float32, contiguous) is used in place: returns one float32 tensor [n, 8] of mi_ray_hit records
-        (columns 1..3 hold the bits of collider, body, hit: view them with .view(torch.int32)), enqueued on the world's stream with no
-        synchronisation."""
+        (columns 1..3 hold the bits of collider, body, hit, column 7 those of the triangle id: view them with .view(torch.int32)),
+        enqueued on the world's stream with no synchronisation."""
         import torch
-        flags = (RAY_STATIC if static else 0) | (RAY_BRUTE_FORCE if brute_force else 0)
+        flags = (RAY_STATIC if static else 0) | (RAY_BRUTE_FORCE if brute_force else 0) | (RAY_TERRAIN if terrain else 0)
         if isinstance(rays, torch.Tensor):
             if not rays.is_cuda or rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous():
                 raise ValueError("raycast: a device tensor must be float32, contiguous and [n, 8]")
@@ -448,7 +472,8 @@ class World:
                 hits = d_out.cpu().numpy().view(RAY_HIT_DTYPE).reshape(n)
         else:
             self._check(self.lib.mi_raycast_batch(self.w, C.c_uint32(0), None, C.c_uint32(flags), None))
-        return hits["t"].copy(), hits["collider"].copy(), hits["body"].copy(), hits["hit"].copy(), hits["point"].copy()
+        out = (hits["t"].copy(), hits["collider"].copy(), hits["body"].copy(), hits["hit"].copy(), hits["point"].copy())
+        return out + (hits["reserved"].view(np.uint32).copy(),) if terrain else out
 
     def accumulators(self):
         """Force and torque accumulators of every body [n, 6]: the pushes the next step will apply and clear."""

@@ -355,7 +355,10 @@ int mi_raycast_batch(mi_world* world, uint32_t numRays, const float* dRays, uint
 	if (!dRays || !dOutHits) return MI_ERR_INVALID_ARGUMENT;
 	if (!W->interactTablesValid) W->buildInteractTables();
 	if (W->lastError) return W->lastError;
-	launch_raycast(*W, numRays, dRays, flags, dOutHits);
+	const bool terrain = (flags & MI_RAY_TERRAIN) != 0 && W->terrainChunksPerDim != 0;
+	if (terrain && (uint64_t)W->terrainChunksPerDim * W->terrainChunksPerDim > 131071u) return MI_ERR_INVALID_ARGUMENT; // the triangle id has 17 bits for the chunk
+	launch_raycast(*W, numRays, dRays, flags, dOutHits); // (no candidate collider: the records are zeroed)
+	if (terrain && !W->lastError) launch_raycast_terrain(*W, numRays, dRays, flags, dOutHits);
 	return W->lastError;
 }
 

@@ -208,6 +208,7 @@ int mi_set_heightmap(mi_world* world, uint32_t chunksPerDim, float chunkSize, co
 	memcpy(W->terrainMinCorner, minCorner, 12); W->terrainMaterial[0] = material->restitution; W->terrainMaterial[1] = material->friction; W->terrainMaterial[2] = material->density;
 	size_t chunks = (size_t)chunksPerDim * chunksPerDim;
 	W->hTerrainHeights.assign(chunks * 129 * 129, 0); W->hTerrainValid.assign(chunks, 0);
+	W->rcTerrainTableValid = false;
 	W->terrainHeights.ensure(W->hTerrainHeights.size(), W->stream); W->terrainValid.ensure(chunks, W->stream);
 	MI_CHECK(hipMemsetAsync(W->terrainValid.p, 0, sizeof(u32) * chunks, W->stream));
 	if (const char* e = getenv("MI_TERRAIN_SLOTS_PER_COLLIDER")) W->terrainSlotsPerCollider = (u32)std::max(1, atoi(e));
@@ -222,6 +223,7 @@ int mi_heightmap_set_chunk(mi_world* world, uint32_t x, uint32_t z, const uint16
 	size_t chunk = (size_t)z * W->terrainChunksPerDim + x, n = 129 * 129;
 	memcpy(W->hTerrainHeights.data() + chunk * n, heights129x129, sizeof(uint16_t) * n);
 	W->hTerrainValid[chunk] = 1;
+	W->rcTerrainTableValid = false;
 	MI_CHECK(hipMemcpyAsync(W->terrainHeights.p + chunk * n, W->hTerrainHeights.data() + chunk * n, sizeof(uint16_t) * n, hipMemcpyHostToDevice, W->stream));
 	MI_CHECK(hipMemcpyAsync(W->terrainValid.p + chunk, W->hTerrainValid.data() + chunk, sizeof(u32), hipMemcpyHostToDevice, W->stream));
 	MI_CHECK(hipStreamSynchronize(W->stream));

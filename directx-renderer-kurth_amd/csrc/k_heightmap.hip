@@ -6,13 +6,12 @@
 // one-contact manifold appended after the pair manifolds, so the colouring, the contact rows and the solver see nothing new.
 // Emission order per collider: chunk z, chunk x, cell z, cell x, triangle; the "lowest point under the terrain" contact last.
 #include "world.h"
+#include "terrain_shared.h"
 #include <rocprim/rocprim.hpp>
 
-#define TERRAIN_VERTS 129u
 #define TERRAIN_SLOT 0x80000000u
 #define KEY_ZONE 62u
 
-struct TerrainParams { u32 chunksPerDim; float chunkSize, invChunkSize, chunkScale, heightScale, invAmplitudeScale, minX, minY, minZ, friction, restitution; };
 struct TerrainContact { V3 point, normal; float depth; };
 
 MI_DEV V3 closestPointSegmentT(V3 q, V3 a, V3 b) { V3 ab = b - a; float t = dot(q - a, ab) / sqlen(ab); t = clampf(t, 0.f, 1.f); return a + t * ab; } // bounding_volumes.h:365-371
@@ -258,7 +257,7 @@ __global__ void __launch_bounds__(64) k_heightmap(const bool write, u32 nc, u32 
 			float relMaxX = (vmax.x > (x + 1)) ? 1.f : fmodf(vmax.x, 1.f), relMaxZ = (vmax.z > (z + 1)) ? 1.f : fmodf(vmax.z, 1.f);
 			u32 cMinX = (u32)(relMinX * TERRAIN_VERTS), cMinZ = (u32)(relMinZ * TERRAIN_VERTS), cMaxX = (u32)(relMaxX * TERRAIN_VERTS), cMaxZ = (u32)(relMaxZ * TERRAIN_VERTS);
 			cMaxX = min(cMaxX, TERRAIN_VERTS - 2u); cMaxZ = min(cMaxZ, TERRAIN_VERTS - 2u); // the pyramid's leaves end at cell 127
-			const V3 chunkMin = v3(x * P.chunkSize, 0.f, z * P.chunkSize) + corner;
+			const V3 chunkMin = terrainChunkMin(P, corner, x, z);
 			const uint16_t* H = heights + (size_t)chunk * TERRAIN_VERTS * TERRAIN_VERTS;
 			for (u32 cz = cMinZ; cz <= cMaxZ; ++cz)
 				for (u32 cx = cMinX; cx <= cMaxX; ++cx)
@@ -266,9 +265,8 @@ __global__ void __launch_bounds__(64) k_heightmap(const bool write, u32 nc, u32 
 					u32 ha = H[TERRAIN_VERTS * cz + cx], hb = H[TERRAIN_VERTS * (cz + 1) + cx], hc = H[TERRAIN_VERTS * cz + cx + 1], hd = H[TERRAIN_VERTS * (cz + 1) + cx + 1];
 					u32 lo = min(min(ha, hb), min(hc, hd)), hi = max(max(ha, hb), max(hc, hd));
 					if (hi < minHeight || lo > maxHeight) continue;
-					float x0 = (float)cx * P.chunkScale, x1 = (float)(cx + 1) * P.chunkScale, z0 = (float)cz * P.chunkScale, z1 = (float)(cz + 1) * P.chunkScale;
-					V3 posA = v3(x0, ha * P.heightScale, z0) + chunkMin, posB = v3(x0, hb * P.heightScale, z1) + chunkMin;
-					V3 posC = v3(x1, hc * P.heightScale, z0) + chunkMin, posD = v3(x1, hd * P.heightScale, z1) + chunkMin;
+					V3 posA, posB, posC, posD;
+					terrainCellVertices(P, chunkMin, cx, cz, ha, hb, hc, hd, posA, posB, posC, posD);
 					TerrainContact t0, t1;
 					bool hit0 = terrainTriangle<TYPE>(p0, p1, r, q, dir, posA, posB, posC, t0);
 					bool hit1 = terrainTriangle<TYPE>(p0, p1, r, q, dir, posC, posB, posD, t1);
@@ -304,10 +302,7 @@ static void launchTerrainPasses(World& w, bool write, const TerrainParams& P, u3
 void launch_heightmap(World& w, u32 numPairs, u32 slotCap)
 {
 	if (!w.terrainChunksPerDim || !w.nc) return;
-	TerrainParams P;
-	P.chunksPerDim = w.terrainChunksPerDim; P.chunkSize = w.terrainChunkSize; P.invChunkSize = 1.f / w.terrainChunkSize; P.chunkScale = w.terrainChunkSize / (TERRAIN_VERTS - 1);
-	P.heightScale = w.terrainAmplitude / 65535; P.invAmplitudeScale = 1.f / w.terrainAmplitude;
-	P.minX = w.terrainMinCorner[0]; P.minY = w.terrainMinCorner[1]; P.minZ = w.terrainMinCorner[2]; P.friction = w.terrainMaterial[1]; P.restitution = w.terrainMaterial[0];
+	const TerrainParams P = terrainParams(w);
 	w.terrainCounts.ensure((size_t)w.nc + 1, w.stream); w.terrainOffsets.ensure((size_t)w.nc + 1, w.stream);
 	MI_CHECK(hipMemsetAsync(w.terrainCounts.p, 0, sizeof(u32) * ((size_t)w.nc + 1), w.stream)); // cylinders and hulls: no kernel touches their entry
 	launchTerrainPasses(w, false, P, slotCap);

@@ -129,6 +129,7 @@ mi_world* mi_world_restore(const mi_world_desc* desc, const void* buffer, uint64
 	in.vec(w.fields); in.vec(w.triggers); in.pod(flags); in.vec(triggerKeys); in.vec(collisionKeys);
 	in.pod(w.terrainChunksPerDim); in.pod(w.terrainChunkSize); in.pod(w.terrainAmplitude); in.get(w.terrainMinCorner, 12); in.get(w.terrainMaterial, 12);
 	in.vec(w.hTerrainHeights); in.vec(w.hTerrainValid);
+	w.rcTerrainTableValid = false;
 	if (in.ok && w.terrainChunksPerDim)
 	{
 		size_t chunks = (size_t)w.terrainChunksPerDim * w.terrainChunksPerDim;

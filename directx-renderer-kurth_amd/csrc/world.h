@@ -289,6 +289,9 @@ struct World
 	// internal nodes (64 bytes each: both children's boxes and ids); the parent of every internal node and of every sorted leaf
 	DevBuf<float4> rcHostRays, rcHostHits; // staging of mi_raycast_host
 	DevBuf<float4> rcLeafBox, rcNodes; DevBuf<u32> rcCount, rcKeys, rcKeysSorted, rcVals, rcValsSorted, rcParentInt, rcParentLeaf;
+	// MI_RAY_TERRAIN (k_raycast_terrain.hip): (max << 16) | min of the uint16 heights per 8 x 8-cell tile (256 per chunk) and per chunk.  Depends on the
+	// heights alone (not on mi_heightmap_update's corner and amplitude): invalid after mi_set_heightmap, mi_heightmap_set_chunk and a restore
+	DevBuf<u32> rcTerrainTiles, rcTerrainChunkRange; bool rcTerrainTableValid = false;
 
 	World(int dev);
 	~World();
@@ -341,6 +344,7 @@ void launch_validate(World& w, u32 stage, u32 numPairs); // stage 0: world colli
 void launch_copy_pose0(World& w);
 void launch_interaction_batch(World& w, u32 numRays, u32 firstBody, u32 bodiesPerRay, const float* dRays, int32_t* dOutBody); // k_interact.hip
 void launch_raycast(World& w, u32 numRays, const float* dRays, u32 flags, mi_ray_hit* dOutHits); // k_raycast.hip
+void launch_raycast_terrain(World& w, u32 numRays, const float* dRays, u32 flags, mi_ray_hit* dOutHits); // k_raycast_terrain.hip: after launch_raycast, on its records
 void launch_lerp_pose(World& w, float t);
 void csort_pairs_u32(World& w, const u32* keys, u32* keysOut, const u32* vals, u32* valsOut, u32 n, u32 numBuckets); // stable, keys < numBuckets <= 272
 void csort_pairs_u64(World& w, const u32* keys, u32* keysOut, const u64* vals, u64* valsOut, u32 n, u32 numBuckets);

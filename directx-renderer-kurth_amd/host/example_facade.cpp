@@ -81,6 +81,7 @@ int main()
 			ray_hit hit;
 			if (!castRay(scene, ray{ vec3(20.f, 10.f, 20.f), vec3(0.f, -1.f, 0.f) }, 100.f, hit)) std::abort();
 			if (hit.body != MI_STATIC_BODY || !(hit.distance > 9.999f && hit.distance < 10.001f) || castRay(scene, ray{ vec3(20.f, 10.f, 20.f), vec3(0.f, -1.f, 0.f) }, 5.f, hit)) std::abort();
+			if (!castRay(scene, ray{ vec3(20.f, 10.f, 20.f), vec3(0.f, -1.f, 0.f) }, 100.f, hit, true) || hit.collider == MI_TERRAIN_COLLIDER || hit.triangle != 0u) std::abort(); // no heightmap here: the terrain flag changes nothing
 			std::printf("ray %.6f %.6f %.6f %.6f\n", hit.distance, hit.point.x, hit.point.y, hit.point.z);
 		}
 		for (auto& e : boxes) { auto t = e.transform(); std::printf("box %.6f %.6f %.6f %.6f %.6f %.6f %.6f\n", t.position.x, t.position.y, t.position.z, t.rotation.x, t.rotation.y, t.rotation.z, t.rotation.w); }

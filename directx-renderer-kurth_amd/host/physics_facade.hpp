@@ -421,15 +421,17 @@ namespace mi
 
 	// A ray cast against the whole scene (rigid bodies and static colliders; no counterpart in the reference's physics.h): the closest
 	// hit within maxDistance, in units of the direction's length, or false.  Nothing is pushed.  One ray through mi_raycast_batch.
-	struct ray_hit { float distance = 0.f; vec3 point; uint32_t collider = 0, body = MI_STATIC_BODY; }; // body: MI_STATIC_BODY for an entity without a rigid body
-	inline bool castRay(game_scene& scene, ray r, float maxDistance, ray_hit& out)
+	// withTerrain: the heightmap's triangles are candidates too; such a hit has collider == MI_TERRAIN_COLLIDER and the triangle id in `triangle`.
+	struct ray_hit { float distance = 0.f; vec3 point; uint32_t collider = 0, body = MI_STATIC_BODY, triangle = 0; }; // body: MI_STATIC_BODY for an entity without a rigid body
+	inline bool castRay(game_scene& scene, ray r, float maxDistance, ray_hit& out, bool withTerrain = false)
 	{
 		scene.flushStaticColliders();
 		const float in[8] = { r.origin.x, r.origin.y, r.origin.z, maxDistance, r.direction.x, r.direction.y, r.direction.z, 1.f };
 		mi_ray_hit h{};
-		scene.check(mi_raycast_host(scene.world, 1u, in, MI_RAY_STATIC, &h), "castRay");
+		scene.check(mi_raycast_host(scene.world, 1u, in, withTerrain ? (uint32_t)(MI_RAY_STATIC | MI_RAY_TERRAIN) : (uint32_t)MI_RAY_STATIC, &h), "castRay");
 		if (!h.hit) return false;
 		out.distance = h.t; out.point = vec3(h.point[0], h.point[1], h.point[2]); out.collider = h.collider; out.body = h.body;
+		memcpy(&out.triangle, &h.reserved, sizeof(uint32_t));
 		return true;
 	}
 

@@ -258,8 +258,8 @@ int mi_test_physics_interaction_batch(mi_world* w, uint32_t numRays, uint32_t fi
  * direction need not be a unit vector: t is in units of its length, as in the reference (whose sphere test, and with it a capsule's
  * ends, is geometric for unit directions only).
  * Candidates: the colliders of rigid bodies that are alive and, in a slab run, simulated here; with MI_RAY_STATIC also the colliders
- * of entities without a rigid body.  Force-field and trigger colliders are never candidates; the heightmap and cloth are not either
- * (the reference's ray test knows neither).
+ * of entities without a rigid body; with MI_RAY_TERRAIN also the heightmap terrain (below).  Force-field and trigger colliders and
+ * cloth are never candidates.
  * Hit rule: a candidate's test is testPhysicsInteraction's test of that collider, in the collider's own frame.  It is a hit if
  * 0 <= t <= maxT; the smallest t wins, and of equal t the lowest collider index.  This is where the cast deviates from
  * testPhysicsInteraction: that function also accepts the negative distances its cylinder and capsule tests report for a cap disk
@@ -269,8 +269,26 @@ int mi_test_physics_interaction_batch(mi_world* w, uint32_t numRays, uint32_t fi
  * or a switched-off ray.  Hit normals are not reported.
  * The acceleration structure (a BVH over the candidates) is rebuilt from the current poses at every call, in buffers of its own: poses
  * written through mi_device_state are seen, and the step's buffers are not touched.  MI_RAY_BRUTE_FORCE tests every ray against every
- * candidate instead (same answers; a yardstick, and cheaper for a handful of colliders). */
-enum { MI_RAY_STATIC = 1, MI_RAY_BRUTE_FORCE = 2 };
+ * candidate instead (same answers; a yardstick, and cheaper for a handful of colliders).
+ * MI_RAY_TERRAIN: the triangles the bodies collide with are candidates too (the reference has no terrain cast: the rule is this
+ * project's).  Without the flag every byte of every record is what it is without a heightmap; with the flag and no heightmap the flag
+ * does nothing.  Cell (cellX, cellZ) of chunk (chunkX, chunkZ) has the vertices A = (cellX, cellZ), B = (cellX, cellZ + 1),
+ * C = (cellX + 1, cellZ), D = (cellX + 1, cellZ + 1), each at chunkMin + (cx * chunkScale, h * heightScale, cz * chunkScale), and the
+ * triangles 0 = (A, B, C) and 1 = (C, B, D).  Per triangle (a, b, c): n = noz(cross(b - a, c - a)); a miss if |dot(direction, n)| <= 1e-6;
+ * t = -(dot(origin, n) - dot(n, a)) / dot(direction, n); accepted if 0 <= t <= maxT; both faces count (a ray from below hits).
+ * Containment: q = origin + t * direction, u = (q.x - A.x) / (D.x - A.x), v = (q.z - A.z) / (D.z - A.z); inside the cell if 0 <= u <= 1
+ * and 0 <= v <= 1, closed on all sides; triangle 0 owns u + v <= 1, triangle 1 owns u + v >= 1.  For a vertical ray q.x and q.z are the
+ * origin's, so within the x/z extent of a chunk that has heights such a ray always hits.  The smallest t wins, of equal t the lowest
+ * triangle id; the terrain replaces a collider's hit only if its t is strictly smaller.  Chunks without heights are holes (a ray
+ * passes and may hit a chunk behind); chunks whose border heights disagree leave a crack without a wall.  A zero direction misses.
+ * A terrain hit: hit = 1, t, collider = MI_TERRAIN_COLLIDER, body = MI_STATIC_BODY, point = origin + t * direction, and in `reserved`
+ * the bits of the uint32 triangle id ((chunkZ * chunksPerDim + chunkX) * 16384 + cellZ * 128 + cellX) * 2 + triangle, from which a
+ * caller can form the normal; for a collider hit or a miss reserved stays 0.  A heightmap of more than 131071 chunks makes a terrain
+ * cast return MI_ERR_INVALID_ARGUMENT.  The walk over the cells under the ray uses a min/max table of the heights per 8 x 8-cell tile,
+ * rebuilt on the world's stream after mi_set_heightmap / mi_heightmap_set_chunk / a restore; mi_heightmap_update needs no rebuild.
+ * MI_RAY_BRUTE_FORCE | MI_RAY_TERRAIN tests every triangle of every chunk instead (same answers). */
+enum { MI_RAY_STATIC = 1, MI_RAY_BRUTE_FORCE = 2, MI_RAY_TERRAIN = 4 };
+#define MI_TERRAIN_COLLIDER 0xFFFFFFFEu
 typedef struct mi_ray_hit { float t; uint32_t collider, body, hit; float point[3]; float reserved; } mi_ray_hit; /* 32 bytes */
 int mi_raycast_batch(mi_world* w, uint32_t numRays, const float* dRays, uint32_t flags, mi_ray_hit* dOutHits);
 /* The same cast for callers without device memory of their own (a single pick: the C++ facade's castRay): rays and hits in HOST memory,
