@@ -56,6 +56,23 @@ class RayHit(C.Structure):
 
 RAY_HIT_DTYPE = np.dtype([("t", "<f4"), ("collider", "<u4"), ("body", "<u4"), ("hit", "<u4"), ("point", "<f4", 3), ("reserved", "<f4")])
 RAY_STATIC, RAY_BRUTE_FORCE, RAY_TERRAIN = 1, 2, 4
+
+
+class SensorRay(C.Structure):
+    """struct mi_sensor_ray (include/mi_physics.h): one ray of mi_raycast_sensors in the frame of body `mount`, 48 bytes"""
+    _fields_ = [("origin", C.c_float * 3), ("maxT", C.c_float), ("direction", C.c_float * 3), ("enabled", C.c_float),
+                ("mount", C.c_uint32), ("excludeFirst", C.c_uint32), ("excludeCount", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class SensorHit(C.Structure):
+    """struct mi_sensor_hit (include/mi_physics.h): mi_ray_hit and the world-space normal, 48 bytes"""
+    _fields_ = [("hit", RayHit), ("normal", C.c_float * 3), ("reserved", C.c_float)]
+
+
+SENSOR_RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("maxT", "<f4"), ("direction", "<f4", 3), ("enabled", "<f4"),
+                             ("mount", "<u4"), ("excludeFirst", "<u4"), ("excludeCount", "<u4"), ("reserved", "<u4")])
+SENSOR_HIT_DTYPE = np.dtype([("t", "<f4"), ("collider", "<u4"), ("body", "<u4"), ("hit", "<u4"), ("point", "<f4", 3), ("reserved", "<f4"),
+                             ("normal", "<f4", 3), ("reserved2", "<f4")])
 STATIC_BODY = 0xFFFFFFFF   # mi_ray_hit.body of a collider without a rigid body (MI_STATIC_BODY)
 TERRAIN_COLLIDER = 0xFFFFFFFE   # mi_ray_hit.collider of a hit on the heightmap terrain (MI_TERRAIN_COLLIDER)
 
@@ -110,6 +127,7 @@ EXPORTED_SYMBOLS = [
     "mi_debug_read_joint_order", "mi_debug_read_joint_update", "mi_debug_read_body_state", "mi_debug_read_accumulators", "mi_debug_flow_trace",
     "mi_debug_set_replay", "mi_debug_num_replay_batches", "mi_debug_read_replay_batches",
     "mi_device_state", "mi_joint_device_pods", "mi_test_physics_interaction_batch", "mi_raycast_batch", "mi_raycast_host",
+    "mi_raycast_sensors", "mi_raycast_sensors_host",
 ]
 
 
@@ -474,6 +492,46 @@ class World:
             self._check(self.lib.mi_raycast_batch(self.w, C.c_uint32(0), None, C.c_uint32(flags), None))
         out = (hits["t"].copy(), hits["collider"].copy(), hits["body"].copy(), hits["hit"].copy(), hits["point"].copy())
         return out + (hits["reserved"].view(np.uint32).copy(),) if terrain else out
+
+    def raycast_sensors(self, rays, mount=None, exclude_first=None, exclude_count=None, static=True, brute_force=False, terrain=False, world_rays=False):
+        """mi_raycast_sensors: rays [n, 8] = origin, maxT, direction, enabled in the frame of body mount[i] at its current pose
+        (mount: an index or an array [n]; STATIC_BODY: the ray is in world space), each blind to the colliders of the bodies
+        exclude_first[i] ... exclude_first[i] + exclude_count[i] - 1 (None: nothing is excluded); flags as raycast.
+        numpy rays go through the world's staging buffers (mi_raycast_sensors_host): returns raycast's tuple (t, collider, body, hit,
+        point[, triangle with terrain=True]) plus normal [n, 3], and plus the world rays [n, 8] with world_rays=True.
+        A torch tensor on the device (float32, contiguous, [n, 12]: the 8 floats and the bits of mount, excludeFirst, excludeCount, 0;
+        mount and the exclusion arguments are then not used) is cast in place: returns one float32 tensor [n, 12] of mi_sensor_hit
+        records (columns 8..10 the normal), with world_rays=True a tuple with the [n, 8] world rays; enqueued on the world's stream
+        with no synchronisation.  (The rays tensor is recorded on that stream, as in raycast: release it before close().)"""
+        import torch
+        flags = (RAY_STATIC if static else 0) | (RAY_BRUTE_FORCE if brute_force else 0) | (RAY_TERRAIN if terrain else 0)
+        if isinstance(rays, torch.Tensor):
+            if not rays.is_cuda or rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 12 or not rays.is_contiguous():
+                raise ValueError("raycast_sensors: a device tensor must be float32, contiguous and [n, 12]")
+            ext = torch.cuda.ExternalStream(self.device_state().stream or 0, device=rays.device)
+            ext.wait_stream(torch.cuda.current_stream(rays.device))   # the rays were written on the caller's stream
+            with torch.cuda.stream(ext):
+                out = torch.empty((rays.shape[0], 12), dtype=torch.float32, device=rays.device)
+                wr = torch.empty((rays.shape[0], 8), dtype=torch.float32, device=rays.device) if world_rays else None
+                self._check(self.lib.mi_raycast_sensors(self.w, C.c_uint32(rays.shape[0]), C.c_void_p(rays.data_ptr()), C.c_uint32(flags), C.c_void_p(out.data_ptr()),
+                                                        C.c_void_p(wr.data_ptr()) if world_rays else None))
+            rays.record_stream(ext)
+            torch.cuda.current_stream(rays.device).wait_stream(ext)   # stream order, not a host synchronisation
+            return (out, wr) if world_rays else out
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+        n = len(rays)
+        rec = np.zeros(n, SENSOR_RAY_DTYPE)
+        rec["origin"], rec["maxT"], rec["direction"], rec["enabled"] = rays[:, 0:3], rays[:, 3], rays[:, 4:7], rays[:, 7]
+        rec["mount"] = STATIC_BODY if mount is None else np.asarray(mount, np.uint32)
+        rec["excludeFirst"] = 0 if exclude_first is None else np.asarray(exclude_first, np.uint32)
+        rec["excludeCount"] = 0 if exclude_count is None else np.asarray(exclude_count, np.uint32)
+        hits, wr = np.zeros(n, SENSOR_HIT_DTYPE), np.zeros((n, 8), np.float32)
+        self._check(self.lib.mi_raycast_sensors_host(self.w, C.c_uint32(n), _p(rec) if n else None, C.c_uint32(flags), _p(hits) if n else None, _p(wr) if (n and world_rays) else None))
+        out = (hits["t"].copy(), hits["collider"].copy(), hits["body"].copy(), hits["hit"].copy(), hits["point"].copy())
+        if terrain:
+            out += (hits["reserved"].view(np.uint32).copy(),)
+        out += (hits["normal"].copy(),)
+        return out + (wr,) if world_rays else out
 
     def accumulators(self):
         """Force and torque accumulators of every body [n, 6]: the pushes the next step will apply and clear."""

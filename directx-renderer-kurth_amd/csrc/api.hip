@@ -377,6 +377,38 @@ int mi_raycast_host(mi_world* world, uint32_t numRays, const float* rays, uint32
 	return W->lastError;
 }
 
+int mi_raycast_sensors(mi_world* world, uint32_t numRays, const mi_sensor_ray* dRays, uint32_t flags, mi_sensor_hit* dOutHits, float* dOutWorldRays)
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	W->resolvePendingFlow();
+	W->upload();
+	if (!numRays) return W->lastError;
+	if (!dRays || !dOutHits) return MI_ERR_INVALID_ARGUMENT;
+	if (!W->interactTablesValid) W->buildInteractTables();
+	if (W->lastError) return W->lastError;
+	const bool terrain = (flags & MI_RAY_TERRAIN) != 0 && W->terrainChunksPerDim != 0;
+	if (terrain && (uint64_t)W->terrainChunksPerDim * W->terrainChunksPerDim > 131071u) return MI_ERR_INVALID_ARGUMENT; // as mi_raycast_batch
+	launch_raycast_sensors(*W, numRays, dRays, flags, terrain, dOutHits, dOutWorldRays);
+	return W->lastError;
+}
+
+int mi_raycast_sensors_host(mi_world* world, uint32_t numRays, const mi_sensor_ray* rays, uint32_t flags, mi_sensor_hit* outHits, float* outWorldRays)
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	if (!numRays) return mi_raycast_sensors(world, 0, nullptr, flags, nullptr, nullptr);
+	if (!rays || !outHits) return MI_ERR_INVALID_ARGUMENT;
+	W->rcSensorHostIn.ensure(3 * (size_t)numRays, W->stream); W->rcSensorHostOut.ensure(3 * (size_t)numRays, W->stream);
+	if (outWorldRays) W->rcSensorHostRays.ensure(2 * (size_t)numRays, W->stream);
+	if (W->lastError) return W->lastError;
+	MI_CHECK(hipMemcpyAsync(W->rcSensorHostIn.p, rays, sizeof(mi_sensor_ray) * (size_t)numRays, hipMemcpyHostToDevice, W->stream));
+	int e = mi_raycast_sensors(world, numRays, (const mi_sensor_ray*)W->rcSensorHostIn.p, flags, (mi_sensor_hit*)W->rcSensorHostOut.p, outWorldRays ? (float*)W->rcSensorHostRays.p : nullptr);
+	if (e) return e;
+	MI_CHECK(hipMemcpyAsync(outHits, W->rcSensorHostOut.p, sizeof(mi_sensor_hit) * (size_t)numRays, hipMemcpyDeviceToHost, W->stream));
+	if (outWorldRays) MI_CHECK(hipMemcpyAsync(outWorldRays, W->rcSensorHostRays.p, 32 * (size_t)numRays, hipMemcpyDeviceToHost, W->stream));
+	MI_CHECK(hipStreamSynchronize(W->stream));
+	return W->lastError;
+}
+
 // ---- multi-GPU slabs: state hand-over in device memory (directx-renderer-kurth_amd/parallel.py drives the halo exchange) ----
 int mi_state_to_device_buffers(mi_world* world, void* dPose, void* dVel)
 {

@@ -7,20 +7,16 @@
 //   (radix sort)  prim_sort_pairs_u32, 31 bits
 //   k_rc_tree     internal nodes after Karras (2012), equal keys separated by their sorted position
 //   k_rc_fit      node boxes bottom-up: the second child to arrive at a node merges and goes on
-//   k_raycast     one lane per ray: near child first, fixed stack in LDS; with MI_RAY_BRUTE_FORCE the same body walks all colliders
+//   k_raycast     one lane per ray: near child first, fixed stack in LDS; with MI_RAY_BRUTE_FORCE the same body walks all colliders;
+//                 <.., EXCLUDE = true> (mi_raycast_sensors, k_raycast_sensors.hip) skips the colliders of the ray's own body range
 // A hit is decided by rayBodyCollider (ray_tests.h) on the collider's LOCAL record and pose alone, as in k_interaction_batch; the
 // boxes only say which colliders need not be asked.
 #include "world.h"
 #include "ray_tests.h"
+#include "raycast_shared.h"
 
 void prim_sort_pairs_u32(World& w, const u32* kin, u32* kout, const u32* vin, u32* vout, u32 n, u32 bits);
 
-struct RcHulls
-{
-	const float4* verts; const uint4* tris; const uint2* range;
-	MI_DEV u32 numTriangles(u32 g) const { return range[g].y; }
-	MI_DEV V3 vertex(u32 g, u32 f, u32 k) const { uint4 t = tris[range[g].x + f]; return v3f4(verts[k == 0 ? t.x : (k == 1 ? t.y : t.z)]); }
-};
 
 // ---- header words of World::rcCount (zeroed before every build; every accumulated word has 0 as its neutral element) ----
 enum
@@ -229,11 +225,15 @@ MI_DEV bool rcBoxTest(const RcRay& q, const float* b, float tmax, float& tEnter)
 	return !(outside || lo > tmax || hi < 0.f || lo > hi);
 }
 
+// The bodies b with b - first < count (unsigned) are no candidates of this ray: mi_raycast_sensors' exclusion range.
+struct RcExclude { u32 first, count; };
 struct RcBest { float t; u32 col, body; V3 point; }; // t starts at MI_FLT_MAX like the reference's minDistance: a test that reports FLT_MAX or +inf (a box whose slab interval is poisoned, rule R2a) has not hit
-MI_DEV void rcTestCollider(u32 c, const RcRay& q, u32 nb, const float4* __restrict__ pose, const float4* __restrict__ colStaticPose, const ColliderRec* __restrict__ cols, const RcHulls& hulls, RcBest& best)
+template <bool EXCLUDE>
+MI_DEV void rcTestCollider(u32 c, const RcRay& q, RcExclude ex, u32 nb, const float4* __restrict__ pose, const float4* __restrict__ colStaticPose, const ColliderRec* __restrict__ cols, const RcHulls& hulls, RcBest& best)
 {
 	const ColliderRec rec = cols[c];
 	const u32 body = colBody(rec);
+	if (EXCLUDE && body < nb && body - ex.first < ex.count) return; // (static colliders are never excluded)
 	const float4* P = (body < nb) ? (pose + 2 * body) : (colStaticPose + 2 * c);
 	const Q4 rot = q4f4(P[1]); const V3 pos = v3f4(P[0]);
 	const float s[10] = { rec.a.x, rec.a.y, rec.a.z, rec.a.w, rec.b.x, rec.b.y, rec.b.z, rec.b.w, rec.c.x, rec.c.y };
@@ -257,13 +257,14 @@ MI_DEV void rcPrepareRay(RcRay& q, float scene, float diag)
 	q.relT = diag / length(q.r.direction);
 }
 // Closest hit among the n >= 1 candidates of the tree.  stack[k * stride]: the caller's RC_STACK entries.
-MI_DEV void rcTraverse(const RcRay& q, u32 n, const float4* __restrict__ nodes, const u32* __restrict__ vals, u32* stack, u32 stride, u32 nb, const float4* __restrict__ pose,
+template <bool EXCLUDE>
+MI_DEV void rcTraverse(const RcRay& q, RcExclude ex, u32 n, const float4* __restrict__ nodes, const u32* __restrict__ vals, u32* stack, u32 stride, u32 nb, const float4* __restrict__ pose,
 	const float4* __restrict__ colStaticPose, const ColliderRec* __restrict__ cols, const RcHulls& hulls, RcBest& best)
 {
 	u32 node = n == 1u ? (RC_LEAF | vals[0]) : 0u, sp = 0u;
 	for (;;)
 	{
-		if (node & RC_LEAF) rcTestCollider(node & ~RC_LEAF, q, nb, pose, colStaticPose, cols, hulls, best);
+		if (node & RC_LEAF) rcTestCollider<EXCLUDE>(node & ~RC_LEAF, q, ex, nb, pose, colStaticPose, cols, hulls, best);
 		else
 		{
 			const float4 w0 = nodes[4 * node], w1 = nodes[4 * node + 1], w2 = nodes[4 * node + 2], w3 = nodes[4 * node + 3];
@@ -286,9 +287,9 @@ MI_DEV void rcTraverse(const RcRay& q, u32 n, const float4* __restrict__ nodes, 
 	}
 }
 
-template <bool BRUTE>
+template <bool BRUTE, bool EXCLUDE>
 __global__ void __launch_bounds__(64) k_raycast(u32 numRays, const float4* __restrict__ rays, float4* __restrict__ out, u32 nb, u32 nc, const float4* __restrict__ pose, const float4* __restrict__ colStaticPose,
-	const ColliderRec* __restrict__ cols, RcHulls hulls, const u32* __restrict__ hdr, const float4* __restrict__ nodes, const u32* __restrict__ vals, const float4* __restrict__ leafBox)
+	const ColliderRec* __restrict__ cols, RcHulls hulls, const u32* __restrict__ hdr, const float4* __restrict__ nodes, const u32* __restrict__ vals, const float4* __restrict__ leafBox, const uint2* __restrict__ exclude)
 {
 	__shared__ u32 stack[BRUTE ? 1 : RC_STACK][64]; // [level][lane]: a wave's access is one row, conflict-free
 	const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -296,17 +297,19 @@ __global__ void __launch_bounds__(64) k_raycast(u32 numRays, const float4* __res
 	const float4 r0 = rays[2 * i], r1 = rays[2 * i + 1];
 	RcBest best; best.t = MI_FLT_MAX; best.col = 0xFFFFFFFFu; best.body = 0u; best.point = v3s(0.f);
 	RcRay q; q.r = HRay{ v3(r0.x, r0.y, r0.z), v3(r1.x, r1.y, r1.z) }; q.maxT = r0.w;
+	RcExclude ex{ 0u, 0u };
+	if (EXCLUDE) { const uint2 e = exclude[i]; ex.first = e.x; ex.count = e.y; }
 	const u32 n = hdr[RC_N];
 	if (r1.w != 0.f && n != 0u)
 	{
 		if (BRUTE)
 		{
-			for (u32 c = 0; c < nc; ++c) if (leafBox[2 * c].w != 0.f) rcTestCollider(c, q, nb, pose, colStaticPose, cols, hulls, best);
+			for (u32 c = 0; c < nc; ++c) if (leafBox[2 * c].w != 0.f) rcTestCollider<EXCLUDE>(c, q, ex, nb, pose, colStaticPose, cols, hulls, best);
 		}
 		else
 		{
 			rcPrepareRay(q, mi_u2f(hdr[RC_ABS]), mi_u2f(hdr[RC_DIAG]));
-			rcTraverse(q, n, nodes, vals, &stack[0][threadIdx.x], 64u, nb, pose, colStaticPose, cols, hulls, best);
+			rcTraverse<EXCLUDE>(q, ex, n, nodes, vals, &stack[0][threadIdx.x], 64u, nb, pose, colStaticPose, cols, hulls, best);
 		}
 	}
 	const bool hit = best.col != 0xFFFFFFFFu;
@@ -314,7 +317,19 @@ __global__ void __launch_bounds__(64) k_raycast(u32 numRays, const float4* __res
 	out[2 * i + 1] = hit ? make_float4(best.point.x, best.point.y, best.point.z, 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
-void launch_raycast(World& w, u32 numRays, const float* dRays, u32 flags, mi_ray_hit* dOutHits)
+template <bool BRUTE>
+static void rcLaunchCast(World& w, u32 numRays, const float* dRays, mi_ray_hit* dOutHits, const RcHulls& hulls, const uint2* dExclude)
+{
+	if (dExclude)
+		hipLaunchKernelGGL((k_raycast<BRUTE, true>), dim3((numRays + 63) / 64), dim3(64), 0, w.stream, numRays, (const float4*)dRays, (float4*)dOutHits, w.nb, w.nc, w.pose.p, w.colStaticPose.p,
+			w.colLocal.p, hulls, w.rcCount.p, (const float4*)w.rcNodes.p, w.rcValsSorted.p, w.rcLeafBox.p, dExclude);
+	else
+		hipLaunchKernelGGL((k_raycast<BRUTE, false>), dim3((numRays + 63) / 64), dim3(64), 0, w.stream, numRays, (const float4*)dRays, (float4*)dOutHits, w.nb, w.nc, w.pose.p, w.colStaticPose.p,
+			w.colLocal.p, hulls, w.rcCount.p, (const float4*)w.rcNodes.p, w.rcValsSorted.p, w.rcLeafBox.p, (const uint2*)nullptr);
+}
+
+// dExclude: NULL, or one {first, count} body range per ray (mi_raycast_sensors): the colliders of those bodies are no candidates of that ray.
+void launch_raycast(World& w, u32 numRays, const float* dRays, u32 flags, mi_ray_hit* dOutHits, const uint2* dExclude)
 {
 	const bool withStatic = (flags & MI_RAY_STATIC) != 0, brute = (flags & MI_RAY_BRUTE_FORCE) != 0;
 	// what the host knows of the candidates (a slab's simulate mask can only take some away): none = every ray misses, nothing is built
@@ -333,8 +348,7 @@ void launch_raycast(World& w, u32 numRays, const float* dRays, u32 flags, mi_ray
 		w.aliveMask.p, w.simMask.p, w.hullInfo.p, w.rcLeafBox.p, w.rcCount.p);
 	if (brute)
 	{
-		hipLaunchKernelGGL(k_raycast<true>, dim3((numRays + 63) / 64), dim3(64), 0, w.stream, numRays, (const float4*)dRays, (float4*)dOutHits, w.nb, nc, w.pose.p, w.colStaticPose.p,
-			w.colLocal.p, hulls, w.rcCount.p, (const float4*)w.rcNodes.p, w.rcValsSorted.p, w.rcLeafBox.p);
+		rcLaunchCast<true>(w, numRays, dRays, dOutHits, hulls, dExclude);
 		return;
 	}
 	hipLaunchKernelGGL(k_rc_keys, dim3(blocks), dim3(256), 0, w.stream, nc, w.rcLeafBox.p, w.rcCount.p, w.rcKeys.p, w.rcVals.p);
@@ -345,6 +359,5 @@ void launch_raycast(World& w, u32 numRays, const float* dRays, u32 flags, mi_ray
 		hipLaunchKernelGGL(k_rc_tree, dim3(treeBlocks), dim3(256), 0, w.stream, w.rcCount.p, w.rcKeysSorted.p, w.rcValsSorted.p, (u32*)w.rcNodes.p, w.rcParentInt.p, w.rcParentLeaf.p);
 		hipLaunchKernelGGL(k_rc_fit, dim3(treeBlocks), dim3(256), 0, w.stream, w.rcCount.p, w.rcValsSorted.p, w.rcLeafBox.p, w.rcParentInt.p, w.rcParentLeaf.p, (float*)w.rcNodes.p, w.rcCount.p + RC_HEADER);
 	}
-	hipLaunchKernelGGL(k_raycast<false>, dim3((numRays + 63) / 64), dim3(64), 0, w.stream, numRays, (const float4*)dRays, (float4*)dOutHits, w.nb, nc, w.pose.p, w.colStaticPose.p,
-		w.colLocal.p, hulls, w.rcCount.p, (const float4*)w.rcNodes.p, w.rcValsSorted.p, w.rcLeafBox.p);
+	rcLaunchCast<false>(w, numRays, dRays, dOutHits, hulls, dExclude);
 }

@@ -292,6 +292,9 @@ struct World
 	// MI_RAY_TERRAIN (k_raycast_terrain.hip): (max << 16) | min of the uint16 heights per 8 x 8-cell tile (256 per chunk) and per chunk.  Depends on the
 	// heights alone (not on mi_heightmap_update's corner and amplitude): invalid after mi_set_heightmap, mi_heightmap_set_chunk and a restore
 	DevBuf<u32> rcTerrainTiles, rcTerrainChunkRange; bool rcTerrainTableValid = false;
+	// mi_raycast_sensors (k_raycast_sensors.hip): per ray the world ray (2 x float4, used when the caller wants none back), the 32-byte
+	// record k_raycast and k_rc_terrain work on (2 x float4) and the exclusion range {first, count}; staging of mi_raycast_sensors_host
+	DevBuf<float4> rcSensorRays, rcSensorHits; DevBuf<uint2> rcSensorExclude; DevBuf<float4> rcSensorHostIn, rcSensorHostOut, rcSensorHostRays;
 
 	World(int dev);
 	~World();
@@ -343,7 +346,8 @@ void launch_slab_unpack(World& w, const void* left, const void* right, u32 capac
 void launch_validate(World& w, u32 stage, u32 numPairs); // stage 0: world colliders + AABBs, 1: contacts, 2: body update records, 3: poses + velocities after the step
 void launch_copy_pose0(World& w);
 void launch_interaction_batch(World& w, u32 numRays, u32 firstBody, u32 bodiesPerRay, const float* dRays, int32_t* dOutBody); // k_interact.hip
-void launch_raycast(World& w, u32 numRays, const float* dRays, u32 flags, mi_ray_hit* dOutHits); // k_raycast.hip
+void launch_raycast(World& w, u32 numRays, const float* dRays, u32 flags, mi_ray_hit* dOutHits, const uint2* dExclude = nullptr); // k_raycast.hip; dExclude: a body range per ray (mi_raycast_sensors)
+void launch_raycast_sensors(World& w, u32 numRays, const mi_sensor_ray* dRays, u32 flags, bool terrain, mi_sensor_hit* dOutHits, float* dOutWorldRays); // k_raycast_sensors.hip
 void launch_raycast_terrain(World& w, u32 numRays, const float* dRays, u32 flags, mi_ray_hit* dOutHits); // k_raycast_terrain.hip: after launch_raycast, on its records
 void launch_lerp_pose(World& w, float t);
 void csort_pairs_u32(World& w, const u32* keys, u32* keysOut, const u32* vals, u32* valsOut, u32 n, u32 numBuckets); // stable, keys < numBuckets <= 272

@@ -76,6 +76,7 @@ World::~World()
 	for (auto& js : joints) { js.dPods.release(); js.dPairs.release(); js.dUpdate.release(); }
 	bodyColStart.release(); bodyColList.release(); hullTris.release(); hullTriRange.release();
 	rcHostRays.release(); rcHostHits.release(); rcLeafBox.release(); rcNodes.release(); rcCount.release(); rcKeys.release(); rcKeysSorted.release(); rcVals.release(); rcValsSorted.release(); rcParentInt.release(); rcParentLeaf.release(); rcTerrainTiles.release(); rcTerrainChunkRange.release();
+	rcSensorRays.release(); rcSensorHits.release(); rcSensorExclude.release(); rcSensorHostIn.release(); rcSensorHostOut.release(); rcSensorHostRays.release();
 	for (auto& e : stageEvents) if (e) (void)hipEventDestroy(e);
 	if (countersEvent) (void)hipEventDestroy(countersEvent);
 	if (hCounters) (void)hipHostFree(hCounters);

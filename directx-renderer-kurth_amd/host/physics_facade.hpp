@@ -435,6 +435,26 @@ namespace mi
 		return true;
 	}
 
+	// A ray sensor fixed to a rigid body: localRay is in the body's frame at its current pose; the closest hit within maxDistance with the
+	// surface's outward normal in world space (include/mi_physics.h states the rule), or false.  excludeSelf: the body's own colliders
+	// are no candidates, so a sensor may sit inside its carrier.  One ray through mi_raycast_sensors.
+	struct sensor_hit : ray_hit { vec3 normal; };
+	inline bool castSensorRay(game_scene& scene, const scene_entity& body, ray localRay, float maxDistance, sensor_hit& out, bool excludeSelf = true, bool withTerrain = false)
+	{
+		scene.flushStaticColliders();
+		mi_sensor_ray in{};
+		in.origin[0] = localRay.origin.x; in.origin[1] = localRay.origin.y; in.origin[2] = localRay.origin.z; in.maxT = maxDistance;
+		in.direction[0] = localRay.direction.x; in.direction[1] = localRay.direction.y; in.direction[2] = localRay.direction.z; in.enabled = 1.f;
+		in.mount = body.body(); in.excludeFirst = in.mount; in.excludeCount = excludeSelf ? 1u : 0u;
+		mi_sensor_hit h{};
+		scene.check(mi_raycast_sensors_host(scene.world, 1u, &in, withTerrain ? (uint32_t)(MI_RAY_STATIC | MI_RAY_TERRAIN) : (uint32_t)MI_RAY_STATIC, &h, nullptr), "castSensorRay");
+		if (!h.hit.hit) return false;
+		out.distance = h.hit.t; out.point = vec3(h.hit.point[0], h.hit.point[1], h.hit.point[2]); out.collider = h.hit.collider; out.body = h.hit.body;
+		memcpy(&out.triangle, &h.hit.reserved, sizeof(uint32_t));
+		out.normal = vec3(h.normal[0], h.normal[1], h.normal[2]);
+		return true;
+	}
+
 	// ---- void physicsStep(game_scene&, memory_arena&, float& timer, const physics_settings&, float dt), physics.h:405
 	inline void physicsStep(game_scene& scene, memory_arena& /*arena*/, float& timer, const physics_settings& settings, float dt)
 	{

@@ -266,7 +266,7 @@ int mi_test_physics_interaction_batch(mi_world* w, uint32_t numRays, uint32_t fi
  * behind the origin; a ray cast reports no hit behind the ray.
  * dOutHits[i] (device): hit = 1, t, the collider, its body (MI_STATIC_BODY for a static collider) and the world hit point
  * rot * (local origin + t * local direction) + pos, bit for bit the point mi_test_physics_interaction pushes at; all zero for a miss
- * or a switched-off ray.  Hit normals are not reported.
+ * or a switched-off ray.  Hit normals are reported by mi_raycast_sensors (below), not here.
  * The acceleration structure (a BVH over the candidates) is rebuilt from the current poses at every call, in buffers of its own: poses
  * written through mi_device_state are seen, and the step's buffers are not touched.  MI_RAY_BRUTE_FORCE tests every ray against every
  * candidate instead (same answers; a yardstick, and cheaper for a handful of colliders).
@@ -294,6 +294,42 @@ int mi_raycast_batch(mi_world* w, uint32_t numRays, const float* dRays, uint32_t
 /* The same cast for callers without device memory of their own (a single pick: the C++ facade's castRay): rays and hits in HOST memory,
  * copied through staging buffers of the world around one mi_raycast_batch; returns after the hits have arrived. */
 int mi_raycast_host(mi_world* w, uint32_t numRays, const float* rays, uint32_t flags, mi_ray_hit* outHits);
+
+/* Ray sensors mounted on bodies: mi_raycast_batch for rays given in a body's frame, each with a range of bodies it does not see, and
+ * with the hit normal.  One call on the world's stream with no host synchronisation; nothing is pushed and no accumulator is written;
+ * the flags are the MI_RAY_* flags with unchanged meaning.  (The reference has no counterpart: the rule is this project's.)
+ * Mount: `mount` is a body index; origin and direction are in that body's frame at its current pose (the pose array the cast itself
+ * reads, so poses written through mi_device_state are seen).  The world ray is origin = rot * origin + pos, direction = rot * direction;
+ * maxT and enabled carry over.  mount == MI_STATIC_BODY: the ray is in world space already and is taken bit for bit.  Any other mount
+ * >= the number of bodies, a deleted body and, in a slab run, a body not simulated here switch the ray off: its record and its world
+ * ray are all zero.  dOutWorldRays (device, may be NULL) receives 8 floats per ray, the world ray in mi_raycast_batch's input layout.
+ * Exclusion: the colliders of the bodies b with b - excludeFirst < excludeCount, in uint32 arithmetic (b - excludeFirst wraps), are no
+ * candidates of this ray: a range that runs past the last body is simply cut, excludeCount == 0 excludes nothing.  Static colliders and
+ * the terrain are never excluded.
+ * Hit: `hit` is what mi_raycast_batch reports for the world ray against the remaining candidates (the tests, 0 <= t <= maxT, smallest
+ * t, then lowest collider index, terrain only if strictly closer, the triangle id in reserved, the point); with excludeCount == 0 its 32
+ * bytes are those of mi_raycast_batch on dOutWorldRays.
+ * Normal: the outward normal of the surface at the hit, not flipped towards the ray; zero for a miss.  It is evaluated in the
+ * collider's frame at p = local origin + t * local direction (the local hit the point is made from) and rotated to world space by the
+ * pose's rotation; for an OBB and a hull it is evaluated in the shape's own frame and rotated by the shape's quaternion first.
+ *   sphere (c, r)       noz(p - c)
+ *   capsule (a, b, r)   s = clamp(dot(p - a, b - a) / dot(b - a, b - a), 0, 1) (0 if a == b); noz(p - (a + s (b - a)))
+ *   cylinder (a, b, r)  u = noz(b - a), h = |b - a|, y = dot(p - a, u), rho = (p - a) - y u; cap depth dc = min(y, h - y), side depth
+ *                       ds = r - |rho|; if dc < ds the cap's normal (+u if y > h / 2, else -u), otherwise noz(rho): a tie goes to the side
+ *   AABB (lo, hi)       q = p - (lo + hi) / 2, e = (hi - lo) / 2; the axis k with the largest |q_k| - e_k, the lowest k on a tie; sign(q_k) on it
+ *   OBB                 the AABB rule for (-radius, radius) in the box's frame
+ *   hull                noz(cross(b - a, c - a)) of the triangle that supplied t (the lowest triangle index on a tie)
+ *   terrain             noz(cross(b - a, c - a)) of the hit triangle (a, b, c) as the hit rule above forms it: its y component is positive
+ *                       for both triangles of a cell, also for a ray from below; no pose rotation
+ * The normal follows the reported point also where the reference's tests report a point that is not on the surface: an origin inside a
+ * sphere (t = 0: the normal points from the centre to the origin; zero at the centre itself) and the cylinder's radially-inside case
+ * (t = 0 without a cap disk).  The rule is defined for every p.
+ * mi_raycast_sensors_host: rays, hits and world rays in HOST memory, staged through buffers of the world as mi_raycast_host does;
+ * returns after the hits have arrived. */
+typedef struct mi_sensor_ray { float origin[3], maxT, direction[3], enabled; uint32_t mount, excludeFirst, excludeCount, reserved; } mi_sensor_ray; /* 48 bytes */
+typedef struct mi_sensor_hit { mi_ray_hit hit; float normal[3], reserved; } mi_sensor_hit;                                                     /* 48 bytes */
+int mi_raycast_sensors(mi_world* w, uint32_t numRays, const mi_sensor_ray* dRays, uint32_t flags, mi_sensor_hit* dOutHits, float* dOutWorldRays);
+int mi_raycast_sensors_host(mi_world* w, uint32_t numRays, const mi_sensor_ray* rays, uint32_t flags, mi_sensor_hit* outHits, float* outWorldRays);
 
 /* Spatial-slab runs (one world per GPU holding ALL bodies, each simulating its slab + ghosts): copy the whole pose / velocity arrays
  * (layout as mi_device_pointers) to / from caller-owned DEVICE buffers, and set the per-body simulate mask (1 byte per body, device
