@@ -649,9 +649,9 @@ int mi_debug_read_replay_batches(mi_world* world, uint32_t* outEntries) { CHECK_
 int mi_debug_flow_trace(mi_world* world, int enable, unsigned long long* out, uint32_t numSlots)
 {
 	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
-	const size_t rows = (size_t)CL_MAX_TASKS * 16u;
-	if (enable && !W->flowTrace.p) { W->flowTrace.ensure(rows * 32, W->stream); if (!W->flowTrace.p) return W->lastError; MI_CHECK(hipMemsetAsync(W->flowTrace.p, 0, sizeof(u64) * rows * 32, W->stream)); }
-	if (out && W->flowTrace.p) d2h(W, out, W->flowTrace.p, sizeof(u64) * 32 * std::min<size_t>(numSlots, rows));
+	const size_t rows = (size_t)CL_MAX_TASKS * CL_TRACE_ROWS;
+	if (enable && !W->flowTrace.p) { W->flowTrace.ensure(rows * CL_TRACE_WORDS, W->stream); if (!W->flowTrace.p) return W->lastError; MI_CHECK(hipMemsetAsync(W->flowTrace.p, 0, sizeof(u64) * rows * CL_TRACE_WORDS, W->stream)); }
+	if (out && W->flowTrace.p) d2h(W, out, W->flowTrace.p, sizeof(u64) * CL_TRACE_WORDS * std::min<size_t>(numSlots, rows));
 	if (!enable) W->flowTrace.release();
 	return W->lastError;
 }

@@ -1,5 +1,5 @@
 // Joint constraint solves (sequential impulses on the per-joint update record written by k_*_init), shared by the launch-per-colour
-// joint kernels (k_joints.hip) and the LDS cluster sweep (k_cluster.hip), which runs them on body velocities held in LDS.
+// joint kernels (k_joints.hip) and the LDS cluster sweep (k_cluster_solve.hip), which runs them on body velocities held in LDS.
 // Scalar formulations of the reference: constraints.cpp:189-264 (distance), 460-528 (ball), 736-823 (fixed), 1079-1307 (hinge),
 // 1782-2070 (cone-twist), 2638-2846 (slider).  `o` is the joint's update record (layouts: k_joints.hip), v the two bodies'
 // velocities, IA / IB their world-space inverse inertia.

@@ -1,5 +1,5 @@
 // Contact rows of the projected Gauss-Seidel sweep, shared by the launch-per-colour sweep (k_solver.hip) and the LDS cluster
-// sweep (k_cluster.hip): the SoA plane layout written by k_contact_init and the two-row solve of one contact (friction, then
+// sweep (k_cluster_solve.hip): the SoA plane layout written by k_contact_init and the two-row solve of one contact (friction, then
 // normal: reference constraints.cpp:3381-3449 / 3618-3709).
 //
 // Row form.  The reference evaluates the relative anchor velocity as (vB + wB x rB) - (vA + wA x rA) and projects it on the row
@@ -31,7 +31,7 @@ MI_DEV void loadRow(ContactRow& r, u32 k, u32 s, size_t rowCap, const float4* __
 // Quad form.  The cluster sweep solves a row with FOUR lanes, one per body vector (vA, wA, vB, wB), so the row velocity is the sum of
 // four 3-term partial dots, each accumulated z, y, x with fused multiply-adds and combined as (pA_lin + pA_ang) + (pB_lin + pB_ang)
 // with body A's terms negated in the operands; the impulse delta d is applied as x = fma(d, a, x) with the "apply vectors"
-// a = -(invMassA * dir), -JA, invMassB * dir, JB.  Every solver path (this scalar-lane restatement, the quad lanes of k_cluster.hip)
+// a = -(invMassA * dir), -JA, invMassB * dir, JB.  Every solver path (this scalar-lane restatement, the quad lanes of k_cluster_solve.hip)
 // evaluates exactly this expression tree, and so does the oracle (oracle/oconstraints.h: solveCollisionConstraintRowForm).
 MI_DEV float rowDot3(V3 x, V3 d) { float s = x.z * d.z; s = __builtin_fmaf(x.y, d.y, s); return __builtin_fmaf(x.x, d.x, s); }
 MI_DEV float rowVelocity(V3 d, V3 cA, V3 cB, V3 vA, V3 wA, V3 vB, V3 wB)

@@ -112,8 +112,9 @@ static constexpr CtrRange CTR_LAYOUT[] = // every entry of the enum, ascending
 	{ CTR_CL_NUM_TASKS, 5 }, { CTR_CL_STATUS, 1 }, { CTR_CL_SHARED, 1 }, { CTR_CL_PHASE_COUNT, 5 }, { CTR_CL_BBOX, 6 }, { CTR_CL_REMAIN, 6 }, { CTR_VALIDATE, 2 }, { CTR_NARROW_LIMITS, 5 },
 };
 constexpr bool ctrLayoutDisjoint() { u32 end = 0; for (const CtrRange& r : CTR_LAYOUT) { if (r.first < end) return false; end = r.first + r.words; } return end <= CTR_WORDS; }
+constexpr u32 ctrWords(u32 first) { for (const CtrRange& r : CTR_LAYOUT) if (r.first == first) return r.words; return 0; } // extent of the entry that begins at `first`
 static_assert(ctrLayoutDisjoint(), "CTR_*: an entry reaches into the next one (or past CTR_WORDS), or CTR_LAYOUT is not in ascending order");
-// Cluster sweep (k_cluster.hip): up to CL_MAX_PARTS partition phases + the rest phase; task key = phase * CL_MAX_TASKS + task.
+// Cluster sweep (cluster.h, k_cluster_*.hip): up to CL_MAX_PARTS partition phases + the rest phase; task key = phase * CL_MAX_TASKS + task.
 #define MI_REPLAY_WIDTH 8u // lanes of the reference's SIMD batches (constraints.cpp: CONSTRAINT_SIMD_WIDTH with AVX)
 #define CL_MAX_PARTS 4u
 #define CL_CURVE_PARTS 2u // curve phases a step uses; the component phase comes on top (phase index CL_CURVE_PARTS)
@@ -122,6 +123,8 @@ static_assert(ctrLayoutDisjoint(), "CTR_*: an entry reaches into the next one (o
 #define CL_BODY_STRIDE 4096u
 #define CL_MAX_JOINT_CLASSES 64u   // (type, colour) classes of joints the cluster sweep can run
 #define CL_TASK_MAX_JOINTS 512u    // joints per task (one lane each)
+#define CL_TRACE_ROWS 16u          // developer timeline (mi_debug_flow_trace): rows per task of k_cl_color and per workgroup of k_cl_solve (at most CL_MAX_TASKS of either) ...
+#define CL_TRACE_WORDS 32u         // ... of this many u64 stamps each
 #define MI_NUM_SCHEDULE_KEYS ((MI_MAX_COLORS + 1) * 4)
 
 // What the host knows about the last internal step.  The step after it is launched before the host has seen how it ended, so this
@@ -214,7 +217,7 @@ struct World
 	DevBuf<u32> epaList; DevBuf<float4> gjkSimplex; // GJK hits -> EPA work list (9 float4 per hit)
 	DevBuf<float4> rowPlanes, rowShared; DevBuf<float2> rowLambda; DevBuf<uint4> rowIds;
 	DevBuf<u64> flow;                     // cluster sweep: 32-byte hand-over record per (phase, shared body): two tagged 16-byte halves
-	// cluster sweep (k_cluster.hip)
+	// cluster sweep (cluster.h, k_cluster_*.hip)
 	bool validate = false;                // MI_PHYSICS_VALIDATE=1 / mi_enable_validation: NaN / Inf guard after every stage (the reference's VALIDATE macros, physics.cpp:807-926)
 	// replay of the reference's batch order (mi_debug_set_replay / MI_PHYSICS_REPLAY=1; a test facility: the whole contact sweep is ONE workgroup)
 	bool replayReferenceOrder = false; DevBuf<u32> replayEntries; std::vector<u32> replayHost; u32 replayBatches = 0;
@@ -235,7 +238,7 @@ struct World
 	DevBuf<u32> clRep, clJointTask, clJointPos, clJointCount, clJointStart, clJointList; DevBuf<uint4> clJointTable; DevBuf<uint2> clTaskJoints; DevBuf<u32> clJointClassStart;
 	bool useClusterJoints = true;         // MI_CLUSTER_NO_JOINTS=1: joints keep their per-colour launches (one cluster launch per iteration then)
 	u32 clNumJoints = 0, clNumJointClasses = 0; bool clJointsInCluster = false; // false: more (type, colour) classes than the kernel's table: joints keep their launches
-	DevBuf<u64> flowTrace;                // developer timeline (mi_debug_flow_trace): 32 x u64 per slot, allocated on request only
+	DevBuf<u64> flowTrace;                // developer timeline (mi_debug_flow_trace): CL_TRACE_WORDS x u64 per slot (a row; CL_TRACE_ROWS of them per task / workgroup), allocated on request only
 	u32 flowEpoch = 0;
 	// Safety net of the persistent kernels: if one gives up waiting (only possible when the GPU is shared with another persistent
 	// kernel), the step's velocity integration is skipped on the device and the host redoes solve + integration with the launch
@@ -333,8 +336,8 @@ void launch_solve_replay(World& w, u32 numBatches);
 void launch_solve_contacts_iteration(World& w, const u32* gridBlocks, u32 numColors, u32 firstTail, bool serialBucket);
 bool cluster_available(World& w);                          // sets up the cluster kernels' LDS budget once; false = this device cannot run them
 void launch_active_list(World& w, u32 numPairs);           // manifolds with contacts -> actIds (no colours)
-void launch_cluster_build(World& w, u32 numPairs);         // body order, tasks, local colouring, final slot order (k_cluster.hip)
-void launch_cluster_solve(World& w, u32 itBegin, u32 itEnd);
+void launch_cluster_build(World& w, u32 numPairs);         // body order, tasks, local colouring, final slot order (k_cluster_partition.hip, k_cluster_color.hip)
+void launch_cluster_solve(World& w, u32 itBegin, u32 itEnd); // iterations [itBegin, itEnd) of the sweep in one launch (k_cluster_solve.hip)
 bool cluster_solves_joints(const World& w);                // the cluster sweep of this step runs the joints too (one launch for all iterations)
 void launch_integrate_velocities(World& w, float dt);
 void launch_joint_init(World& w, float dt);

@@ -399,7 +399,7 @@ uint32_t mi_debug_num_replay_batches(mi_world* w);
 int mi_debug_read_replay_batches(mi_world* w, uint32_t* outEntries8PerBatch);
 /* Developer timeline of the cluster contact sweep: enable != 0 allocates it (16 rows of 32 u64 per workgroup of the solve launch), out (may be
  * NULL) receives numSlots rows: per task and iteration the wall-clock stamps (10 ns ticks) "shared bodies acquired" / "colours done", the cost of
- * every colour step of iteration 10, and the stages of the task's colouring (csrc/k_cluster.hip documents the rows; tests/cluster_timeline.py prints them). */
+ * every colour step of iteration 10, and the stages of the task's colouring (csrc/k_cluster_solve.hip documents the rows; tests/cluster_timeline.py prints them). */
 int mi_debug_flow_trace(mi_world* w, int enable, unsigned long long* out, uint32_t numSlots);
 
 #ifdef __cplusplus

@@ -1,4 +1,4 @@
-"""The cluster contact sweep (k_cluster.hip: spatial tasks solved out of LDS by one workgroup each, bodies handed between tasks
+"""The cluster contact sweep (k_cluster_*.hip: spatial tasks solved out of LDS by one workgroup each, bodies handed between tasks
 through tagged records) against the CPU oracle in follow mode, on worlds large enough for many tasks and several phases, at the
 benchmark's full size, with tiny tasks (many phases, a full rest task), through an injected give-up, and against the
 launch-per-colour fallback.  The order differs between the two device sweeps, so they are not compared with each other bit for bit:
