@@ -74,6 +74,23 @@ SENSOR_RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("maxT", "<f4"), ("direction"
 SENSOR_HIT_DTYPE = np.dtype([("t", "<f4"), ("collider", "<u4"), ("body", "<u4"), ("hit", "<u4"), ("point", "<f4", 3), ("reserved", "<f4"),
                              ("normal", "<f4", 3), ("reserved2", "<f4")])
 STATIC_BODY = 0xFFFFFFFF   # mi_ray_hit.body of a collider without a rigid body (MI_STATIC_BODY)
+
+
+class ContactSensor(C.Structure):
+    """struct mi_contact_sensor (include/mi_physics.h): a body and the partners whose contacts count, 16 bytes"""
+    _fields_ = [("body", C.c_uint32), ("partners", C.c_uint32), ("excludeFirst", C.c_uint32), ("excludeCount", C.c_uint32)]
+
+
+class ContactReading(C.Structure):
+    """struct mi_contact_reading (include/mi_physics.h): what the last step's contacts did to the sensor's body, 48 bytes"""
+    _fields_ = [("impulse", C.c_float * 3), ("normalImpulse", C.c_float), ("angularImpulse", C.c_float * 3), ("numContacts", C.c_uint32),
+                ("numManifolds", C.c_uint32), ("strongestPartner", C.c_uint32), ("valid", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+CONTACT_SENSOR_DTYPE = np.dtype([("body", "<u4"), ("partners", "<u4"), ("excludeFirst", "<u4"), ("excludeCount", "<u4")])
+CONTACT_READING_DTYPE = np.dtype([("impulse", "<f4", 3), ("normalImpulse", "<f4"), ("angularImpulse", "<f4", 3), ("numContacts", "<u4"),
+                                  ("numManifolds", "<u4"), ("strongestPartner", "<u4"), ("valid", "<u4"), ("reserved", "<u4")])
+CONTACT_DYNAMIC, CONTACT_STATIC = 1, 2   # mi_contact_sensor.partners (MI_CONTACT_*)
 TERRAIN_COLLIDER = 0xFFFFFFFE   # mi_ray_hit.collider of a hit on the heightmap terrain (MI_TERRAIN_COLLIDER)
 
 
@@ -128,6 +145,7 @@ EXPORTED_SYMBOLS = [
     "mi_debug_set_replay", "mi_debug_num_replay_batches", "mi_debug_read_replay_batches",
     "mi_device_state", "mi_joint_device_pods", "mi_test_physics_interaction_batch", "mi_raycast_batch", "mi_raycast_host",
     "mi_raycast_sensors", "mi_raycast_sensors_host",
+    "mi_contact_sensors", "mi_contact_sensors_host", "mi_debug_read_contact_rows",
 ]
 
 
@@ -533,6 +551,32 @@ class World:
         out += (hits["normal"].copy(),)
         return out + (wr,) if world_rays else out
 
+    def contact_sensors(self, sensors, device=False):
+        """mi_contact_sensors: per sensor the impulses the contacts of the last internal step applied to its body, summed on the device
+        (the rule is in include/mi_physics.h).  sensors: a CONTACT_SENSOR_DTYPE array or a uint32 array [n, 4] = body, partners
+        (CONTACT_DYNAMIC | CONTACT_STATIC), excludeFirst, excludeCount.  Returns a CONTACT_READING_DTYPE array [n]: through the world's
+        staging buffers (mi_contact_sensors_host), or with device=True through device tensors of the caller's (mi_contact_sensors)."""
+        if isinstance(sensors, np.ndarray) and sensors.dtype == CONTACT_SENSOR_DTYPE:
+            rec = np.ascontiguousarray(sensors).reshape(-1)
+        else:
+            rec = np.ascontiguousarray(sensors, np.uint32).reshape(-1, 4).view(CONTACT_SENSOR_DTYPE).reshape(-1)
+        n = len(rec)
+        out = np.zeros(n, CONTACT_READING_DTYPE)
+        if not device:
+            self._check(self.lib.mi_contact_sensors_host(self.w, C.c_uint32(n), _p(rec) if n else None, _p(out) if n else None))
+            return out
+        if not n:
+            self._check(self.lib.mi_contact_sensors(self.w, C.c_uint32(0), None, None))
+            return out
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device())
+        d_in = torch.from_numpy(rec.view(np.uint32).reshape(n, 4).view(np.int32).copy()).to(dev)
+        d_out = torch.empty((n, 12), dtype=torch.float32, device=dev)
+        torch.cuda.current_stream(dev).synchronize()   # the sensors are on the device before the world's stream reads them
+        self._check(self.lib.mi_contact_sensors(self.w, C.c_uint32(n), C.c_void_p(d_in.data_ptr()), C.c_void_p(d_out.data_ptr())))
+        self.synchronize()
+        return d_out.cpu().numpy().view(CONTACT_READING_DTYPE).reshape(n)
+
     def accumulators(self):
         """Force and torque accumulators of every body [n, 6]: the pushes the next step will apply and clear."""
         out = np.zeros((self.num_bodies, 6), np.float32)
@@ -682,6 +726,14 @@ class World:
         n = len(self.schedule()[0])
         out = np.zeros((max(n, 1), 4, 2), np.float32)
         self._check(self.lib.mi_debug_read_contact_impulses(self.w, _p(out)))
+        return out[:n]
+
+    def contact_rows(self):
+        """The direction vectors of the last step's contact rows [positions, 4, 15], by position in schedule()'s order and contact:
+        t, rA x t, rB x t, rA x n, rB x n (mi_debug_read_contact_rows)."""
+        n = len(self.schedule()[0])
+        out = np.zeros((max(n, 1), 4, 15), np.float32)
+        self._check(self.lib.mi_debug_read_contact_rows(self.w, _p(out)))
         return out[:n]
 
     def joint_order(self, ctype, n):

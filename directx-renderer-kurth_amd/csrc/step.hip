@@ -405,7 +405,7 @@ int World::stepInternal(float dt, u32 iters)
 	if (!settlePreviousStep(*this, early)) return lastError;
 
 	StepRecord cur;                                        // this step; it becomes `last` below
-	cur.dt = dt; cur.iters = iters;
+	cur.dt = dt; cur.iters = iters; cur.bodies = nb;
 	cur.axis = hCounters[CTR_SAP_AXIS + (stats.numInternalSteps & 1u)]; // (written by the previous step's broadphase: kept for a recovery at the next step)
 	cur.truePairs = hCounters[CTR_NUM_PAIRS];
 	cur.slabOverflow = hCounters[CTR_PAIR_OVERFLOW] != 0u;

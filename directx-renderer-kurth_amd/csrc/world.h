@@ -141,6 +141,7 @@ struct StepRecord
 	bool unsettled = false;            // ... which is not yet known to have completed (CTR_FLOW_STATUS not looked at)
 	u32 jointPath = MI_JOINT_PATH_NONE;// where it solved its joints (mi_debug_read_joint_update)
 	bool counted = true;               // its counts are in the running sums (nothing to count before the first step)
+	u32 bodies = 0;                    // the bodies it ran with: its rows name the static dummy by this index (0: no step yet; mi_contact_sensors)
 };
 
 struct World
@@ -298,6 +299,10 @@ struct World
 	// mi_raycast_sensors (k_raycast_sensors.hip): per ray the world ray (2 x float4, used when the caller wants none back), the 32-byte
 	// record k_raycast and k_rc_terrain work on (2 x float4) and the exclusion range {first, count}; staging of mi_raycast_sensors_host
 	DevBuf<float4> rcSensorRays, rcSensorHits; DevBuf<uint2> rcSensorExclude; DevBuf<float4> rcSensorHostIn, rcSensorHostOut, rcSensorHostRays;
+	// mi_contact_sensors (k_contact_sensors.hip): rebuilt at every call.  Per body of the last step {wanted by a sensor, its manifolds, its
+	// first entry, fill cursor}; the entries (manifold slot << 32 | schedule position), a segment per wanted body, two per position at most;
+	// the bodies whose segment one lane does not sort; {entries handed out, length of that list}; staging of mi_contact_sensors_host
+	DevBuf<uint4> csBody; DevBuf<u64> csEntries; DevBuf<u32> csLarge, csMeta; DevBuf<float4> csHostIn, csHostOut;
 
 	World(int dev);
 	~World();
@@ -352,6 +357,7 @@ void launch_interaction_batch(World& w, u32 numRays, u32 firstBody, u32 bodiesPe
 void launch_raycast(World& w, u32 numRays, const float* dRays, u32 flags, mi_ray_hit* dOutHits, const uint2* dExclude = nullptr); // k_raycast.hip; dExclude: a body range per ray (mi_raycast_sensors)
 void launch_raycast_sensors(World& w, u32 numRays, const mi_sensor_ray* dRays, u32 flags, bool terrain, mi_sensor_hit* dOutHits, float* dOutWorldRays); // k_raycast_sensors.hip
 void launch_raycast_terrain(World& w, u32 numRays, const float* dRays, u32 flags, mi_ray_hit* dOutHits); // k_raycast_terrain.hip: after launch_raycast, on its records
+void launch_contact_sensors(World& w, u32 numSensors, const mi_contact_sensor* dSensors, mi_contact_reading* dOut, bool withRows); // k_contact_sensors.hip
 void launch_lerp_pose(World& w, float t);
 void csort_pairs_u32(World& w, const u32* keys, u32* keysOut, const u32* vals, u32* valsOut, u32 n, u32 numBuckets); // stable, keys < numBuckets <= 272
 void csort_pairs_u64(World& w, const u32* keys, u32* keysOut, const u64* vals, u64* valsOut, u32 n, u32 numBuckets);

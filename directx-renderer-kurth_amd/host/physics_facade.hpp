@@ -455,6 +455,24 @@ namespace mi
 		return true;
 	}
 
+	// What the contacts of the last internal step did to a rigid body (no counterpart in the reference's physics.h; include/mi_physics.h
+	// states the rule): the linear and angular impulse they applied to it, the sum of the normal impulses, how many contacts and manifolds
+	// were summed and the partner that pressed hardest.  partners: MI_CONTACT_DYNAMIC | MI_CONTACT_STATIC; the bodies excludeFirst ..
+	// excludeFirst + excludeCount - 1 are not counted (a robot's own links).  valid = false: no reading (no step yet, or the body is
+	// gone).  One sensor through mi_contact_sensors.
+	struct contact_impulse { bool valid = false; vec3 impulse, angularImpulse; float normalImpulse = 0.f; uint32_t numContacts = 0, numManifolds = 0, strongestPartner = 0; };
+	inline contact_impulse contactImpulse(const scene_entity& entity, uint32_t partners = MI_CONTACT_DYNAMIC | MI_CONTACT_STATIC, uint32_t excludeFirst = 0u, uint32_t excludeCount = 0u)
+	{
+		const mi_contact_sensor in{ entity.body(), partners, excludeFirst, excludeCount };
+		mi_contact_reading r{};
+		entity.scene->check(mi_contact_sensors_host(entity.scene->world, 1u, &in, &r), "contactImpulse");
+		contact_impulse out;
+		out.valid = r.valid != 0u;
+		out.impulse = vec3(r.impulse[0], r.impulse[1], r.impulse[2]); out.angularImpulse = vec3(r.angularImpulse[0], r.angularImpulse[1], r.angularImpulse[2]);
+		out.normalImpulse = r.normalImpulse; out.numContacts = r.numContacts; out.numManifolds = r.numManifolds; out.strongestPartner = r.strongestPartner;
+		return out;
+	}
+
 	// ---- void physicsStep(game_scene&, memory_arena&, float& timer, const physics_settings&, float dt), physics.h:405
 	inline void physicsStep(game_scene& scene, memory_arena& /*arena*/, float& timer, const physics_settings& settings, float dt)
 	{

@@ -331,6 +331,38 @@ typedef struct mi_sensor_hit { mi_ray_hit hit; float normal[3], reserved; } mi_s
 int mi_raycast_sensors(mi_world* w, uint32_t numRays, const mi_sensor_ray* dRays, uint32_t flags, mi_sensor_hit* dOutHits, float* dOutWorldRays);
 int mi_raycast_sensors_host(mi_world* w, uint32_t numRays, const mi_sensor_ray* rays, uint32_t flags, mi_sensor_hit* outHits, float* outWorldRays);
 
+/* Contact sensors: what the contacts of the LAST INTERNAL STEP did to a body, summed on the device from the rows its solve left behind.
+ * One call on the world's stream; like the ray entries it first settles a step whose cluster sweep is not yet known to have completed
+ * (after a give-up the readings describe the redone solve) and otherwise does not synchronise with the host.  The step's buffers are only
+ * read.  (The reference has no counterpart: the rule is this project's.)
+ * Which step: the last internal step as it was solved.  Poses or velocities written afterwards and a partner body deleted afterwards do
+ * not change a reading.  A world that has not stepped since it was created or restored, a sensor `body` >= the number of bodies (or a
+ * body added after that step), a deleted body and, in a slab run, a body not simulated here give an all-zero record (valid = 0).  A step
+ * without any manifold gives valid = 1 and zeros.
+ * Which manifolds: those of the step's schedule whose body A or body B is `body` and whose partner (the other one) passes the filter.  A
+ * partner that is the static dummy (static colliders, the heightmap terrain) counts iff partners & MI_CONTACT_STATIC.  Any other partner
+ * (dynamic or kinematic) counts iff partners & MI_CONTACT_DYNAMIC and not partner - excludeFirst < excludeCount in uint32 arithmetic
+ * (the subtraction wraps, as for mi_sensor_ray; excludeCount == 0 excludes nothing).
+ * The sums, over the contacts k < count of those manifolds, with the manifold's normal n, the contact's tangent t, its accumulated
+ * impulses ln (normal) and lt (tangent), s = +1 if `body` is B and -1 if it is A, and r = contact point - centre of gravity of `body`:
+ *   impulse        += s (ln n + lt t)              linear impulse applied to the body, N s, world frame
+ *   angularImpulse += s (ln (r x n) + lt (r x t))  angular impulse about its centre of gravity (the r x vectors are the rows' own)
+ *   normalImpulse  += ln
+ * numContacts and numManifolds count what was summed.  strongestPartner is the partner of the manifold with the largest sum of ln (summed
+ * ((ln0 + ln1) + ln2) + ln3), the lowest manifold slot on a tie, MI_STATIC_BODY for the dummy, 0 without a manifold.
+ * Arithmetic: float32 throughout, no fused multiply-add.  A term is formed per component as fl(fl(ln n_x) + fl(lt t_x)), negated for A,
+ * and the terms are added to the accumulator (which starts at 0) in ascending manifold slot (mi_debug_read_schedule's values), then
+ * ascending contact index; so a reading is a function of the step's rows alone: two calls, and two runs of the same world, return the
+ * same bytes.  Several sensors may name one body, with different filters.  numSensors == 0 launches nothing.
+ * mi_contact_sensors_host: sensors and readings in HOST memory, staged through buffers of the world; returns after the readings have
+ * arrived. */
+enum { MI_CONTACT_DYNAMIC = 1, MI_CONTACT_STATIC = 2 };
+typedef struct mi_contact_sensor { uint32_t body, partners, excludeFirst, excludeCount; } mi_contact_sensor; /* 16 bytes */
+typedef struct mi_contact_reading { float impulse[3], normalImpulse; float angularImpulse[3]; uint32_t numContacts;
+                                    uint32_t numManifolds, strongestPartner, valid, reserved; } mi_contact_reading; /* 48 bytes */
+int mi_contact_sensors(mi_world* w, uint32_t numSensors, const mi_contact_sensor* dSensors, mi_contact_reading* dOut);
+int mi_contact_sensors_host(mi_world* w, uint32_t numSensors, const mi_contact_sensor* sensors, mi_contact_reading* out);
+
 /* Spatial-slab runs (one world per GPU holding ALL bodies, each simulating its slab + ghosts): copy the whole pose / velocity arrays
  * (layout as mi_device_pointers) to / from caller-owned DEVICE buffers, and set the per-body simulate mask (1 byte per body, device
  * memory; 0 = body lives on another GPU: no AABB, no integration).  The halo exchange itself (RCCL send/recv of boundary bodies) is
@@ -379,6 +411,9 @@ int mi_debug_read_schedule(mi_world* w, uint32_t* outManifoldSlots, uint32_t* ou
 /* Accumulated impulses of the last step's contacts: per schedule position (the order of mi_debug_read_schedule) 4 contacts x {normal, tangent}
  * impulse, 8 floats; contacts a manifold does not have read 0.  A copy of what the sweep left behind: it costs the step nothing. */
 int mi_debug_read_contact_impulses(mi_world* w, float* outImpulses4x2PerPosition);
+/* The direction vectors of the same rows: per schedule position 4 contacts x {t, rA x t, rB x t, rA x n, rB x n}, 15 floats each; contacts a
+ * manifold does not have read 0.  Also a plain copy. */
+int mi_debug_read_contact_rows(mi_world* w, float* outRows4x15PerPosition);
 int mi_debug_read_joint_order(mi_world* w, uint32_t type, uint32_t* outJointIds);
 /* The joint update records of the last step (what k_*_init wrote and the solve accumulated its impulses into): numJoints(type) records in
  * joint ORDER (mi_debug_read_joint_order), each MI_JOINT_UPDATE_FLOATS = {20, 20, 36, 56, 80, 72}[type] floats long (layouts: the comments of

@@ -1,0 +1,76 @@
+"""Developer tool (not part of bench.py): what contact sensors cost.
+
+    python tests/contact_sensor_bench.py [c4] [c3] [--settle STEPS] [--repeats N]
+
+c4: config 4, 256 ragdolls, one sensor per body (3 584), each blind to the 14 bodies of its own ragdoll, both partner classes.
+c3: config 3, the 100 k-body pile, one sensor per body, both partner classes.
+Per scene: time of one mi_contact_sensors call on device buffers (HIP events around the call on the world's stream, median of
+repeated calls after a warm-up, with the smallest and largest), and next to it the world's own step time measured the same way
+(mi_step_internal, median over the same number of steps), so the cost reads as a share of a step."""
+import argparse
+import ctypes
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import directx_renderer_kurth_amd as mi  # noqa: E402
+from directx_renderer_kurth_amd import scenes  # noqa: E402
+
+
+def time_calls(call, stream, repeats, warmup=3):
+    ms = []
+    for k in range(warmup + repeats):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(stream)
+        code = call()
+        b.record(stream)
+        b.synchronize()
+        assert code == 0, code
+        if k >= warmup:
+            ms.append(a.elapsed_time(b))
+    return float(np.median(ms)), float(np.min(ms)), float(np.max(ms))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("scenes", nargs="*", default=["c4", "c3"])
+    ap.add_argument("--settle", type=int, default=120)
+    ap.add_argument("--repeats", type=int, default=15)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("contact_sensor_bench: no GPU; there is nothing to measure on a CPU")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    for name in args.scenes:
+        s = scenes.c4_ragdolls(256) if name == "c4" else scenes.by_name(name)
+        w = s.instantiate(mi.World())
+        for _ in range(args.settle):
+            w.step_internal(s.dt)
+        w.synchronize()
+        nb = w.num_bodies
+        rec = np.zeros((nb, 4), np.uint32)
+        rec[:, 0], rec[:, 1] = np.arange(nb), mi.CONTACT_DYNAMIC | mi.CONTACT_STATIC
+        if name == "c4":
+            rec[:, 2], rec[:, 3] = 14 * (np.arange(nb) // 14), 14
+        stream = torch.cuda.ExternalStream(w.device_state().stream or 0, device=dev)
+        with torch.cuda.stream(stream):
+            d_in = torch.from_numpy(rec.view(np.int32)).to(dev)
+            d_out = torch.zeros((nb, 12), dtype=torch.float32, device=dev)
+            stream.synchronize()
+            step = time_calls(lambda: w.lib.mi_step_internal(w.w, ctypes.c_float(s.dt), ctypes.c_uint32(30)), stream, args.repeats)
+            w.synchronize()
+            call = time_calls(lambda: w.lib.mi_contact_sensors(w.w, ctypes.c_uint32(nb), ctypes.c_void_p(d_in.data_ptr()), ctypes.c_void_p(d_out.data_ptr())), stream, args.repeats)
+            stream.synchronize()
+            out = d_out.cpu().numpy().view(mi.CONTACT_READING_DTYPE).reshape(nb)
+        st = w.stats()
+        print("%s: %d bodies, %d sensors, %d manifolds in the last step; %d readings with contacts, %d contacts counted, longest segment %d" % (
+            name, nb, nb, st["numCollisions"], int((out["numManifolds"] > 0).sum()), int(out["numContacts"].sum()), int(out["numManifolds"].max())), flush=True)
+        print("  mi_contact_sensors %.1f us/call [%.1f, %.1f]; mi_step_internal %.1f us/step [%.1f, %.1f]; the call is %.1f %% of a step" % (
+            1e3 * call[0], 1e3 * call[1], 1e3 * call[2], 1e3 * step[0], 1e3 * step[1], 1e3 * step[2], 100.0 * call[0] / step[0]), flush=True)
+        w.close()
+
+
+if __name__ == "__main__":
+    main()
