@@ -91,6 +91,22 @@ CONTACT_SENSOR_DTYPE = np.dtype([("body", "<u4"), ("partners", "<u4"), ("exclude
 CONTACT_READING_DTYPE = np.dtype([("impulse", "<f4", 3), ("normalImpulse", "<f4"), ("angularImpulse", "<f4", 3), ("numContacts", "<u4"),
                                   ("numManifolds", "<u4"), ("strongestPartner", "<u4"), ("valid", "<u4"), ("reserved", "<u4")])
 CONTACT_DYNAMIC, CONTACT_STATIC = 1, 2   # mi_contact_sensor.partners (MI_CONTACT_*)
+class ProximityQuery(C.Structure):
+    """struct mi_proximity_query (include/mi_physics.h): one point of mi_proximity in the frame of body `mount`, 32 bytes"""
+    _fields_ = [("point", C.c_float * 3), ("radius", C.c_float), ("mount", C.c_uint32), ("excludeFirst", C.c_uint32), ("excludeCount", C.c_uint32),
+                ("enabled", C.c_uint32)]
+
+
+class ProximityReading(C.Structure):
+    """struct mi_proximity_reading (include/mi_physics.h): the nearest surface within the radius and the number of colliders within it, 48 bytes"""
+    _fields_ = [("distance", C.c_float), ("collider", C.c_uint32), ("body", C.c_uint32), ("found", C.c_uint32), ("point", C.c_float * 3),
+                ("numWithin", C.c_uint32), ("normal", C.c_float * 3), ("reserved", C.c_float)]
+
+
+PROXIMITY_QUERY_DTYPE = np.dtype([("point", "<f4", 3), ("radius", "<f4"), ("mount", "<u4"), ("excludeFirst", "<u4"), ("excludeCount", "<u4"), ("enabled", "<u4")])
+PROXIMITY_READING_DTYPE = np.dtype([("distance", "<f4"), ("collider", "<u4"), ("body", "<u4"), ("found", "<u4"), ("point", "<f4", 3), ("numWithin", "<u4"),
+                                    ("normal", "<f4", 3), ("reserved", "<f4")])
+PROX_STATIC, PROX_BRUTE_FORCE, PROX_COUNT = 1, 2, 4   # mi_proximity's flags (MI_PROX_*)
 TERRAIN_COLLIDER = 0xFFFFFFFE   # mi_ray_hit.collider of a hit on the heightmap terrain (MI_TERRAIN_COLLIDER)
 
 
@@ -146,6 +162,7 @@ EXPORTED_SYMBOLS = [
     "mi_device_state", "mi_joint_device_pods", "mi_test_physics_interaction_batch", "mi_raycast_batch", "mi_raycast_host",
     "mi_raycast_sensors", "mi_raycast_sensors_host",
     "mi_contact_sensors", "mi_contact_sensors_host", "mi_debug_read_contact_rows",
+    "mi_proximity", "mi_proximity_host",
 ]
 
 
@@ -550,6 +567,64 @@ class World:
             out += (hits["reserved"].view(np.uint32).copy(),)
         out += (hits["normal"].copy(),)
         return out + (wr,) if world_rays else out
+
+    def proximity(self, points, radius=np.inf, mount=None, exclude_first=None, exclude_count=None, static=True, brute_force=False, count=True,
+                  world_points=False, device=False):
+        """mi_proximity: per point the nearest collider surface within `radius` (signed distance, negative inside; closest point; outward
+        normal) and, with `count`, the number of colliders within it (the rule is in include/mi_physics.h; the heightmap is no candidate).
+        points [n, 3] in the frame of body mount[i] at its current pose (mount: an index or an array [n]; None / STATIC_BODY: world space);
+        radius: a number or an array [n], may be inf; blind to the colliders of the bodies exclude_first[i] ... + exclude_count[i] - 1.
+        `points` may also be a PROXIMITY_QUERY_DTYPE array (radius, mount and the exclusion arguments are then not used).
+        numpy queries return a PROXIMITY_READING_DTYPE array [n], with world_points=True a tuple with the world points [n, 4] = xyz, radius:
+        through the world's staging buffers (mi_proximity_host), or with device=True through device tensors of the caller's (mi_proximity).
+        A torch tensor on the device (float32, contiguous, [n, 8]: the bits of mi_proximity_query) is queried in place: returns one float32
+        tensor [n, 12] of mi_proximity_reading records (with world_points=True a tuple with the [n, 4] world points), enqueued on the
+        world's stream with no synchronisation.  (The tensor is recorded on that stream, as in raycast: release it before close().)"""
+        flags = (PROX_STATIC if static else 0) | (PROX_BRUTE_FORCE if brute_force else 0) | (PROX_COUNT if count else 0)
+        if not isinstance(points, np.ndarray) and type(points).__module__.startswith("torch"):
+            import torch
+            q = points
+            if not q.is_cuda or q.dtype != torch.float32 or q.dim() != 2 or q.shape[1] != 8 or not q.is_contiguous():
+                raise ValueError("proximity: a device tensor must be float32, contiguous and [n, 8]")
+            ext = torch.cuda.ExternalStream(self.device_state().stream or 0, device=q.device)
+            ext.wait_stream(torch.cuda.current_stream(q.device))   # the queries were written on the caller's stream
+            with torch.cuda.stream(ext):
+                out = torch.empty((q.shape[0], 12), dtype=torch.float32, device=q.device)
+                wp = torch.empty((q.shape[0], 4), dtype=torch.float32, device=q.device) if world_points else None
+                self._check(self.lib.mi_proximity(self.w, C.c_uint32(q.shape[0]), C.c_void_p(q.data_ptr()), C.c_uint32(flags), C.c_void_p(out.data_ptr()),
+                                                  C.c_void_p(wp.data_ptr()) if world_points else None))
+            q.record_stream(ext)
+            torch.cuda.current_stream(q.device).wait_stream(ext)   # stream order, not a host synchronisation
+            return (out, wp) if world_points else out
+        if isinstance(points, np.ndarray) and points.dtype == PROXIMITY_QUERY_DTYPE:
+            rec = np.ascontiguousarray(points).reshape(-1)
+        else:
+            pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+            rec = np.zeros(len(pts), PROXIMITY_QUERY_DTYPE)
+            rec["point"], rec["radius"], rec["enabled"] = pts, np.asarray(radius, np.float32), 1
+            rec["mount"] = STATIC_BODY if mount is None else np.asarray(mount, np.uint32)
+            rec["excludeFirst"] = 0 if exclude_first is None else np.asarray(exclude_first, np.uint32)
+            rec["excludeCount"] = 0 if exclude_count is None else np.asarray(exclude_count, np.uint32)
+        n = len(rec)
+        out, wp = np.zeros(n, PROXIMITY_READING_DTYPE), np.zeros((n, 4), np.float32)
+        if not device:
+            self._check(self.lib.mi_proximity_host(self.w, C.c_uint32(n), _p(rec) if n else None, C.c_uint32(flags), _p(out) if n else None, _p(wp) if (n and world_points) else None))
+        elif not n:
+            self._check(self.lib.mi_proximity(self.w, C.c_uint32(0), None, C.c_uint32(flags), None, None))
+        else:
+            import torch
+            dev = torch.device("cuda", torch.cuda.current_device())
+            d_in = torch.from_numpy(rec.view(np.int32).reshape(n, 8).copy()).to(dev)
+            d_out = torch.empty((n, 12), dtype=torch.float32, device=dev)
+            d_wp = torch.empty((n, 4), dtype=torch.float32, device=dev) if world_points else None
+            torch.cuda.current_stream(dev).synchronize()   # the queries are on the device before the world's stream reads them
+            self._check(self.lib.mi_proximity(self.w, C.c_uint32(n), C.c_void_p(d_in.data_ptr()), C.c_uint32(flags), C.c_void_p(d_out.data_ptr()),
+                                              C.c_void_p(d_wp.data_ptr()) if world_points else None))
+            self.synchronize()
+            out = d_out.cpu().numpy().view(PROXIMITY_READING_DTYPE).reshape(n)
+            if world_points:
+                wp = d_wp.cpu().numpy()
+        return (out, wp) if world_points else out
 
     def contact_sensors(self, sensors, device=False):
         """mi_contact_sensors: per sensor the impulses the contacts of the last internal step applied to its body, summed on the device

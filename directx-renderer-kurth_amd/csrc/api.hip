@@ -409,6 +409,37 @@ int mi_raycast_sensors_host(mi_world* world, uint32_t numRays, const mi_sensor_r
 	return W->lastError;
 }
 
+// ---- proximity sensors (the rule: include/mi_physics.h; the tests: point_tests.h; the walk: k_proximity.hip) ----
+int mi_proximity(mi_world* world, uint32_t numQueries, const mi_proximity_query* dQueries, uint32_t flags, mi_proximity_reading* dOut, float* dOutWorldPoints)
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	W->resolvePendingFlow();
+	W->upload();
+	if (!numQueries) return W->lastError;
+	if (!dQueries || !dOut) return MI_ERR_INVALID_ARGUMENT;
+	if (!W->interactTablesValid) W->buildInteractTables();
+	if (W->lastError) return W->lastError;
+	launch_proximity(*W, numQueries, dQueries, flags, dOut, dOutWorldPoints);
+	return W->lastError;
+}
+
+int mi_proximity_host(mi_world* world, uint32_t numQueries, const mi_proximity_query* queries, uint32_t flags, mi_proximity_reading* out, float* outWorldPoints)
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	if (!numQueries) return mi_proximity(world, 0, nullptr, flags, nullptr, nullptr);
+	if (!queries || !out) return MI_ERR_INVALID_ARGUMENT;
+	W->pxHostIn.ensure(2 * (size_t)numQueries, W->stream); W->pxHostOut.ensure(3 * (size_t)numQueries, W->stream);
+	if (outWorldPoints) W->pxHostPoints.ensure(numQueries, W->stream);
+	if (W->lastError) return W->lastError;
+	MI_CHECK(hipMemcpyAsync(W->pxHostIn.p, queries, sizeof(mi_proximity_query) * (size_t)numQueries, hipMemcpyHostToDevice, W->stream));
+	int e = mi_proximity(world, numQueries, (const mi_proximity_query*)W->pxHostIn.p, flags, (mi_proximity_reading*)W->pxHostOut.p, outWorldPoints ? (float*)W->pxHostPoints.p : nullptr);
+	if (e) return e;
+	MI_CHECK(hipMemcpyAsync(out, W->pxHostOut.p, sizeof(mi_proximity_reading) * (size_t)numQueries, hipMemcpyDeviceToHost, W->stream));
+	if (outWorldPoints) MI_CHECK(hipMemcpyAsync(outWorldPoints, W->pxHostPoints.p, 16 * (size_t)numQueries, hipMemcpyDeviceToHost, W->stream));
+	MI_CHECK(hipStreamSynchronize(W->stream));
+	return W->lastError;
+}
+
 // ---- contact sensors (the rule: include/mi_physics.h; the reduction: k_contact_sensors.hip) ----
 int mi_contact_sensors(mi_world* world, uint32_t numSensors, const mi_contact_sensor* dSensors, mi_contact_reading* dOut)
 {

@@ -18,30 +18,8 @@
 void prim_sort_pairs_u32(World& w, const u32* kin, u32* kout, const u32* vin, u32* vout, u32 n, u32 bits);
 
 
-// ---- header words of World::rcCount (zeroed before every build; every accumulated word has 0 as its neutral element) ----
-enum
-{
-	RC_N = 0,        // candidates
-	RC_NEG_MIN = 1,  // 3 words: max of rcOrdered(-centre): the lower bound of the box centres
-	RC_MAX = 4,      // 3 words: max of rcOrdered(centre)
-	RC_DIAG = 7,     // float bits: largest diagonal of a padded leaf box
-	RC_ABS = 8,      // float bits: largest |coordinate| of a padded leaf box
-	RC_HEADER = 16,  // the arrival counters of the internal nodes follow
-};
-#define RC_LEAF 0x80000000u
-#define RC_NO_PARENT 0xFFFFFFFFu
-#define RC_NOT_A_CANDIDATE (1u << 30)
-#define RC_KEY_BITS 30
-// Depth of the tree = length of the longest chain of internal nodes.  Going down, the length of the common prefix of a node's range
-// grows strictly; the prefix is counted over the 30 key bits and then, for equal keys, over the 32 bits of the sorted position.  The
-// root's range has a prefix of >= 0 key bits and a node with two different leaves one of <= 61, so a chain has <= 62 nodes, and
-// the stack, which holds one pending sibling per node of the chain, <= 62 entries.
-#define RC_STACK 64
-static_assert(RC_KEY_BITS + 32 <= RC_STACK, "k_raycast's stack holds one entry per level of the tree: key bits + position bits");
-
 // Leaf pad, per axis: RC_PAD_ULPS ulps of (largest |coordinate| of the box + its diagonal) + RC_PAD_FLOOR.  Slack of the slab test:
 // RC_SLACK_ULPS ulps of (|origin| + largest |coordinate| of the scene) in space, RC_SLACK_REL of the distance in t.  DESIGN.md derives them.
-#define RC_EPS 1.1920929e-7f
 #define RC_PAD_ULPS 8.f
 #define RC_PAD_FLOOR 1e-5f
 #define RC_SLACK_ULPS 16.f
@@ -137,7 +115,7 @@ __global__ void __launch_bounds__(256) k_rc_keys(u32 nc, const float4* __restric
 
 // One internal node: 64 bytes = the boxes of its two children {min xyz, max xyz} x 2 (written by k_rc_fit), their ids (a leaf: RC_LEAF |
 // collider index) and two unused words.  Node 0 is the root.
-#define RC_NODE_WORDS 16u
+// (RC_NODE_WORDS = 16: raycast_shared.h)
 // Common prefix of the sorted keys i and j (Karras 2012, section 4): -1 outside the list; equal keys go on with their positions.
 MI_DEV int rcDelta(const u32* __restrict__ keys, int n, int i, int j)
 {
@@ -328,29 +306,24 @@ static void rcLaunchCast(World& w, u32 numRays, const float* dRays, mi_ray_hit* 
 			w.colLocal.p, hulls, w.rcCount.p, (const float4*)w.rcNodes.p, w.rcValsSorted.p, w.rcLeafBox.p, (const uint2*)nullptr);
 }
 
-// dExclude: NULL, or one {first, count} body range per ray (mi_raycast_sensors): the colliders of those bodies are no candidates of that ray.
-void launch_raycast(World& w, u32 numRays, const float* dRays, u32 flags, mi_ray_hit* dOutHits, const uint2* dExclude)
+// The tree over the current candidates in World::rc*, enqueued on the world's stream: what mi_raycast_batch and mi_proximity both walk.
+// brute: only the leaves (candidate flags, padded boxes, header words), which is all a brute-force walk reads.
+RcBuild launch_raycast_build(World& w, bool withStatic, bool brute)
 {
-	const bool withStatic = (flags & MI_RAY_STATIC) != 0, brute = (flags & MI_RAY_BRUTE_FORCE) != 0;
-	// what the host knows of the candidates (a slab's simulate mask can only take some away): none = every ray misses, nothing is built
+	// what the host knows of the candidates (a slab's simulate mask can only take some away): none = nothing is built
 	u32 hostCandidates = 0;
 	for (const World::HCollider& c : w.colliders) if (c.zoneType == 0u && (c.body == MI_STATIC_BODY ? withStatic : !w.bodies[c.body].removed)) hostCandidates++;
-	if (!hostCandidates || !w.nc) { MI_CHECK(hipMemsetAsync(dOutHits, 0, sizeof(mi_ray_hit) * (size_t)numRays, w.stream)); return; }
+	if (!hostCandidates || !w.nc) return RC_BUILD_NO_CANDIDATES;
 	const u32 nc = w.nc;
 	w.rcLeafBox.ensure(2 * (size_t)nc, w.stream); w.rcCount.ensure(RC_HEADER + (size_t)nc, w.stream);
 	w.rcKeys.ensure(nc, w.stream); w.rcKeysSorted.ensure(nc, w.stream); w.rcVals.ensure(nc, w.stream); w.rcValsSorted.ensure(nc, w.stream);
 	w.rcNodes.ensure(4 * (size_t)nc, w.stream); w.rcParentInt.ensure(nc, w.stream); w.rcParentLeaf.ensure(nc, w.stream);
-	if (w.lastError) return;
-	const RcHulls hulls{ w.hullVerts.p, w.hullTris.p, w.hullTriRange.p };
+	if (w.lastError) return RC_BUILD_FAILED;
 	const u32 blocks = (nc + 255u) / 256u;
 	MI_CHECK(hipMemsetAsync(w.rcCount.p, 0, sizeof(u32) * (brute ? (size_t)RC_HEADER : RC_HEADER + (size_t)nc), w.stream));
 	hipLaunchKernelGGL(k_rc_leaves, dim3(std::min(blocks, 256u)), dim3(256), 0, w.stream, nc, w.nb, withStatic ? 1u : 0u, w.colLocal.p, w.pose.p, w.colStaticPose.p,
 		w.aliveMask.p, w.simMask.p, w.hullInfo.p, w.rcLeafBox.p, w.rcCount.p);
-	if (brute)
-	{
-		rcLaunchCast<true>(w, numRays, dRays, dOutHits, hulls, dExclude);
-		return;
-	}
+	if (brute) return RC_BUILD_DONE;
 	hipLaunchKernelGGL(k_rc_keys, dim3(blocks), dim3(256), 0, w.stream, nc, w.rcLeafBox.p, w.rcCount.p, w.rcKeys.p, w.rcVals.p);
 	prim_sort_pairs_u32(w, w.rcKeys.p, w.rcKeysSorted.p, w.rcVals.p, w.rcValsSorted.p, nc, RC_KEY_BITS + 1);
 	if (hostCandidates > 1u)
@@ -359,5 +332,17 @@ void launch_raycast(World& w, u32 numRays, const float* dRays, u32 flags, mi_ray
 		hipLaunchKernelGGL(k_rc_tree, dim3(treeBlocks), dim3(256), 0, w.stream, w.rcCount.p, w.rcKeysSorted.p, w.rcValsSorted.p, (u32*)w.rcNodes.p, w.rcParentInt.p, w.rcParentLeaf.p);
 		hipLaunchKernelGGL(k_rc_fit, dim3(treeBlocks), dim3(256), 0, w.stream, w.rcCount.p, w.rcValsSorted.p, w.rcLeafBox.p, w.rcParentInt.p, w.rcParentLeaf.p, (float*)w.rcNodes.p, w.rcCount.p + RC_HEADER);
 	}
-	rcLaunchCast<false>(w, numRays, dRays, dOutHits, hulls, dExclude);
+	return RC_BUILD_DONE;
+}
+
+// dExclude: NULL, or one {first, count} body range per ray (mi_raycast_sensors): the colliders of those bodies are no candidates of that ray.
+void launch_raycast(World& w, u32 numRays, const float* dRays, u32 flags, mi_ray_hit* dOutHits, const uint2* dExclude)
+{
+	const bool brute = (flags & MI_RAY_BRUTE_FORCE) != 0;
+	const RcBuild built = launch_raycast_build(w, (flags & MI_RAY_STATIC) != 0, brute);
+	if (built == RC_BUILD_NO_CANDIDATES) { MI_CHECK(hipMemsetAsync(dOutHits, 0, sizeof(mi_ray_hit) * (size_t)numRays, w.stream)); return; } // every ray misses
+	if (built == RC_BUILD_FAILED) return;
+	const RcHulls hulls{ w.hullVerts.p, w.hullTris.p, w.hullTriRange.p };
+	if (brute) rcLaunchCast<true>(w, numRays, dRays, dOutHits, hulls, dExclude);
+	else rcLaunchCast<false>(w, numRays, dRays, dOutHits, hulls, dExclude);
 }

@@ -77,6 +77,7 @@ World::~World()
 	bodyColStart.release(); bodyColList.release(); hullTris.release(); hullTriRange.release();
 	rcHostRays.release(); rcHostHits.release(); rcLeafBox.release(); rcNodes.release(); rcCount.release(); rcKeys.release(); rcKeysSorted.release(); rcVals.release(); rcValsSorted.release(); rcParentInt.release(); rcParentLeaf.release(); rcTerrainTiles.release(); rcTerrainChunkRange.release();
 	rcSensorRays.release(); rcSensorHits.release(); rcSensorExclude.release(); rcSensorHostIn.release(); rcSensorHostOut.release(); rcSensorHostRays.release();
+	pxHostIn.release(); pxHostOut.release(); pxHostPoints.release();
 	csBody.release(); csEntries.release(); csLarge.release(); csMeta.release(); csHostIn.release(); csHostOut.release();
 	for (auto& e : stageEvents) if (e) (void)hipEventDestroy(e);
 	if (countersEvent) (void)hipEventDestroy(countersEvent);

@@ -455,6 +455,36 @@ namespace mi
 		return true;
 	}
 
+	// A proximity sensor fixed to a rigid body: localPoint is in the body's frame at its current pose; the nearest collider surface within
+	// `radius` of it (signed distance, negative inside; the closest point and the outward normal in world space; include/mi_physics.h
+	// states the rule), the number of colliders within the radius, or false.  excludeSelf: the body's own colliders are no candidates.
+	// The heightmap is no candidate.  One query through mi_proximity.
+	struct proximity_hit { float distance = 0.f; vec3 point, normal; uint32_t collider = 0, body = MI_STATIC_BODY, numWithin = 0; };
+	inline bool nearestSurface(game_scene& scene, const scene_entity& body, vec3 localPoint, float radius, proximity_hit& out, bool excludeSelf = true)
+	{
+		scene.flushStaticColliders();
+		mi_proximity_query in{};
+		in.point[0] = localPoint.x; in.point[1] = localPoint.y; in.point[2] = localPoint.z; in.radius = radius;
+		in.mount = body.body(); in.excludeFirst = in.mount; in.excludeCount = excludeSelf ? 1u : 0u; in.enabled = 1u;
+		mi_proximity_reading r{};
+		scene.check(mi_proximity_host(scene.world, 1u, &in, (uint32_t)(MI_PROX_STATIC | MI_PROX_COUNT), &r, nullptr), "nearestSurface");
+		if (!r.found) return false;
+		out.distance = r.distance; out.point = vec3(r.point[0], r.point[1], r.point[2]); out.normal = vec3(r.normal[0], r.normal[1], r.normal[2]);
+		out.collider = r.collider; out.body = r.body; out.numWithin = r.numWithin;
+		return true;
+	}
+	// How many colliders (rigid bodies' and static ones) lie within `radius` of a world-space point: 0 means that sphere of space is free.
+	inline uint32_t countWithin(game_scene& scene, vec3 worldPoint, float radius)
+	{
+		scene.flushStaticColliders();
+		mi_proximity_query in{};
+		in.point[0] = worldPoint.x; in.point[1] = worldPoint.y; in.point[2] = worldPoint.z; in.radius = radius;
+		in.mount = MI_STATIC_BODY; in.enabled = 1u;
+		mi_proximity_reading r{};
+		scene.check(mi_proximity_host(scene.world, 1u, &in, (uint32_t)(MI_PROX_STATIC | MI_PROX_COUNT), &r, nullptr), "countWithin");
+		return r.numWithin;
+	}
+
 	// What the contacts of the last internal step did to a rigid body (no counterpart in the reference's physics.h; include/mi_physics.h
 	// states the rule): the linear and angular impulse they applied to it, the sum of the normal impulses, how many contacts and manifolds
 	// were summed and the partner that pressed hardest.  partners: MI_CONTACT_DYNAMIC | MI_CONTACT_STATIC; the bodies excludeFirst ..

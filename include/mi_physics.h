@@ -331,6 +331,59 @@ typedef struct mi_sensor_hit { mi_ray_hit hit; float normal[3], reserved; } mi_s
 int mi_raycast_sensors(mi_world* w, uint32_t numRays, const mi_sensor_ray* dRays, uint32_t flags, mi_sensor_hit* dOutHits, float* dOutWorldRays);
 int mi_raycast_sensors_host(mi_world* w, uint32_t numRays, const mi_sensor_ray* rays, uint32_t flags, mi_sensor_hit* outHits, float* outWorldRays);
 
+/* Proximity sensors: for a point, possibly fixed to a body, the nearest collider surface within a radius and the number of colliders
+ * within it.  One call on the world's stream; like the ray entries it first settles a step whose cluster sweep is not yet known to have
+ * completed and otherwise does not synchronise with the host; no step buffer and no accumulator is written; numQueries == 0 launches
+ * nothing.  (The reference has no counterpart: the rule is this project's.)
+ * Mount and exclusion are mi_sensor_ray's: `point` is in the frame of body `mount` at its current pose (the pose array the call itself
+ * reads, so poses written through mi_device_state are seen), world point = rot * point + pos; mount == MI_STATIC_BODY: the point is in
+ * world space already and is taken bit for bit.  Any other mount >= the number of bodies, a deleted body, in a slab run a body not
+ * simulated here, and enabled == 0 switch the query off: its reading and its world point are all zero.  dOutWorldPoints (device, may be
+ * NULL) receives 4 floats per query: the world point and the radius.  The colliders of the bodies b with b - excludeFirst < excludeCount,
+ * in uint32 arithmetic (the subtraction wraps), are no candidates of this query; static colliders are never excluded.
+ * Candidates are mi_raycast_batch's: the colliders of alive bodies simulated here and, with MI_PROX_STATIC, those of entities without a
+ * rigid body; never force-field or trigger colliders, never cloth.  The heightmap terrain is NOT a candidate of this entry point.
+ * Distance: the signed Euclidean distance d from the world point to each candidate, negative inside, with the closest surface point c
+ * and the outward unit normal n there.  It is evaluated in the collider's own frame, p = conjugate(rot) * (world point - pos), for an
+ * OBB and a hull further through the conjugate of the shape's quaternion; c and n are rotated (and c translated) back the same way.
+ * Arithmetic is float32 without contraction in the order csrc/point_tests.h writes out.  unit(v) = v / |v|, and zero where |v| is 0.
+ *   sphere (ce, r)      v = p - ce; d = |v| - r; n = unit(v); c = ce + r n
+ *   capsule (a, b, r)   s = clamp(dot(p - a, b - a) / dot(b - a, b - a), 0, 1) (0 if a == b): the sensor normal rule's s; the sphere
+ *                       (a + s (b - a), r)
+ *   cylinder (a, b, r)  u = unit(b - a), h = |b - a|, y = dot(p - a, u), rho = (p - a) - y u, l = |rho|; dax = |y - h / 2| - h / 2,
+ *                       drad = l - r.  Inside or on the surface (dax <= 0 and drad <= 0): d = max(dax, drad); if dax > drad the nearer
+ *                       cap (the upper one iff y > h / 2): n = +u or -u, c = p + (h - y) u or p - y u; otherwise the side: n = unit(rho),
+ *                       c = a + y u + r n: a tie goes to the side, as in the sensor normal rule (on the axis itself n is zero).
+ *                       Outside: c = a + clamp(y, 0, h) u + (l > r ? r unit(rho) : rho); d = |p - c|; n = unit(p - c)
+ *   AABB (lo, hi)       q = p - (lo + hi) / 2, e = (hi - lo) / 2, w_k = |q_k| - e_k.  All w_k <= 0: the axis k with the largest w_k, the
+ *                       lowest k on a tie; d = w_k; n = sign(q_k) on axis k (the sign of +0 and -0 is positive); c = p with its k-th
+ *                       coordinate set to centre_k + sign(q_k) e_k.  Otherwise c = centre + clamp(q, -e, e); d = |p - c|; n = unit(p - c)
+ *   OBB                 the AABB rule for (-radius, radius) in the box's frame
+ *   hull                over its triangles f = (a, b, c) with n_f = unit(cross(b - a, c - a)): plane = max_f dot(p - a_f, n_f), the
+ *                       lowest f on a tie.  plane <= 0: d = plane; n = n_f; c = p - plane n_f.  Otherwise the closest point c_f of every
+ *                       triangle, with ab = b - a, ac = c - a, d1 = dot(ab, p - a), d2 = dot(ac, p - a), d3 = dot(ab, p - b),
+ *                       d4 = dot(ac, p - b), d5 = dot(ab, p - c), d6 = dot(ac, p - c), the first that applies of
+ *                         d1 <= 0 and d2 <= 0: a;   d3 >= 0 and d4 <= d3: b;
+ *                         d1 d4 - d3 d2 <= 0 and d1 >= 0 and d3 <= 0: a + (d1 / (d1 - d3)) ab;   d6 >= 0 and d5 <= d6: c;
+ *                         d5 d2 - d1 d6 <= 0 and d2 >= 0 and d6 <= 0: a + (d2 / (d2 - d6)) ac;
+ *                         d3 d6 - d5 d4 <= 0 and d4 - d3 >= 0 and d5 - d6 >= 0: b + ((d4 - d3) / ((d4 - d3) + (d5 - d6))) (c - b);
+ *                         else the face: p - dot(p - a, n_f) n_f;
+ *                       d = min_f |p - c_f|, the lowest f on a tie; c = that c_f; n = unit(p - c)
+ * Reading: a candidate is within iff d <= radius; radius may be +INFINITY; a negative or NaN radius finds nothing.  found = 1 and
+ * distance, collider, body, point (= c), normal (= n) describe the within-candidate with the smallest d, of equal d the one with the
+ * lowest collider index; body is MI_STATIC_BODY for a static collider.  With MI_PROX_COUNT numWithin is the number of within-candidates,
+ * without the flag 0.  With nothing within the whole record is zero.
+ * The candidates and the tree over them are mi_raycast_batch's, rebuilt from the current poses at every call in the same buffers;
+ * MI_PROX_BRUTE_FORCE asks every candidate instead (same bytes; a yardstick).  Calls of the two kinds may follow each other freely.
+ * mi_proximity_host: queries, readings and world points in HOST memory, staged through buffers of the world; returns after the
+ * readings have arrived. */
+enum { MI_PROX_STATIC = 1, MI_PROX_BRUTE_FORCE = 2, MI_PROX_COUNT = 4 };
+typedef struct mi_proximity_query { float point[3], radius; uint32_t mount, excludeFirst, excludeCount, enabled; } mi_proximity_query; /* 32 bytes */
+typedef struct mi_proximity_reading { float distance; uint32_t collider, body, found; float point[3]; uint32_t numWithin;
+                                      float normal[3], reserved; } mi_proximity_reading; /* 48 bytes */
+int mi_proximity(mi_world* w, uint32_t numQueries, const mi_proximity_query* dQueries, uint32_t flags, mi_proximity_reading* dOut, float* dOutWorldPoints);
+int mi_proximity_host(mi_world* w, uint32_t numQueries, const mi_proximity_query* queries, uint32_t flags, mi_proximity_reading* out, float* outWorldPoints);
+
 /* Contact sensors: what the contacts of the LAST INTERNAL STEP did to a body, summed on the device from the rows its solve left behind.
  * One call on the world's stream; like the ray entries it first settles a step whose cluster sweep is not yet known to have completed
  * (after a give-up the readings describe the redone solve) and otherwise does not synchronise with the host.  The step's buffers are only
