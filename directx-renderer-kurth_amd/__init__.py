@@ -768,7 +768,7 @@ class World:
         return int(out[0]), int(out[1])
 
     def narrow_limits(self):
-        """High-water marks of the GJK / EPA caps (k_narrow.hip: GJK_MAX_ITERATIONS, EPA_MAX_*) since the world was created, with the
+        """High-water marks of the GJK / EPA caps (narrow_gjk.h: GJK_MAX_ITERATIONS, k_narrow_gjk.hip: EPA_MAX_*) since the world was created, with the
         number of EPA runs that stopped at an out-of-memory exit; same keys as the oracle's stats()."""
         out = np.zeros(8, np.uint32)
         self._check(self.lib.mi_debug_narrow_limits(self.w, _p(out)))

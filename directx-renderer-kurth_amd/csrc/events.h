@@ -14,6 +14,7 @@ enum { EVENT_TRIGGER_ENTER = 0, EVENT_TRIGGER_LEAVE = 1, EVENT_COLLISION_BEGIN =
 
 struct PairSetView { u64* cur; u64* prev; u32 mask, shift; };
 struct EventSink { EventRec* events; u32* counters; u32 capacity, step; const uint8_t* slabCode; };
+EventSink sinkOf(World& w); // the world's event ring for this step (k_events.hip)
 // Slab worlds (one rank per GPU): a pair near a cut is simulated — and its overlap sets are kept — on both ranks.  Exactly one of
 // them REPORTS its events: the rank that owns the pair's dynamic body with the lower index (for a trigger: the body).  That rank
 // always simulates both bodies while they touch (the partner is its ghost); the sets themselves are not filtered, so a pair that stays

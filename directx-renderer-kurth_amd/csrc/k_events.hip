@@ -1,6 +1,7 @@
 // Force fields, trigger events, collision begin/end events (row N2 of SURVEY §8f) — reference physics.cpp:759-787, 952-1178.
 // None of this is launched for a world without force fields / triggers / enabled collision events.
 #include "events.h"
+#include "narrow.h" // KEY_ZONE: the pair manifolds end where its bucket starts
 #include <cstdlib>
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -88,7 +89,7 @@ __global__ void __launch_bounds__(256) k_collision_begin(u32* __restrict__ count
 	const float4* __restrict__ vel, const float4* __restrict__ cog, u32 nb, PairSetView set, EventSink sink, u32 emit)
 {
 	u32 slot = blockIdx.x * blockDim.x + threadIdx.x;
-	if (slot >= counters[CTR_BUCKET_START + 62]) return; // pair manifolds only: terrain contacts raise no events (physics.cpp:1049: colliderB < numColliders)
+	if (slot >= counters[CTR_BUCKET_START + KEY_ZONE]) return; // pair manifolds only: terrain contacts raise no events (physics.cpp:1049: colliderB < numColliders)
 	uint4 ids = manifolds[slot].ids;
 	u32 count = ids.z;
 	if (!count) return;

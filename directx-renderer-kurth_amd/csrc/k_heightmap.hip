@@ -6,11 +6,11 @@
 // one-contact manifold appended after the pair manifolds, so the colouring, the contact rows and the solver see nothing new.
 // Emission order per collider: chunk z, chunk x, cell z, cell x, triangle; the "lowest point under the terrain" contact last.
 #include "world.h"
+#include "narrow.h" // KEY_ZONE: the terrain manifolds start where the pair manifolds end
 #include "terrain_shared.h"
 #include <rocprim/rocprim.hpp>
 
 #define TERRAIN_SLOT 0x80000000u
-#define KEY_ZONE 62u
 
 struct TerrainContact { V3 point, normal; float depth; };
 

@@ -78,7 +78,7 @@ enum
 	CTR_FLOW_STATUS = 13,   // cluster sweep: non-zero = the launch could not run or a lane gave up waiting (result invalid): the host redoes the step
 	CTR_FLOW_PROBES = 14,   // always 0: no kernel counts probes any more; the word stays because mi_stats.flowProbes reports it (ABI)
 	CTR_EPA_COUNT_HULL = 15,// GJK hits among the hull pairs (their EPA work list grows from the end of epaList)
-	CTR_BUCKET_START = 16,  // 65 words: first slot of narrowphase bucket key b (tA*6+tB); [64] unused
+	CTR_BUCKET_START = 16,  // 65 words: first slot of narrowphase bucket key b (narrow.h: pairKey, KEY_ZONE, KEY_INVALID); [64] unused
 	CTR_KEY_START = 96,     // (MI_MAX_COLORS+1)*4 + 1 words: first schedule slot of key colour*4 + (4-count); last = numManifolds
 	CTR_COLOR_BARRIER = 360,// 4 words: grid barrier of the fused colouring kernel (arrivals, 3 x manifolds left)
 	CTR_SAP_AXIS = 368,     // 2 words: the reference sweep's sorting axis (collision_broad.cpp:443-444) for internal step k at [k & 1]: written by step k - 1 from its AABB centres, read by k_classify

@@ -412,7 +412,7 @@ static inline bool gjkIntersectionTest(const A& shapeA, const B& shapeB, gjk_sim
 // 24 points exist.  We keep the algorithm and the out-of-memory exits and size the arrays EPA_MAX_*;
 // g_epaMax* record the high-water marks so tests can assert the caps are never the binding limit.
 // ---------------------------------------------------------------------------------------------------
-// Same caps as the device kernels (k_narrow.hip).  Measured high-water marks with the reference's 1024-entry arrays on the golden
+// Same caps as the device kernels (narrow_gjk.h, k_narrow_gjk.hip).  Measured high-water marks with the reference's 1024-entry arrays on the golden
 // poses and the config-3/4 scenes: 98 triangles, 100 edges, 8 border edges, 16 GJK iterations — these caps never bind there.
 static const u32 EPA_MAX_POINTS = 24, EPA_MAX_TRIANGLES = 128, EPA_MAX_EDGES = 160, EPA_MAX_BORDER = 32;
 extern u32 g_epaMaxTriangles, g_epaMaxEdges, g_epaMaxBorder, g_epaOutOfMemory;

@@ -1,7 +1,7 @@
 """Float64 geometry of the world-space collider records (COLLIDER_DTYPE) and the collision edge-case batteries.
 
 This is an independent reference for the narrowphase: it shares no formula with the oracle or the device, only the record
-layout (k_narrow.hip asSphere / asCapsule / asBox / asObb / asHull).  Every value is computed in float64 on the float32 records.
+layout (narrow.h asSphere / asCapsule / asBox / asObb / asHull).  Every value is computed in float64 on the float32 records.
 
 Signed depth of a pair: d = min over unit n of h_A(n) + h_B(-n), h = support function.  d > 0: the shapes overlap and d is the
 penetration depth (minimum translation distance); d < 0: they are apart by -d.  n points from A to B (the contact normal's sense).
