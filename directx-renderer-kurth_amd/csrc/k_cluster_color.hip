@@ -5,7 +5,7 @@
 #define CL_LANES 1024u                    // k_cl_color
 #define CL_TASK_MAX_MANIFOLDS 2048u       // hard limits of k_cl_color's LDS tables (a task normally holds <= taskManifolds + one body's degree)
 #define CL_TASK_MAX_BODIES 4095u
-#define CL_HASH_SIZE 8192u
+#define CL_HASH_SIZE 8192u                // largest body hash; a task uses clHashSize(manifolds + joints) slots of it
 #define CL_KEY_HIST_WORDS 264u            // k_cl_color's histogram of the manifold keys colour * 4 + (4 - count): (CL_SERIAL_COLOR + 1) * 4 = 260 keys, in whole rows of 8 words
 static_assert(CL_KEY_HIST_WORDS >= (CL_SERIAL_COLOR + 1u) * 4u && CL_KEY_HIST_WORDS % 8u == 0u, "one histogram word per (colour or serial tail, contact count)");
 #define CL_TRACE_ROW_COLOR 14u            // developer timeline (mi_debug_flow_trace): the row of a task's CL_TRACE_ROWS that k_cl_color stamps (k_cl_solve documents the others)
@@ -16,6 +16,30 @@ static_assert(CL_TRACE_ROW_COLOR < CL_TRACE_ROWS, "k_cl_color's row lies inside 
 // (20 % of a mixed pile) out of most colours.  Then a pseudo-random priority (hash of the narrowphase slot and the round), then
 // the position inside the task, which makes the bid unique.
 MI_DEV u32 clBid(u32 slot, u32 count, u32 round, u32 i) { return (((4u - count) & 3u) << 22) | ((clHash(slot * 2654435761u + round) & 0x3FFu) << 12) | (i & 0xFFFu); } // 24 bits
+
+// Slots of a task's body hash: a power of two with at most every second slot taken (a manifold or joint brings two bodies at most), and
+// whole waves in the sweeps over it.  A task of 450 bodies clears and sweeps 4096 slots instead of all 8192.
+MI_DEV u32 clHashSize(u32 items) { u32 hs = 64u; while (hs < 4u * items && hs < CL_HASH_SIZE) hs <<= 1; return hs; }
+static_assert(2u * (CL_TASK_MAX_MANIFOLDS + CL_TASK_MAX_JOINTS) < CL_HASH_SIZE, "the largest task's bodies leave free slots in the largest hash");
+// Insert body g: whoever takes the slot fetches the body's phase mask and parks "shared" (touched in more than one phase) beside
+// the key, so that the sweep that hands out the local indices reads LDS only.
+MI_DEV void clHashInsert(u32* hKey, u32* hVal, u32 hashMask, u32 g, const u32* __restrict__ phaseMask)
+{
+	u32 h = clHash(g) & hashMask;
+	for (;;)
+	{
+		u32 old = atomicCAS(&hKey[h], 0u, g + 1u);
+		if (old == 0u) { hVal[h] = __popc(phaseMask[g]) > 1 ? 1u : 0u; break; }
+		if (old == g + 1u) break;
+		h = (h + 1u) & hashMask;
+	}
+}
+MI_DEV u32 clHashFind(const u32* hKey, const u32* hVal, u32 hashMask, u32 g)
+{
+	u32 h = clHash(g) & hashMask;
+	while (hKey[h] != g + 1u) h = (h + 1u) & hashMask;
+	return hVal[h];
+}
 
 // ---------------------------------------------------------------------------------------------------------------
 // Per task, one workgroup: local body table, local colouring, order by (colour, 4 - contacts), task header.
@@ -31,8 +55,8 @@ __global__ void __launch_bounds__(CL_LANES) k_cl_color(u32* __restrict__ counter
 	const u32* __restrict__ jointStart, const u32* __restrict__ jointList, const uint4* __restrict__ jointTable, uint2* __restrict__ taskJoints, u32* __restrict__ jointClassStart, u64* __restrict__ trace)
 {
 	extern __shared__ u32 clds[];
-	u32* hKey = clds;                                   // [CL_HASH_SIZE] global id + 1, 0 = empty
-	u32* hVal = hKey + CL_HASH_SIZE;                    // [CL_HASH_SIZE] local index
+	u32* hKey = clds;                                   // [CL_HASH_SIZE] global id + 1, 0 = empty; the task's first clHashSize() slots are in use
+	u32* hVal = hKey + CL_HASH_SIZE;                    // [CL_HASH_SIZE] shared or not, then the local index
 	u64* mask = (u64*)(hVal + CL_HASH_SIZE);            // [CL_TASK_MAX_BODIES + 1]
 	u32* claim = (u32*)(mask + CL_TASK_MAX_BODIES + 1); // [CL_TASK_MAX_BODIES + 1]
 	u32* mAB = claim + CL_TASK_MAX_BODIES + 1;          // [CL_TASK_MAX_MANIFOLDS] la | lb << 16
@@ -66,7 +90,8 @@ __global__ void __launch_bounds__(CL_LANES) k_cl_color(u32* __restrict__ counter
 		if (!n && !nj) { if (tid == 0) { T->first = first; T->count = 0; T->numBodies = 0; T->numShared = 0; T->numColors = 0; T->serialStart = 0; T->numRows = 0; } continue; }
 		if (n > CL_TASK_MAX_MANIFOLDS || nj > CL_TASK_MAX_JOINTS) { if (tid == 0) { atomicOr(&counters[CTR_CL_STATUS], 2u); T->first = first; T->count = 0; T->numBodies = 0; T->numShared = 0; T->numColors = 0; T->serialStart = 0; T->numRows = 0; } continue; }
 		u32 phase = key / CL_MAX_TASKS;
-		for (u32 h = tid; h < CL_HASH_SIZE; h += CL_LANES) hKey[h] = 0;
+		const u32 hashSize = clHashSize(n + nj), hashMask = hashSize - 1u; // (this task's: the one before may have used more or fewer slots)
+		for (u32 h = tid; h < hashSize; h += CL_LANES) hKey[h] = 0;
 		for (u32 h = tid; h < CL_KEY_HIST_WORDS + CL_MAX_JOINT_CLASSES + 1u + CL_SERIAL_COLOR + 2u; h += CL_LANES) hist[h] = 0;
 		if (tid == 0) { sNumShared = 0; sNumPrivate = 0; sMaxColor = 0; }
 		__syncthreads();
@@ -82,13 +107,7 @@ __global__ void __launch_bounds__(CL_LANES) k_cl_color(u32* __restrict__ counter
 			{
 				u32 g = e ? ids.y : ids.x;
 				if (g >= nb) continue;
-				u32 h = clHash(g) & (CL_HASH_SIZE - 1u);
-				for (;;)
-				{
-					u32 old = atomicCAS(&hKey[h], 0u, g + 1u);
-					if (old == 0u || old == g + 1u) break;
-					h = (h + 1u) & (CL_HASH_SIZE - 1u);
-				}
+				clHashInsert(hKey, hVal, hashMask, g, phaseMask);
 			}
 		}
 		for (u32 i = tid; i < nj; i += CL_LANES) // the joints' bodies: a limb in the air has joints and no contact
@@ -98,22 +117,16 @@ __global__ void __launch_bounds__(CL_LANES) k_cl_color(u32* __restrict__ counter
 			{
 				u32 g = e ? e4.w : e4.z;
 				if (g >= nb) continue;
-				u32 h = clHash(g) & (CL_HASH_SIZE - 1u);
-				for (;;)
-				{
-					u32 old = atomicCAS(&hKey[h], 0u, g + 1u);
-					if (old == 0u || old == g + 1u) break;
-					h = (h + 1u) & (CL_HASH_SIZE - 1u);
-				}
+				clHashInsert(hKey, hVal, hashMask, g, phaseMask);
 			}
 		}
 		__syncthreads();
-		for (u32 h = tid; h < CL_HASH_SIZE; h += CL_LANES) // (uniform trip count: the ballots below see whole waves)
+		for (u32 h = tid; h < hashSize; h += CL_LANES) // (hashSize is a multiple of 64: the ballots below see whole waves)
 		{
 			// local index = running count of the shared / private bodies: one LDS atomic per wave, not per body (same-address LDS
 			// atomics are served one lane at a time)
 			const bool has = hKey[h] != 0u;
-			const bool shared = has && __popc(phaseMask[hKey[h] - 1u]) > 1;
+			const bool shared = has && hVal[h] != 0u;
 			const u64 bs = __ballot(shared), bp = __ballot(has && !shared);
 			const u32 lane = tid & 63u;
 			u32 baseS = 0, baseP = 0;
@@ -132,7 +145,7 @@ __global__ void __launch_bounds__(CL_LANES) k_cl_color(u32* __restrict__ counter
 		if (tid == 0) sSharedBase = atomicAdd(&counters[CTR_CL_SHARED], numShared);
 		__syncthreads();
 		const u32 sharedBase = sSharedBase;
-		for (u32 h = tid; h < CL_HASH_SIZE; h += CL_LANES)
+		for (u32 h = tid; h < hashSize; h += CL_LANES)
 			if (hKey[h])
 			{
 				u32 v = hVal[h];
@@ -192,9 +205,7 @@ __global__ void __launch_bounds__(CL_LANES) k_cl_color(u32* __restrict__ counter
 					u32 g = e ? gy[r] : gx[r];
 					loc[e] = CL_LOCAL_STATIC;
 					if (g >= nb) continue;
-					u32 h = clHash(g) & (CL_HASH_SIZE - 1u);
-					while (hKey[h] != g + 1u) h = (h + 1u) & (CL_HASH_SIZE - 1u);
-					loc[e] = hVal[h];
+					loc[e] = clHashFind(hKey, hVal, hashMask, g);
 				}
 				mAB[i] = loc[0] | (loc[1] << 16);
 				mKey[i] = 0xFFFFFFFFu;
@@ -224,9 +235,7 @@ __global__ void __launch_bounds__(CL_LANES) k_cl_color(u32* __restrict__ counter
 					u32 g = e ? e4.w : e4.z;
 					loc[e] = CL_LOCAL_STATIC;
 					if (g >= nb) continue;
-					u32 h = clHash(g) & (CL_HASH_SIZE - 1u);
-					while (hKey[h] != g + 1u) h = (h + 1u) & (CL_HASH_SIZE - 1u);
-					loc[e] = hVal[h];
+					loc[e] = clHashFind(hKey, hVal, hashMask, g);
 				}
 				u32 p = atomicAdd(&jHist[min(e4.x >> 8, CL_MAX_JOINT_CLASSES - 1u)], 1u); // (order inside a class is free: its joints share no body)
 				taskJoints[jFirst + p] = make_uint2(ji, loc[0] | (loc[1] << 16));

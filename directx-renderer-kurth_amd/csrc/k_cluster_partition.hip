@@ -59,7 +59,8 @@ __global__ void __launch_bounds__(256) k_cl_keys(u32 nb, u32 numParts, ClShifts 
 	for (u32 p = 0; p < numParts; ++p)
 	{
 		u32 key = clSpread10((u32)q[0] + shifts.s[p][0]) | (clSpread10((u32)q[1] + shifts.s[p][1]) << 1) | (clSpread10((u32)q[2] + shifts.s[p][2]) << 2);
-		keys[(size_t)p * nb + i] = sim ? key : 0x3FFFFFFFu; // bodies simulated elsewhere sort last; no manifold refers to them
+		// bodies simulated elsewhere sort last; no manifold refers to them.  Bits 30-31: the curve, so that ONE sort orders all curves (clRefreshBodyOrder)
+		keys[(size_t)p * nb + i] = (sim ? key : 0x3FFFFFFFu) | (p << 30);
 		vals[(size_t)p * nb + i] = i;
 	}
 }
@@ -127,25 +128,27 @@ static_assert(CTR_CL_SHARED == CTR_CL_STATUS + ctrWords(CTR_CL_STATUS) && CTR_CL
 MI_DEV u32 clSubCounter(u32 block) { return block & (CL_SUBCOUNTERS - 1u); }
 // Equal-key wave append: the active lanes of a wave each append one entry to the cursor of their key.  Groups of equal keys first
 // (ballots only), then ALL the groups' leaders issue their atomics together: one round trip to the memory-side atomic unit per
-// wave, not one per distinct key.  block: the workgroup that handles the lane's manifold (clSubCounter).  Returns the lane's position.
-MI_DEV u32 clAppendByKey(u32* taskCount, u32 key, u32 block)
+// wave, not one per distinct key.  Returns the lane's position.  clAppendByCursor: the lanes name their cursor (a task key's
+// sub-counter) themselves; clAppendByKey: one workgroup handles all the wave's manifolds (block, clSubCounter), so equal keys are equal cursors.
+MI_DEV u32 clAppendByCursor(u32* taskCount, u32 cursor)
 {
 	u64 todo = __ballot(1), mine = 0;
 	const u32 lane = threadIdx.x & 63u;
 	while (todo)
 	{
 		u32 leader = (u32)__ffsll((long long)todo) - 1u;
-		u32 k0 = __shfl(key, leader);
-		u64 same = __ballot(key == k0) & todo;
-		if (key == k0) mine = same;
+		u32 c0 = __shfl(cursor, leader);
+		u64 same = __ballot(cursor == c0) & todo;
+		if (cursor == c0) mine = same;
 		todo &= ~same;
 	}
 	const u32 myLeader = (u32)__ffsll((long long)mine) - 1u, cnt = (u32)__popcll(mine);
 	u32 base = 0;
-	if (lane == myLeader) base = atomicAdd(&taskCount[key * CL_SUBCOUNTERS + clSubCounter(block)], cnt);
+	if (lane == myLeader) base = atomicAdd(&taskCount[cursor], cnt);
 	base = __shfl(base, myLeader);
 	return base + (u32)__popcll(mine & ((1ull << lane) - 1ull));
 }
+MI_DEV u32 clAppendByKey(u32* taskCount, u32 key, u32 block) { return clAppendByCursor(taskCount, key * CL_SUBCOUNTERS + clSubCounter(block)); }
 // Wave append to the left-over list (what the last curve phase leaves goes to the component phase), one atomic per wave.  Returns
 // the position of the lane's entry; the list holds leftCap entries.
 MI_DEV u32 clAppendLeft(u32* counters)
@@ -433,7 +436,9 @@ __global__ void __launch_bounds__(CL_ASSIGN_LANES) k_cl_comp_assign(u32* __restr
 		if (la == lb && compWeight[la] <= CL_COMP_MAX_WEIGHT) key = phase * CL_MAX_TASKS + clHash(la * 2654435761u) % numTasks;
 		else if (la != lb) atomicAdd(&counters[CTR_CL_LEFT + 3], 1u); else atomicMax(&counters[CTR_CL_LEFT + 4], compWeight[la]); // (statistics: not converged / too large)
 		taskKey[j] = key;
-		taskPos[j] = atomicAdd(&taskCount[key * CL_SUBCOUNTERS + clSubCounter(j / CL_ASSIGN_LANES)], 1u); // (the sub-counter k_cl_scatter derives from j's workgroup in ITS launch)
+		// (the sub-counter k_cl_scatter derives from j's workgroup in ITS launch.  One atomic per wave and cursor: the phase has a dozen
+		// tasks, and ~5 k returning atomics on their ~100 cursors, served one after the other, were most of this kernel's 12 us)
+		taskPos[j] = clAppendByCursor(taskCount, key * CL_SUBCOUNTERS + clSubCounter(j / CL_ASSIGN_LANES));
 		const u32 ph = key / CL_MAX_TASKS;
 		if (da) atomicOr(&phaseMask[ids.x], 1u << ph);
 		if (db) atomicOr(&phaseMask[ids.y], 1u << ph);
@@ -468,13 +473,19 @@ __global__ void __launch_bounds__(1024) k_cl_offsets(u32* __restrict__ counters,
 	u32 sum = 0;
 	for (u32 k = 0; k < per; ++k) if (t * per + k < total) sum += cnt[t * per + k];
 	u32 run = clBlockInclusive1024(sum, part) - sum;
-	for (u32 k = 0; k < per; ++k)
+	// (a lane's 20 consecutive starts leave as five 16-byte stores: 20 word stores per lane, each wave's spread over 5 KB, were
+	// ~13 k cache-line writes through ONE compute unit: 12.9 -> 7.1 us)
+	static_assert(CL_TASK_CURSORS % (1024u * 4u) == 0u, "every lane scans the same number of cursors, in whole groups of four");
+	for (u32 k = 0; k < per; k += 4u)
 	{
-		u32 e = t * per + k;
-		if (e >= total) break;
-		u32 c = cnt[e], key = e / CL_SUBCOUNTERS;
-		taskStart[e] = run; run += c;
-		if (c) atomicMax(&lastTask[key / CL_MAX_TASKS], (key % CL_MAX_TASKS) + 1u);
+		u32 v[4];
+		for (u32 q = 0; q < 4u; ++q)
+		{
+			u32 e = t * per + k + q, c = cnt[e], key = e / CL_SUBCOUNTERS;
+			v[q] = run; run += c;
+			if (c) atomicMax(&lastTask[key / CL_MAX_TASKS], (key % CL_MAX_TASKS) + 1u);
+		}
+		*(uint4*)(taskStart + t * per + k) = make_uint4(v[0], v[1], v[2], v[3]);
 	}
 	if (t == 1023u) taskStart[total] = run;
 	__syncthreads();
@@ -546,7 +557,7 @@ static bool clSizeListBuffers(World& w, u32 nj)
 }
 
 // Body order along the phases' curves.  Any order is correct, this one makes the clusters compact; bodies move a fraction of
-// their size per step, so the order is refreshed every few steps only (four radix sorts of all bodies), at once when bodies were
+// their size per step, so the order is refreshed every few steps only (one sort of all bodies along all curves), at once when bodies were
 // added and after a snapshot was taken or restored (so that a restored world and its original keep making the same choices).
 // Returns whether this step re-sorted (and so re-cuts the chunks); the steps in between reuse the stored chunks.
 static bool clRefreshBodyOrder(World& w)
@@ -562,8 +573,12 @@ static bool clRefreshBodyOrder(World& w)
 		for (const auto& s : CL_SHIFTS.s) for (u32 v : s) maxShift = std::max(maxShift, v);
 		hipLaunchKernelGGL(k_cl_bbox, dim3(std::min<u32>(clGrid(nb).x, 64u)), CL_BLOCK, 0, w.stream, nb, w.cog.p, w.simMask.p, w.dCounters.p);
 		hipLaunchKernelGGL(k_cl_keys, clGrid(nb), CL_BLOCK, 0, w.stream, nb, P, CL_SHIFTS, maxShift, w.cog.p, w.simMask.p, w.dCounters.p, w.clKeys.p, w.clVals.p);
-		for (u32 p = 0; p < sortParts; ++p)
-			prim_sort_pairs_u32(w, w.clKeys.p + (size_t)p * nb, w.clKeysSorted.p + (size_t)p * nb, w.clVals.p + (size_t)p * nb, w.clSorted.p + (size_t)p * nb, nb, 30);
+		// The curves lie curve-major in clKeys / clVals and carry their index in the keys' top bits: one stable sort of sortParts x nb
+		// items leaves curve p's order in [p * nb, (p + 1) * nb), equal keys by ascending body, as one sort per curve did (at 100 k
+		// bodies rocPRIM runs a block sort and 7 merge launches per curve; the 300 k items of three curves take one block sort and 18
+		// merge launches: 146 -> 111 us of kernel time per refresh, profiles/cluster_build.txt).
+		static_assert(CL_MAX_PARTS <= 4u, "the curve index has two key bits above the 30-bit Morton code");
+		prim_sort_pairs_u32(w, w.clKeys.p, w.clKeysSorted.p, w.clVals.p, w.clSorted.p, sortParts * nb, 32);
 		hipLaunchKernelGGL(k_cl_ranks, clGrid(nb), CL_BLOCK, 0, w.stream, nb, sortParts, w.clSorted.p, w.clRank.p);
 		w.clusterSortDue = false; w.clusterSortAge = 0; w.clusterSortBodies = nb;
 	}
