@@ -240,6 +240,28 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def _is_tensor(a):
+    """a torch tensor?  (without importing torch for callers who pass numpy)"""
+    return not isinstance(a, np.ndarray) and type(a).__module__.startswith("torch")
+
+
+def _ray_flags(static, brute_force, terrain):
+    return (RAY_STATIC if static else 0) | (RAY_BRUTE_FORCE if brute_force else 0) | (RAY_TERRAIN if terrain else 0)
+
+
+def _fill_mount(rec, mount, exclude_first, exclude_count):
+    """mount (None: world space) and the exclusion range (None: nothing) of SENSOR_RAY_DTYPE / PROXIMITY_QUERY_DTYPE records"""
+    rec["mount"] = STATIC_BODY if mount is None else np.asarray(mount, np.uint32)
+    rec["excludeFirst"] = 0 if exclude_first is None else np.asarray(exclude_first, np.uint32)
+    rec["excludeCount"] = 0 if exclude_count is None else np.asarray(exclude_count, np.uint32)
+
+
+def _hit_tuple(hits, terrain):
+    """(t, collider, body, hit, point[, triangle]) of RAY_HIT_DTYPE / SENSOR_HIT_DTYPE records"""
+    out = (hits["t"].copy(), hits["collider"].copy(), hits["body"].copy(), hits["hit"].copy(), hits["point"].copy())
+    return out + (hits["reserved"].view(np.uint32).copy(),) if terrain else out
+
+
 class PhysicsError(RuntimeError):
     pass
 
@@ -486,6 +508,44 @@ class World:
         self._check(code)
         return out
 
+    # The query methods below hand one of these helpers a call(n, in, out, aux): the C entry on addresses (None: a null pointer).
+    def _query_in_place(self, name, call, q, cols_in, cols_out, cols_aux=0):
+        """A device entry on the caller's device tensor q (float32, contiguous, [n, cols_in]): outputs [n, cols_out] and, if wanted,
+        [n, cols_aux], enqueued on the world's stream behind the caller's current stream, which then waits for it; no host synchronisation."""
+        import torch
+        if not q.is_cuda or q.dtype != torch.float32 or q.dim() != 2 or q.shape[1] != cols_in or not q.is_contiguous():
+            raise ValueError("%s: a device tensor must be float32, contiguous and [n, %d]" % (name, cols_in))
+        ext = torch.cuda.ExternalStream(self.device_state().stream or 0, device=q.device)
+        ext.wait_stream(torch.cuda.current_stream(q.device))   # q was written on the caller's stream
+        with torch.cuda.stream(ext):
+            out = torch.empty((q.shape[0], cols_out), dtype=torch.float32, device=q.device)
+            aux = torch.empty((q.shape[0], cols_aux), dtype=torch.float32, device=q.device) if cols_aux else None
+            self._check(call(q.shape[0], q.data_ptr(), out.data_ptr(), aux.data_ptr() if cols_aux else None))
+        q.record_stream(ext)
+        torch.cuda.current_stream(q.device).wait_stream(ext)   # stream order, not a host synchronisation
+        return (out, aux) if cols_aux else out
+
+    def _query_numpy(self, call, rec, out, aux=None, device=False):
+        """numpy records `rec` [n] in, `out` [n] and `aux` [n, k] (or None) filled: `call` is a _host entry on the arrays themselves or,
+        with device=True, a device entry on device tensors made here."""
+        n = len(rec)
+        if not n:
+            self._check(call(0, None, None, None))
+        elif not device:
+            self._check(call(n, rec.ctypes.data, out.ctypes.data, aux.ctypes.data if aux is not None else None))
+        else:
+            import torch
+            dev = torch.device("cuda", torch.cuda.current_device())
+            d_in = torch.from_numpy(rec.view(np.int32).reshape(n, -1).copy()).to(dev)
+            d_out = torch.empty((n, out.itemsize // 4), dtype=torch.float32, device=dev)
+            d_aux = torch.empty(aux.shape, dtype=torch.float32, device=dev) if aux is not None else None
+            torch.cuda.current_stream(dev).synchronize()   # the records are on the device before the world's stream reads them
+            self._check(call(n, d_in.data_ptr(), d_out.data_ptr(), d_aux.data_ptr() if aux is not None else None))
+            self.synchronize()
+            out[:] = d_out.cpu().numpy().view(out.dtype).reshape(n)
+            if aux is not None:
+                aux[:] = d_aux.cpu().numpy()
+
     def raycast(self, rays, static=True, brute_force=False, terrain=False):
         """mi_raycast_batch: rays [n, 8] = origin, maxT, direction, enabled, each against every candidate collider of the world (with
         `static` also the colliders of entities without a rigid body); nothing is pushed.  brute_force: every ray against every
@@ -497,36 +557,16 @@ class World:
         A torch tensor on the device (float32, contiguous) is used in place: returns one float32 tensor [n, 8] of mi_ray_hit records
         (columns 1..3 hold the bits of collider, body, hit, column 7 those of the triangle id: view them with .view(torch.int32)),
         enqueued on the world's stream with no synchronisation."""
-        import torch
-        flags = (RAY_STATIC if static else 0) | (RAY_BRUTE_FORCE if brute_force else 0) | (RAY_TERRAIN if terrain else 0)
-        if isinstance(rays, torch.Tensor):
-            if not rays.is_cuda or rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous():
-                raise ValueError("raycast: a device tensor must be float32, contiguous and [n, 8]")
-            ext = torch.cuda.ExternalStream(self.device_state().stream or 0, device=rays.device)
-            ext.wait_stream(torch.cuda.current_stream(rays.device))   # the rays were written on the caller's stream
-            with torch.cuda.stream(ext):
-                out = torch.empty((rays.shape[0], 8), dtype=torch.float32, device=rays.device)
-                self._check(self.lib.mi_raycast_batch(self.w, C.c_uint32(rays.shape[0]), C.c_void_p(rays.data_ptr()), C.c_uint32(flags), C.c_void_p(out.data_ptr())))
-            rays.record_stream(ext)
-            torch.cuda.current_stream(rays.device).wait_stream(ext)   # stream order, not a host synchronisation
-            return out
+        flags = _ray_flags(static, brute_force, terrain)
+
+        def entry(fn):
+            return lambda n, d_in, d_out, d_aux: fn(self.w, C.c_uint32(n), C.c_void_p(d_in), C.c_uint32(flags), C.c_void_p(d_out))
+        if _is_tensor(rays):
+            return self._query_in_place("raycast", entry(self.lib.mi_raycast_batch), rays, 8, 8)
         rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
-        n = len(rays)
-        hits = np.zeros(n, RAY_HIT_DTYPE)
-        if n:
-            dev = torch.device("cuda", torch.cuda.current_device())
-            ext = torch.cuda.ExternalStream(self.device_state().stream or 0, device=dev)
-            with torch.cuda.stream(ext):
-                d_rays = torch.from_numpy(rays).to(dev)
-                d_out = torch.empty((n, 8), dtype=torch.float32, device=dev)
-                code = self.lib.mi_raycast_batch(self.w, C.c_uint32(n), C.c_void_p(d_rays.data_ptr()), C.c_uint32(flags), C.c_void_p(d_out.data_ptr()))
-                ext.synchronize()
-                self._check(code)
-                hits = d_out.cpu().numpy().view(RAY_HIT_DTYPE).reshape(n)
-        else:
-            self._check(self.lib.mi_raycast_batch(self.w, C.c_uint32(0), None, C.c_uint32(flags), None))
-        out = (hits["t"].copy(), hits["collider"].copy(), hits["body"].copy(), hits["hit"].copy(), hits["point"].copy())
-        return out + (hits["reserved"].view(np.uint32).copy(),) if terrain else out
+        hits = np.zeros(len(rays), RAY_HIT_DTYPE)
+        self._query_numpy(entry(self.lib.mi_raycast_host), rays, hits)
+        return _hit_tuple(hits, terrain)
 
     def raycast_sensors(self, rays, mount=None, exclude_first=None, exclude_count=None, static=True, brute_force=False, terrain=False, world_rays=False):
         """mi_raycast_sensors: rays [n, 8] = origin, maxT, direction, enabled in the frame of body mount[i] at its current pose
@@ -538,34 +578,20 @@ class World:
         mount and the exclusion arguments are then not used) is cast in place: returns one float32 tensor [n, 12] of mi_sensor_hit
         records (columns 8..10 the normal), with world_rays=True a tuple with the [n, 8] world rays; enqueued on the world's stream
         with no synchronisation.  (The rays tensor is recorded on that stream, as in raycast: release it before close().)"""
-        import torch
-        flags = (RAY_STATIC if static else 0) | (RAY_BRUTE_FORCE if brute_force else 0) | (RAY_TERRAIN if terrain else 0)
-        if isinstance(rays, torch.Tensor):
-            if not rays.is_cuda or rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 12 or not rays.is_contiguous():
-                raise ValueError("raycast_sensors: a device tensor must be float32, contiguous and [n, 12]")
-            ext = torch.cuda.ExternalStream(self.device_state().stream or 0, device=rays.device)
-            ext.wait_stream(torch.cuda.current_stream(rays.device))   # the rays were written on the caller's stream
-            with torch.cuda.stream(ext):
-                out = torch.empty((rays.shape[0], 12), dtype=torch.float32, device=rays.device)
-                wr = torch.empty((rays.shape[0], 8), dtype=torch.float32, device=rays.device) if world_rays else None
-                self._check(self.lib.mi_raycast_sensors(self.w, C.c_uint32(rays.shape[0]), C.c_void_p(rays.data_ptr()), C.c_uint32(flags), C.c_void_p(out.data_ptr()),
-                                                        C.c_void_p(wr.data_ptr()) if world_rays else None))
-            rays.record_stream(ext)
-            torch.cuda.current_stream(rays.device).wait_stream(ext)   # stream order, not a host synchronisation
-            return (out, wr) if world_rays else out
+        flags = _ray_flags(static, brute_force, terrain)
+
+        def entry(fn):
+            return lambda n, d_in, d_out, d_aux: fn(self.w, C.c_uint32(n), C.c_void_p(d_in), C.c_uint32(flags), C.c_void_p(d_out), C.c_void_p(d_aux))
+        if _is_tensor(rays):
+            return self._query_in_place("raycast_sensors", entry(self.lib.mi_raycast_sensors), rays, 12, 12, 8 if world_rays else 0)
         rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
         n = len(rays)
         rec = np.zeros(n, SENSOR_RAY_DTYPE)
         rec["origin"], rec["maxT"], rec["direction"], rec["enabled"] = rays[:, 0:3], rays[:, 3], rays[:, 4:7], rays[:, 7]
-        rec["mount"] = STATIC_BODY if mount is None else np.asarray(mount, np.uint32)
-        rec["excludeFirst"] = 0 if exclude_first is None else np.asarray(exclude_first, np.uint32)
-        rec["excludeCount"] = 0 if exclude_count is None else np.asarray(exclude_count, np.uint32)
+        _fill_mount(rec, mount, exclude_first, exclude_count)
         hits, wr = np.zeros(n, SENSOR_HIT_DTYPE), np.zeros((n, 8), np.float32)
-        self._check(self.lib.mi_raycast_sensors_host(self.w, C.c_uint32(n), _p(rec) if n else None, C.c_uint32(flags), _p(hits) if n else None, _p(wr) if (n and world_rays) else None))
-        out = (hits["t"].copy(), hits["collider"].copy(), hits["body"].copy(), hits["hit"].copy(), hits["point"].copy())
-        if terrain:
-            out += (hits["reserved"].view(np.uint32).copy(),)
-        out += (hits["normal"].copy(),)
+        self._query_numpy(entry(self.lib.mi_raycast_sensors_host), rec, hits, wr if world_rays else None)
+        out = _hit_tuple(hits, terrain) + (hits["normal"].copy(),)
         return out + (wr,) if world_rays else out
 
     def proximity(self, points, radius=np.inf, mount=None, exclude_first=None, exclude_count=None, static=True, brute_force=False, count=True,
@@ -581,49 +607,20 @@ class World:
         tensor [n, 12] of mi_proximity_reading records (with world_points=True a tuple with the [n, 4] world points), enqueued on the
         world's stream with no synchronisation.  (The tensor is recorded on that stream, as in raycast: release it before close().)"""
         flags = (PROX_STATIC if static else 0) | (PROX_BRUTE_FORCE if brute_force else 0) | (PROX_COUNT if count else 0)
-        if not isinstance(points, np.ndarray) and type(points).__module__.startswith("torch"):
-            import torch
-            q = points
-            if not q.is_cuda or q.dtype != torch.float32 or q.dim() != 2 or q.shape[1] != 8 or not q.is_contiguous():
-                raise ValueError("proximity: a device tensor must be float32, contiguous and [n, 8]")
-            ext = torch.cuda.ExternalStream(self.device_state().stream or 0, device=q.device)
-            ext.wait_stream(torch.cuda.current_stream(q.device))   # the queries were written on the caller's stream
-            with torch.cuda.stream(ext):
-                out = torch.empty((q.shape[0], 12), dtype=torch.float32, device=q.device)
-                wp = torch.empty((q.shape[0], 4), dtype=torch.float32, device=q.device) if world_points else None
-                self._check(self.lib.mi_proximity(self.w, C.c_uint32(q.shape[0]), C.c_void_p(q.data_ptr()), C.c_uint32(flags), C.c_void_p(out.data_ptr()),
-                                                  C.c_void_p(wp.data_ptr()) if world_points else None))
-            q.record_stream(ext)
-            torch.cuda.current_stream(q.device).wait_stream(ext)   # stream order, not a host synchronisation
-            return (out, wp) if world_points else out
+
+        def entry(fn):
+            return lambda n, d_in, d_out, d_aux: fn(self.w, C.c_uint32(n), C.c_void_p(d_in), C.c_uint32(flags), C.c_void_p(d_out), C.c_void_p(d_aux))
+        if _is_tensor(points):
+            return self._query_in_place("proximity", entry(self.lib.mi_proximity), points, 8, 12, 4 if world_points else 0)
         if isinstance(points, np.ndarray) and points.dtype == PROXIMITY_QUERY_DTYPE:
             rec = np.ascontiguousarray(points).reshape(-1)
         else:
             pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
             rec = np.zeros(len(pts), PROXIMITY_QUERY_DTYPE)
             rec["point"], rec["radius"], rec["enabled"] = pts, np.asarray(radius, np.float32), 1
-            rec["mount"] = STATIC_BODY if mount is None else np.asarray(mount, np.uint32)
-            rec["excludeFirst"] = 0 if exclude_first is None else np.asarray(exclude_first, np.uint32)
-            rec["excludeCount"] = 0 if exclude_count is None else np.asarray(exclude_count, np.uint32)
-        n = len(rec)
-        out, wp = np.zeros(n, PROXIMITY_READING_DTYPE), np.zeros((n, 4), np.float32)
-        if not device:
-            self._check(self.lib.mi_proximity_host(self.w, C.c_uint32(n), _p(rec) if n else None, C.c_uint32(flags), _p(out) if n else None, _p(wp) if (n and world_points) else None))
-        elif not n:
-            self._check(self.lib.mi_proximity(self.w, C.c_uint32(0), None, C.c_uint32(flags), None, None))
-        else:
-            import torch
-            dev = torch.device("cuda", torch.cuda.current_device())
-            d_in = torch.from_numpy(rec.view(np.int32).reshape(n, 8).copy()).to(dev)
-            d_out = torch.empty((n, 12), dtype=torch.float32, device=dev)
-            d_wp = torch.empty((n, 4), dtype=torch.float32, device=dev) if world_points else None
-            torch.cuda.current_stream(dev).synchronize()   # the queries are on the device before the world's stream reads them
-            self._check(self.lib.mi_proximity(self.w, C.c_uint32(n), C.c_void_p(d_in.data_ptr()), C.c_uint32(flags), C.c_void_p(d_out.data_ptr()),
-                                              C.c_void_p(d_wp.data_ptr()) if world_points else None))
-            self.synchronize()
-            out = d_out.cpu().numpy().view(PROXIMITY_READING_DTYPE).reshape(n)
-            if world_points:
-                wp = d_wp.cpu().numpy()
+            _fill_mount(rec, mount, exclude_first, exclude_count)
+        out, wp = np.zeros(len(rec), PROXIMITY_READING_DTYPE), np.zeros((len(rec), 4), np.float32)
+        self._query_numpy(entry(self.lib.mi_proximity if device else self.lib.mi_proximity_host), rec, out, wp if world_points else None, device)
         return (out, wp) if world_points else out
 
     def contact_sensors(self, sensors, device=False):
@@ -635,22 +632,10 @@ class World:
             rec = np.ascontiguousarray(sensors).reshape(-1)
         else:
             rec = np.ascontiguousarray(sensors, np.uint32).reshape(-1, 4).view(CONTACT_SENSOR_DTYPE).reshape(-1)
-        n = len(rec)
-        out = np.zeros(n, CONTACT_READING_DTYPE)
-        if not device:
-            self._check(self.lib.mi_contact_sensors_host(self.w, C.c_uint32(n), _p(rec) if n else None, _p(out) if n else None))
-            return out
-        if not n:
-            self._check(self.lib.mi_contact_sensors(self.w, C.c_uint32(0), None, None))
-            return out
-        import torch
-        dev = torch.device("cuda", torch.cuda.current_device())
-        d_in = torch.from_numpy(rec.view(np.uint32).reshape(n, 4).view(np.int32).copy()).to(dev)
-        d_out = torch.empty((n, 12), dtype=torch.float32, device=dev)
-        torch.cuda.current_stream(dev).synchronize()   # the sensors are on the device before the world's stream reads them
-        self._check(self.lib.mi_contact_sensors(self.w, C.c_uint32(n), C.c_void_p(d_in.data_ptr()), C.c_void_p(d_out.data_ptr())))
-        self.synchronize()
-        return d_out.cpu().numpy().view(CONTACT_READING_DTYPE).reshape(n)
+        fn = self.lib.mi_contact_sensors if device else self.lib.mi_contact_sensors_host
+        out = np.zeros(len(rec), CONTACT_READING_DTYPE)
+        self._query_numpy(lambda n, d_in, d_out, d_aux: fn(self.w, C.c_uint32(n), C.c_void_p(d_in), C.c_void_p(d_out)), rec, out, None, device)
+        return out
 
     def accumulators(self):
         """Force and torque accumulators of every body [n, 6]: the pushes the next step will apply and clear."""

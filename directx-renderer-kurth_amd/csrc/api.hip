@@ -6,6 +6,7 @@
 #include <cstring>
 #include <cmath>
 #include <algorithm>
+#include <functional>
 
 extern "C" {
 
@@ -346,109 +347,99 @@ int mi_test_physics_interaction_batch(mi_world* world, uint32_t numRays, uint32_
 	return W->lastError;
 }
 
+// ---- world queries: ray casts, ray sensors, proximity sensors, contact sensors.  Each has a device entry (the caller's device
+// buffers, enqueued on the world's stream) and a _host entry that stages host arrays around it. ----
+// What every device entry does first: settle a pending give-up of the last step's cluster sweep (the queries see the redone solve),
+// upload, answer a count of zero and missing pointers, build the collider / hull tables if the entry reads them.  true: go on and
+// launch; false: return `code`.
+static bool queryBegin(World* w, u32 count, bool pointers, bool tables, int& code)
+{
+	w->resolvePendingFlow();
+	w->upload();
+	code = w->lastError;
+	if (!count) return false;
+	if (!pointers) { code = MI_ERR_INVALID_ARGUMENT; return false; }
+	if (tables && !w->interactTablesValid) w->buildInteractTables();
+	code = w->lastError;
+	return !code;
+}
+// Does a cast with these flags meet the heightmap?  MI_ERR_INVALID_ARGUMENT for a terrain with more chunks than the 17 chunk bits of a triangle id count.
+static int queryTerrain(const World* w, u32 flags, bool& terrain)
+{
+	terrain = (flags & MI_RAY_TERRAIN) != 0 && w->terrainChunksPerDim != 0;
+	return terrain && (uint64_t)w->terrainChunksPerDim * w->terrainChunksPerDim > 131071u ? MI_ERR_INVALID_ARGUMENT : MI_OK;
+}
+// A _host entry: `count` records of inBytes each to the device, deviceEntry(dIn, dOut, dAux) on them, outBytes per record back into `out`
+// and, if `aux` is given, auxBytes per record into it.  The staging (World::queryHost*) is shared by all of them: every call ends with
+// the world's stream drained.  A count of zero is the device entry's to answer.
+static int queryStaged(World* w, u32 count, const void* in, size_t inBytes, void* out, size_t outBytes, void* aux, size_t auxBytes, const std::function<int(void*, void*, void*)>& deviceEntry)
+{
+	if (!count) return deviceEntry(nullptr, nullptr, nullptr);
+	if (!in || !out) return MI_ERR_INVALID_ARGUMENT;
+	w->queryHostIn.ensure(inBytes * count, w->stream); w->queryHostOut.ensure(outBytes * count, w->stream);
+	if (aux) w->queryHostAux.ensure(auxBytes * count, w->stream);
+	if (w->lastError) return w->lastError;
+	MI_CHECK(hipMemcpyAsync(w->queryHostIn.p, in, inBytes * count, hipMemcpyHostToDevice, w->stream));
+	int e = deviceEntry(w->queryHostIn.p, w->queryHostOut.p, aux ? w->queryHostAux.p : nullptr);
+	if (e) return e;
+	MI_CHECK(hipMemcpyAsync(out, w->queryHostOut.p, outBytes * count, hipMemcpyDeviceToHost, w->stream));
+	if (aux) MI_CHECK(hipMemcpyAsync(aux, w->queryHostAux.p, auxBytes * count, hipMemcpyDeviceToHost, w->stream));
+	MI_CHECK(hipStreamSynchronize(w->stream));
+	return w->lastError;
+}
+
 int mi_raycast_batch(mi_world* world, uint32_t numRays, const float* dRays, uint32_t flags, mi_ray_hit* dOutHits)
 {
 	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
-	W->resolvePendingFlow();
-	W->upload();
-	if (!numRays) return W->lastError;
-	if (!dRays || !dOutHits) return MI_ERR_INVALID_ARGUMENT;
-	if (!W->interactTablesValid) W->buildInteractTables();
-	if (W->lastError) return W->lastError;
-	const bool terrain = (flags & MI_RAY_TERRAIN) != 0 && W->terrainChunksPerDim != 0;
-	if (terrain && (uint64_t)W->terrainChunksPerDim * W->terrainChunksPerDim > 131071u) return MI_ERR_INVALID_ARGUMENT; // the triangle id has 17 bits for the chunk
+	int code; bool terrain;
+	if (!queryBegin(W, numRays, dRays && dOutHits, true, code) || (code = queryTerrain(W, flags, terrain)) != MI_OK) return code;
 	launch_raycast(*W, numRays, dRays, flags, dOutHits); // (no candidate collider: the records are zeroed)
 	if (terrain && !W->lastError) launch_raycast_terrain(*W, numRays, dRays, flags, dOutHits);
 	return W->lastError;
 }
-
 int mi_raycast_host(mi_world* world, uint32_t numRays, const float* rays, uint32_t flags, mi_ray_hit* outHits)
 {
 	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
-	if (!numRays) return mi_raycast_batch(world, 0, nullptr, flags, nullptr);
-	if (!rays || !outHits) return MI_ERR_INVALID_ARGUMENT;
-	W->rcHostRays.ensure(2 * (size_t)numRays, W->stream); W->rcHostHits.ensure(2 * (size_t)numRays, W->stream);
-	if (W->lastError) return W->lastError;
-	MI_CHECK(hipMemcpyAsync(W->rcHostRays.p, rays, 32 * (size_t)numRays, hipMemcpyHostToDevice, W->stream));
-	int e = mi_raycast_batch(world, numRays, (const float*)W->rcHostRays.p, flags, (mi_ray_hit*)W->rcHostHits.p);
-	if (e) return e;
-	MI_CHECK(hipMemcpyAsync(outHits, W->rcHostHits.p, 32 * (size_t)numRays, hipMemcpyDeviceToHost, W->stream));
-	MI_CHECK(hipStreamSynchronize(W->stream));
-	return W->lastError;
+	return queryStaged(W, numRays, rays, 32, outHits, sizeof(mi_ray_hit), nullptr, 0, [&](void* dIn, void* dOut, void*) { return mi_raycast_batch(world, numRays, (const float*)dIn, flags, (mi_ray_hit*)dOut); });
 }
 
 int mi_raycast_sensors(mi_world* world, uint32_t numRays, const mi_sensor_ray* dRays, uint32_t flags, mi_sensor_hit* dOutHits, float* dOutWorldRays)
 {
 	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
-	W->resolvePendingFlow();
-	W->upload();
-	if (!numRays) return W->lastError;
-	if (!dRays || !dOutHits) return MI_ERR_INVALID_ARGUMENT;
-	if (!W->interactTablesValid) W->buildInteractTables();
-	if (W->lastError) return W->lastError;
-	const bool terrain = (flags & MI_RAY_TERRAIN) != 0 && W->terrainChunksPerDim != 0;
-	if (terrain && (uint64_t)W->terrainChunksPerDim * W->terrainChunksPerDim > 131071u) return MI_ERR_INVALID_ARGUMENT; // as mi_raycast_batch
+	int code; bool terrain;
+	if (!queryBegin(W, numRays, dRays && dOutHits, true, code) || (code = queryTerrain(W, flags, terrain)) != MI_OK) return code;
 	launch_raycast_sensors(*W, numRays, dRays, flags, terrain, dOutHits, dOutWorldRays);
 	return W->lastError;
 }
-
 int mi_raycast_sensors_host(mi_world* world, uint32_t numRays, const mi_sensor_ray* rays, uint32_t flags, mi_sensor_hit* outHits, float* outWorldRays)
 {
 	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
-	if (!numRays) return mi_raycast_sensors(world, 0, nullptr, flags, nullptr, nullptr);
-	if (!rays || !outHits) return MI_ERR_INVALID_ARGUMENT;
-	W->rcSensorHostIn.ensure(3 * (size_t)numRays, W->stream); W->rcSensorHostOut.ensure(3 * (size_t)numRays, W->stream);
-	if (outWorldRays) W->rcSensorHostRays.ensure(2 * (size_t)numRays, W->stream);
-	if (W->lastError) return W->lastError;
-	MI_CHECK(hipMemcpyAsync(W->rcSensorHostIn.p, rays, sizeof(mi_sensor_ray) * (size_t)numRays, hipMemcpyHostToDevice, W->stream));
-	int e = mi_raycast_sensors(world, numRays, (const mi_sensor_ray*)W->rcSensorHostIn.p, flags, (mi_sensor_hit*)W->rcSensorHostOut.p, outWorldRays ? (float*)W->rcSensorHostRays.p : nullptr);
-	if (e) return e;
-	MI_CHECK(hipMemcpyAsync(outHits, W->rcSensorHostOut.p, sizeof(mi_sensor_hit) * (size_t)numRays, hipMemcpyDeviceToHost, W->stream));
-	if (outWorldRays) MI_CHECK(hipMemcpyAsync(outWorldRays, W->rcSensorHostRays.p, 32 * (size_t)numRays, hipMemcpyDeviceToHost, W->stream));
-	MI_CHECK(hipStreamSynchronize(W->stream));
-	return W->lastError;
+	return queryStaged(W, numRays, rays, sizeof(mi_sensor_ray), outHits, sizeof(mi_sensor_hit), outWorldRays, 32,
+		[&](void* dIn, void* dOut, void* dAux) { return mi_raycast_sensors(world, numRays, (const mi_sensor_ray*)dIn, flags, (mi_sensor_hit*)dOut, (float*)dAux); });
 }
 
-// ---- proximity sensors (the rule: include/mi_physics.h; the tests: point_tests.h; the walk: k_proximity.hip) ----
+// (proximity sensors: the rule is in include/mi_physics.h, the tests in point_tests.h, the walk in k_proximity.hip)
 int mi_proximity(mi_world* world, uint32_t numQueries, const mi_proximity_query* dQueries, uint32_t flags, mi_proximity_reading* dOut, float* dOutWorldPoints)
 {
 	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
-	W->resolvePendingFlow();
-	W->upload();
-	if (!numQueries) return W->lastError;
-	if (!dQueries || !dOut) return MI_ERR_INVALID_ARGUMENT;
-	if (!W->interactTablesValid) W->buildInteractTables();
-	if (W->lastError) return W->lastError;
+	int code;
+	if (!queryBegin(W, numQueries, dQueries && dOut, true, code)) return code;
 	launch_proximity(*W, numQueries, dQueries, flags, dOut, dOutWorldPoints);
 	return W->lastError;
 }
-
 int mi_proximity_host(mi_world* world, uint32_t numQueries, const mi_proximity_query* queries, uint32_t flags, mi_proximity_reading* out, float* outWorldPoints)
 {
 	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
-	if (!numQueries) return mi_proximity(world, 0, nullptr, flags, nullptr, nullptr);
-	if (!queries || !out) return MI_ERR_INVALID_ARGUMENT;
-	W->pxHostIn.ensure(2 * (size_t)numQueries, W->stream); W->pxHostOut.ensure(3 * (size_t)numQueries, W->stream);
-	if (outWorldPoints) W->pxHostPoints.ensure(numQueries, W->stream);
-	if (W->lastError) return W->lastError;
-	MI_CHECK(hipMemcpyAsync(W->pxHostIn.p, queries, sizeof(mi_proximity_query) * (size_t)numQueries, hipMemcpyHostToDevice, W->stream));
-	int e = mi_proximity(world, numQueries, (const mi_proximity_query*)W->pxHostIn.p, flags, (mi_proximity_reading*)W->pxHostOut.p, outWorldPoints ? (float*)W->pxHostPoints.p : nullptr);
-	if (e) return e;
-	MI_CHECK(hipMemcpyAsync(out, W->pxHostOut.p, sizeof(mi_proximity_reading) * (size_t)numQueries, hipMemcpyDeviceToHost, W->stream));
-	if (outWorldPoints) MI_CHECK(hipMemcpyAsync(outWorldPoints, W->pxHostPoints.p, 16 * (size_t)numQueries, hipMemcpyDeviceToHost, W->stream));
-	MI_CHECK(hipStreamSynchronize(W->stream));
-	return W->lastError;
+	return queryStaged(W, numQueries, queries, sizeof(mi_proximity_query), out, sizeof(mi_proximity_reading), outWorldPoints, 16,
+		[&](void* dIn, void* dOut, void* dAux) { return mi_proximity(world, numQueries, (const mi_proximity_query*)dIn, flags, (mi_proximity_reading*)dOut, (float*)dAux); });
 }
 
-// ---- contact sensors (the rule: include/mi_physics.h; the reduction: k_contact_sensors.hip) ----
+// (contact sensors: the rule is in include/mi_physics.h, the reduction in k_contact_sensors.hip)
 int mi_contact_sensors(mi_world* world, uint32_t numSensors, const mi_contact_sensor* dSensors, mi_contact_reading* dOut)
 {
 	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
-	W->resolvePendingFlow(); // a give-up of the last step's cluster sweep is settled first: the readings describe the redone solve
-	W->upload();
-	if (!numSensors) return W->lastError;
-	if (!dSensors || !dOut) return MI_ERR_INVALID_ARGUMENT;
-	if (W->lastError) return W->lastError;
+	int code;
+	if (!queryBegin(W, numSensors, dSensors && dOut, false, code)) return code;
 	if (!W->last.bodies) // no step since the world was created or restored: every record is zero
 	{
 		MI_CHECK(hipMemsetAsync(dOut, 0, sizeof(mi_contact_reading) * (size_t)numSensors, W->stream));
@@ -458,20 +449,11 @@ int mi_contact_sensors(mi_world* world, uint32_t numSensors, const mi_contact_se
 	launch_contact_sensors(*W, numSensors, dSensors, dOut, W->last.numPairs != 0u);
 	return W->lastError;
 }
-
 int mi_contact_sensors_host(mi_world* world, uint32_t numSensors, const mi_contact_sensor* sensors, mi_contact_reading* out)
 {
 	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
-	if (!numSensors) return mi_contact_sensors(world, 0, nullptr, nullptr);
-	if (!sensors || !out) return MI_ERR_INVALID_ARGUMENT;
-	W->csHostIn.ensure(numSensors, W->stream); W->csHostOut.ensure(3 * (size_t)numSensors, W->stream);
-	if (W->lastError) return W->lastError;
-	MI_CHECK(hipMemcpyAsync(W->csHostIn.p, sensors, sizeof(mi_contact_sensor) * (size_t)numSensors, hipMemcpyHostToDevice, W->stream));
-	int e = mi_contact_sensors(world, numSensors, (const mi_contact_sensor*)W->csHostIn.p, (mi_contact_reading*)W->csHostOut.p);
-	if (e) return e;
-	MI_CHECK(hipMemcpyAsync(out, W->csHostOut.p, sizeof(mi_contact_reading) * (size_t)numSensors, hipMemcpyDeviceToHost, W->stream));
-	MI_CHECK(hipStreamSynchronize(W->stream));
-	return W->lastError;
+	return queryStaged(W, numSensors, sensors, sizeof(mi_contact_sensor), out, sizeof(mi_contact_reading), nullptr, 0,
+		[&](void* dIn, void* dOut, void*) { return mi_contact_sensors(world, numSensors, (const mi_contact_sensor*)dIn, (mi_contact_reading*)dOut); });
 }
 
 // ---- multi-GPU slabs: state hand-over in device memory (directx-renderer-kurth_amd/parallel.py drives the halo exchange) ----

@@ -1,19 +1,14 @@
 // mi_test_physics_interaction_batch: testPhysicsInteraction (physics.cpp:556-628) for many rays, one lane per ray.  Ray i tests only
 // the colliders of its own body range, so lanes never share a body: the push is a plain read-add-write of the accumulators, with no
-// atomics, and the result does not depend on the schedule.  The ray tests are those of the host entry point (ray_tests.h).
+// atomics, and the result does not depend on the schedule.  The ray tests are those of the host entry point (ray_tests.h); the hull
+// table and the shape words of a collider record are the world queries' (RcHulls, rcShape: raycast_shared.h).
 #include "world.h"
 #include "ray_tests.h"
-
-struct DeviceHulls
-{
-	const float4* verts; const uint4* tris; const uint2* range;
-	MI_DEV u32 numTriangles(u32 g) const { return range[g].y; }
-	MI_DEV V3 vertex(u32 g, u32 f, u32 k) const { uint4 t = tris[range[g].x + f]; return v3f4(verts[k == 0 ? t.x : (k == 1 ? t.y : t.z)]); }
-};
+#include "raycast_shared.h"
 
 __global__ void __launch_bounds__(64) k_interaction_batch(u32 numRays, u32 firstBody, u32 bodiesPerRay, const float4* __restrict__ rays, int32_t* __restrict__ outBody,
 	const float4* __restrict__ pose, const float4* __restrict__ bprops, const uint8_t* __restrict__ alive, const ColliderRec* __restrict__ cols,
-	const u32* __restrict__ colStart, const u32* __restrict__ colList, DeviceHulls hulls, float4* __restrict__ force)
+	const u32* __restrict__ colStart, const u32* __restrict__ colList, RcHulls hulls, float4* __restrict__ force)
 {
 	const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= numRays) return;
@@ -31,8 +26,8 @@ __global__ void __launch_bounds__(64) k_interaction_batch(u32 numRays, u32 first
 		{
 			const u32 c = colList[k];
 			const ColliderRec rec = cols[c];
-			const float s[10] = { rec.a.x, rec.a.y, rec.a.z, rec.a.w, rec.b.x, rec.b.y, rec.b.z, rec.b.w, rec.c.x, rec.c.y };
-			HRay lr; float t;
+			float s[10]; HRay lr; float t;
+			rcShape(rec, s);
 			// the host walks all colliders in index order and keeps the first of equal distances: the same choice here
 			if (rayBodyCollider(r, rot, pos, colType(rec), s, hulls, lr, t) && (t < minT || (minBody >= 0 && t == minT && c < minCol)))
 			{
@@ -50,7 +45,6 @@ __global__ void __launch_bounds__(64) k_interaction_batch(u32 numRays, u32 first
 
 void launch_interaction_batch(World& w, u32 numRays, u32 firstBody, u32 bodiesPerRay, const float* dRays, int32_t* dOutBody)
 {
-	const DeviceHulls hulls{ w.hullVerts.p, w.hullTris.p, w.hullTriRange.p };
 	hipLaunchKernelGGL(k_interaction_batch, dim3((numRays + 63) / 64), dim3(64), 0, w.stream, numRays, firstBody, bodiesPerRay, (const float4*)dRays, dOutBody,
-		w.pose.p, w.bprops.p, w.aliveMask.p, w.colLocal.p, w.bodyColStart.p, w.bodyColList.p, hulls, w.force.p);
+		w.pose.p, w.bprops.p, w.aliveMask.p, w.colLocal.p, w.bodyColStart.p, w.bodyColList.p, rcHulls(w), w.force.p);
 }

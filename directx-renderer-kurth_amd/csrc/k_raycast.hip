@@ -7,10 +7,11 @@
 //   (radix sort)  prim_sort_pairs_u32, 31 bits
 //   k_rc_tree     internal nodes after Karras (2012), equal keys separated by their sorted position
 //   k_rc_fit      node boxes bottom-up: the second child to arrive at a node merges and goes on
-//   k_raycast     one lane per ray: near child first, fixed stack in LDS; with MI_RAY_BRUTE_FORCE the same body walks all colliders;
-//                 <.., EXCLUDE = true> (mi_raycast_sensors, k_raycast_sensors.hip) skips the colliders of the ray's own body range
-// A hit is decided by rayBodyCollider (ray_tests.h) on the collider's LOCAL record and pose alone, as in k_interaction_batch; the
-// boxes only say which colliders need not be asked.
+//   k_raycast     one lane per ray: rcWalk (raycast_shared.h: near child first, fixed stack in LDS) with RcRayVisitor, the slab test and
+//                 the leaf test of a ray; with MI_RAY_BRUTE_FORCE the same leaf test on all colliders; <.., EXCLUDE = true>
+//                 (mi_raycast_sensors, k_raycast_sensors.hip) skips the colliders of the ray's own body range
+// A hit is decided by rayBodyCollider (ray_tests.h) on the collider's LOCAL record and pose alone (rcFetch), as in k_interaction_batch;
+// the boxes only say which colliders need not be asked.  The kernel reads the world through one RcScene argument (raycast_shared.h).
 #include "world.h"
 #include "ray_tests.h"
 #include "raycast_shared.h"
@@ -203,25 +204,23 @@ MI_DEV bool rcBoxTest(const RcRay& q, const float* b, float tmax, float& tEnter)
 	return !(outside || lo > tmax || hi < 0.f || lo > hi);
 }
 
-// The bodies b with b - first < count (unsigned) are no candidates of this ray: mi_raycast_sensors' exclusion range.
-struct RcExclude { u32 first, count; };
 struct RcBest { float t; u32 col, body; V3 point; }; // t starts at MI_FLT_MAX like the reference's minDistance: a test that reports FLT_MAX or +inf (a box whose slab interval is poisoned, rule R2a) has not hit
-template <bool EXCLUDE>
-MI_DEV void rcTestCollider(u32 c, const RcRay& q, RcExclude ex, u32 nb, const float4* __restrict__ pose, const float4* __restrict__ colStaticPose, const ColliderRec* __restrict__ cols, const RcHulls& hulls, RcBest& best)
+// rcWalk's visitor of a ray: a box is held against the closest hit so far, a leaf may become it.  ex: mi_raycast_sensors' exclusion range.
+struct RcRayVisitor
 {
-	const ColliderRec rec = cols[c];
-	const u32 body = colBody(rec);
-	if (EXCLUDE && body < nb && body - ex.first < ex.count) return; // (static colliders are never excluded)
-	const float4* P = (body < nb) ? (pose + 2 * body) : (colStaticPose + 2 * c);
-	const Q4 rot = q4f4(P[1]); const V3 pos = v3f4(P[0]);
-	const float s[10] = { rec.a.x, rec.a.y, rec.a.z, rec.a.w, rec.b.x, rec.b.y, rec.b.z, rec.b.w, rec.c.x, rec.c.y };
-	HRay lr; float t;
-	if (rayBodyCollider(q.r, rot, pos, colType(rec), s, hulls, lr, t) && t >= 0.f && t <= q.maxT && (t < best.t || (best.col != 0xFFFFFFFFu && t == best.t && c < best.col)))
+	const RcRay& q; RcExclude ex; const RcScene& sc; RcBest& best;
+	MI_DEV bool box(const float* b, float& tEnter) const { return rcBoxTest(q, b, fminf(q.maxT, best.t), tEnter); }
+	MI_DEV void leaf(u32 c)
 	{
-		best.t = t; best.col = c; best.body = body < nb ? body : MI_STATIC_BODY;
-		best.point = rot * (lr.origin + t * lr.direction) + pos; // interactionPush's globalHit
+		RcCollider col; HRay lr; float t;
+		if (!rcFetch(sc, c, ex, col)) return;
+		if (rayBodyCollider(q.r, col.rot, col.pos, col.type, col.s, sc.hulls, lr, t) && t >= 0.f && t <= q.maxT && (t < best.t || (best.col != 0xFFFFFFFFu && t == best.t && c < best.col)))
+		{
+			best.t = t; best.col = c; best.body = col.reported;
+			best.point = col.rot * (lr.origin + t * lr.direction) + col.pos; // interactionPush's globalHit
+		}
 	}
-}
+};
 
 // The slack of the slab test for this ray (RcRay::inv ... relT); scene = largest |coordinate|, diag = largest diagonal of the leaf boxes.
 MI_DEV void rcPrepareRay(RcRay& q, float scene, float diag)
@@ -234,40 +233,9 @@ MI_DEV void rcPrepareRay(RcRay& q, float scene, float diag)
 	q.absT = q.space * fmaxf(fmaxf(fabsf(q.inv.x), fabsf(q.inv.y)), fabsf(q.inv.z));
 	q.relT = diag / length(q.r.direction);
 }
-// Closest hit among the n >= 1 candidates of the tree.  stack[k * stride]: the caller's RC_STACK entries.
-template <bool EXCLUDE>
-MI_DEV void rcTraverse(const RcRay& q, RcExclude ex, u32 n, const float4* __restrict__ nodes, const u32* __restrict__ vals, u32* stack, u32 stride, u32 nb, const float4* __restrict__ pose,
-	const float4* __restrict__ colStaticPose, const ColliderRec* __restrict__ cols, const RcHulls& hulls, RcBest& best)
-{
-	u32 node = n == 1u ? (RC_LEAF | vals[0]) : 0u, sp = 0u;
-	for (;;)
-	{
-		if (node & RC_LEAF) rcTestCollider<EXCLUDE>(node & ~RC_LEAF, q, ex, nb, pose, colStaticPose, cols, hulls, best);
-		else
-		{
-			const float4 w0 = nodes[4 * node], w1 = nodes[4 * node + 1], w2 = nodes[4 * node + 2], w3 = nodes[4 * node + 3];
-			const float bl[6] = { w0.x, w0.y, w0.z, w0.w, w1.x, w1.y }, br[6] = { w1.z, w1.w, w2.x, w2.y, w2.z, w2.w };
-			const u32 idL = mi_f2u(w3.x), idR = mi_f2u(w3.y);
-			const float tmax = fminf(q.maxT, best.t);
-			float tL, tR;
-			const bool hitL = rcBoxTest(q, bl, tmax, tL), hitR = rcBoxTest(q, br, tmax, tR);
-			if (hitL && hitR)
-			{
-				const bool leftFirst = tL <= tR;
-				if (sp < RC_STACK) stack[stride * sp++] = leftFirst ? idR : idL; // (sp < RC_STACK always: see RC_STACK)
-				node = leftFirst ? idL : idR;
-				continue;
-			}
-			if (hitL || hitR) { node = hitL ? idL : idR; continue; }
-		}
-		if (sp == 0u) break;
-		node = stack[stride * --sp];
-	}
-}
-
+// exclude: NULL, or one {first, count} body range per ray (EXCLUDE: it is read).
 template <bool BRUTE, bool EXCLUDE>
-__global__ void __launch_bounds__(64) k_raycast(u32 numRays, const float4* __restrict__ rays, float4* __restrict__ out, u32 nb, u32 nc, const float4* __restrict__ pose, const float4* __restrict__ colStaticPose,
-	const ColliderRec* __restrict__ cols, RcHulls hulls, const u32* __restrict__ hdr, const float4* __restrict__ nodes, const u32* __restrict__ vals, const float4* __restrict__ leafBox, const uint2* __restrict__ exclude)
+__global__ void __launch_bounds__(64) k_raycast(u32 numRays, const float4* __restrict__ rays, float4* __restrict__ out, RcScene sc, const uint2* __restrict__ exclude)
 {
 	__shared__ u32 stack[BRUTE ? 1 : RC_STACK][64]; // [level][lane]: a wave's access is one row, conflict-free
 	const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -277,33 +245,23 @@ __global__ void __launch_bounds__(64) k_raycast(u32 numRays, const float4* __res
 	RcRay q; q.r = HRay{ v3(r0.x, r0.y, r0.z), v3(r1.x, r1.y, r1.z) }; q.maxT = r0.w;
 	RcExclude ex{ 0u, 0u };
 	if (EXCLUDE) { const uint2 e = exclude[i]; ex.first = e.x; ex.count = e.y; }
-	const u32 n = hdr[RC_N];
+	RcRayVisitor v{ q, ex, sc, best };
+	const u32 n = sc.hdr[RC_N];
 	if (r1.w != 0.f && n != 0u)
 	{
 		if (BRUTE)
 		{
-			for (u32 c = 0; c < nc; ++c) if (leafBox[2 * c].w != 0.f) rcTestCollider<EXCLUDE>(c, q, ex, nb, pose, colStaticPose, cols, hulls, best);
+			for (u32 c = 0; c < sc.nc; ++c) if (sc.leafBox[2 * c].w != 0.f) v.leaf(c);
 		}
 		else
 		{
-			rcPrepareRay(q, mi_u2f(hdr[RC_ABS]), mi_u2f(hdr[RC_DIAG]));
-			rcTraverse<EXCLUDE>(q, ex, n, nodes, vals, &stack[0][threadIdx.x], 64u, nb, pose, colStaticPose, cols, hulls, best);
+			rcPrepareRay(q, mi_u2f(sc.hdr[RC_ABS]), mi_u2f(sc.hdr[RC_DIAG]));
+			rcWalk(v, sc, n, &stack[0][threadIdx.x], 64u);
 		}
 	}
 	const bool hit = best.col != 0xFFFFFFFFu;
 	out[2 * i] = hit ? make_float4(best.t, mi_u2f(best.col), mi_u2f(best.body), mi_u2f(1u)) : make_float4(0.f, 0.f, 0.f, 0.f);
 	out[2 * i + 1] = hit ? make_float4(best.point.x, best.point.y, best.point.z, 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
-}
-
-template <bool BRUTE>
-static void rcLaunchCast(World& w, u32 numRays, const float* dRays, mi_ray_hit* dOutHits, const RcHulls& hulls, const uint2* dExclude)
-{
-	if (dExclude)
-		hipLaunchKernelGGL((k_raycast<BRUTE, true>), dim3((numRays + 63) / 64), dim3(64), 0, w.stream, numRays, (const float4*)dRays, (float4*)dOutHits, w.nb, w.nc, w.pose.p, w.colStaticPose.p,
-			w.colLocal.p, hulls, w.rcCount.p, (const float4*)w.rcNodes.p, w.rcValsSorted.p, w.rcLeafBox.p, dExclude);
-	else
-		hipLaunchKernelGGL((k_raycast<BRUTE, false>), dim3((numRays + 63) / 64), dim3(64), 0, w.stream, numRays, (const float4*)dRays, (float4*)dOutHits, w.nb, w.nc, w.pose.p, w.colStaticPose.p,
-			w.colLocal.p, hulls, w.rcCount.p, (const float4*)w.rcNodes.p, w.rcValsSorted.p, w.rcLeafBox.p, (const uint2*)nullptr);
 }
 
 // The tree over the current candidates in World::rc*, enqueued on the world's stream: what mi_raycast_batch and mi_proximity both walk.
@@ -342,7 +300,6 @@ void launch_raycast(World& w, u32 numRays, const float* dRays, u32 flags, mi_ray
 	const RcBuild built = launch_raycast_build(w, (flags & MI_RAY_STATIC) != 0, brute);
 	if (built == RC_BUILD_NO_CANDIDATES) { MI_CHECK(hipMemsetAsync(dOutHits, 0, sizeof(mi_ray_hit) * (size_t)numRays, w.stream)); return; } // every ray misses
 	if (built == RC_BUILD_FAILED) return;
-	const RcHulls hulls{ w.hullVerts.p, w.hullTris.p, w.hullTriRange.p };
-	if (brute) rcLaunchCast<true>(w, numRays, dRays, dOutHits, hulls, dExclude);
-	else rcLaunchCast<false>(w, numRays, dRays, dOutHits, hulls, dExclude);
+	const auto kernel = brute ? (dExclude ? k_raycast<true, true> : k_raycast<true, false>) : (dExclude ? k_raycast<false, true> : k_raycast<false, false>);
+	hipLaunchKernelGGL(kernel, dim3((numRays + 63) / 64), dim3(64), 0, w.stream, numRays, (const float4*)dRays, (float4*)dOutHits, rcScene(w), dExclude);
 }

@@ -1,10 +1,11 @@
 // mi_raycast_sensors: rays given in the frame of a body, a body range per ray that is no candidate, and the hit normal (DESIGN.md,
 // "Body-mounted ray sensors"; the rule is stated in include/mi_physics.h).  Around the one traversal of mi_raycast_batch:
-//   k_rc_sensor_rays      one lane per ray: the world ray from the mount's current pose (World::pose, the array the cast reads) into the
-//                         caller's buffer or World::rcSensorRays, and the exclusion range into World::rcSensorExclude
+//   k_rc_sensor_rays      one lane per ray: the world ray from the mount's current pose (rcMount, raycast_shared.h, on World::pose, the
+//                         array the cast reads) into the caller's buffer or World::rcSensorRays, and the exclusion range into
+//                         World::rcSensorExclude
 //   (launch_raycast)      the BVH of k_raycast.hip, built once; k_raycast<.., EXCLUDE = true> writes 32-byte records into
 //                         World::rcSensorHits; with MI_RAY_TERRAIN k_rc_terrain runs on them unchanged
-//   k_rc_sensor_normals   one lane per ray: the local ray of the winning collider again (the expression of rayBodyCollider), the normal
+//   k_rc_sensor_normals   one lane per ray: the winning collider again (rcFetch), its local ray (the expression of rayBodyCollider), the normal
 //                         rule of ray_normals.h, or the terrain triangle from its id; writes the 48-byte records
 // The two passes are kernels of their own and not folded into k_raycast: that kernel sits at 75 VGPRs with its 16 KiB stack, and the
 // normal of a hull repeats the hull's triangle loop, which inside the traversal would run for every leaf that improves the best hit.
@@ -22,12 +23,12 @@ __global__ void __launch_bounds__(256) k_rc_sensor_rays(u32 numRays, const float
 	const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= numRays) return;
 	const float4 r0 = in[3 * i], r1 = in[3 * i + 1], r2 = in[3 * i + 2];
-	const u32 mount = mi_f2u(r2.x);
-	float4 w0 = make_float4(0.f, 0.f, 0.f, 0.f), w1 = w0; // a mount that is no body, a deleted one, one simulated elsewhere: the ray is off
-	if (mount == MI_STATIC_BODY) { w0 = r0; w1 = r1; }  // already in world space: every bit as it came
-	else if (mount < nb && alive[mount] && simMask[mount])
+	Q4 rot; V3 pos;
+	const RcMount m = rcMount(mi_f2u(r2.x), nb, pose, alive, simMask, rot, pos);
+	float4 w0 = make_float4(0.f, 0.f, 0.f, 0.f), w1 = w0; // off: the ray is disabled
+	if (m == RC_MOUNT_WORLD) { w0 = r0; w1 = r1; }
+	else if (m == RC_MOUNT_BODY)
 	{
-		const V3 pos = v3f4(pose[2 * mount]); const Q4 rot = q4f4(pose[2 * mount + 1]);
 		const V3 o = rot * v3(r0.x, r0.y, r0.z) + pos, d = rot * v3(r1.x, r1.y, r1.z);
 		w0 = make_float4(o.x, o.y, o.z, r0.w); w1 = make_float4(d.x, d.y, d.z, r1.w);
 	}
@@ -47,8 +48,8 @@ MI_DEV V3 rsTerrainNormal(u32 id, const TerrainParams& P, const uint16_t* __rest
 }
 
 // hits: the 32-byte records of k_raycast / k_rc_terrain; out: 3 x float4 per ray = mi_sensor_hit.
-__global__ void __launch_bounds__(64) k_rc_sensor_normals(u32 numRays, const float4* __restrict__ worldRays, const float4* __restrict__ hits, float4* __restrict__ out, u32 nb,
-	const float4* __restrict__ pose, const float4* __restrict__ colStaticPose, const ColliderRec* __restrict__ cols, RcHulls hulls, TerrainParams P, const uint16_t* __restrict__ heights)
+__global__ void __launch_bounds__(64) k_rc_sensor_normals(u32 numRays, const float4* __restrict__ worldRays, const float4* __restrict__ hits, float4* __restrict__ out, RcScene sc,
+	TerrainParams P, const uint16_t* __restrict__ heights)
 {
 	const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= numRays) return;
@@ -61,13 +62,10 @@ __global__ void __launch_bounds__(64) k_rc_sensor_normals(u32 numRays, const flo
 		else
 		{
 			const float4 r0 = worldRays[2 * i], r1 = worldRays[2 * i + 1];
-			const ColliderRec rec = cols[c];
-			const u32 body = colBody(rec);
-			const float4* B = (body < nb) ? (pose + 2 * body) : (colStaticPose + 2 * c);
-			const Q4 rot = q4f4(B[1]); const V3 pos = v3f4(B[0]);
-			const float s[10] = { rec.a.x, rec.a.y, rec.a.z, rec.a.w, rec.b.x, rec.b.y, rec.b.z, rec.b.w, rec.c.x, rec.c.y };
-			const HRay lr{ conjugate(rot) * (v3(r0.x, r0.y, r0.z) - pos), conjugate(rot) * v3(r1.x, r1.y, r1.z) }; // rayBodyCollider's lr
-			n = rot * rayBodyColliderNormal(lr, h0.x, colType(rec), s, hulls);
+			RcCollider col;
+			rcFetch(sc, c, RcExclude{ 0u, 0u }, col); // (the winner was no excluded one)
+			const HRay lr{ conjugate(col.rot) * (v3(r0.x, r0.y, r0.z) - col.pos), conjugate(col.rot) * v3(r1.x, r1.y, r1.z) }; // rayBodyCollider's lr
+			n = col.rot * rayBodyColliderNormal(lr, h0.x, col.type, col.s, sc.hulls);
 		}
 	}
 	out[3 * i] = h0; out[3 * i + 1] = h1; out[3 * i + 2] = make_float4(n.x, n.y, n.z, 0.f);
@@ -83,7 +81,6 @@ void launch_raycast_sensors(World& w, u32 numRays, const mi_sensor_ray* dRays, u
 	launch_raycast(w, numRays, (const float*)worldRays, flags, (mi_ray_hit*)w.rcSensorHits.p, w.rcSensorExclude.p); // (no candidate collider: the records are zeroed)
 	if (terrain && !w.lastError) launch_raycast_terrain(w, numRays, (const float*)worldRays, flags, (mi_ray_hit*)w.rcSensorHits.p);
 	if (w.lastError) return;
-	const RcHulls hulls{ w.hullVerts.p, w.hullTris.p, w.hullTriRange.p };
-	hipLaunchKernelGGL(k_rc_sensor_normals, dim3((numRays + 63) / 64), dim3(64), 0, w.stream, numRays, (const float4*)worldRays, (const float4*)w.rcSensorHits.p, (float4*)dOutHits, w.nb,
-		w.pose.p, w.colStaticPose.p, w.colLocal.p, hulls, terrainParams(w), w.terrainHeights.p);
+	hipLaunchKernelGGL(k_rc_sensor_normals, dim3((numRays + 63) / 64), dim3(64), 0, w.stream, numRays, (const float4*)worldRays, (const float4*)w.rcSensorHits.p, (float4*)dOutHits, rcScene(w),
+		terrainParams(w), w.terrainHeights.p);
 }

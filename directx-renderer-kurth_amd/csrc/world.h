@@ -291,21 +291,21 @@ struct World
 	// mi_raycast_batch (k_raycast.hip): rebuilt at every call, read and written by nothing else.  Per collider: candidate flag + padded
 	// world AABB; header words + arrival counter per internal node; Morton keys and collider indices, before and after the sort; the
 	// internal nodes (64 bytes each: both children's boxes and ids); the parent of every internal node and of every sorted leaf
-	DevBuf<float4> rcHostRays, rcHostHits; // staging of mi_raycast_host
 	DevBuf<float4> rcLeafBox, rcNodes; DevBuf<u32> rcCount, rcKeys, rcKeysSorted, rcVals, rcValsSorted, rcParentInt, rcParentLeaf;
 	// MI_RAY_TERRAIN (k_raycast_terrain.hip): (max << 16) | min of the uint16 heights per 8 x 8-cell tile (256 per chunk) and per chunk.  Depends on the
 	// heights alone (not on mi_heightmap_update's corner and amplitude): invalid after mi_set_heightmap, mi_heightmap_set_chunk and a restore
 	DevBuf<u32> rcTerrainTiles, rcTerrainChunkRange; bool rcTerrainTableValid = false;
 	// mi_raycast_sensors (k_raycast_sensors.hip): per ray the world ray (2 x float4, used when the caller wants none back), the 32-byte
-	// record k_raycast and k_rc_terrain work on (2 x float4) and the exclusion range {first, count}; staging of mi_raycast_sensors_host
-	DevBuf<float4> rcSensorRays, rcSensorHits; DevBuf<uint2> rcSensorExclude; DevBuf<float4> rcSensorHostIn, rcSensorHostOut, rcSensorHostRays;
-	// mi_proximity (k_proximity.hip) walks the tree above and keeps nothing of its own; staging of mi_proximity_host: queries (2 x float4),
-	// readings (3 x float4), world points (1 x float4)
-	DevBuf<float4> pxHostIn, pxHostOut, pxHostPoints;
+	// record k_raycast and k_rc_terrain work on (2 x float4) and the exclusion range {first, count}
+	DevBuf<float4> rcSensorRays, rcSensorHits; DevBuf<uint2> rcSensorExclude;
+	// (mi_proximity, k_proximity.hip, walks the tree above and keeps nothing of its own)
 	// mi_contact_sensors (k_contact_sensors.hip): rebuilt at every call.  Per body of the last step {wanted by a sensor, its manifolds, its
 	// first entry, fill cursor}; the entries (manifold slot << 32 | schedule position), a segment per wanted body, two per position at most;
-	// the bodies whose segment one lane does not sort; {entries handed out, length of that list}; staging of mi_contact_sensors_host
-	DevBuf<uint4> csBody; DevBuf<u64> csEntries; DevBuf<u32> csLarge, csMeta; DevBuf<float4> csHostIn, csHostOut;
+	// the bodies whose segment one lane does not sort; {entries handed out, length of that list}
+	DevBuf<uint4> csBody; DevBuf<u64> csEntries; DevBuf<u32> csLarge, csMeta;
+	// Staging of the queries' _host entries (api.hip, queryStaged), in bytes: the records in, the records out, the optional second output
+	// (world rays, world points).  One set for all of them: every _host entry drains the world's stream before it returns
+	DevBuf<uint8_t> queryHostIn, queryHostOut, queryHostAux;
 
 	World(int dev);
 	~World();

@@ -75,10 +75,10 @@ World::~World()
 	rowLambda.release(); rowIds.release(); tempStorage.release(); actIds.release(); epaList.release(); gjkSimplex.release(); pairSlab.release(); simMask.release();
 	for (auto& js : joints) { js.dPods.release(); js.dPairs.release(); js.dUpdate.release(); }
 	bodyColStart.release(); bodyColList.release(); hullTris.release(); hullTriRange.release();
-	rcHostRays.release(); rcHostHits.release(); rcLeafBox.release(); rcNodes.release(); rcCount.release(); rcKeys.release(); rcKeysSorted.release(); rcVals.release(); rcValsSorted.release(); rcParentInt.release(); rcParentLeaf.release(); rcTerrainTiles.release(); rcTerrainChunkRange.release();
-	rcSensorRays.release(); rcSensorHits.release(); rcSensorExclude.release(); rcSensorHostIn.release(); rcSensorHostOut.release(); rcSensorHostRays.release();
-	pxHostIn.release(); pxHostOut.release(); pxHostPoints.release();
-	csBody.release(); csEntries.release(); csLarge.release(); csMeta.release(); csHostIn.release(); csHostOut.release();
+	rcLeafBox.release(); rcNodes.release(); rcCount.release(); rcKeys.release(); rcKeysSorted.release(); rcVals.release(); rcValsSorted.release(); rcParentInt.release(); rcParentLeaf.release(); rcTerrainTiles.release(); rcTerrainChunkRange.release();
+	rcSensorRays.release(); rcSensorHits.release(); rcSensorExclude.release();
+	csBody.release(); csEntries.release(); csLarge.release(); csMeta.release();
+	queryHostIn.release(); queryHostOut.release(); queryHostAux.release();
 	for (auto& e : stageEvents) if (e) (void)hipEventDestroy(e);
 	if (countersEvent) (void)hipEventDestroy(countersEvent);
 	if (hCounters) (void)hipHostFree(hCounters);

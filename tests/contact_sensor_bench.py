@@ -18,20 +18,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import directx_renderer_kurth_amd as mi  # noqa: E402
 from directx_renderer_kurth_amd import scenes  # noqa: E402
-
-
-def time_calls(call, stream, repeats, warmup=3):
-    ms = []
-    for k in range(warmup + repeats):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(stream)
-        code = call()
-        b.record(stream)
-        b.synchronize()
-        assert code == 0, code
-        if k >= warmup:
-            ms.append(a.elapsed_time(b))
-    return float(np.median(ms)), float(np.min(ms)), float(np.max(ms))
+from bench_util import time_calls  # noqa: E402
 
 
 def main():

@@ -18,20 +18,11 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import directx_renderer_kurth_amd as mi  # noqa: E402
 from directx_renderer_kurth_amd import scenes  # noqa: E402
+from bench_util import time_calls  # noqa: E402
 
 
-def time_calls(w, stream, d_in, d_out, n, flags, repeats, warmup=3):
-    ms = []
-    for k in range(warmup + repeats):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(stream)
-        code = w.lib.mi_proximity(w.w, ctypes.c_uint32(n), ctypes.c_void_p(d_in.data_ptr()), ctypes.c_uint32(flags), ctypes.c_void_p(d_out.data_ptr()), None)
-        b.record(stream)
-        b.synchronize()
-        assert code == 0, code
-        if k >= warmup:
-            ms.append(a.elapsed_time(b))
-    return float(np.median(ms)), float(np.min(ms)), float(np.max(ms))
+def time_queries(w, stream, d_in, d_out, n, flags, repeats, warmup=3):
+    return time_calls(lambda: w.lib.mi_proximity(w.w, ctypes.c_uint32(n), ctypes.c_void_p(d_in.data_ptr()), ctypes.c_uint32(flags), ctypes.c_void_p(d_out.data_ptr()), None), stream, repeats, warmup)
 
 
 def main():
@@ -64,9 +55,9 @@ def main():
                 d_in = torch.from_numpy(rec.view(np.float32).reshape(n, 8).copy()).to(dev)
                 d_tree, d_brute = torch.zeros((n, 12), dtype=torch.float32, device=dev), torch.zeros((n, 12), dtype=torch.float32, device=dev)
                 stream.synchronize()
-                build = time_calls(w, stream, d_in, d_tree, 1, mi.PROX_STATIC | count, args.repeats)
-                tree = time_calls(w, stream, d_in, d_tree, n, mi.PROX_STATIC | count, args.repeats)
-                brute = time_calls(w, stream, d_in, d_brute, n, mi.PROX_STATIC | count | mi.PROX_BRUTE_FORCE, args.brute_repeats, warmup=1)
+                build = time_queries(w, stream, d_in, d_tree, 1, mi.PROX_STATIC | count, args.repeats)
+                tree = time_queries(w, stream, d_in, d_tree, n, mi.PROX_STATIC | count, args.repeats)
+                brute = time_queries(w, stream, d_in, d_brute, n, mi.PROX_STATIC | count | mi.PROX_BRUTE_FORCE, args.brute_repeats, warmup=1)
                 stream.synchronize()
                 same = bool(torch.equal(d_tree.view(torch.int32), d_brute.view(torch.int32)))
                 found = int(d_tree.view(torch.int32)[:, 3].sum().item())

@@ -19,6 +19,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import directx_renderer_kurth_amd as mi  # noqa: E402
 from directx_renderer_kurth_amd import scenes  # noqa: E402
+from bench_util import time_calls  # noqa: E402
 
 
 def make_rays(n, lo, hi, top, seed=99):
@@ -39,18 +40,8 @@ def make_rays(n, lo, hi, top, seed=99):
     return rays
 
 
-def time_calls(w, stream, d_rays, d_out, n, flags, repeats, warmup=3):
-    ms = []
-    for k in range(warmup + repeats):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(stream)
-        code = w.lib.mi_raycast_batch(w.w, ctypes.c_uint32(n), ctypes.c_void_p(d_rays.data_ptr()), ctypes.c_uint32(flags), ctypes.c_void_p(d_out.data_ptr()))
-        b.record(stream)
-        b.synchronize()
-        assert code == 0, code
-        if k >= warmup:
-            ms.append(a.elapsed_time(b))
-    return float(np.median(ms)), float(np.min(ms)), float(np.max(ms))
+def time_cast(w, stream, d_rays, d_out, n, flags, repeats, warmup=3):
+    return time_calls(lambda: w.lib.mi_raycast_batch(w.w, ctypes.c_uint32(n), ctypes.c_void_p(d_rays.data_ptr()), ctypes.c_uint32(flags), ctypes.c_void_p(d_out.data_ptr())), stream, repeats, warmup)
 
 
 def main():
@@ -80,9 +71,9 @@ def main():
                 d_rays = torch.from_numpy(rays).to(dev)
                 d_tree, d_brute = torch.zeros((n, 8), dtype=torch.float32, device=dev), torch.zeros((n, 8), dtype=torch.float32, device=dev)
                 stream.synchronize()
-                build = time_calls(w, stream, d_rays, d_tree, 1, mi.RAY_STATIC, args.repeats)
-                tree = time_calls(w, stream, d_rays, d_tree, n, mi.RAY_STATIC, args.repeats)
-                brute = time_calls(w, stream, d_rays, d_brute, n, mi.RAY_STATIC | mi.RAY_BRUTE_FORCE, args.brute_repeats, warmup=1)
+                build = time_cast(w, stream, d_rays, d_tree, 1, mi.RAY_STATIC, args.repeats)
+                tree = time_cast(w, stream, d_rays, d_tree, n, mi.RAY_STATIC, args.repeats)
+                brute = time_cast(w, stream, d_rays, d_brute, n, mi.RAY_STATIC | mi.RAY_BRUTE_FORCE, args.brute_repeats, warmup=1)
                 stream.synchronize()
                 same = bool(torch.equal(d_tree.view(torch.int32), d_brute.view(torch.int32)))
                 hits = int(d_tree.view(torch.int32)[:, 3].sum().item())

@@ -18,6 +18,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import directx_renderer_kurth_amd as mi  # noqa: E402
 from directx_renderer_kurth_amd import scenes  # noqa: E402
+from bench_util import time_calls  # noqa: E402
 
 
 def vertical_scan(n, lo, hi, y):
@@ -40,18 +41,8 @@ def slanted(n, lo, hi, y, seed=99):
     return rays
 
 
-def time_calls(w, stream, d_rays, d_out, n, flags, repeats, warmup=3):
-    ms = []
-    for k in range(warmup + repeats):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(stream)
-        code = w.lib.mi_raycast_batch(w.w, ctypes.c_uint32(n), ctypes.c_void_p(d_rays.data_ptr()), ctypes.c_uint32(flags), ctypes.c_void_p(d_out.data_ptr()))
-        b.record(stream)
-        b.synchronize()
-        assert code == 0, code
-        if k >= warmup:
-            ms.append(a.elapsed_time(b))
-    return float(np.median(ms)), float(np.min(ms)), float(np.max(ms))
+def time_cast(w, stream, d_rays, d_out, n, flags, repeats, warmup=3):
+    return time_calls(lambda: w.lib.mi_raycast_batch(w.w, ctypes.c_uint32(n), ctypes.c_void_p(d_rays.data_ptr()), ctypes.c_uint32(flags), ctypes.c_void_p(d_out.data_ptr())), stream, repeats, warmup)
 
 
 def main():
@@ -79,13 +70,13 @@ def main():
                 d_rays = torch.from_numpy(rays).to(dev)
                 d_plain, d_walk, d_brute = (torch.zeros((n, 8), dtype=torch.float32, device=dev) for _ in range(3))
                 stream.synchronize()
-                plain = time_calls(w, stream, d_rays, d_plain, n, mi.RAY_STATIC, args.repeats)
-                walk = time_calls(w, stream, d_rays, d_walk, n, mi.RAY_STATIC | mi.RAY_TERRAIN, args.repeats)
+                plain = time_cast(w, stream, d_rays, d_plain, n, mi.RAY_STATIC, args.repeats)
+                walk = time_cast(w, stream, d_rays, d_walk, n, mi.RAY_STATIC | mi.RAY_TERRAIN, args.repeats)
                 line = "  %6d rays, %-13s: colliders only %.3f ms/call [%.3f, %.3f]; with terrain (walk) %.3f ms/call [%.3f, %.3f] = %.3g rays/s; the terrain pass adds %.3f ms" % (
                     n, name, plain[0], plain[1], plain[2], walk[0], walk[1], walk[2], n / (walk[0] * 1e-3), walk[0] - plain[0])
                 if n <= 4096:
-                    brute = time_calls(w, stream, d_rays, d_brute, n, mi.RAY_STATIC | mi.RAY_TERRAIN | mi.RAY_BRUTE_FORCE, args.brute_repeats, warmup=1)
-                    plain_brute = time_calls(w, stream, d_rays, d_plain, n, mi.RAY_STATIC | mi.RAY_BRUTE_FORCE, args.brute_repeats, warmup=1)
+                    brute = time_cast(w, stream, d_rays, d_brute, n, mi.RAY_STATIC | mi.RAY_TERRAIN | mi.RAY_BRUTE_FORCE, args.brute_repeats, warmup=1)
+                    plain_brute = time_cast(w, stream, d_rays, d_plain, n, mi.RAY_STATIC | mi.RAY_BRUTE_FORCE, args.brute_repeats, warmup=1)
                     stream.synchronize()
                     same = bool(torch.equal(d_walk.view(torch.int32), d_brute.view(torch.int32)))
                     line += "; brute force %.3f ms/call [%.3f, %.3f], of it the terrain %.3f ms; records identical: %s" % (brute[0], brute[1], brute[2], brute[0] - plain_brute[0], same)
