@@ -143,8 +143,14 @@ MI_DEV void writeManifold(ManifoldRec* __restrict__ out, u32 slot, const Man& m,
 	out[slot] = r;
 }
 
-// The stages in the order launch_narrowphase runs them after classify / sort / bucket offsets, all on w.stream; numPairs sizes the
-// grids (the launch may be larger than the device's pair count: every kernel cuts itself to the bucket ranges in the counters).
+// The stages launch_narrowphase runs after classify / sort / bucket offsets; numPairs sizes the grids (the launch may be larger than
+// the device's pair count: every kernel cuts itself to the bucket ranges in the counters).  They form two chains that share no data:
+// each reads its own buckets of the sorted pair list and writes those buckets' manifold slots, the counters k_bucket_offsets wrote
+// are read-only to both, and CTR_EPA_COUNT* / CTR_NARROW_LIMITS belong to GJK + EPA alone.  So behind k_bucket_offsets the pair
+// kernels run on the world's side stream (World::narrowStream) while GJK -> EPA run on w.stream, and w.stream waits for the side
+// stream before anything else is launched: in launch_narrowphase, or, for the launch a step makes ahead of its host
+// synchronisation, in launch_narrow_side behind it (k_narrow_classify.hip says why).  With MI_NARROW_SIDE_STREAM=0 all of them
+// run on w.stream: GJK, pair kernels, EPA.
 void launch_gjk(World& w, u32 numPairs);           // k_narrow_gjk.hip: GJK on the tube family, and on the hull family if the world has hulls; fills the EPA work lists
-void launch_pair_kernels(World& w, u32 numPairs);  // k_narrow_pairs.hip: closed forms, then box-box
+void launch_pair_kernels(World& w, u32 numPairs, hipStream_t stream); // k_narrow_pairs.hip: closed forms, then box-box, on `stream`
 void launch_epa(World& w, u32 numPairs);           // k_narrow_gjk.hip: EPA + face clipping on the GJK hits of both families

@@ -295,7 +295,7 @@ static bool launchStepStart(World& w, hipEvent_t* ev, u32& guess)
 	if ((size_t)guess + w.terrainSlotCap() > w.pairCap) return false;
 	launch_broadphase_write(w, guess, w.last.slabOverflow);
 	stamp(w, ev, 1);
-	launch_narrowphase(w, guess, w.stats.numInternalSteps & 1u);
+	launch_narrowphase(w, guess, w.stats.numInternalSteps & 1u, true); // (its side chain: launchCollisionStages, if this launch stands)
 	return true;
 }
 
@@ -351,6 +351,7 @@ static bool launchCollisionStages(World& w, hipEvent_t* ev, const StepRecord& cu
 		stamp(w, ev, 1);
 		launch_narrowphase(w, cur.truePairs, w.stats.numInternalSteps & 1u);
 	}
+	else launch_narrow_side(w);                            // the early launch stands: its side-stream chain and the join
 	launch_zone_overlap(w, early ? guess : cur.truePairs);
 	launch_heightmap(w, cur.truePairs, cur.numPairs);      // physics.cpp:1236-1249
 	launch_trigger_events(w);                              // physics.cpp:1255 (handleNonCollisionInteractions)

@@ -1,5 +1,5 @@
 // Host-side World of the MI355X rigid-body stepper: owns the SoA device buffers (HBM layout in DESIGN.md), one HIP
-// stream, and the per-step launch sequence.  The C-ABI in include/mi_physics.h is a thin shell over this class.
+// stream (plus a side stream that only the narrowphase forks to and joins from), and the per-step launch sequence.  The C-ABI in include/mi_physics.h is a thin shell over this class.
 #pragma once
 #include "mi_common.h"
 #include "../../include/mi_physics.h"
@@ -148,6 +148,11 @@ struct World
 {
 	int device = 0;
 	hipStream_t stream = nullptr;
+	// The narrowphase's second chain (closed forms + box-box beside GJK + EPA): forked from `stream` in launch_narrowphase and joined
+	// into it again by launch_narrow_side, before anything else is launched, so nothing else ever sees it.  narrowSidePairs: the
+	// launch size of a side chain that launch_narrowphase left to a later launch_narrow_side (0: none owed).
+	// MI_NARROW_SIDE_STREAM=0: not used, every kernel on `stream`.
+	hipStream_t narrowStream = nullptr; hipEvent_t narrowFork = nullptr, narrowJoin = nullptr; bool narrowSideStream = true; u32 narrowSidePairs = 0;
 	int lastError = 0; std::string lastErrorText;
 
 	// ---- host mirrors (add API) ----
@@ -329,7 +334,8 @@ u32 active_grid(u32 estimate, u32 total);
 void launch_build_colliders(World& w);
 void launch_broadphase_count(World& w);                    // grid build + pair count + scan; leaves numPairs in dCounters
 void launch_broadphase_write(World& w, u32 numPairs, bool slabOverflow);       // slabOverflow: some collider has more partners than its slab holds (CTR_PAIR_OVERFLOW)
-void launch_narrowphase(World& w, u32 numPairs, u32 stepParity); // numPairs may exceed the device's pair count (a launch sized before the host knows it); stepParity: the internal step's k & 1 (its sorting-axis word)
+void launch_narrowphase(World& w, u32 numPairs, u32 stepParity, bool deferSide = false); // numPairs may exceed the device's pair count (a launch sized before the host knows it); stepParity: the internal step's k & 1 (its sorting-axis word); deferSide: the side-stream chain and the join are left to launch_narrow_side
+void launch_narrow_side(World& w);                           // side chain + join that the last launch_narrowphase deferred (nothing if it deferred none): before anything else is launched on the results
 void launch_zone_overlap(World& w, u32 numPairs);           // force-field / trigger overlap tests on the classified pairs (once per step)
 void launch_integrate_forces(World& w, float dt, bool backupVelocities); // backupVelocities: keep the pre-solve velocities in velBackup (a cluster step)
 void launch_heightmap(World& w, u32 numPairs, u32 slotCap);  // terrain contacts appended after the pair manifolds (physics.cpp:1236-1249)

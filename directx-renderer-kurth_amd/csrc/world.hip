@@ -38,6 +38,15 @@ World::World(int dev) : device(dev)
 	g_currentWorld = this;
 	MI_CHECK(hipSetDevice(dev));
 	MI_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+	if (const char* e = getenv("MI_NARROW_SIDE_STREAM")) narrowSideStream = atoi(e) != 0; // 0: the narrowphase's pair kernels stay on `stream`
+	if (narrowSideStream)
+	{
+		MI_CHECK(hipStreamCreateWithFlags(&narrowStream, hipStreamNonBlocking));
+		// (device-scope, like the stage events: both streams are this device's, nothing of the host's is ordered by them)
+		MI_CHECK(hipEventCreateWithFlags(&narrowFork, hipEventDisableTiming | hipEventDisableSystemFence));
+		MI_CHECK(hipEventCreateWithFlags(&narrowJoin, hipEventDisableTiming | hipEventDisableSystemFence));
+		if (!narrowStream || !narrowFork || !narrowJoin) narrowSideStream = false; // (the world's error is set)
+	}
 	MI_CHECK(hipHostMalloc((void**)&hCounters, CTR_WORDS * sizeof(u32), hipHostMallocDefault));
 	if (hCounters) memset(hCounters, 0, CTR_WORDS * sizeof(u32));
 	dCounters.ensure(CTR_WORDS, stream);
@@ -65,6 +74,7 @@ World::World(int dev) : device(dev)
 World::~World()
 {
 	g_currentWorld = this;
+	if (narrowStream) (void)hipStreamSynchronize(narrowStream);
 	if (stream) (void)hipStreamSynchronize(stream);
 	DevBuf<float4>* f4[] = { &pose, &pose0, &poseLerp, &vel, &bprops, &force, &cog, &invIw, &colStaticPose, &aabbMin, &aabbMax, &sBox, &rowPlanes, &rowShared };
 	for (auto b : f4) b->release();
@@ -82,6 +92,9 @@ World::~World()
 	for (auto& e : stageEvents) if (e) (void)hipEventDestroy(e);
 	if (countersEvent) (void)hipEventDestroy(countersEvent);
 	if (hCounters) (void)hipHostFree(hCounters);
+	if (narrowFork) (void)hipEventDestroy(narrowFork);
+	if (narrowJoin) (void)hipEventDestroy(narrowJoin);
+	if (narrowStream) (void)hipStreamDestroy(narrowStream);
 	if (stream) (void)hipStreamDestroy(stream);
 	g_currentWorld = nullptr;
 }
