@@ -107,6 +107,25 @@ PROXIMITY_QUERY_DTYPE = np.dtype([("point", "<f4", 3), ("radius", "<f4"), ("moun
 PROXIMITY_READING_DTYPE = np.dtype([("distance", "<f4"), ("collider", "<u4"), ("body", "<u4"), ("found", "<u4"), ("point", "<f4", 3), ("numWithin", "<u4"),
                                     ("normal", "<f4", 3), ("reserved", "<f4")])
 PROX_STATIC, PROX_BRUTE_FORCE, PROX_COUNT = 1, 2, 4   # mi_proximity's flags (MI_PROX_*)
+
+
+class SphereCast(C.Structure):
+    """struct mi_sphere_cast (include/mi_physics.h): one swept sphere of mi_sphere_cast_batch in the frame of body `mount`, 48 bytes"""
+    _fields_ = [("origin", C.c_float * 3), ("maxT", C.c_float), ("direction", C.c_float * 3), ("radius", C.c_float),
+                ("mount", C.c_uint32), ("excludeFirst", C.c_uint32), ("excludeCount", C.c_uint32), ("enabled", C.c_uint32)]
+
+
+class SphereHit(C.Structure):
+    """struct mi_sphere_hit (include/mi_physics.h): where the sphere stops (t), on what, the surface point, gap and normal there, 48 bytes"""
+    _fields_ = [("t", C.c_float), ("collider", C.c_uint32), ("body", C.c_uint32), ("hit", C.c_uint32), ("point", C.c_float * 3), ("gap", C.c_float),
+                ("normal", C.c_float * 3), ("iterations", C.c_uint32)]
+
+
+SPHERE_CAST_DTYPE = np.dtype([("origin", "<f4", 3), ("maxT", "<f4"), ("direction", "<f4", 3), ("radius", "<f4"),
+                              ("mount", "<u4"), ("excludeFirst", "<u4"), ("excludeCount", "<u4"), ("enabled", "<u4")])
+SPHERE_HIT_DTYPE = np.dtype([("t", "<f4"), ("collider", "<u4"), ("body", "<u4"), ("hit", "<u4"), ("point", "<f4", 3), ("gap", "<f4"),
+                             ("normal", "<f4", 3), ("iterations", "<u4")])
+SPHERE_STATIC, SPHERE_BRUTE_FORCE = 1, 2   # mi_sphere_cast_batch's flags (MI_SPHERE_*)
 TERRAIN_COLLIDER = 0xFFFFFFFE   # mi_ray_hit.collider of a hit on the heightmap terrain (MI_TERRAIN_COLLIDER)
 
 
@@ -163,6 +182,7 @@ EXPORTED_SYMBOLS = [
     "mi_raycast_sensors", "mi_raycast_sensors_host",
     "mi_contact_sensors", "mi_contact_sensors_host", "mi_debug_read_contact_rows",
     "mi_proximity", "mi_proximity_host",
+    "mi_sphere_cast_batch", "mi_sphere_cast_host",
 ]
 
 
@@ -250,7 +270,7 @@ def _ray_flags(static, brute_force, terrain):
 
 
 def _fill_mount(rec, mount, exclude_first, exclude_count):
-    """mount (None: world space) and the exclusion range (None: nothing) of SENSOR_RAY_DTYPE / PROXIMITY_QUERY_DTYPE records"""
+    """mount (None: world space) and the exclusion range (None: nothing) of SENSOR_RAY_DTYPE / PROXIMITY_QUERY_DTYPE / SPHERE_CAST_DTYPE records"""
     rec["mount"] = STATIC_BODY if mount is None else np.asarray(mount, np.uint32)
     rec["excludeFirst"] = 0 if exclude_first is None else np.asarray(exclude_first, np.uint32)
     rec["excludeCount"] = 0 if exclude_count is None else np.asarray(exclude_count, np.uint32)
@@ -622,6 +642,38 @@ class World:
         out, wp = np.zeros(len(rec), PROXIMITY_READING_DTYPE), np.zeros((len(rec), 4), np.float32)
         self._query_numpy(entry(self.lib.mi_proximity if device else self.lib.mi_proximity_host), rec, out, wp if world_points else None, device)
         return (out, wp) if world_points else out
+
+    def sphere_cast(self, origins, directions=None, radius=0.0, max_t=np.inf, mount=None, exclude_first=None, exclude_count=None, static=True, brute_force=False,
+                    world_casts=False, device=False):
+        """mi_sphere_cast_batch: per query how far a sphere of `radius` travels from origins[i] along directions[i] (t in units of the
+        direction's length, at most max_t) before it touches a collider, and where and on what (the rule is in include/mi_physics.h; the
+        heightmap is no candidate).  origins, directions [n, 3] in the frame of body mount[i] at its current pose (mount: an index or an
+        array [n]; None / STATIC_BODY: world space); radius, max_t: numbers or arrays [n]; blind to the colliders of the bodies
+        exclude_first[i] ... + exclude_count[i] - 1.  `origins` may also be a SPHERE_CAST_DTYPE array (the other query arguments are then
+        not used).
+        numpy queries return a SPHERE_HIT_DTYPE array [n] (hit = 1, or 2 for a cast that used up its iterations; all zero for a miss), with
+        world_casts=True a tuple with the world casts [n, 8] = origin, maxT, direction, radius: through the world's staging buffers
+        (mi_sphere_cast_host), or with device=True through device tensors of the caller's (mi_sphere_cast_batch).
+        A torch tensor on the device (float32, contiguous, [n, 12]: the bits of mi_sphere_cast) is cast in place: returns one float32
+        tensor [n, 12] of mi_sphere_hit records (with world_casts=True a tuple with the [n, 8] world casts), enqueued on the world's
+        stream with no synchronisation.  (The tensor is recorded on that stream, as in raycast: release it before close().)"""
+        flags = (SPHERE_STATIC if static else 0) | (SPHERE_BRUTE_FORCE if brute_force else 0)
+
+        def entry(fn):
+            return lambda n, d_in, d_out, d_aux: fn(self.w, C.c_uint32(n), C.c_void_p(d_in), C.c_uint32(flags), C.c_void_p(d_out), C.c_void_p(d_aux))
+        if _is_tensor(origins):
+            return self._query_in_place("sphere_cast", entry(self.lib.mi_sphere_cast_batch), origins, 12, 12, 8 if world_casts else 0)
+        if isinstance(origins, np.ndarray) and origins.dtype == SPHERE_CAST_DTYPE:
+            rec = np.ascontiguousarray(origins).reshape(-1)
+        else:
+            o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+            rec = np.zeros(len(o), SPHERE_CAST_DTYPE)
+            rec["origin"], rec["direction"], rec["enabled"] = o, np.ascontiguousarray(directions, np.float32).reshape(-1, 3), 1
+            rec["radius"], rec["maxT"] = np.asarray(radius, np.float32), np.asarray(max_t, np.float32)
+            _fill_mount(rec, mount, exclude_first, exclude_count)
+        out, wc = np.zeros(len(rec), SPHERE_HIT_DTYPE), np.zeros((len(rec), 8), np.float32)
+        self._query_numpy(entry(self.lib.mi_sphere_cast_batch if device else self.lib.mi_sphere_cast_host), rec, out, wc if world_casts else None, device)
+        return (out, wc) if world_casts else out
 
     def contact_sensors(self, sensors, device=False):
         """mi_contact_sensors: per sensor the impulses the contacts of the last internal step applied to its body, summed on the device

@@ -434,6 +434,22 @@ int mi_proximity_host(mi_world* world, uint32_t numQueries, const mi_proximity_q
 		[&](void* dIn, void* dOut, void* dAux) { return mi_proximity(world, numQueries, (const mi_proximity_query*)dIn, flags, (mi_proximity_reading*)dOut, (float*)dAux); });
 }
 
+// (sphere casts: the rule is in include/mi_physics.h, the march in sphere_cast.h, the walk in k_spherecast.hip)
+int mi_sphere_cast_batch(mi_world* world, uint32_t numQueries, const mi_sphere_cast* dQueries, uint32_t flags, mi_sphere_hit* dOut, float* dOutWorldCasts)
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	int code;
+	if (!queryBegin(W, numQueries, dQueries && dOut, true, code)) return code;
+	launch_sphere_cast(*W, numQueries, dQueries, flags, dOut, dOutWorldCasts);
+	return W->lastError;
+}
+int mi_sphere_cast_host(mi_world* world, uint32_t numQueries, const mi_sphere_cast* queries, uint32_t flags, mi_sphere_hit* out, float* outWorldCasts)
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	return queryStaged(W, numQueries, queries, sizeof(mi_sphere_cast), out, sizeof(mi_sphere_hit), outWorldCasts, 32,
+		[&](void* dIn, void* dOut, void* dAux) { return mi_sphere_cast_batch(world, numQueries, (const mi_sphere_cast*)dIn, flags, (mi_sphere_hit*)dOut, (float*)dAux); });
+}
+
 // (contact sensors: the rule is in include/mi_physics.h, the reduction in k_contact_sensors.hip)
 int mi_contact_sensors(mi_world* world, uint32_t numSensors, const mi_contact_sensor* dSensors, mi_contact_reading* dOut)
 {

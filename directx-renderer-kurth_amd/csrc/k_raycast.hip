@@ -19,12 +19,10 @@
 void prim_sort_pairs_u32(World& w, const u32* kin, u32* kout, const u32* vin, u32* vout, u32 n, u32 bits);
 
 
-// Leaf pad, per axis: RC_PAD_ULPS ulps of (largest |coordinate| of the box + its diagonal) + RC_PAD_FLOOR.  Slack of the slab test:
-// RC_SLACK_ULPS ulps of (|origin| + largest |coordinate| of the scene) in space, RC_SLACK_REL of the distance in t.  DESIGN.md derives them.
+// Leaf pad, per axis: RC_PAD_ULPS ulps of (largest |coordinate| of the box + its diagonal) + RC_PAD_FLOOR.  DESIGN.md derives them.
+// (The slack of the slab test, RC_SLACK_ULPS and RC_SLACK_REL: raycast_shared.h.)
 #define RC_PAD_ULPS 8.f
 #define RC_PAD_FLOOR 1e-5f
-#define RC_SLACK_ULPS 16.f
-#define RC_SLACK_REL (1.f / 256.f)
 
 MI_DEV u32 rcOrdered(float f) { u32 u = mi_f2u(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); } // order-preserving, never 0 for a finite f
 MI_DEV float rcUnordered(u32 u) { return mi_u2f((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u); }
@@ -181,29 +179,7 @@ __global__ void __launch_bounds__(256) k_rc_fit(const u32* __restrict__ hdr, con
 	if (n >= 2u && j < n) rcFitLeaf(j, vals, leafBox, parentInt, parentLeaf, nodes, arrivals);
 }
 
-struct RcRay
-{
-	HRay r; float maxT;
-	V3 inv; bool par[3];        // 1 / direction; axes the ray does not move along are tested by containment
-	float space, absT, relT;    // slack of the slab test: in space, in t, and the share of the largest leaf in the relative part
-};
-// May the ray hit something in this padded box at a distance in [0, tmax]?  Conservative: the interval is widened by the slack, a box
-// entered exactly at tmax is visited (a lower collider index may win the tie), and a comparison with a NaN visits.  tEnter orders the visit.
-MI_DEV bool rcBoxTest(const RcRay& q, const float* b, float tmax, float& tEnter)
-{
-	float tE = -MI_FLT_MAX, tX = MI_FLT_MAX; bool outside = false;
-	const float o[3] = { q.r.origin.x, q.r.origin.y, q.r.origin.z }, inv[3] = { q.inv.x, q.inv.y, q.inv.z };
-	#pragma unroll
-	for (u32 a = 0; a < 3; ++a)
-	{
-		if (q.par[a]) outside = outside || o[a] < b[a] - q.space || o[a] > b[3 + a] + q.space;
-		else { const float t1 = (b[a] - o[a]) * inv[a], t2 = (b[3 + a] - o[a]) * inv[a]; tE = fmaxf(tE, fminf(t1, t2)); tX = fminf(tX, fmaxf(t1, t2)); }
-	}
-	const float lo = tE - q.absT - RC_SLACK_REL * (fmaxf(tE, 0.f) + q.relT), hi = tX + q.absT + RC_SLACK_REL * (fabsf(tX) + q.relT);
-	tEnter = tE;
-	return !(outside || lo > tmax || hi < 0.f || lo > hi);
-}
-
+// (RcRay, rcBoxTest, rcPrepareRay and the slack of the slab test: raycast_shared.h, shared with k_spherecast.hip)
 struct RcBest { float t; u32 col, body; V3 point; }; // t starts at MI_FLT_MAX like the reference's minDistance: a test that reports FLT_MAX or +inf (a box whose slab interval is poisoned, rule R2a) has not hit
 // rcWalk's visitor of a ray: a box is held against the closest hit so far, a leaf may become it.  ex: mi_raycast_sensors' exclusion range.
 struct RcRayVisitor
@@ -222,17 +198,6 @@ struct RcRayVisitor
 	}
 };
 
-// The slack of the slab test for this ray (RcRay::inv ... relT); scene = largest |coordinate|, diag = largest diagonal of the leaf boxes.
-MI_DEV void rcPrepareRay(RcRay& q, float scene, float diag)
-{
-	const V3 ad = vabs(q.r.direction), ao = vabs(q.r.origin);
-	const float dMax = fmaxf(fmaxf(ad.x, ad.y), ad.z);
-	q.par[0] = !(ad.x > 1e-12f * dMax); q.par[1] = !(ad.y > 1e-12f * dMax); q.par[2] = !(ad.z > 1e-12f * dMax);
-	q.inv = v3(q.par[0] ? 0.f : 1.f / q.r.direction.x, q.par[1] ? 0.f : 1.f / q.r.direction.y, q.par[2] ? 0.f : 1.f / q.r.direction.z);
-	q.space = RC_SLACK_ULPS * RC_EPS * (fmaxf(fmaxf(ao.x, ao.y), ao.z) + scene);
-	q.absT = q.space * fmaxf(fmaxf(fabsf(q.inv.x), fabsf(q.inv.y)), fabsf(q.inv.z));
-	q.relT = diag / length(q.r.direction);
-}
 // exclude: NULL, or one {first, count} body range per ray (EXCLUDE: it is read).
 template <bool BRUTE, bool EXCLUDE>
 __global__ void __launch_bounds__(64) k_raycast(u32 numRays, const float4* __restrict__ rays, float4* __restrict__ out, RcScene sc, const uint2* __restrict__ exclude)

@@ -1,11 +1,13 @@
-// What the query kernels share (k_raycast.hip, k_raycast_sensors.hip, k_proximity.hip, k_interact.hip):
+// What the query kernels share (k_raycast.hip, k_raycast_sensors.hip, k_proximity.hip, k_spherecast.hip, k_interact.hip):
 //   RcHulls     the hull geometry tables as the Hull argument of rayBodyCollider / pointBodyCollider
 //   RcScene     what a walk over the world's colliders reads, as one kernel argument
 //   rcFetch     collider c of the scene in its current frame, and whether a query's exclusion range hides it
 //   rcMount     a query's mount index: off, world space, or the frame of a body
 //   rcWalk      the walk over the tree k_raycast.hip builds in World::rc* (its layout is declared here too), nearer child first
+//   rcBoxTest   the slab test of a ray (RcRay, rcPrepareRay) against a node's box: the ray cast's and the sphere cast's box visitor
 #pragma once
 #include "world.h"
+#include "ray_tests.h"
 
 struct RcHulls
 {
@@ -116,4 +118,45 @@ MI_DEV void rcWalk(Visitor& v, const RcScene& sc, u32 n, u32* stack, u32 stride)
 		if (sp == 0u) break;
 		node = stack[stride * --sp];
 	}
+}
+
+// ---- the slab test of a ray against a node's box (k_raycast.hip, k_spherecast.hip) ----
+// Slack of the slab test: RC_SLACK_ULPS ulps of (|origin| + largest |coordinate| of the scene) in space, RC_SLACK_REL of the distance
+// in t.  DESIGN.md derives them.
+#define RC_SLACK_ULPS 16.f
+#define RC_SLACK_REL (1.f / 256.f)
+
+struct RcRay
+{
+	HRay r; float maxT;
+	V3 inv; bool par[3];        // 1 / direction; axes the ray does not move along are tested by containment
+	float space, absT, relT;    // slack of the slab test: in space, in t, and the share of the largest leaf in the relative part
+};
+// May the ray hit something in this padded box at a distance in [0, tmax]?  Conservative: the interval is widened by the slack, a box
+// entered exactly at tmax is visited (a lower collider index may win the tie), and a comparison with a NaN visits.  tEnter orders the visit.
+MI_DEV bool rcBoxTest(const RcRay& q, const float* b, float tmax, float& tEnter)
+{
+	float tE = -MI_FLT_MAX, tX = MI_FLT_MAX; bool outside = false;
+	const float o[3] = { q.r.origin.x, q.r.origin.y, q.r.origin.z }, inv[3] = { q.inv.x, q.inv.y, q.inv.z };
+	#pragma unroll
+	for (u32 a = 0; a < 3; ++a)
+	{
+		if (q.par[a]) outside = outside || o[a] < b[a] - q.space || o[a] > b[3 + a] + q.space;
+		else { const float t1 = (b[a] - o[a]) * inv[a], t2 = (b[3 + a] - o[a]) * inv[a]; tE = fmaxf(tE, fminf(t1, t2)); tX = fminf(tX, fmaxf(t1, t2)); }
+	}
+	const float lo = tE - q.absT - RC_SLACK_REL * (fmaxf(tE, 0.f) + q.relT), hi = tX + q.absT + RC_SLACK_REL * (fabsf(tX) + q.relT);
+	tEnter = tE;
+	return !(outside || lo > tmax || hi < 0.f || lo > hi);
+}
+
+// The slack of the slab test for this ray (RcRay::inv ... relT); scene = largest |coordinate|, diag = largest diagonal of the leaf boxes.
+MI_DEV void rcPrepareRay(RcRay& q, float scene, float diag)
+{
+	const V3 ad = vabs(q.r.direction), ao = vabs(q.r.origin);
+	const float dMax = fmaxf(fmaxf(ad.x, ad.y), ad.z);
+	q.par[0] = !(ad.x > 1e-12f * dMax); q.par[1] = !(ad.y > 1e-12f * dMax); q.par[2] = !(ad.z > 1e-12f * dMax);
+	q.inv = v3(q.par[0] ? 0.f : 1.f / q.r.direction.x, q.par[1] ? 0.f : 1.f / q.r.direction.y, q.par[2] ? 0.f : 1.f / q.r.direction.z);
+	q.space = RC_SLACK_ULPS * RC_EPS * (fmaxf(fmaxf(ao.x, ao.y), ao.z) + scene);
+	q.absT = q.space * fmaxf(fmaxf(fabsf(q.inv.x), fabsf(q.inv.y)), fabsf(q.inv.z));
+	q.relT = diag / length(q.r.direction);
 }

@@ -485,6 +485,42 @@ namespace mi
 		return r.numWithin;
 	}
 
+	// A sphere cast ("thick ray") against the whole scene (rigid bodies and static colliders; the heightmap is no candidate): how far a
+	// sphere of `radius` travels from origin along direction, in units of the direction's length and at most maxT, before it touches
+	// something (include/mi_physics.h states the rule), or false.  distance: the t at which it stops (0 when it starts in touch), its
+	// centre is then origin + distance * direction; point and normal: the closest surface point and the outward normal there, in world
+	// space; gap: what is left between sphere and surface (negative when overlapping); unresolved: the cast used up its iterations and the
+	// sphere is only known to be free up to distance.  One query through mi_sphere_cast_batch.
+	struct sphere_hit { float distance = 0.f, gap = 0.f; vec3 point, normal; uint32_t collider = 0, body = MI_STATIC_BODY; bool unresolved = false; };
+	inline bool castSphereQuery(game_scene& scene, const mi_sphere_cast& in, sphere_hit& out, const char* what)
+	{
+		scene.flushStaticColliders();
+		mi_sphere_hit h{};
+		scene.check(mi_sphere_cast_host(scene.world, 1u, &in, (uint32_t)MI_SPHERE_STATIC, &h, nullptr), what);
+		if (!h.hit) return false;
+		out.distance = h.t; out.gap = h.gap; out.point = vec3(h.point[0], h.point[1], h.point[2]); out.normal = vec3(h.normal[0], h.normal[1], h.normal[2]);
+		out.collider = h.collider; out.body = h.body; out.unresolved = h.hit == 2u;
+		return true;
+	}
+	inline bool castSphere(game_scene& scene, vec3 origin, vec3 direction, float radius, float maxT, sphere_hit& out)
+	{
+		mi_sphere_cast in{};
+		in.origin[0] = origin.x; in.origin[1] = origin.y; in.origin[2] = origin.z; in.maxT = maxT;
+		in.direction[0] = direction.x; in.direction[1] = direction.y; in.direction[2] = direction.z; in.radius = radius;
+		in.mount = MI_STATIC_BODY; in.enabled = 1u;
+		return castSphereQuery(scene, in, out, "castSphere");
+	}
+	// The same cast fixed to a rigid body: localOrigin and localDirection are in the body's frame at its current pose.  excludeSelf: the
+	// body's own colliders are no candidates, so the sphere may start inside its carrier (a foot probe).
+	inline bool castSensorSphere(game_scene& scene, const scene_entity& body, vec3 localOrigin, vec3 localDirection, float radius, float maxT, sphere_hit& out, bool excludeSelf = true)
+	{
+		mi_sphere_cast in{};
+		in.origin[0] = localOrigin.x; in.origin[1] = localOrigin.y; in.origin[2] = localOrigin.z; in.maxT = maxT;
+		in.direction[0] = localDirection.x; in.direction[1] = localDirection.y; in.direction[2] = localDirection.z; in.radius = radius;
+		in.mount = body.body(); in.excludeFirst = in.mount; in.excludeCount = excludeSelf ? 1u : 0u; in.enabled = 1u;
+		return castSphereQuery(scene, in, out, "castSensorSphere");
+	}
+
 	// What the contacts of the last internal step did to a rigid body (no counterpart in the reference's physics.h; include/mi_physics.h
 	// states the rule): the linear and angular impulse they applied to it, the sum of the normal impulses, how many contacts and manifolds
 	// were summed and the partner that pressed hardest.  partners: MI_CONTACT_DYNAMIC | MI_CONTACT_STATIC; the bodies excludeFirst ..

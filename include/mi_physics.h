@@ -384,6 +384,47 @@ typedef struct mi_proximity_reading { float distance; uint32_t collider, body, f
 int mi_proximity(mi_world* w, uint32_t numQueries, const mi_proximity_query* dQueries, uint32_t flags, mi_proximity_reading* dOut, float* dOutWorldPoints);
 int mi_proximity_host(mi_world* w, uint32_t numQueries, const mi_proximity_query* queries, uint32_t flags, mi_proximity_reading* out, float* outWorldPoints);
 
+/* Sphere casts ("thick rays"): how far a sphere of a given radius can travel from a point in a direction before it touches a collider,
+ * and where and on what it touches.  One call on the world's stream; like the ray entries it first settles a step whose cluster sweep
+ * is not yet known to have completed and otherwise does not synchronise with the host; no step buffer and no accumulator is written;
+ * numQueries == 0 launches nothing.  (The reference has no counterpart: the rule is this project's.)
+ * Mount, exclusion and candidates are mi_sensor_ray's and mi_proximity_query's: origin and direction are in the frame of body `mount`
+ * at its current pose, world origin = rot * origin + pos, world direction = rot * direction; mount == MI_STATIC_BODY: both are in world
+ * space already and are taken bit for bit.  Any other mount >= the number of bodies, a deleted body, in a slab run a body not simulated
+ * here, and enabled == 0 switch the query off: its hit and its world cast are all zero.  dOutWorldCasts (device, may be NULL) receives
+ * 8 floats per query: {world origin, maxT, world direction, radius}.  The colliders of the bodies b with b - excludeFirst <
+ * excludeCount, in uint32 arithmetic (the subtraction wraps), are no candidates of this query; static colliders are never excluded.
+ * Candidates: the colliders of alive bodies simulated here and, with MI_SPHERE_STATIC, those of entities without a rigid body; never
+ * force-field or trigger colliders, never cloth.  The heightmap terrain is NOT a candidate of this entry point.
+ * Query: the direction need not be a unit vector and t is in units of its length, as for the ray cast; L = |world direction| is formed
+ * once per query.  maxT may be +INFINITY.  A negative or NaN radius and a negative or NaN maxT find nothing, also from inside a shape.
+ * radius == 0 is allowed: a ray cast by the distance rule below (not by the reference's ray tests).
+ * Per candidate, in the collider's frame: o = conjugate(rot) * (world origin - pos), v = conjugate(rot) * world direction, and the gap
+ * g(t) = d(o + t v) - radius with d the signed distance of mi_proximity (above; csrc/point_tests.h).  d is convex along a line and
+ * 1-Lipschitz.  With tol(t) = SC_GAP + SC_GUARD_ULPS * 2^-23 * ((|o| + t L) + radius), SC_GAP = 1e-4 m, SC_GUARD_ULPS = 16:
+ *   t = 0; repeat at most SC_MAX_ITER = 32 times:
+ *     evaluate g = g(t); if g <= tol(t): the candidate hits at t (an origin in touch or inside: t = 0 and a negative gap)
+ *     if not L > 0: miss (a zero direction is an overlap test at the origin)
+ *     with a previous sample: slope = (g - gPrev) / (t - tPrev); if slope >= 0: miss (receding: by convexity g does not come down again)
+ *     t = t + max(g / L, -g / slope)   (without a previous sample t + g / L); if not t <= maxT: miss
+ *   after SC_MAX_ITER samples: a hit at the last sample's t with hit = 2 (unresolved): the sphere is free up to there.
+ * g / L is conservative advancement (d is 1-Lipschitz), -g / slope the root of the chord through the last two samples (a convex function
+ * lies above the extension of its chord): in exact arithmetic neither passes the first contact.  Arithmetic is float32 without
+ * contraction in the order csrc/sphere_cast.h writes out.
+ * Result: the candidate with the smallest t wins, of equal t the lowest collider index.  hit = 1 (or 2), t, collider, body
+ * (MI_STATIC_BODY for a static collider); point = the closest surface point c at the stop and normal = the outward unit normal n there,
+ * both of the distance rule, rotated (and c translated) back by the pose; gap = g at the stop (negative when overlapping); iterations =
+ * the samples the winner took.  The sphere's centre at the stop is world origin + t * world direction.  A miss is all zero.
+ * The candidates and the tree over them are mi_raycast_batch's, rebuilt from the current poses at every call in the same buffers;
+ * MI_SPHERE_BRUTE_FORCE asks every candidate instead (same bytes; a yardstick).  Calls of all query kinds may follow each other freely.
+ * mi_sphere_cast_host: queries, hits and world casts in HOST memory, staged through buffers of the world; returns after the hits have
+ * arrived. */
+enum { MI_SPHERE_STATIC = 1, MI_SPHERE_BRUTE_FORCE = 2 };
+typedef struct mi_sphere_cast { float origin[3], maxT, direction[3], radius; uint32_t mount, excludeFirst, excludeCount, enabled; } mi_sphere_cast; /* 48 bytes */
+typedef struct mi_sphere_hit { float t; uint32_t collider, body, hit; float point[3], gap; float normal[3]; uint32_t iterations; } mi_sphere_hit; /* 48 bytes */
+int mi_sphere_cast_batch(mi_world* w, uint32_t numQueries, const mi_sphere_cast* dQueries, uint32_t flags, mi_sphere_hit* dOut, float* dOutWorldCasts);
+int mi_sphere_cast_host(mi_world* w, uint32_t numQueries, const mi_sphere_cast* queries, uint32_t flags, mi_sphere_hit* out, float* outWorldCasts);
+
 /* Contact sensors: what the contacts of the LAST INTERNAL STEP did to a body, summed on the device from the rows its solve left behind.
  * One call on the world's stream; like the ray entries it first settles a step whose cluster sweep is not yet known to have completed
  * (after a give-up the readings describe the redone solve) and otherwise does not synchronise with the host.  The step's buffers are only
