@@ -78,14 +78,14 @@ void World::buildInteractTables()
 		for (size_t f = 0; f + 2 < g.triangles.size(); f += 3) tris.push_back(make_uint4(firstVertex + g.triangles[f], firstVertex + g.triangles[f + 1], firstVertex + g.triangles[f + 2], 0u));
 		firstVertex += (u32)(g.vertices.size() / 3);
 	}
-	bodyColStart.ensure(start.size(), stream); bodyColList.ensure(std::max<size_t>(list.size(), 1), stream);
-	hullTris.ensure(std::max<size_t>(tris.size(), 1), stream); hullTriRange.ensure(std::max<size_t>(range.size(), 1), stream);
-	MI_CHECK(hipMemcpyAsync(bodyColStart.p, start.data(), sizeof(u32) * start.size(), hipMemcpyHostToDevice, stream));
-	if (!list.empty()) MI_CHECK(hipMemcpyAsync(bodyColList.p, list.data(), sizeof(u32) * list.size(), hipMemcpyHostToDevice, stream));
-	if (!tris.empty()) MI_CHECK(hipMemcpyAsync(hullTris.p, tris.data(), sizeof(uint4) * tris.size(), hipMemcpyHostToDevice, stream));
-	if (!range.empty()) MI_CHECK(hipMemcpyAsync(hullTriRange.p, range.data(), sizeof(uint2) * range.size(), hipMemcpyHostToDevice, stream));
+	queries.bodyColStart.ensure(start.size(), stream); queries.bodyColList.ensure(std::max<size_t>(list.size(), 1), stream);
+	queries.hullTris.ensure(std::max<size_t>(tris.size(), 1), stream); queries.hullTriRange.ensure(std::max<size_t>(range.size(), 1), stream);
+	MI_CHECK(hipMemcpyAsync(queries.bodyColStart.p, start.data(), sizeof(u32) * start.size(), hipMemcpyHostToDevice, stream));
+	if (!list.empty()) MI_CHECK(hipMemcpyAsync(queries.bodyColList.p, list.data(), sizeof(u32) * list.size(), hipMemcpyHostToDevice, stream));
+	if (!tris.empty()) MI_CHECK(hipMemcpyAsync(queries.hullTris.p, tris.data(), sizeof(uint4) * tris.size(), hipMemcpyHostToDevice, stream));
+	if (!range.empty()) MI_CHECK(hipMemcpyAsync(queries.hullTriRange.p, range.data(), sizeof(uint2) * range.size(), hipMemcpyHostToDevice, stream));
 	MI_CHECK(hipStreamSynchronize(stream));
-	interactTablesValid = true;
+	queries.interactTablesValid = true;
 }
 
 struct HostHulls
@@ -272,23 +272,23 @@ int mi_get_stats(mi_world* world, mi_stats* out)
 	W->refreshCounters();     // counts of the last step (one small read-back if the step did not do it itself)
 	W->harvestTiming();
 	mi_stats& st = W->stats;
-	if (W->accTimed)
+	if (W->timing.accTimed)
 	{
-		double n = W->accTimed;
-		st.msCollidersBroad = (float)(W->accMs[0] / n); st.msNarrow = (float)(W->accMs[1] / n); st.msSolverSetup = (float)(W->accMs[2] / n); st.msSolve = (float)(W->accMs[3] / n); st.msIntegrate = (float)(W->accMs[4] / n);
+		double n = W->timing.accTimed;
+		st.msCollidersBroad = (float)(W->timing.accMs[0] / n); st.msNarrow = (float)(W->timing.accMs[1] / n); st.msSolverSetup = (float)(W->timing.accMs[2] / n); st.msSolve = (float)(W->timing.accMs[3] / n); st.msIntegrate = (float)(W->timing.accMs[4] / n);
 		st.msTotal = st.msCollidersBroad + st.msNarrow + st.msSolverSetup + st.msSolve + st.msIntegrate;
-		for (double& a : W->accMs) a = 0; W->accTimed = 0;
+		for (double& a : W->timing.accMs) a = 0; W->timing.accTimed = 0;
 	}
-	st.avgSteps = W->sumSteps;
-	double n = W->sumSteps ? W->sumSteps : 1;
-	st.avgContacts = (float)(W->sumContacts / n); st.avgCollisions = (float)(W->sumManifolds / n); st.avgColors = (float)(W->sumColors / n);
-	st.avgBroadphaseOverlaps = (float)(W->sumPairs / n); st.avgFlowProbes = (float)(W->sumProbes / n);
-	W->sumContacts = W->sumManifolds = W->sumColors = W->sumPairs = W->sumProbes = 0; W->sumSteps = 0;
+	st.avgSteps = W->timing.sumSteps;
+	double n = W->timing.sumSteps ? W->timing.sumSteps : 1;
+	st.avgContacts = (float)(W->timing.sumContacts / n); st.avgCollisions = (float)(W->timing.sumManifolds / n); st.avgColors = (float)(W->timing.sumColors / n);
+	st.avgBroadphaseOverlaps = (float)(W->timing.sumPairs / n); st.avgFlowProbes = (float)(W->timing.sumProbes / n);
+	W->timing.sumContacts = W->timing.sumManifolds = W->timing.sumColors = W->timing.sumPairs = W->timing.sumProbes = 0; W->timing.sumSteps = 0;
 	*out = st;
 	return W->lastError;
 }
 int mi_enable_validation(mi_world* world, int enable) { CHECK_WORLD(MI_ERR_INVALID_ARGUMENT); W->validate = enable != 0; return MI_OK; }
-int mi_enable_stage_timing(mi_world* world, int enable) { CHECK_WORLD(MI_ERR_INVALID_ARGUMENT); if (!enable) W->harvestTiming(); W->timeStages = enable != 0; return MI_OK; }
+int mi_enable_stage_timing(mi_world* world, int enable) { CHECK_WORLD(MI_ERR_INVALID_ARGUMENT); if (!enable) W->harvestTiming(); W->timing.timeStages = enable != 0; return MI_OK; }
 uint32_t mi_num_bodies(mi_world* world) { CHECK_WORLD(0); return (u32)W->bodies.size(); }
 uint32_t mi_num_colliders(mi_world* world) { CHECK_WORLD(0); return (u32)W->colliders.size(); }
 
@@ -342,7 +342,7 @@ int mi_test_physics_interaction_batch(mi_world* world, uint32_t numRays, uint32_
 		W->fail(MI_ERR_INVALID_ARGUMENT, "mi_test_physics_interaction_batch: body range outside the world");
 		return MI_ERR_INVALID_ARGUMENT;
 	}
-	if (!W->interactTablesValid) W->buildInteractTables();
+	if (!W->queries.interactTablesValid) W->buildInteractTables();
 	launch_interaction_batch(*W, numRays, firstBody, bodiesPerRay, dRays, dOutBody);
 	return W->lastError;
 }
@@ -359,15 +359,15 @@ static bool queryBegin(World* w, u32 count, bool pointers, bool tables, int& cod
 	code = w->lastError;
 	if (!count) return false;
 	if (!pointers) { code = MI_ERR_INVALID_ARGUMENT; return false; }
-	if (tables && !w->interactTablesValid) w->buildInteractTables();
+	if (tables && !w->queries.interactTablesValid) w->buildInteractTables();
 	code = w->lastError;
 	return !code;
 }
 // Does a cast with these flags meet the heightmap?  MI_ERR_INVALID_ARGUMENT for a terrain with more chunks than the 17 chunk bits of a triangle id count.
 static int queryTerrain(const World* w, u32 flags, bool& terrain)
 {
-	terrain = (flags & MI_RAY_TERRAIN) != 0 && w->terrainChunksPerDim != 0;
-	return terrain && (uint64_t)w->terrainChunksPerDim * w->terrainChunksPerDim > 131071u ? MI_ERR_INVALID_ARGUMENT : MI_OK;
+	terrain = (flags & MI_RAY_TERRAIN) != 0 && w->terrain.chunksPerDim != 0;
+	return terrain && (uint64_t)w->terrain.chunksPerDim * w->terrain.chunksPerDim > 131071u ? MI_ERR_INVALID_ARGUMENT : MI_OK;
 }
 // A _host entry: `count` records of inBytes each to the device, deviceEntry(dIn, dOut, dAux) on them, outBytes per record back into `out`
 // and, if `aux` is given, auxBytes per record into it.  The staging (World::queryHost*) is shared by all of them: every call ends with
@@ -376,14 +376,14 @@ static int queryStaged(World* w, u32 count, const void* in, size_t inBytes, void
 {
 	if (!count) return deviceEntry(nullptr, nullptr, nullptr);
 	if (!in || !out) return MI_ERR_INVALID_ARGUMENT;
-	w->queryHostIn.ensure(inBytes * count, w->stream); w->queryHostOut.ensure(outBytes * count, w->stream);
-	if (aux) w->queryHostAux.ensure(auxBytes * count, w->stream);
+	w->queries.hostIn.ensure(inBytes * count, w->stream); w->queries.hostOut.ensure(outBytes * count, w->stream);
+	if (aux) w->queries.hostAux.ensure(auxBytes * count, w->stream);
 	if (w->lastError) return w->lastError;
-	MI_CHECK(hipMemcpyAsync(w->queryHostIn.p, in, inBytes * count, hipMemcpyHostToDevice, w->stream));
-	int e = deviceEntry(w->queryHostIn.p, w->queryHostOut.p, aux ? w->queryHostAux.p : nullptr);
+	MI_CHECK(hipMemcpyAsync(w->queries.hostIn.p, in, inBytes * count, hipMemcpyHostToDevice, w->stream));
+	int e = deviceEntry(w->queries.hostIn.p, w->queries.hostOut.p, aux ? w->queries.hostAux.p : nullptr);
 	if (e) return e;
-	MI_CHECK(hipMemcpyAsync(out, w->queryHostOut.p, outBytes * count, hipMemcpyDeviceToHost, w->stream));
-	if (aux) MI_CHECK(hipMemcpyAsync(aux, w->queryHostAux.p, auxBytes * count, hipMemcpyDeviceToHost, w->stream));
+	MI_CHECK(hipMemcpyAsync(out, w->queries.hostOut.p, outBytes * count, hipMemcpyDeviceToHost, w->stream));
+	if (aux) MI_CHECK(hipMemcpyAsync(aux, w->queries.hostAux.p, auxBytes * count, hipMemcpyDeviceToHost, w->stream));
 	MI_CHECK(hipStreamSynchronize(w->stream));
 	return w->lastError;
 }
@@ -508,37 +508,37 @@ int mi_slab_configure(mi_world* world, uint32_t rank, uint32_t size, uint32_t ax
 	W->resolvePendingFlow();
 	W->upload();
 	if (W->lastError) return W->lastError;
-	W->slabRank = rank; W->slabSize = size; W->slabAxis = axis; W->slabLo = lo; W->slabHi = hi; W->slabMargin = margin; W->slabStamp = 0;
-	W->slabCode.ensure((size_t)W->nb + 1, W->stream); W->slabFresh.ensure((size_t)W->nb + 1, W->stream);
+	W->slab.rank = rank; W->slab.size = size; W->slab.axis = axis; W->slab.lo = lo; W->slab.hi = hi; W->slab.margin = margin; W->slab.stamp = 0;
+	W->slab.code.ensure((size_t)W->nb + 1, W->stream); W->slab.fresh.ensure((size_t)W->nb + 1, W->stream);
 	if (W->lastError) return W->lastError;
 	launch_slab_classify(*W);
-	W->clusterSortDue = true;
+	W->cluster.sortDue = true;
 	return W->lastError;
 }
 uint64_t mi_slab_message_bytes(uint32_t capacity) { return 16ull + 72ull * capacity; }
 int mi_slab_pack(mi_world* world, void* dMessageLeft, void* dMessageRight, uint32_t capacity)
 {
 	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
-	if (!W->slabSize || W->topologyDirty || W->slabCode.cap < (size_t)W->nb) { W->fail(MI_ERR_INVALID_ARGUMENT, "mi_slab_pack: configure the slab after the last add call"); return W->lastError; }
+	if (!W->slab.size || W->topologyDirty || W->slab.code.cap < (size_t)W->nb) { W->fail(MI_ERR_INVALID_ARGUMENT, "mi_slab_pack: configure the slab after the last add call"); return W->lastError; }
 	// (a give-up of the previous step's cluster sweep is settled first: the message must carry that step's real result)
 	W->resolvePendingFlow();
-	W->slabStamp++;
+	W->slab.stamp++;
 	launch_slab_pack(*W, dMessageLeft, dMessageRight, capacity);
 	return W->lastError;
 }
 int mi_slab_unpack(mi_world* world, const void* dMessageLeft, const void* dMessageRight, uint32_t capacity)
 {
 	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
-	if (!W->slabSize || W->topologyDirty) { W->fail(MI_ERR_INVALID_ARGUMENT, "mi_slab_unpack: configure the slab after the last add call"); return W->lastError; }
+	if (!W->slab.size || W->topologyDirty) { W->fail(MI_ERR_INVALID_ARGUMENT, "mi_slab_unpack: configure the slab after the last add call"); return W->lastError; }
 	launch_slab_unpack(*W, dMessageLeft, dMessageRight, capacity);
 	return W->lastError;
 }
 int mi_slab_read_codes(mi_world* world, uint8_t* outCodes, uint32_t n)
 {
 	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
-	if (!W->slabSize) return MI_ERR_INVALID_ARGUMENT;
+	if (!W->slab.size) return MI_ERR_INVALID_ARGUMENT;
 	n = std::min<u32>(n, W->nb);
-	MI_CHECK(hipMemcpyAsync(outCodes, W->slabCode.p, n, hipMemcpyDeviceToHost, W->stream));
+	MI_CHECK(hipMemcpyAsync(outCodes, W->slab.code.p, n, hipMemcpyDeviceToHost, W->stream));
 	MI_CHECK(hipStreamSynchronize(W->stream));
 	return W->lastError;
 }
@@ -571,7 +571,7 @@ int mi_debug_read_world_colliders(mi_world* world, void* outColliders64, float* 
 	}
 	return W->lastError;
 }
-uint32_t mi_debug_num_manifold_slots(mi_world* world) { CHECK_WORLD(0); W->refreshCounters(); return (W->hCounters[CTR_NUM_PAIRS] || W->terrainChunksPerDim) ? W->hCounters[CTR_NUM_VALID] : 0; }
+uint32_t mi_debug_num_manifold_slots(mi_world* world) { CHECK_WORLD(0); W->refreshCounters(); return (W->hCounters[CTR_NUM_PAIRS] || W->terrain.chunksPerDim) ? W->hCounters[CTR_NUM_VALID] : 0; }
 int mi_debug_read_manifolds(mi_world* world, uint32_t* outPairs2, uint32_t* outCounts, void* outContacts4x32, uint32_t* outBodyPairs2)
 {
 	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
@@ -617,7 +617,7 @@ int mi_debug_read_schedule(mi_world* world, uint32_t* outManifoldSlots, uint32_t
 {
 	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
 	W->refreshCounters();
-	u32 n = (W->hCounters[CTR_NUM_PAIRS] || W->terrainChunksPerDim) ? W->hCounters[CTR_NUM_MANIFOLDS] : 0;
+	u32 n = (W->hCounters[CTR_NUM_PAIRS] || W->terrain.chunksPerDim) ? W->hCounters[CTR_NUM_MANIFOLDS] : 0;
 	std::vector<uint4> ids(n);
 	d2h(W, ids.data(), W->rowIds.p, sizeof(uint4) * n); // rowIds[s].w = manifold slot executed at schedule position s
 	for (u32 s = 0; s < n; ++s) outManifoldSlots[s] = ids[s].w;
@@ -637,7 +637,7 @@ int mi_debug_read_contact_impulses(mi_world* world, float* outImpulses4x2)
 {
 	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
 	W->refreshCounters();
-	u32 n = (W->hCounters[CTR_NUM_PAIRS] || W->terrainChunksPerDim) ? W->hCounters[CTR_NUM_MANIFOLDS] : 0;
+	u32 n = (W->hCounters[CTR_NUM_PAIRS] || W->terrain.chunksPerDim) ? W->hCounters[CTR_NUM_MANIFOLDS] : 0;
 	if (!n) return MI_OK;
 	if (!outImpulses4x2 || n > W->rowCap) return MI_ERR_INVALID_ARGUMENT;
 	std::vector<uint4> ids(n); std::vector<float2> lam((size_t)MI_MAX_CONTACTS_PER_MANIFOLD * n);
@@ -658,7 +658,7 @@ int mi_debug_read_contact_rows(mi_world* world, float* outRows4x15)
 {
 	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
 	W->refreshCounters();
-	u32 n = (W->hCounters[CTR_NUM_PAIRS] || W->terrainChunksPerDim) ? W->hCounters[CTR_NUM_MANIFOLDS] : 0;
+	u32 n = (W->hCounters[CTR_NUM_PAIRS] || W->terrain.chunksPerDim) ? W->hCounters[CTR_NUM_MANIFOLDS] : 0;
 	if (!n) return MI_OK;
 	if (!outRows4x15 || n > W->rowCap) return MI_ERR_INVALID_ARGUMENT;
 	std::vector<uint4> ids(n); std::vector<float4> plane(n);
@@ -725,21 +725,21 @@ int mi_debug_set_replay(mi_world* world, int on)
 {
 	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
 	W->resolvePendingFlow();
-	W->replayReferenceOrder = on != 0;
+	W->replay.referenceOrder = on != 0;
 	W->forceFullColoring = true;
 	return MI_OK;
 }
-uint32_t mi_debug_num_replay_batches(mi_world* world) { CHECK_WORLD(0); return W->replayBatches; }
-int mi_debug_read_replay_batches(mi_world* world, uint32_t* outEntries) { CHECK_WORLD(MI_ERR_INVALID_ARGUMENT); if (!W->replayHost.empty()) memcpy(outEntries, W->replayHost.data(), sizeof(u32) * W->replayHost.size()); return MI_OK; }
+uint32_t mi_debug_num_replay_batches(mi_world* world) { CHECK_WORLD(0); return W->replay.batches; }
+int mi_debug_read_replay_batches(mi_world* world, uint32_t* outEntries) { CHECK_WORLD(MI_ERR_INVALID_ARGUMENT); if (!W->replay.host.empty()) memcpy(outEntries, W->replay.host.data(), sizeof(u32) * W->replay.host.size()); return MI_OK; }
 /* Developer timeline of the cluster sweep: enable (allocates 16 rows of 32 stamps per workgroup of the solve launch), step, then read
  * numSlots rows of 32 u64 (k_cl_solve documents the rows; wall-clock stamps are 10 ns ticks). */
 int mi_debug_flow_trace(mi_world* world, int enable, unsigned long long* out, uint32_t numSlots)
 {
 	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
 	const size_t rows = (size_t)CL_MAX_TASKS * CL_TRACE_ROWS;
-	if (enable && !W->flowTrace.p) { W->flowTrace.ensure(rows * CL_TRACE_WORDS, W->stream); if (!W->flowTrace.p) return W->lastError; MI_CHECK(hipMemsetAsync(W->flowTrace.p, 0, sizeof(u64) * rows * CL_TRACE_WORDS, W->stream)); }
-	if (out && W->flowTrace.p) d2h(W, out, W->flowTrace.p, sizeof(u64) * CL_TRACE_WORDS * std::min<size_t>(numSlots, rows));
-	if (!enable) W->flowTrace.release();
+	if (enable && !W->cluster.flowTrace.p) { W->cluster.flowTrace.ensure(rows * CL_TRACE_WORDS, W->stream); if (!W->cluster.flowTrace.p) return W->lastError; MI_CHECK(hipMemsetAsync(W->cluster.flowTrace.p, 0, sizeof(u64) * rows * CL_TRACE_WORDS, W->stream)); }
+	if (out && W->cluster.flowTrace.p) d2h(W, out, W->cluster.flowTrace.p, sizeof(u64) * CL_TRACE_WORDS * std::min<size_t>(numSlots, rows));
+	if (!enable) W->cluster.flowTrace.release();
 	return W->lastError;
 }
 

@@ -80,26 +80,26 @@ uint32_t mi_add_force_field(mi_world* world, const float force[3], const float p
 {
 	CHECK_WORLD(0xFFFFFFFFu);
 	if (!force) { W->fail(MI_ERR_INVALID_ARGUMENT, "mi_add_force_field: force is NULL"); return 0xFFFFFFFFu; }
-	if (W->fields.size() >= (1u << 24)) { W->fail(MI_ERR_CAPACITY, "mi_add_force_field: too many fields"); return 0xFFFFFFFFu; }
+	if (W->zones.fields.size() >= (1u << 24)) { W->fail(MI_ERR_CAPACITY, "mi_add_force_field: too many fields"); return 0xFFFFFFFFu; }
 	World::HField f; memset(&f, 0, sizeof(f));
 	memcpy(f.force, force, 12); setPose(f.pos, f.rot, pos, rot); f.hasTransform = (pos || rot) ? 1u : 0u;
-	W->fields.push_back(f); W->fieldsDirty = true;
-	return (uint32_t)W->fields.size() - 1;
+	W->zones.fields.push_back(f); W->zones.fieldsDirty = true;
+	return (uint32_t)W->zones.fields.size() - 1;
 }
 int mi_set_force_field(mi_world* world, uint32_t field, const float force[3])
 {
 	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
-	if (field >= W->fields.size() || !force) { W->fail(MI_ERR_INVALID_ARGUMENT, "mi_set_force_field: field out of range"); return W->lastError; }
-	memcpy(W->fields[field].force, force, 12); W->fieldsDirty = true;
+	if (field >= W->zones.fields.size() || !force) { W->fail(MI_ERR_INVALID_ARGUMENT, "mi_set_force_field: field out of range"); return W->lastError; }
+	memcpy(W->zones.fields[field].force, force, 12); W->zones.fieldsDirty = true;
 	return MI_OK;
 }
 uint32_t mi_add_trigger(mi_world* world, const float pos[3], const float rot[4])
 {
 	CHECK_WORLD(0xFFFFFFFFu);
-	if (W->triggers.size() >= (1u << 24)) { W->fail(MI_ERR_CAPACITY, "mi_add_trigger: too many triggers"); return 0xFFFFFFFFu; }
+	if (W->zones.triggers.size() >= (1u << 24)) { W->fail(MI_ERR_CAPACITY, "mi_add_trigger: too many triggers"); return 0xFFFFFFFFu; }
 	World::HTrigger t; memset(&t, 0, sizeof(t)); setPose(t.pos, t.rot, pos, rot);
-	W->triggers.push_back(t);
-	return (uint32_t)W->triggers.size() - 1;
+	W->zones.triggers.push_back(t);
+	return (uint32_t)W->zones.triggers.size() - 1;
 }
 static uint32_t addZoneCollider(World* w, u32 zoneType, u32 zoneIndex, const float* pos, const float* rot, uint32_t type, const float* shape)
 {
@@ -111,17 +111,17 @@ static uint32_t addZoneCollider(World* w, u32 zoneType, u32 zoneIndex, const flo
 uint32_t mi_add_force_field_collider(mi_world* world, uint32_t field, uint32_t type, const float* shape)
 {
 	CHECK_WORLD(0xFFFFFFFFu);
-	if (field >= W->fields.size() || !shape) { W->fail(MI_ERR_INVALID_ARGUMENT, "mi_add_force_field_collider: field out of range"); return 0xFFFFFFFFu; }
-	World::HField& f = W->fields[field];
+	if (field >= W->zones.fields.size() || !shape) { W->fail(MI_ERR_INVALID_ARGUMENT, "mi_add_force_field_collider: field out of range"); return 0xFFFFFFFFu; }
+	World::HField& f = W->zones.fields[field];
 	uint32_t id = addZoneCollider(W, 2u, field, f.pos, f.rot, type, shape);
-	if (id != 0xFFFFFFFFu) { f.numColliders++; W->fieldsDirty = true; }
+	if (id != 0xFFFFFFFFu) { f.numColliders++; W->zones.fieldsDirty = true; }
 	return id;
 }
 uint32_t mi_add_trigger_collider(mi_world* world, uint32_t trigger, uint32_t type, const float* shape)
 {
 	CHECK_WORLD(0xFFFFFFFFu);
-	if (trigger >= W->triggers.size() || !shape) { W->fail(MI_ERR_INVALID_ARGUMENT, "mi_add_trigger_collider: trigger out of range"); return 0xFFFFFFFFu; }
-	World::HTrigger& t = W->triggers[trigger];
+	if (trigger >= W->zones.triggers.size() || !shape) { W->fail(MI_ERR_INVALID_ARGUMENT, "mi_add_trigger_collider: trigger out of range"); return 0xFFFFFFFFu; }
+	World::HTrigger& t = W->zones.triggers[trigger];
 	uint32_t id = addZoneCollider(W, 3u, trigger, t.pos, t.rot, type, shape);
 	if (id != 0xFFFFFFFFu) t.numColliders++;
 	return id;
@@ -147,39 +147,39 @@ static int moveZone(World* w, u32 zoneType, u32 zoneIndex, float* zpos, float* z
 int mi_set_force_field_transform(mi_world* world, uint32_t field, const float pos[3], const float rot[4])
 {
 	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
-	if (field >= W->fields.size()) { W->fail(MI_ERR_INVALID_ARGUMENT, "mi_set_force_field_transform: field out of range"); return W->lastError; }
-	W->fields[field].hasTransform = 1u; W->fieldsDirty = true;
-	return moveZone(W, 2u, field, W->fields[field].pos, W->fields[field].rot, pos, rot);
+	if (field >= W->zones.fields.size()) { W->fail(MI_ERR_INVALID_ARGUMENT, "mi_set_force_field_transform: field out of range"); return W->lastError; }
+	W->zones.fields[field].hasTransform = 1u; W->zones.fieldsDirty = true;
+	return moveZone(W, 2u, field, W->zones.fields[field].pos, W->zones.fields[field].rot, pos, rot);
 }
 int mi_set_trigger_transform(mi_world* world, uint32_t trigger, const float pos[3], const float rot[4])
 {
 	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
-	if (trigger >= W->triggers.size()) { W->fail(MI_ERR_INVALID_ARGUMENT, "mi_set_trigger_transform: trigger out of range"); return W->lastError; }
-	return moveZone(W, 3u, trigger, W->triggers[trigger].pos, W->triggers[trigger].rot, pos, rot);
+	if (trigger >= W->zones.triggers.size()) { W->fail(MI_ERR_INVALID_ARGUMENT, "mi_set_trigger_transform: trigger out of range"); return W->lastError; }
+	return moveZone(W, 3u, trigger, W->zones.triggers[trigger].pos, W->zones.triggers[trigger].rot, pos, rot);
 }
 int mi_enable_collision_events(mi_world* world, int begin, int end)
 {
 	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
-	W->collisionBeginEvents = begin != 0; W->collisionEndEvents = end != 0;
+	W->zones.collisionBeginEvents = begin != 0; W->zones.collisionEndEvents = end != 0;
 	return MI_OK;
 }
 uint32_t mi_drain_events(mi_world* world, mi_event* out, uint32_t capacity)
 {
 	CHECK_WORLD(0);
-	if (W->eventRing.p)
+	if (W->zones.eventRing.p)
 	{
 		u32 head[2] = { 0, 0 };
 		MI_CHECK(hipMemcpyAsync(head, W->dCounters.p + CTR_EVENT_COUNT, sizeof(head), hipMemcpyDeviceToHost, W->stream));
 		MI_CHECK(hipStreamSynchronize(W->stream));
-		u32 n = std::min(head[0], W->eventCap);
+		u32 n = std::min(head[0], W->zones.eventCap);
 		if (n)
 		{
-			size_t first = W->pendingEvents.size();
-			W->pendingEvents.resize(first + n);
-			MI_CHECK(hipMemcpyAsync(W->pendingEvents.data() + first, W->eventRing.p, sizeof(mi_event) * n, hipMemcpyDeviceToHost, W->stream));
+			size_t first = W->zones.pendingEvents.size();
+			W->zones.pendingEvents.resize(first + n);
+			MI_CHECK(hipMemcpyAsync(W->zones.pendingEvents.data() + first, W->zones.eventRing.p, sizeof(mi_event) * n, hipMemcpyDeviceToHost, W->stream));
 			MI_CHECK(hipStreamSynchronize(W->stream));
 			// the order the reference's merge loops call back in: per step the trigger events, then the collision events, each by pair
-			std::sort(W->pendingEvents.begin() + first, W->pendingEvents.end(), [](const mi_event& x, const mi_event& y)
+			std::sort(W->zones.pendingEvents.begin() + first, W->zones.pendingEvents.end(), [](const mi_event& x, const mi_event& y)
 			{
 				if (x.step != y.step) return x.step < y.step;
 				u32 cx = x.kind >> 1, cy = y.kind >> 1;
@@ -192,9 +192,9 @@ uint32_t mi_drain_events(mi_world* world, mi_event* out, uint32_t capacity)
 		if (head[1] & 1u) W->fail(MI_ERR_CAPACITY, "the event ring overflowed: events were lost (drain more often or raise MI_EVENT_CAPACITY)");
 		if (head[1] & 2u) W->hCounters[CTR_EVENT_OVERFLOW] |= 2u; // ensureEventBuffers grows the table
 	}
-	uint32_t n = (uint32_t)std::min<size_t>(capacity, W->pendingEvents.size());
-	if (n && out) memcpy(out, W->pendingEvents.data(), sizeof(mi_event) * n);
-	W->pendingEvents.erase(W->pendingEvents.begin(), W->pendingEvents.begin() + n);
+	uint32_t n = (uint32_t)std::min<size_t>(capacity, W->zones.pendingEvents.size());
+	if (n && out) memcpy(out, W->zones.pendingEvents.data(), sizeof(mi_event) * n);
+	W->zones.pendingEvents.erase(W->zones.pendingEvents.begin(), W->zones.pendingEvents.begin() + n);
 	return n;
 }
 
@@ -204,54 +204,54 @@ int mi_set_heightmap(mi_world* world, uint32_t chunksPerDim, float chunkSize, co
 	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
 	if (!chunksPerDim || chunksPerDim > 256 || !(chunkSize > 0.f) || !(amplitudeScale > 0.f) || !material || !minCorner) { W->fail(MI_ERR_INVALID_ARGUMENT, "mi_set_heightmap: 1..256 chunks per dimension, positive chunk size and amplitude"); return W->lastError; }
 	W->resolvePendingFlow();
-	W->terrainChunksPerDim = chunksPerDim; W->terrainChunkSize = chunkSize; W->terrainAmplitude = amplitudeScale;
-	memcpy(W->terrainMinCorner, minCorner, 12); W->terrainMaterial[0] = material->restitution; W->terrainMaterial[1] = material->friction; W->terrainMaterial[2] = material->density;
+	W->terrain.chunksPerDim = chunksPerDim; W->terrain.chunkSize = chunkSize; W->terrain.amplitude = amplitudeScale;
+	memcpy(W->terrain.minCorner, minCorner, 12); W->terrain.material[0] = material->restitution; W->terrain.material[1] = material->friction; W->terrain.material[2] = material->density;
 	size_t chunks = (size_t)chunksPerDim * chunksPerDim;
-	W->hTerrainHeights.assign(chunks * 129 * 129, 0); W->hTerrainValid.assign(chunks, 0);
-	W->rcTerrainTableValid = false;
-	W->terrainHeights.ensure(W->hTerrainHeights.size(), W->stream); W->terrainValid.ensure(chunks, W->stream);
-	MI_CHECK(hipMemsetAsync(W->terrainValid.p, 0, sizeof(u32) * chunks, W->stream));
-	if (const char* e = getenv("MI_TERRAIN_SLOTS_PER_COLLIDER")) W->terrainSlotsPerCollider = (u32)std::max(1, atoi(e));
-	if (const char* e = getenv("MI_TERRAIN_MIN_SLOTS")) W->terrainMinSlots = (u32)std::max(1, atoi(e));
+	W->terrain.hHeights.assign(chunks * 129 * 129, 0); W->terrain.hValid.assign(chunks, 0);
+	W->queries.terrainTableValid = false;
+	W->terrain.heights.ensure(W->terrain.hHeights.size(), W->stream); W->terrain.valid.ensure(chunks, W->stream);
+	MI_CHECK(hipMemsetAsync(W->terrain.valid.p, 0, sizeof(u32) * chunks, W->stream));
+	if (const char* e = getenv("MI_TERRAIN_SLOTS_PER_COLLIDER")) W->terrain.slotsPerCollider = (u32)std::max(1, atoi(e));
+	if (const char* e = getenv("MI_TERRAIN_MIN_SLOTS")) W->terrain.minSlots = (u32)std::max(1, atoi(e));
 	return W->lastError;
 }
 int mi_heightmap_set_chunk(mi_world* world, uint32_t x, uint32_t z, const uint16_t* heights129x129) // heightmap_collider_chunk::setHeights
 {
 	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
-	if (!W->terrainChunksPerDim || x >= W->terrainChunksPerDim || z >= W->terrainChunksPerDim || !heights129x129) { W->fail(MI_ERR_INVALID_ARGUMENT, "mi_heightmap_set_chunk: chunk out of range (mi_set_heightmap first)"); return W->lastError; }
+	if (!W->terrain.chunksPerDim || x >= W->terrain.chunksPerDim || z >= W->terrain.chunksPerDim || !heights129x129) { W->fail(MI_ERR_INVALID_ARGUMENT, "mi_heightmap_set_chunk: chunk out of range (mi_set_heightmap first)"); return W->lastError; }
 	W->resolvePendingFlow();
-	size_t chunk = (size_t)z * W->terrainChunksPerDim + x, n = 129 * 129;
-	memcpy(W->hTerrainHeights.data() + chunk * n, heights129x129, sizeof(uint16_t) * n);
-	W->hTerrainValid[chunk] = 1;
-	W->rcTerrainTableValid = false;
-	MI_CHECK(hipMemcpyAsync(W->terrainHeights.p + chunk * n, W->hTerrainHeights.data() + chunk * n, sizeof(uint16_t) * n, hipMemcpyHostToDevice, W->stream));
-	MI_CHECK(hipMemcpyAsync(W->terrainValid.p + chunk, W->hTerrainValid.data() + chunk, sizeof(u32), hipMemcpyHostToDevice, W->stream));
+	size_t chunk = (size_t)z * W->terrain.chunksPerDim + x, n = 129 * 129;
+	memcpy(W->terrain.hHeights.data() + chunk * n, heights129x129, sizeof(uint16_t) * n);
+	W->terrain.hValid[chunk] = 1;
+	W->queries.terrainTableValid = false;
+	MI_CHECK(hipMemcpyAsync(W->terrain.heights.p + chunk * n, W->terrain.hHeights.data() + chunk * n, sizeof(uint16_t) * n, hipMemcpyHostToDevice, W->stream));
+	MI_CHECK(hipMemcpyAsync(W->terrain.valid.p + chunk, W->terrain.hValid.data() + chunk, sizeof(u32), hipMemcpyHostToDevice, W->stream));
 	MI_CHECK(hipStreamSynchronize(W->stream));
 	return W->lastError;
 }
 int mi_heightmap_update(mi_world* world, const float minCorner[3], float amplitudeScale) // heightmap_collider_component::update
 {
 	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
-	if (!W->terrainChunksPerDim || !minCorner || !(amplitudeScale > 0.f)) { W->fail(MI_ERR_INVALID_ARGUMENT, "mi_heightmap_update: no heightmap, or amplitude not positive"); return W->lastError; }
-	memcpy(W->terrainMinCorner, minCorner, 12); W->terrainAmplitude = amplitudeScale;
+	if (!W->terrain.chunksPerDim || !minCorner || !(amplitudeScale > 0.f)) { W->fail(MI_ERR_INVALID_ARGUMENT, "mi_heightmap_update: no heightmap, or amplitude not positive"); return W->lastError; }
+	memcpy(W->terrain.minCorner, minCorner, 12); W->terrain.amplitude = amplitudeScale;
 	return MI_OK;
 }
 float mi_heightmap_height_at(mi_world* world, float wx, float wz) // heightmap_collider_component::getHeightAt: -FLT_MAX outside the terrain
 {
 	CHECK_WORLD(-MI_FLT_MAX);
-	if (!W->terrainChunksPerDim) return -MI_FLT_MAX;
-	float invChunkSize = 1.f / W->terrainChunkSize, heightScale = W->terrainAmplitude / 65535;
-	float cx = (wx - W->terrainMinCorner[0]) * invChunkSize, cz = (wz - W->terrainMinCorner[2]) * invChunkSize;
-	if (cx < 0.f || cz < 0.f || cx >= W->terrainChunksPerDim || cz >= W->terrainChunksPerDim) return -MI_FLT_MAX;
-	u32 chunk = (u32)cz * W->terrainChunksPerDim + (u32)cx;
-	if (!W->hTerrainValid[chunk]) return -MI_FLT_MAX;
+	if (!W->terrain.chunksPerDim) return -MI_FLT_MAX;
+	float invChunkSize = 1.f / W->terrain.chunkSize, heightScale = W->terrain.amplitude / 65535;
+	float cx = (wx - W->terrain.minCorner[0]) * invChunkSize, cz = (wz - W->terrain.minCorner[2]) * invChunkSize;
+	if (cx < 0.f || cz < 0.f || cx >= W->terrain.chunksPerDim || cz >= W->terrain.chunksPerDim) return -MI_FLT_MAX;
+	u32 chunk = (u32)cz * W->terrain.chunksPerDim + (u32)cx;
+	if (!W->terrain.hValid[chunk]) return -MI_FLT_MAX;
 	cx = fmodf(cx, 1.f) * 128; cz = fmodf(cz, 1.f) * 128;
 	u32 x = (u32)cx, z = (u32)cz;
 	float relX = cx - x, relZ = cz - z;
-	const uint16_t* H = W->hTerrainHeights.data() + (size_t)chunk * 129 * 129;
+	const uint16_t* H = W->terrain.hHeights.data() + (size_t)chunk * 129 * 129;
 	float a = H[129 * z + x] * heightScale, b = H[129 * (z + 1) + x] * heightScale, c = H[129 * z + x + 1] * heightScale, d = H[129 * (z + 1) + x + 1] * heightScale;
 	float l0 = a + relX * (c - a), l1 = b + relX * (d - b);
-	return (l0 + relZ * (l1 - l0)) + W->terrainMinCorner[1];
+	return (l0 + relZ * (l1 - l0)) + W->terrain.minCorner[1];
 }
 
 // ---- cloth (cloth.h:5-60) ----
@@ -299,15 +299,15 @@ uint32_t mi_add_cloth(mi_world* world, float width, float height, uint32_t gridS
 			if (y + 2 < gridSizeY) add(index, index + gridSizeX * 2, 10 + ((y >> 1) & 1));
 		}
 	std::stable_sort(c.constraints.begin(), c.constraints.end(), [](const World::HClothConstraint& l, const World::HClothConstraint& r) { return l.color < r.color; });
-	W->cloths.push_back(std::move(c)); W->clothsDirty = true;
-	return (uint32_t)W->cloths.size() - 1;
+	W->cloth.cloths.push_back(std::move(c)); W->cloth.dirty = true;
+	return (uint32_t)W->cloth.cloths.size() - 1;
 }
 int mi_cloth_set_fixed_vertices(mi_world* world, uint32_t cloth, const float pos[3], const float rot[4], int moveRigid) // cloth.cpp:90-132
 {
 	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
-	if (cloth >= W->cloths.size() || !pos || !rot) { W->fail(MI_ERR_INVALID_ARGUMENT, "mi_cloth_set_fixed_vertices: cloth out of range"); return W->lastError; }
+	if (cloth >= W->cloth.cloths.size() || !pos || !rot) { W->fail(MI_ERR_INVALID_ARGUMENT, "mi_cloth_set_fixed_vertices: cloth out of range"); return W->lastError; }
 	W->downloadCloths();
-	World::HCloth& c = W->cloths[cloth];
+	World::HCloth& c = W->cloth.cloths[cloth];
 	Q4 q = q4(rot[0], rot[1], rot[2], rot[3]); V3 t = v3(pos[0], pos[1], pos[2]);
 	auto P = [&c](u32 i) { return v3(c.pos[3 * i], c.pos[3 * i + 1], c.pos[3 * i + 2]); };
 	auto xform = [&](V3 p) { return q * p + t; };
@@ -331,32 +331,32 @@ int mi_cloth_set_fixed_vertices(mi_world* world, uint32_t cloth, const float pos
 		V3 p = xform(clothParticlePosition(c, x / (float)(c.gridX - 1), 0.f));
 		c.pos[3 * x] = p.x; c.pos[3 * x + 1] = p.y; c.pos[3 * x + 2] = p.z;
 	}
-	W->clothsDirty = true;
+	W->cloth.dirty = true;
 	return MI_OK;
 }
 int mi_cloth_set_properties(mi_world* world, uint32_t cloth, float totalMass, float stiffness, float damping, float gravityFactor)
 {
 	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
-	if (cloth >= W->cloths.size() || !(totalMass > 0.f)) { W->fail(MI_ERR_INVALID_ARGUMENT, "mi_cloth_set_properties: cloth out of range or mass not positive"); return W->lastError; }
-	World::HCloth& c = W->cloths[cloth];
+	if (cloth >= W->cloth.cloths.size() || !(totalMass > 0.f)) { W->fail(MI_ERR_INVALID_ARGUMENT, "mi_cloth_set_properties: cloth out of range or mass not positive"); return W->lastError; }
+	World::HCloth& c = W->cloth.cloths[cloth];
 	c.totalMass = totalMass; c.stiffness = stiffness; c.damping = damping; c.gravityFactor = gravityFactor;
-	W->clothsDirty = true;
+	W->cloth.dirty = true;
 	return MI_OK;
 }
 int mi_set_cloth_iterations(mi_world* world, uint32_t velocityIterations, uint32_t positionIterations, uint32_t driftIterations)
 {
 	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
-	W->clothIterations[0] = velocityIterations; W->clothIterations[1] = positionIterations; W->clothIterations[2] = driftIterations;
+	W->cloth.iterations[0] = velocityIterations; W->cloth.iterations[1] = positionIterations; W->cloth.iterations[2] = driftIterations;
 	return MI_OK;
 }
-uint32_t mi_num_cloths(mi_world* world) { CHECK_WORLD(0); return (uint32_t)W->cloths.size(); }
-uint32_t mi_cloth_num_particles(mi_world* world, uint32_t cloth) { CHECK_WORLD(0); return cloth < W->cloths.size() ? W->cloths[cloth].gridX * W->cloths[cloth].gridY : 0; }
+uint32_t mi_num_cloths(mi_world* world) { CHECK_WORLD(0); return (uint32_t)W->cloth.cloths.size(); }
+uint32_t mi_cloth_num_particles(mi_world* world, uint32_t cloth) { CHECK_WORLD(0); return cloth < W->cloth.cloths.size() ? W->cloth.cloths[cloth].gridX * W->cloth.cloths[cloth].gridY : 0; }
 int mi_cloth_read(mi_world* world, uint32_t cloth, float* positions3, float* velocities3)
 {
 	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
-	if (cloth >= W->cloths.size()) { W->fail(MI_ERR_INVALID_ARGUMENT, "mi_cloth_read: cloth out of range"); return W->lastError; }
+	if (cloth >= W->cloth.cloths.size()) { W->fail(MI_ERR_INVALID_ARGUMENT, "mi_cloth_read: cloth out of range"); return W->lastError; }
 	W->downloadCloths();
-	const World::HCloth& c = W->cloths[cloth];
+	const World::HCloth& c = W->cloth.cloths[cloth];
 	if (positions3) memcpy(positions3, c.pos.data(), sizeof(float) * c.pos.size());
 	if (velocities3) memcpy(velocities3, c.vel.data(), sizeof(float) * c.vel.size());
 	return W->lastError;

@@ -310,13 +310,13 @@ __global__ void __launch_bounds__(256) k_restore_velocities(u32 nb, const u32* _
 }
 void launch_restore_velocities(World& w)
 {
-	hipLaunchKernelGGL(k_restore_velocities, dim3(std::max(1u, active_grid(w.estActiveBodies + 1, w.nb + 1))), dim3(256), 0, w.stream, w.nb, w.dCounters.p, w.actBodies.p, w.velBackup.p, w.vel.p);
+	hipLaunchKernelGGL(k_restore_velocities, dim3(std::max(1u, active_grid(w.estActiveBodies + 1, w.nb + 1))), dim3(256), 0, w.stream, w.nb, w.dCounters.p, w.actBodies.p, w.cluster.velBackup.p, w.vel.p);
 }
 
 void launch_integrate_forces(World& w, float dt, bool backupVelocities)
 {
 	hipLaunchKernelGGL(k_integrate_forces, dim3(std::max(1u, active_grid(w.estActiveBodies + 1, w.nb + 1))), dim3(256), 0, w.stream, w.nb, dt, w.dCounters.p, w.actBodies.p, w.pose.p, w.bprops.p, w.force.p,
-		w.vel.p, w.cog.p, w.invIw.p, w.bodyMask.p, w.claim.p, backupVelocities ? w.velBackup.p : nullptr);
+		w.vel.p, w.cog.p, w.invIw.p, w.bodyMask.p, w.claim.p, backupVelocities ? w.cluster.velBackup.p : nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -501,7 +501,7 @@ __global__ void __launch_bounds__(256) k_slab_retire(u32 nb, u32 stamp, bool hav
 void launch_slab_classify(World& w)
 {
 	if (!w.nb) return;
-	hipLaunchKernelGGL(k_slab_classify, dim3((w.nb + 255) / 256), dim3(256), 0, w.stream, w.nb, w.slabAxis, w.slabLo, w.slabHi, w.slabMargin, w.pose.p, w.aliveMask.p, w.slabCode.p, w.simMask.p, w.slabFresh.p);
+	hipLaunchKernelGGL(k_slab_classify, dim3((w.nb + 255) / 256), dim3(256), 0, w.stream, w.nb, w.slab.axis, w.slab.lo, w.slab.hi, w.slab.margin, w.pose.p, w.aliveMask.p, w.slab.code.p, w.simMask.p, w.slab.fresh.p);
 	w.activeDirty = true;
 }
 void launch_slab_pack(World& w, void* left, void* right, u32 capacity)
@@ -509,15 +509,15 @@ void launch_slab_pack(World& w, void* left, void* right, u32 capacity)
 	if (!w.nb) return;
 	if (left) MI_CHECK(hipMemsetAsync(left, 0, 16, w.stream));
 	if (right) MI_CHECK(hipMemsetAsync(right, 0, 16, w.stream));
-	hipLaunchKernelGGL(k_slab_pack, dim3((w.nb + 255) / 256), dim3(256), 0, w.stream, w.nb, w.slabAxis, w.slabLo, w.slabHi, w.slabMargin, capacity, w.slabStamp, w.pose.p, w.vel.p,
-		w.aliveMask.p, w.slabCode.p, w.slabFresh.p, (u32*)left, (u32*)right);
+	hipLaunchKernelGGL(k_slab_pack, dim3((w.nb + 255) / 256), dim3(256), 0, w.stream, w.nb, w.slab.axis, w.slab.lo, w.slab.hi, w.slab.margin, capacity, w.slab.stamp, w.pose.p, w.vel.p,
+		w.aliveMask.p, w.slab.code.p, w.slab.fresh.p, (u32*)left, (u32*)right);
 }
 void launch_slab_unpack(World& w, const void* left, const void* right, u32 capacity)
 {
 	if (!w.nb) return;
 	dim3 grid((capacity + 255) / 256), block(256);
-	if (left && capacity) hipLaunchKernelGGL(k_slab_apply, grid, block, 0, w.stream, w.nb, capacity, w.slabStamp, (uint8_t)MI_SLAB_GHOST_LEFT, (const u32*)left, w.pose.p, w.pose0.p, w.poseLerp.p, w.vel.p, w.slabCode.p, w.slabFresh.p);
-	if (right && capacity) hipLaunchKernelGGL(k_slab_apply, grid, block, 0, w.stream, w.nb, capacity, w.slabStamp, (uint8_t)MI_SLAB_GHOST_RIGHT, (const u32*)right, w.pose.p, w.pose0.p, w.poseLerp.p, w.vel.p, w.slabCode.p, w.slabFresh.p);
-	hipLaunchKernelGGL(k_slab_retire, dim3((w.nb + 255) / 256), block, 0, w.stream, w.nb, w.slabStamp, left != nullptr, right != nullptr, w.aliveMask.p, w.slabCode.p, w.slabFresh.p, w.simMask.p);
+	if (left && capacity) hipLaunchKernelGGL(k_slab_apply, grid, block, 0, w.stream, w.nb, capacity, w.slab.stamp, (uint8_t)MI_SLAB_GHOST_LEFT, (const u32*)left, w.pose.p, w.pose0.p, w.poseLerp.p, w.vel.p, w.slab.code.p, w.slab.fresh.p);
+	if (right && capacity) hipLaunchKernelGGL(k_slab_apply, grid, block, 0, w.stream, w.nb, capacity, w.slab.stamp, (uint8_t)MI_SLAB_GHOST_RIGHT, (const u32*)right, w.pose.p, w.pose0.p, w.poseLerp.p, w.vel.p, w.slab.code.p, w.slab.fresh.p);
+	hipLaunchKernelGGL(k_slab_retire, dim3((w.nb + 255) / 256), block, 0, w.stream, w.nb, w.slab.stamp, left != nullptr, right != nullptr, w.aliveMask.p, w.slab.code.p, w.slab.fresh.p, w.simMask.p);
 	w.activeDirty = true; // ghosts came and went
 }

@@ -145,17 +145,17 @@ u32 cloth_lds_particle_limit() { return (64u * 1024u) / (7u * sizeof(float)); }
 
 void launch_cloth(World& w, float dt)
 {
-	if (w.cloths.empty()) return;
+	if (w.cloth.cloths.empty()) return;
 	w.uploadCloths();
-	const ClothDesc* descs = (const ClothDesc*)w.clothDescs.p;
-	if (w.numSmallCloths)
-		hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cloth_simulate<true>), dim3(w.numSmallCloths), dim3(CLOTH_BLOCK), 7 * sizeof(float) * w.maxSmallClothParticles, w.stream, descs, w.clothList.p, w.clothPlanes.p,
-			(size_t)w.clothStride, w.clothAB.p, w.clothRestIms.p, w.clothTemp.p, w.globalForce[0], w.globalForce[1], w.globalForce[2], w.clothIterations[0], w.clothIterations[1], w.clothIterations[2], dt);
-	w.clothStateOnDevice = true; // the host mirror is stale from here on (World::downloadCloths)
-	u32 numLarge = (u32)w.cloths.size() - w.numSmallCloths;
+	const ClothDesc* descs = (const ClothDesc*)w.cloth.descs.p;
+	if (w.cloth.numSmall)
+		hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cloth_simulate<true>), dim3(w.cloth.numSmall), dim3(CLOTH_BLOCK), 7 * sizeof(float) * w.cloth.maxSmallParticles, w.stream, descs, w.cloth.list.p, w.cloth.planes.p,
+			(size_t)w.cloth.stride, w.cloth.ab.p, w.cloth.restIms.p, w.cloth.temp.p, w.zones.globalForce[0], w.zones.globalForce[1], w.zones.globalForce[2], w.cloth.iterations[0], w.cloth.iterations[1], w.cloth.iterations[2], dt);
+	w.cloth.stateOnDevice = true; // the host mirror is stale from here on (World::downloadCloths)
+	u32 numLarge = (u32)w.cloth.cloths.size() - w.cloth.numSmall;
 	if (numLarge)
-		hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cloth_simulate<false>), dim3(numLarge), dim3(CLOTH_BLOCK), 0, w.stream, descs, w.clothList.p + w.numSmallCloths, w.clothPlanes.p,
-			(size_t)w.clothStride, w.clothAB.p, w.clothRestIms.p, w.clothTemp.p, w.globalForce[0], w.globalForce[1], w.globalForce[2], w.clothIterations[0], w.clothIterations[1], w.clothIterations[2], dt);
+		hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cloth_simulate<false>), dim3(numLarge), dim3(CLOTH_BLOCK), 0, w.stream, descs, w.cloth.list.p + w.cloth.numSmall, w.cloth.planes.p,
+			(size_t)w.cloth.stride, w.cloth.ab.p, w.cloth.restIms.p, w.cloth.temp.p, w.zones.globalForce[0], w.zones.globalForce[1], w.zones.globalForce[2], w.cloth.iterations[0], w.cloth.iterations[1], w.cloth.iterations[2], dt);
 }
 
 // ---- host side: the particle state and the descriptors between World::HCloth and the device (cloth.cpp:198-204, 331-347) ----
@@ -170,53 +170,53 @@ static void clothRecalculateProperties(World::HCloth& c) // cloth.cpp:331-347
 }
 void World::downloadCloths()
 {
-	if (!clothStateOnDevice || cloths.empty()) return;
+	if (!cloth.stateOnDevice || cloth.cloths.empty()) return;
 	resolvePendingFlow();
-	std::vector<float> planes((size_t)9 * clothStride);
-	MI_CHECK(hipMemcpyAsync(planes.data(), clothPlanes.p, sizeof(float) * planes.size(), hipMemcpyDeviceToHost, stream));
+	std::vector<float> planes((size_t)9 * cloth.stride);
+	MI_CHECK(hipMemcpyAsync(planes.data(), cloth.planes.p, sizeof(float) * planes.size(), hipMemcpyDeviceToHost, stream));
 	MI_CHECK(hipStreamSynchronize(stream));
 	size_t first = 0;
-	for (HCloth& c : cloths)
+	for (HCloth& c : cloth.cloths)
 	{
 		size_t n = (size_t)c.gridX * c.gridY;
 		for (size_t i = 0; i < n; ++i)
 			for (int k = 0; k < 3; ++k)
 			{
-				c.pos[3 * i + k] = planes[(size_t)k * clothStride + first + i];
-				c.vel[3 * i + k] = planes[(size_t)(3 + k) * clothStride + first + i];
-				c.prev[3 * i + k] = planes[(size_t)(6 + k) * clothStride + first + i];
+				c.pos[3 * i + k] = planes[(size_t)k * cloth.stride + first + i];
+				c.vel[3 * i + k] = planes[(size_t)(3 + k) * cloth.stride + first + i];
+				c.prev[3 * i + k] = planes[(size_t)(6 + k) * cloth.stride + first + i];
 			}
 		first += n;
 	}
-	clothStateOnDevice = false;
+	cloth.stateOnDevice = false;
 }
 void World::uploadCloths()
 {
-	for (HCloth& c : cloths)
-		if (c.totalMass != c.oldTotalMass || c.stiffness != c.oldStiffness) { clothRecalculateProperties(c); c.oldTotalMass = c.totalMass; c.oldStiffness = c.stiffness; clothsDirty = true; } // cloth.cpp:198-204
-	if (!clothsDirty) return;
+	for (HCloth& c : cloth.cloths)
+		if (c.totalMass != c.oldTotalMass || c.stiffness != c.oldStiffness) { clothRecalculateProperties(c); c.oldTotalMass = c.totalMass; c.oldStiffness = c.stiffness; cloth.dirty = true; } // cloth.cpp:198-204
+	if (!cloth.dirty) return;
 	downloadCloths();
 	size_t totalParticles = 0, totalConstraints = 0;
-	for (const HCloth& c : cloths) { totalParticles += (size_t)c.gridX * c.gridY; totalConstraints += c.constraints.size(); }
-	clothStride = (u32)totalParticles;
-	std::vector<float> planes((size_t)10 * clothStride);
+	for (const HCloth& c : cloth.cloths) { totalParticles += (size_t)c.gridX * c.gridY; totalConstraints += c.constraints.size(); }
+	cloth.stride = (u32)totalParticles;
+	std::vector<float> planes((size_t)10 * cloth.stride);
 	std::vector<uint2> ab(totalConstraints); std::vector<float2> rk(totalConstraints);
-	std::vector<ClothDesc> descs(cloths.size());
+	std::vector<ClothDesc> descs(cloth.cloths.size());
 	std::vector<u32> small, large;
-	size_t firstP = 0, firstC = 0; maxSmallClothParticles = 0;
-	for (size_t ci = 0; ci < cloths.size(); ++ci)
+	size_t firstP = 0, firstC = 0; cloth.maxSmallParticles = 0;
+	for (size_t ci = 0; ci < cloth.cloths.size(); ++ci)
 	{
-		const HCloth& c = cloths[ci];
+		const HCloth& c = cloth.cloths[ci];
 		size_t n = (size_t)c.gridX * c.gridY;
 		for (size_t i = 0; i < n; ++i)
 		{
 			for (int k = 0; k < 3; ++k)
 			{
-				planes[(size_t)k * clothStride + firstP + i] = c.pos[3 * i + k];
-				planes[(size_t)(3 + k) * clothStride + firstP + i] = c.vel[3 * i + k];
-				planes[(size_t)(6 + k) * clothStride + firstP + i] = c.prev[3 * i + k];
+				planes[(size_t)k * cloth.stride + firstP + i] = c.pos[3 * i + k];
+				planes[(size_t)(3 + k) * cloth.stride + firstP + i] = c.vel[3 * i + k];
+				planes[(size_t)(6 + k) * cloth.stride + firstP + i] = c.prev[3 * i + k];
 			}
-			planes[(size_t)9 * clothStride + firstP + i] = c.invMass[i];
+			planes[(size_t)9 * cloth.stride + firstP + i] = c.invMass[i];
 		}
 		ClothDesc& d = descs[ci];
 		d.firstParticle = (u32)firstP; d.numParticles = (u32)n; d.gridX = c.gridX; d.gridY = c.gridY; d.firstConstraint = (u32)firstC;
@@ -229,21 +229,21 @@ void World::uploadCloths()
 			ab[firstC + k] = make_uint2(e.a, e.b); rk[firstC + k] = make_float2(e.restDistance, e.inverseMassSum);
 		}
 		while (color < 12) d.colorStart[++color] = (u32)c.constraints.size();
-		if (n <= cloth_lds_particle_limit()) { small.push_back((u32)ci); maxSmallClothParticles = std::max(maxSmallClothParticles, (u32)n); } else large.push_back((u32)ci);
+		if (n <= cloth_lds_particle_limit()) { small.push_back((u32)ci); cloth.maxSmallParticles = std::max(cloth.maxSmallParticles, (u32)n); } else large.push_back((u32)ci);
 		firstP += n; firstC += c.constraints.size();
 	}
-	numSmallCloths = (u32)small.size();
+	cloth.numSmall = (u32)small.size();
 	small.insert(small.end(), large.begin(), large.end());
-	clothPlanes.ensure(planes.size(), stream); clothAB.ensure(std::max<size_t>(totalConstraints, 1), stream); clothRestIms.ensure(std::max<size_t>(totalConstraints, 1), stream);
-	clothTemp.ensure(std::max<size_t>(totalConstraints, 1), stream); clothDescs.ensure(sizeof(ClothDesc) * descs.size(), stream); clothList.ensure(small.size(), stream);
-	MI_CHECK(hipMemcpyAsync(clothPlanes.p, planes.data(), sizeof(float) * planes.size(), hipMemcpyHostToDevice, stream));
+	cloth.planes.ensure(planes.size(), stream); cloth.ab.ensure(std::max<size_t>(totalConstraints, 1), stream); cloth.restIms.ensure(std::max<size_t>(totalConstraints, 1), stream);
+	cloth.temp.ensure(std::max<size_t>(totalConstraints, 1), stream); cloth.descs.ensure(sizeof(ClothDesc) * descs.size(), stream); cloth.list.ensure(small.size(), stream);
+	MI_CHECK(hipMemcpyAsync(cloth.planes.p, planes.data(), sizeof(float) * planes.size(), hipMemcpyHostToDevice, stream));
 	if (totalConstraints)
 	{
-		MI_CHECK(hipMemcpyAsync(clothAB.p, ab.data(), sizeof(uint2) * ab.size(), hipMemcpyHostToDevice, stream));
-		MI_CHECK(hipMemcpyAsync(clothRestIms.p, rk.data(), sizeof(float2) * rk.size(), hipMemcpyHostToDevice, stream));
+		MI_CHECK(hipMemcpyAsync(cloth.ab.p, ab.data(), sizeof(uint2) * ab.size(), hipMemcpyHostToDevice, stream));
+		MI_CHECK(hipMemcpyAsync(cloth.restIms.p, rk.data(), sizeof(float2) * rk.size(), hipMemcpyHostToDevice, stream));
 	}
-	MI_CHECK(hipMemcpyAsync(clothDescs.p, descs.data(), sizeof(ClothDesc) * descs.size(), hipMemcpyHostToDevice, stream));
-	MI_CHECK(hipMemcpyAsync(clothList.p, small.data(), sizeof(u32) * small.size(), hipMemcpyHostToDevice, stream));
+	MI_CHECK(hipMemcpyAsync(cloth.descs.p, descs.data(), sizeof(ClothDesc) * descs.size(), hipMemcpyHostToDevice, stream));
+	MI_CHECK(hipMemcpyAsync(cloth.list.p, small.data(), sizeof(u32) * small.size(), hipMemcpyHostToDevice, stream));
 	MI_CHECK(hipStreamSynchronize(stream));
-	clothsDirty = false; clothStateOnDevice = false; // both copies are equal until the next launch
+	cloth.dirty = false; cloth.stateOnDevice = false; // both copies are equal until the next launch
 }

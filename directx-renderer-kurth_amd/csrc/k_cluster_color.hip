@@ -394,7 +394,7 @@ bool cluster_color_setup()
 // Colours the tasks k_cl_offsets / k_cl_scatter laid out; one workgroup per workgroup of the solve launch (the same task rotation).
 void cluster_color_launch(World& w, u32 nj)
 {
-	hipLaunchKernelGGL(k_cl_color, dim3(w.clusterBlocks), dim3(CL_LANES), clColorLdsBytes(), w.stream, w.dCounters.p, w.nb, w.clTaskStart.p, w.clPre.p, w.actIds.p,
-		w.clPhaseMask.p, (ClTask*)w.clTasks.p, w.clBodyList.p, w.mOrder.p, w.mKeySorted.p, w.clLocal.p, w.clEntry.p, w.clSharedSlot.p,
-		nj ? w.clJointStart.p : (const u32*)nullptr, w.clJointList.p, w.clJointTable.p, w.clTaskJoints.p, w.clJointClassStart.p, w.flowTrace.p);
+	hipLaunchKernelGGL(k_cl_color, dim3(w.cluster.blocks), dim3(CL_LANES), clColorLdsBytes(), w.stream, w.dCounters.p, w.nb, w.cluster.taskStart.p, w.cluster.pre.p, w.actIds.p,
+		w.cluster.phaseMask.p, (ClTask*)w.cluster.tasks.p, w.cluster.bodyList.p, w.mOrder.p, w.mKeySorted.p, w.cluster.local.p, w.cluster.entry.p, w.cluster.sharedSlot.p,
+		nj ? w.cluster.jointStart.p : (const u32*)nullptr, w.cluster.jointList.p, w.cluster.jointTable.p, w.cluster.taskJoints.p, w.cluster.jointClassStart.p, w.cluster.flowTrace.p);
 }

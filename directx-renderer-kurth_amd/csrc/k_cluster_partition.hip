@@ -111,7 +111,7 @@ MI_DEV u32 clEffectiveWeight(u32 taskWeightArg, u32 totalWeight, u32 maxTasks)
 #define CL_WEIGHT_EXTRA 64u               // ... plus this per contact beyond the first (the sweep's unit is the contact)
 #define CL_REST_CAP 1024u                 // once no more than this many manifolds are unassigned, they all go to the rest task (it must fit k_cl_color's tables)
 #define CL_REMAIN_SUBS 64u // the 'still unassigned after phase p' count is kept in 64 partial counters: ~2000 workgroups adding to ONE word queue up behind each other
-// The cursors the assignment accumulates into (World::clTaskCount): CL_SUBCOUNTERS per task key, then CL_REMAIN_SUBS per word of CTR_CL_REMAIN.
+// The cursors the assignment accumulates into (World::cluster.taskCount): CL_SUBCOUNTERS per task key, then CL_REMAIN_SUBS per word of CTR_CL_REMAIN.
 constexpr u32 CL_TASK_CURSORS = CL_MAX_PHASES * CL_MAX_TASKS * CL_SUBCOUNTERS;
 constexpr u32 CL_REMAIN_WORDS = ctrWords(CTR_CL_REMAIN);
 constexpr u32 CL_REMAIN_CURSORS = CL_REMAIN_WORDS * CL_REMAIN_SUBS;
@@ -375,7 +375,7 @@ __global__ void __launch_bounds__(256) k_cl_joint_assign_cached(u32 numJoints, c
 // dealt to tasks by a hash of their label (the clumps are tens of manifolds against tasks of hundreds: the load evens out), a
 // component too large for a task is sent to the rest task.
 #define CL_COMP_ROUNDS 4u
-#define CL_COMP_LABEL_BUFFERS 2u // World::clCompLabel: nb + 1 labels each; a round reads one and writes the other, k_cl_clear initialises both
+#define CL_COMP_LABEL_BUFFERS 2u // World::cluster.compLabel: nb + 1 labels each; a round reads one and writes the other, k_cl_clear initialises both
 static_assert(CL_COMP_ROUNDS % CL_COMP_LABEL_BUFFERS == 0u, "the last round must write the first label buffer: the weights and the assignment read it");
 #define CL_COMP_MAX_WEIGHT (64u * 1400u) // a component heavier than this cannot be a task's (k_cl_color's tables): rest task
 #define CL_COMP_BLOCKS 64u               // workgroups of the component kernels (they stride over the list: its length is only known on the device)
@@ -527,32 +527,32 @@ static const dim3 CL_BLOCK(256);
 static dim3 clGrid(u32 items) { return dim3((items + 255) / 256); }
 static dim3 clManifoldGrid(u32 numPairs) { return dim3((numPairs + CL_ASSIGN_LANES - 1u) / CL_ASSIGN_LANES); } // one lane per manifold: k_cl_assign, k_cl_assign_cached, k_cl_scatter (clSubCounter)
 // tasks per phase, with a margin for the chunks' rounding
-static u32 clMaxTasks(const World& w) { return std::min<u32>(CL_MAX_TASKS / CL_TASKS_PER_PHASE, w.clusterBlocks) - std::min<u32>(8u, w.clusterBlocks / 8u); }
+static u32 clMaxTasks(const World& w) { return std::min<u32>(CL_MAX_TASKS / CL_TASKS_PER_PHASE, w.cluster.blocks) - std::min<u32>(8u, w.cluster.blocks / 8u); }
 
 // The buffers sized by the bodies, the pair capacity and the task table.  false = an allocation failed.
 static bool clSizeBuffers(World& w)
 {
 	const u32 nb = w.nb, P = CL_MAX_PARTS;
 	const size_t nb1 = (size_t)nb + 1;
-	w.clKeys.ensure((size_t)P * nb, w.stream); w.clKeysSorted.ensure((size_t)P * nb, w.stream); w.clVals.ensure((size_t)P * nb, w.stream); w.clSorted.ensure((size_t)P * nb, w.stream);
-	w.clRank.ensure((size_t)P * nb1, w.stream); w.clSharedSlot.ensure((size_t)CL_MAX_PHASES * nb1, w.stream); w.clWsum.ensure(P * nb1, w.stream); w.clCum.ensure(nb1, w.stream); w.clPhaseMask.ensure(nb1, w.stream);
-	w.clTaskKey.ensure(w.pairCap, w.stream); w.clTaskPos.ensure(w.pairCap, w.stream); w.clPre.ensure(w.pairCap, w.stream); w.clLocal.ensure(w.pairCap, w.stream); w.clEntry.ensure(4 * w.pairCap, w.stream);
+	w.cluster.keys.ensure((size_t)P * nb, w.stream); w.cluster.keysSorted.ensure((size_t)P * nb, w.stream); w.cluster.vals.ensure((size_t)P * nb, w.stream); w.cluster.sorted.ensure((size_t)P * nb, w.stream);
+	w.cluster.rank.ensure((size_t)P * nb1, w.stream); w.cluster.sharedSlot.ensure((size_t)CL_MAX_PHASES * nb1, w.stream); w.cluster.wsum.ensure(P * nb1, w.stream); w.cluster.cum.ensure(nb1, w.stream); w.cluster.phaseMask.ensure(nb1, w.stream);
+	w.cluster.taskKey.ensure(w.pairCap, w.stream); w.cluster.taskPos.ensure(w.pairCap, w.stream); w.cluster.pre.ensure(w.pairCap, w.stream); w.cluster.local.ensure(w.pairCap, w.stream); w.cluster.entry.ensure(4 * w.pairCap, w.stream);
 	const u32 totalKeys = CL_MAX_PHASES * CL_MAX_TASKS;
-	w.clTaskCount.ensure(CL_TASK_CURSORS + CL_REMAIN_CURSORS, w.stream); w.clTaskStart.ensure(CL_TASK_CURSORS + 1, w.stream);
-	w.clTasks.ensure((size_t)totalKeys * sizeof(ClTask), w.stream); w.clBodyList.ensure((size_t)totalKeys * CL_BODY_STRIDE, w.stream);
+	w.cluster.taskCount.ensure(CL_TASK_CURSORS + CL_REMAIN_CURSORS, w.stream); w.cluster.taskStart.ensure(CL_TASK_CURSORS + 1, w.stream);
+	w.cluster.tasks.ensure((size_t)totalKeys * sizeof(ClTask), w.stream); w.cluster.bodyList.ensure((size_t)totalKeys * CL_BODY_STRIDE, w.stream);
 	return !w.lastError;
 }
 // The joints' task lists (nj joints run inside the sweep), the component phase's labels and list, the cached chunks.
 static bool clSizeListBuffers(World& w, u32 nj)
 {
 	const size_t nb1 = (size_t)w.nb + 1;
-	w.clJointCount.ensure(CL_MAX_TASKS, w.stream); w.clJointStart.ensure(CL_MAX_TASKS + 1, w.stream);
-	w.clJointTask.ensure(std::max(nj, 1u), w.stream); w.clJointPos.ensure(std::max(nj, 1u), w.stream); w.clJointList.ensure(std::max(nj, 1u), w.stream); w.clTaskJoints.ensure(std::max(nj, 1u), w.stream);
-	w.clJointClassStart.ensure((size_t)CL_MAX_TASKS * (CL_MAX_JOINT_CLASSES + 2u), w.stream);
+	w.cluster.jointCount.ensure(CL_MAX_TASKS, w.stream); w.cluster.jointStart.ensure(CL_MAX_TASKS + 1, w.stream);
+	w.cluster.jointTask.ensure(std::max(nj, 1u), w.stream); w.cluster.jointPos.ensure(std::max(nj, 1u), w.stream); w.cluster.jointList.ensure(std::max(nj, 1u), w.stream); w.cluster.taskJoints.ensure(std::max(nj, 1u), w.stream);
+	w.cluster.jointClassStart.ensure((size_t)CL_MAX_TASKS * (CL_MAX_JOINT_CLASSES + 2u), w.stream);
 	if (w.lastError) return false;
-	w.clCompLabel.ensure(CL_COMP_LABEL_BUFFERS * nb1, w.stream); w.clLeftList.ensure(w.pairCap, w.stream);
+	w.cluster.compLabel.ensure(CL_COMP_LABEL_BUFFERS * nb1, w.stream); w.cluster.leftList.ensure(w.pairCap, w.stream);
 	if (w.lastError) return false;
-	w.clChunk.ensure((size_t)CL_MAX_PARTS * nb1, w.stream);
+	w.cluster.chunk.ensure((size_t)CL_MAX_PARTS * nb1, w.stream);
 	return !w.lastError;
 }
 
@@ -563,26 +563,26 @@ static bool clSizeListBuffers(World& w, u32 nj)
 static bool clRefreshBodyOrder(World& w)
 {
 	const u32 nb = w.nb, P = CL_MAX_PARTS;
-	const bool due = w.clusterSortDue || w.clusterSortAge >= CL_SORT_INTERVAL || w.clusterSortBodies != nb;
+	const bool due = w.cluster.sortDue || w.cluster.sortAge >= CL_SORT_INTERVAL || w.cluster.sortBodies != nb;
 	if (due)
 	{
 		// the curves in use and the one behind them (phase p attributes what it leaves over along curve p + 1) are sorted; all of them the first
 		// time and when the body count changed, so that every rank array holds valid positions (each sort is ~80 us at 100 k bodies)
-		const u32 sortParts = (w.clusterSortBodies != nb) ? P : CL_CURVE_PARTS + 1u;
+		const u32 sortParts = (w.cluster.sortBodies != nb) ? P : CL_CURVE_PARTS + 1u;
 		u32 maxShift = 0;
 		for (const auto& s : CL_SHIFTS.s) for (u32 v : s) maxShift = std::max(maxShift, v);
 		hipLaunchKernelGGL(k_cl_bbox, dim3(std::min<u32>(clGrid(nb).x, 64u)), CL_BLOCK, 0, w.stream, nb, w.cog.p, w.simMask.p, w.dCounters.p);
-		hipLaunchKernelGGL(k_cl_keys, clGrid(nb), CL_BLOCK, 0, w.stream, nb, P, CL_SHIFTS, maxShift, w.cog.p, w.simMask.p, w.dCounters.p, w.clKeys.p, w.clVals.p);
-		// The curves lie curve-major in clKeys / clVals and carry their index in the keys' top bits: one stable sort of sortParts x nb
+		hipLaunchKernelGGL(k_cl_keys, clGrid(nb), CL_BLOCK, 0, w.stream, nb, P, CL_SHIFTS, maxShift, w.cog.p, w.simMask.p, w.dCounters.p, w.cluster.keys.p, w.cluster.vals.p);
+		// The curves lie curve-major in cluster.keys / cluster.vals and carry their index in the keys' top bits: one stable sort of sortParts x nb
 		// items leaves curve p's order in [p * nb, (p + 1) * nb), equal keys by ascending body, as one sort per curve did (at 100 k
 		// bodies rocPRIM runs a block sort and 7 merge launches per curve; the 300 k items of three curves take one block sort and 18
 		// merge launches: 146 -> 111 us of kernel time per refresh, profiles/cluster_build.txt).
 		static_assert(CL_MAX_PARTS <= 4u, "the curve index has two key bits above the 30-bit Morton code");
-		prim_sort_pairs_u32(w, w.clKeys.p, w.clKeysSorted.p, w.clVals.p, w.clSorted.p, sortParts * nb, 32);
-		hipLaunchKernelGGL(k_cl_ranks, clGrid(nb), CL_BLOCK, 0, w.stream, nb, sortParts, w.clSorted.p, w.clRank.p);
-		w.clusterSortDue = false; w.clusterSortAge = 0; w.clusterSortBodies = nb;
+		prim_sort_pairs_u32(w, w.cluster.keys.p, w.cluster.keysSorted.p, w.cluster.vals.p, w.cluster.sorted.p, sortParts * nb, 32);
+		hipLaunchKernelGGL(k_cl_ranks, clGrid(nb), CL_BLOCK, 0, w.stream, nb, sortParts, w.cluster.sorted.p, w.cluster.rank.p);
+		w.cluster.sortDue = false; w.cluster.sortAge = 0; w.cluster.sortBodies = nb;
 	}
-	w.clusterSortAge++;
+	w.cluster.sortAge++;
 	return due;
 }
 
@@ -591,30 +591,30 @@ static void clClear(World& w, u32 nj, bool keepJointLists)
 {
 	const size_t nb1 = (size_t)w.nb + 1;
 	const u32 clearItems = std::max<u32>((u32)(CL_MAX_PARTS * nb1), CL_TASK_CURSORS + CL_REMAIN_CURSORS);
-	hipLaunchKernelGGL(k_cl_clear, clGrid(clearItems), CL_BLOCK, 0, w.stream, (u32)nb1, w.clWsum.p, w.clPhaseMask.p, w.clTaskCount.p, w.clJointCount.p, w.dCounters.p, w.clCompLabel.p,
-		nj ? w.clJointBodyMask.p : (const u32*)nullptr, keepJointLists ? 1u : 0u);
+	hipLaunchKernelGGL(k_cl_clear, clGrid(clearItems), CL_BLOCK, 0, w.stream, (u32)nb1, w.cluster.wsum.p, w.cluster.phaseMask.p, w.cluster.taskCount.p, w.cluster.jointCount.p, w.dCounters.p, w.cluster.compLabel.p,
+		nj ? w.cluster.jointBodyMask.p : (const u32*)nullptr, keepJointLists ? 1u : 0u);
 }
 
 // A refresh step: the full pipeline per curve phase (weights, scan, assignment), which also stores every body's chunk for the cached pass.
 // withJoints: joints run inside the sweep (islands are not cut); leftList: where the last phase's left-overs go (null: the rest task).
 static void clAssignByPhase(World& w, u32 numPairs, u32 nj, bool withJoints, u32* leftList)
 {
-	const u32* rep = withJoints ? w.clRep.p : nullptr;
+	const u32* rep = withJoints ? w.cluster.rep.p : nullptr;
 	const u32 nb = w.nb, parts = CL_CURVE_PARTS, maxTasks = clMaxTasks(w), leftCap = (u32)w.pairCap;
 	const size_t nb1 = (size_t)nb + 1;
 	const u32 firstFlags = withJoints ? CL_WEIGHT_ISLANDS : 0u; // (goes with the first phase's weight)
-	const u32 weight0 = w.clusterTaskWeight - (u32)((u64)w.clusterTaskWeight * CL_CHUNK_HEADROOM_PERCENT / 100u), weightLater = w.clusterTaskWeightLater - (u32)((u64)w.clusterTaskWeightLater * CL_CHUNK_HEADROOM_PERCENT / 100u);
-	hipLaunchKernelGGL(k_cl_weights0, clGrid(numPairs), CL_BLOCK, 0, w.stream, w.dCounters.p, nb, w.actIds.p, w.clRank.p, rep, w.clWsum.p, w.clTaskKey.p);
-	if (nj) hipLaunchKernelGGL(k_cl_joint_weights, clGrid(nj), CL_BLOCK, 0, w.stream, nj, w.clJointTable.p, w.clRank.p, rep, w.clWsum.p);
+	const u32 weight0 = w.cluster.taskWeight - (u32)((u64)w.cluster.taskWeight * CL_CHUNK_HEADROOM_PERCENT / 100u), weightLater = w.cluster.taskWeightLater - (u32)((u64)w.cluster.taskWeightLater * CL_CHUNK_HEADROOM_PERCENT / 100u);
+	hipLaunchKernelGGL(k_cl_weights0, clGrid(numPairs), CL_BLOCK, 0, w.stream, w.dCounters.p, nb, w.actIds.p, w.cluster.rank.p, rep, w.cluster.wsum.p, w.cluster.taskKey.p);
+	if (nj) hipLaunchKernelGGL(k_cl_joint_weights, clGrid(nj), CL_BLOCK, 0, w.stream, nj, w.cluster.jointTable.p, w.cluster.rank.p, rep, w.cluster.wsum.p);
 	for (u32 p = 0; p < parts; ++p)
 	{
-		u32* wsum = w.clWsum.p + (size_t)p * nb1; u32* wsumNext = w.clWsum.p + (size_t)std::min(p + 1, CL_MAX_PARTS - 1) * nb1;
-		prim_exclusive_scan_u32(w, wsum, w.clCum.p, nb + 1);
-		hipLaunchKernelGGL(k_cl_assign, clManifoldGrid(numPairs), dim3(CL_ASSIGN_LANES), 0, w.stream, w.dCounters.p, nb, p, parts, p ? weightLater : (weight0 | firstFlags), maxTasks, w.actIds.p, w.clRank.p + (size_t)p * nb1, w.clCum.p,
-			w.clRank.p + (size_t)std::min(p + 1, CL_MAX_PARTS - 1) * nb1, wsumNext, w.clTaskKey.p, w.clTaskPos.p, w.clTaskCount.p, w.clPhaseMask.p, w.dCounters.p + CTR_CL_STATUS, p == 0 ? rep : nullptr, leftList, leftCap);
+		u32* wsum = w.cluster.wsum.p + (size_t)p * nb1; u32* wsumNext = w.cluster.wsum.p + (size_t)std::min(p + 1, CL_MAX_PARTS - 1) * nb1;
+		prim_exclusive_scan_u32(w, wsum, w.cluster.cum.p, nb + 1);
+		hipLaunchKernelGGL(k_cl_assign, clManifoldGrid(numPairs), dim3(CL_ASSIGN_LANES), 0, w.stream, w.dCounters.p, nb, p, parts, p ? weightLater : (weight0 | firstFlags), maxTasks, w.actIds.p, w.cluster.rank.p + (size_t)p * nb1, w.cluster.cum.p,
+			w.cluster.rank.p + (size_t)std::min(p + 1, CL_MAX_PARTS - 1) * nb1, wsumNext, w.cluster.taskKey.p, w.cluster.taskPos.p, w.cluster.taskCount.p, w.cluster.phaseMask.p, w.dCounters.p + CTR_CL_STATUS, p == 0 ? rep : nullptr, leftList, leftCap);
 		if (p == 0 && nj) // (cum still holds phase 0's scan)
-			hipLaunchKernelGGL(k_cl_joint_assign, clGrid(nj), CL_BLOCK, 0, w.stream, nj, nb, weight0 | firstFlags, maxTasks, w.clJointTable.p, w.clRank.p, rep, w.clCum.p, w.clJointTask.p, w.clJointPos.p, w.clJointCount.p, w.clPhaseMask.p, w.dCounters.p + CTR_CL_STATUS);
-		hipLaunchKernelGGL(k_cl_store_chunks, clGrid(nb), CL_BLOCK, 0, w.stream, nb, p ? weightLater : (weight0 | firstFlags), maxTasks, w.clRank.p + (size_t)p * nb1, w.clCum.p, p == 0 ? rep : nullptr, w.clChunk.p + (size_t)p * nb1);
+			hipLaunchKernelGGL(k_cl_joint_assign, clGrid(nj), CL_BLOCK, 0, w.stream, nj, nb, weight0 | firstFlags, maxTasks, w.cluster.jointTable.p, w.cluster.rank.p, rep, w.cluster.cum.p, w.cluster.jointTask.p, w.cluster.jointPos.p, w.cluster.jointCount.p, w.cluster.phaseMask.p, w.dCounters.p + CTR_CL_STATUS);
+		hipLaunchKernelGGL(k_cl_store_chunks, clGrid(nb), CL_BLOCK, 0, w.stream, nb, p ? weightLater : (weight0 | firstFlags), maxTasks, w.cluster.rank.p + (size_t)p * nb1, w.cluster.cum.p, p == 0 ? rep : nullptr, w.cluster.chunk.p + (size_t)p * nb1);
 	}
 }
 // Between two refreshes: one pass over the manifolds with the stored chunks; the joints' lists are rebuilt unless they are kept.
@@ -622,30 +622,30 @@ static void clAssignCached(World& w, u32 numPairs, u32 nj, bool withJoints, bool
 {
 	const u32 nb = w.nb, parts = CL_CURVE_PARTS;
 	const size_t nb1 = (size_t)nb + 1;
-	hipLaunchKernelGGL(k_cl_assign_cached, clManifoldGrid(numPairs), dim3(CL_ASSIGN_LANES), 0, w.stream, w.dCounters.p, nb, parts, parts, withJoints ? 1u : 0u, w.actIds.p, w.clChunk.p,
-		w.clRank.p + (size_t)parts * nb1, w.clWsum.p + (size_t)parts * nb1, w.clTaskKey.p, w.clTaskPos.p, w.clTaskCount.p, w.clPhaseMask.p, leftList, (u32)w.pairCap);
-	if (nj && !keepJointLists) hipLaunchKernelGGL(k_cl_joint_assign_cached, clGrid(nj), CL_BLOCK, 0, w.stream, nj, w.clJointTable.p, w.clChunk.p, w.clJointTask.p, w.clJointPos.p, w.clJointCount.p, w.clPhaseMask.p);
+	hipLaunchKernelGGL(k_cl_assign_cached, clManifoldGrid(numPairs), dim3(CL_ASSIGN_LANES), 0, w.stream, w.dCounters.p, nb, parts, parts, withJoints ? 1u : 0u, w.actIds.p, w.cluster.chunk.p,
+		w.cluster.rank.p + (size_t)parts * nb1, w.cluster.wsum.p + (size_t)parts * nb1, w.cluster.taskKey.p, w.cluster.taskPos.p, w.cluster.taskCount.p, w.cluster.phaseMask.p, leftList, (u32)w.pairCap);
+	if (nj && !keepJointLists) hipLaunchKernelGGL(k_cl_joint_assign_cached, clGrid(nj), CL_BLOCK, 0, w.stream, nj, w.cluster.jointTable.p, w.cluster.chunk.p, w.cluster.jointTask.p, w.cluster.jointPos.p, w.cluster.jointCount.p, w.cluster.phaseMask.p);
 }
-// What the curve phases left over (World::clLeftList): whole connected components to the tasks of one more phase (index CL_CURVE_PARTS).
+// What the curve phases left over (World::cluster.leftList): whole connected components to the tasks of one more phase (index CL_CURVE_PARTS).
 static void clAssignComponents(World& w)
 {
 	const u32 nb = w.nb, leftCap = (u32)w.pairCap;
 	const size_t nb1 = (size_t)nb + 1;
-	u32* compWeight = w.clWsum.p + (size_t)(CL_MAX_PARTS - 1) * nb1; // (the last curve's weight sums are not in use: zeroed by k_cl_clear)
+	u32* compWeight = w.cluster.wsum.p + (size_t)(CL_MAX_PARTS - 1) * nb1; // (the last curve's weight sums are not in use: zeroed by k_cl_clear)
 	for (u32 r = 0; r < CL_COMP_ROUNDS; ++r) // (the label buffers alternate: round r reads buffer r % 2 and writes the other)
-		hipLaunchKernelGGL(k_cl_comp_round, dim3(CL_COMP_BLOCKS), CL_BLOCK, 0, w.stream, w.dCounters.p, nb, leftCap, w.clLeftList.p, w.actIds.p,
-			(const u32*)(w.clCompLabel.p + (size_t)(r % CL_COMP_LABEL_BUFFERS) * nb1), w.clCompLabel.p + (size_t)((r + 1u) % CL_COMP_LABEL_BUFFERS) * nb1);
-	hipLaunchKernelGGL(k_cl_comp_weights, dim3(CL_COMP_BLOCKS), CL_BLOCK, 0, w.stream, w.dCounters.p, nb, leftCap, w.clLeftList.p, w.actIds.p, w.clCompLabel.p, compWeight);
-	hipLaunchKernelGGL(k_cl_comp_assign, dim3(CL_COMP_BLOCKS), dim3(CL_ASSIGN_LANES), 0, w.stream, w.dCounters.p, nb, CL_CURVE_PARTS, w.clusterTaskWeightLater, leftCap, w.clLeftList.p, w.actIds.p, w.clCompLabel.p, compWeight,
-		w.clTaskKey.p, w.clTaskPos.p, w.clTaskCount.p, w.clPhaseMask.p);
+		hipLaunchKernelGGL(k_cl_comp_round, dim3(CL_COMP_BLOCKS), CL_BLOCK, 0, w.stream, w.dCounters.p, nb, leftCap, w.cluster.leftList.p, w.actIds.p,
+			(const u32*)(w.cluster.compLabel.p + (size_t)(r % CL_COMP_LABEL_BUFFERS) * nb1), w.cluster.compLabel.p + (size_t)((r + 1u) % CL_COMP_LABEL_BUFFERS) * nb1);
+	hipLaunchKernelGGL(k_cl_comp_weights, dim3(CL_COMP_BLOCKS), CL_BLOCK, 0, w.stream, w.dCounters.p, nb, leftCap, w.cluster.leftList.p, w.actIds.p, w.cluster.compLabel.p, compWeight);
+	hipLaunchKernelGGL(k_cl_comp_assign, dim3(CL_COMP_BLOCKS), dim3(CL_ASSIGN_LANES), 0, w.stream, w.dCounters.p, nb, CL_CURVE_PARTS, w.cluster.taskWeightLater, leftCap, w.cluster.leftList.p, w.actIds.p, w.cluster.compLabel.p, compWeight,
+		w.cluster.taskKey.p, w.cluster.taskPos.p, w.cluster.taskCount.p, w.cluster.phaseMask.p);
 }
 // First slot of every task, then every manifold (and, unless kept, joint) to its slot.
 static void clOffsetsAndScatter(World& w, u32 numPairs, u32 nj, bool keepJointLists)
 {
-	hipLaunchKernelGGL(k_cl_offsets, dim3(1), dim3(1024), 0, w.stream, w.dCounters.p, CL_CURVE_PARTS, w.clTaskCount.p, w.clTaskStart.p, nj ? w.clJointCount.p : (u32*)nullptr, nj ? w.clJointStart.p : (u32*)nullptr);
-	if (nj && !keepJointLists) hipLaunchKernelGGL(k_cl_joint_scatter, clGrid(nj), CL_BLOCK, 0, w.stream, nj, w.clJointTask.p, w.clJointPos.p, w.clJointStart.p, w.clJointList.p);
-	w.clJointListsValid = nj != 0u;
-	hipLaunchKernelGGL(k_cl_scatter, clManifoldGrid(numPairs), dim3(CL_ASSIGN_LANES), 0, w.stream, w.dCounters.p, w.clTaskKey.p, w.clTaskPos.p, w.clTaskStart.p, w.clPre.p);
+	hipLaunchKernelGGL(k_cl_offsets, dim3(1), dim3(1024), 0, w.stream, w.dCounters.p, CL_CURVE_PARTS, w.cluster.taskCount.p, w.cluster.taskStart.p, nj ? w.cluster.jointCount.p : (u32*)nullptr, nj ? w.cluster.jointStart.p : (u32*)nullptr);
+	if (nj && !keepJointLists) hipLaunchKernelGGL(k_cl_joint_scatter, clGrid(nj), CL_BLOCK, 0, w.stream, nj, w.cluster.jointTask.p, w.cluster.jointPos.p, w.cluster.jointStart.p, w.cluster.jointList.p);
+	w.cluster.jointListsValid = nj != 0u;
+	hipLaunchKernelGGL(k_cl_scatter, clManifoldGrid(numPairs), dim3(CL_ASSIGN_LANES), 0, w.stream, w.dCounters.p, w.cluster.taskKey.p, w.cluster.taskPos.p, w.cluster.taskStart.p, w.cluster.pre.p);
 }
 
 // Everything between "manifolds exist" and "rows can be initialised": order of the bodies, tasks, local colouring, final slot order.
@@ -653,7 +653,7 @@ void launch_cluster_build(World& w, u32 numPairs)
 {
 	if (!numPairs) return;
 	const bool withJoints = cluster_solves_joints(w);
-	const u32 nj = withJoints ? w.clNumJoints : 0u;
+	const u32 nj = withJoints ? w.cluster.numJoints : 0u;
 	if (!clSizeBuffers(w)) return;
 	launch_active_list(w, numPairs); // active manifolds (k_active_list of the colouring: also counts contacts); no warm colours, no global colour masks
 	bool refresh = clRefreshBodyOrder(w);
@@ -661,16 +661,16 @@ void launch_cluster_build(World& w, u32 numPairs)
 	// A world whose curve phases left nothing over in the last step (ragdolls standing apart: every island interior to its task) skips
 	// the component phase's six launches; what the curves do leave over in this step then goes to the rest task, as without the
 	// component phase, and the next step runs the components again (World::countPreviousStep).
-	u32* leftList = !w.compIdle ? w.clLeftList.p : nullptr;
-	if (w.clChunkJointVersion != w.jointVersion || w.clChunkWithJoints != withJoints) refresh = true; // (the stored chunks were cut for other joints)
+	u32* leftList = !w.cluster.compIdle ? w.cluster.leftList.p : nullptr;
+	if (w.cluster.chunkJointVersion != w.jointVersion || w.cluster.chunkWithJoints != withJoints) refresh = true; // (the stored chunks were cut for other joints)
 	// The joints' tasks follow their islands' chunks, which change at a refresh only: in between, the task lists of the joints (task,
 	// position, counts, the scattered list) are kept as the refresh step built them — two launches less per step for a ragdoll world.
-	const bool keepJointLists = !refresh && nj != 0u && w.clJointListsValid;
+	const bool keepJointLists = !refresh && nj != 0u && w.cluster.jointListsValid;
 	clClear(w, nj, keepJointLists);
 	if (refresh)
 	{
 		clAssignByPhase(w, numPairs, nj, withJoints, leftList);
-		w.clChunkJointVersion = w.jointVersion; w.clChunkWithJoints = withJoints;
+		w.cluster.chunkJointVersion = w.jointVersion; w.cluster.chunkWithJoints = withJoints;
 	}
 	else clAssignCached(w, numPairs, nj, withJoints, keepJointLists, leftList);
 	if (leftList) clAssignComponents(w);

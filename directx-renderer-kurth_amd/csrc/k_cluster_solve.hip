@@ -493,7 +493,7 @@ template <bool JOINTS> __global__ void __launch_bounds__(CLS_LANES) k_cl_solve(C
 // ---------------------------------------------------------------------------------------------------------------
 // Host side
 // ---------------------------------------------------------------------------------------------------------------
-bool cluster_solves_joints(const World& w) { return w.clJointsInCluster && w.useClusterJoints; }
+bool cluster_solves_joints(const World& w) { return w.cluster.jointsInCluster && w.cluster.jointsEnabled; }
 
 // All of a workgroup's LDS beyond the kernel's static tables, less a margin, in whole float4s.
 u32 cluster_solve_setup(const World& w)
@@ -511,18 +511,18 @@ u32 cluster_solve_setup(const World& w)
 
 bool cluster_available(World& w)
 {
-	if (w.clusterLdsBytes) return w.clusterLdsBytes != ~0u;
+	if (w.cluster.ldsBytes) return w.cluster.ldsBytes != ~0u;
 	int cus = 0;
 	MI_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, w.device));
 	const u32 dyn = cluster_solve_setup(w);
 	if (!dyn || !cluster_color_setup())
 	{
 		(void)hipGetLastError();
-		w.clusterLdsBytes = ~0u;
+		w.cluster.ldsBytes = ~0u;
 		return false;
 	}
-	w.clusterLdsBytes = dyn; w.clusterBlocks = (u32)std::max(1, cus);
-	if (w.clusterBlocksLimit) w.clusterBlocks = std::min(w.clusterBlocks, w.clusterBlocksLimit); // MI_CLUSTER_BLOCKS (tests: a small launch, so that phases wrap around)
+	w.cluster.ldsBytes = dyn; w.cluster.blocks = (u32)std::max(1, cus);
+	if (w.cluster.blocksLimit) w.cluster.blocks = std::min(w.cluster.blocks, w.cluster.blocksLimit); // MI_CLUSTER_BLOCKS (tests: a small launch, so that phases wrap around)
 	return true;
 }
 
@@ -534,33 +534,33 @@ void launch_cluster_solve(World& w, u32 itBegin, u32 itEnd)
 {
 	if (itBegin >= itEnd) return;
 	size_t words = (size_t)(w.nb + 1) * CL_MAX_PHASES * 4; // one 32-byte hand-over record per (phase, body) at most
-	if (w.flow.cap < words) { w.flow.ensure(words, w.stream); w.flowEpoch = 0; if (w.lastError) return; } // (a failed allocation leaves the old, smaller buffer: nothing may be launched over it)
-	if (w.flowEpoch == 0 || w.flowEpoch >= 0xFFFEu) // first use or the turn counter about to wrap: no stale record may ever match
+	if (w.cluster.flow.cap < words) { w.cluster.flow.ensure(words, w.stream); w.cluster.flowEpoch = 0; if (w.lastError) return; } // (a failed allocation leaves the old, smaller buffer: nothing may be launched over it)
+	if (w.cluster.flowEpoch == 0 || w.cluster.flowEpoch >= 0xFFFEu) // first use or the turn counter about to wrap: no stale record may ever match
 	{
-		MI_CHECK(hipMemsetAsync(w.flow.p, 0, sizeof(u64) * words, w.stream));
-		w.flowEpoch = 0;
+		MI_CHECK(hipMemsetAsync(w.cluster.flow.p, 0, sizeof(u64) * words, w.stream));
+		w.cluster.flowEpoch = 0;
 	}
-	w.flowEpoch++;
-	if (w.flowTestAbortStep == w.stats.numInternalSteps) // tests: pretend a lane timed out; everybody drains without solving
+	w.cluster.flowEpoch++;
+	if (w.cluster.flowTestAbortStep == w.stats.numInternalSteps) // tests: pretend a lane timed out; everybody drains without solving
 	{
 		u32 one = 16u;
 		MI_CHECK(hipMemcpyAsync(w.dCounters.p + CTR_FLOW_STATUS, &one, sizeof(u32), hipMemcpyHostToDevice, w.stream));
 		MI_CHECK(hipStreamSynchronize(w.stream));
 	}
 	const size_t scratchContacts = std::min<size_t>(2 * w.pairCap, 512u * 1024u); // rows that fit neither the registers nor LDS (224 B each)
-	w.clRowScratch.ensure(scratchContacts * CLQ_ROW_FLOAT4S, w.stream);
+	w.cluster.rowScratch.ensure(scratchContacts * CLQ_ROW_FLOAT4S, w.stream);
 	if (w.lastError) return;
 	if (itBegin) MI_CHECK(hipMemsetAsync(w.dCounters.p + CTR_CL_SCRATCH, 0, sizeof(u32), w.stream)); // (the step's first launch finds it cleared by k_cl_clear)
 	ClArgs A;
-	A.rowScratch = w.clRowScratch.p; A.scratchContacts = (u32)scratchContacts;
-	A.counters = w.dCounters.p; A.tasks = (const ClTask*)w.clTasks.p; A.bodyList = w.clBodyList.p; A.phaseMask = w.clPhaseMask.p; A.sharedSlot = w.clSharedSlot.p;
-	A.mKeySorted = w.mKeySorted.p; A.mLocal = w.clLocal.p; A.cEntry = w.clEntry.p;
-	A.rowPlanes = w.rowPlanes.p; A.rowShared = w.rowShared.p; A.rowLambda = w.rowLambda.p; A.vel = w.vel.p; A.flow = w.flow.p; A.trace = w.flowTrace.p; A.predictDiv = CL_PREDICT_DIV; A.pollSleep = CL_POLL_SLEEP;
-	A.rowCap = w.rowCap; A.nb = w.nb; A.flowBytes = (u32)(words * sizeof(u64)); A.epoch = w.flowEpoch << 16; A.itBegin = itBegin; A.itEnd = itEnd;
-	A.ldsFloat4s = w.clusterLdsBytes / 16u;
+	A.rowScratch = w.cluster.rowScratch.p; A.scratchContacts = (u32)scratchContacts;
+	A.counters = w.dCounters.p; A.tasks = (const ClTask*)w.cluster.tasks.p; A.bodyList = w.cluster.bodyList.p; A.phaseMask = w.cluster.phaseMask.p; A.sharedSlot = w.cluster.sharedSlot.p;
+	A.mKeySorted = w.mKeySorted.p; A.mLocal = w.cluster.local.p; A.cEntry = w.cluster.entry.p;
+	A.rowPlanes = w.rowPlanes.p; A.rowShared = w.rowShared.p; A.rowLambda = w.rowLambda.p; A.vel = w.vel.p; A.flow = w.cluster.flow.p; A.trace = w.cluster.flowTrace.p; A.predictDiv = CL_PREDICT_DIV; A.pollSleep = CL_POLL_SLEEP;
+	A.rowCap = w.rowCap; A.nb = w.nb; A.flowBytes = (u32)(words * sizeof(u64)); A.epoch = w.cluster.flowEpoch << 16; A.itBegin = itBegin; A.itEnd = itEnd;
+	A.ldsFloat4s = w.cluster.ldsBytes / 16u;
 	const bool withJoints = cluster_solves_joints(w);
-	A.jointClassStart = withJoints ? w.clJointClassStart.p : nullptr; A.taskJoints = w.clTaskJoints.p; A.jointTable = w.clJointTable.p; A.invIw = w.invIw.p; A.numJointClasses = withJoints ? w.clNumJointClasses : 0u;
+	A.jointClassStart = withJoints ? w.cluster.jointClassStart.p : nullptr; A.taskJoints = w.cluster.taskJoints.p; A.jointTable = w.cluster.jointTable.p; A.invIw = w.invIw.p; A.numJointClasses = withJoints ? w.cluster.numJointClasses : 0u;
 	for (u32 t = 0; t < MI_JOINT_TYPES; ++t) A.jointUpd[t] = w.joints[t].dUpdate.p;
-	if (withJoints) hipLaunchKernelGGL(k_cl_solve<true>, dim3(w.clusterBlocks), dim3(CLS_LANES), w.clusterLdsBytes, w.stream, A);
-	else hipLaunchKernelGGL(k_cl_solve<false>, dim3(w.clusterBlocks), dim3(CLS_LANES), w.clusterLdsBytes, w.stream, A);
+	if (withJoints) hipLaunchKernelGGL(k_cl_solve<true>, dim3(w.cluster.blocks), dim3(CLS_LANES), w.cluster.ldsBytes, w.stream, A);
+	else hipLaunchKernelGGL(k_cl_solve<false>, dim3(w.cluster.blocks), dim3(CLS_LANES), w.cluster.ldsBytes, w.stream, A);
 }

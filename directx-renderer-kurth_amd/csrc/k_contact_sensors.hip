@@ -2,9 +2,9 @@
 // ("Contact sensors"; the rule is stated in include/mi_physics.h).  The step's buffers are only read.  A reading adds its
 // terms in ascending manifold slot, then contact index, whatever order the sweep ran in, so the work is a grouping of the schedule
 // positions by body and an ordered walk:
-//   k_cs_mark        one lane per sensor: its body is wanted (World::csBody[b].x)
+//   k_cs_mark        one lane per sensor: its body is wanted (World::queries.csBody[b].x)
 //   k_cs_count       one pass over the schedule positions: manifolds per wanted body, on either side (integer atomics: a count has no order)
-//   k_cs_alloc       one lane per body: its segment of World::csEntries, taken from one cursor (where a segment lies is of no
+//   k_cs_alloc       one lane per body: its segment of World::queries.csEntries, taken from one cursor (where a segment lies is of no
 //                    consequence: every segment is sorted on its own); bodies with more than CS_SMALL manifolds go on a list
 //   k_cs_fill        the second pass: (slot << 32 | position) into the segments, in whatever order the lanes arrive
 //   k_cs_sort_small  one lane per body: insertion sort of a segment of 2 .. CS_SMALL keys (a body in a pile has 4 to 8)
@@ -211,22 +211,22 @@ void launch_contact_sensors(World& w, u32 numSensors, const mi_contact_sensor* d
 	const u32 nb = w.last.bodies; // the bodies of that step: its rows name the static dummy by this index
 	const size_t bound = withRows ? std::min<size_t>(w.last.numPairs, w.rowCap) : 0;
 	const size_t entryCap = std::max<size_t>(2 * bound, 1);
-	w.csBody.ensure((size_t)nb + 1, w.stream); w.csLarge.ensure((size_t)nb + 1, w.stream); w.csMeta.ensure(4, w.stream); w.csEntries.ensure(entryCap, w.stream);
+	w.queries.csBody.ensure((size_t)nb + 1, w.stream); w.queries.csLarge.ensure((size_t)nb + 1, w.stream); w.queries.csMeta.ensure(4, w.stream); w.queries.csEntries.ensure(entryCap, w.stream);
 	if (w.lastError) return;
 	const uint4* sensors = (const uint4*)dSensors;
-	MI_CHECK(hipMemsetAsync(w.csBody.p, 0, sizeof(uint4) * ((size_t)nb + 1), w.stream));
+	MI_CHECK(hipMemsetAsync(w.queries.csBody.p, 0, sizeof(uint4) * ((size_t)nb + 1), w.stream));
 	if (bound)
 	{
-		MI_CHECK(hipMemsetAsync(w.csMeta.p, 0, sizeof(u32) * 4, w.stream));
+		MI_CHECK(hipMemsetAsync(w.queries.csMeta.p, 0, sizeof(u32) * 4, w.stream));
 		const u32 rowGrid = (u32)std::min<size_t>((bound + 255) / 256, 4096), bodyGrid = (nb + 255) / 256;
-		hipLaunchKernelGGL(k_cs_mark, dim3((numSensors + 255) / 256), dim3(256), 0, w.stream, numSensors, sensors, nb, w.csBody.p);
-		hipLaunchKernelGGL(k_cs_count, dim3(rowGrid), dim3(256), 0, w.stream, w.dCounters.p, (u32)bound, w.rowIds.p, nb, w.csBody.p);
-		hipLaunchKernelGGL(k_cs_alloc, dim3(bodyGrid), dim3(256), 0, w.stream, nb, w.csBody.p, w.csMeta.p, w.csLarge.p);
-		hipLaunchKernelGGL(k_cs_fill, dim3(rowGrid), dim3(256), 0, w.stream, w.dCounters.p, (u32)bound, w.rowIds.p, nb, w.csBody.p, w.csEntries.p, (u32)std::min<size_t>(entryCap, 0xFFFFFFFFu));
-		hipLaunchKernelGGL(k_cs_sort_small, dim3(bodyGrid), dim3(256), 0, w.stream, nb, w.csBody.p, w.csEntries.p);
-		hipLaunchKernelGGL(k_cs_sort_large, dim3(std::min(bodyGrid, 256u)), dim3(256), 0, w.stream, w.csMeta.p, w.csLarge.p, w.csBody.p, w.csEntries.p);
+		hipLaunchKernelGGL(k_cs_mark, dim3((numSensors + 255) / 256), dim3(256), 0, w.stream, numSensors, sensors, nb, w.queries.csBody.p);
+		hipLaunchKernelGGL(k_cs_count, dim3(rowGrid), dim3(256), 0, w.stream, w.dCounters.p, (u32)bound, w.rowIds.p, nb, w.queries.csBody.p);
+		hipLaunchKernelGGL(k_cs_alloc, dim3(bodyGrid), dim3(256), 0, w.stream, nb, w.queries.csBody.p, w.queries.csMeta.p, w.queries.csLarge.p);
+		hipLaunchKernelGGL(k_cs_fill, dim3(rowGrid), dim3(256), 0, w.stream, w.dCounters.p, (u32)bound, w.rowIds.p, nb, w.queries.csBody.p, w.queries.csEntries.p, (u32)std::min<size_t>(entryCap, 0xFFFFFFFFu));
+		hipLaunchKernelGGL(k_cs_sort_small, dim3(bodyGrid), dim3(256), 0, w.stream, nb, w.queries.csBody.p, w.queries.csEntries.p);
+		hipLaunchKernelGGL(k_cs_sort_large, dim3(std::min(bodyGrid, 256u)), dim3(256), 0, w.stream, w.queries.csMeta.p, w.queries.csLarge.p, w.queries.csBody.p, w.queries.csEntries.p);
 	}
 	const u32 groupsPerBlock = 256u / CS_GROUP;
 	hipLaunchKernelGGL(k_cs_read, dim3((numSensors + groupsPerBlock - 1) / groupsPerBlock), dim3(256), 0, w.stream, numSensors, sensors, nb, w.aliveMask.p, w.simMask.p,
-		w.csBody.p, w.csEntries.p, w.rowCap, w.rowIds.p, w.rowShared.p, w.rowPlanes.p, w.rowLambda.p, (float4*)dOut);
+		w.queries.csBody.p, w.queries.csEntries.p, w.rowCap, w.rowIds.p, w.rowShared.p, w.rowPlanes.p, w.rowLambda.p, (float4*)dOut);
 }

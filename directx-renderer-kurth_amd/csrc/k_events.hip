@@ -37,11 +37,11 @@ __global__ void __launch_bounds__(256) k_apply_fields(u32 nb, float4* __restrict
 
 void launch_apply_fields(World& w)
 {
-	if (w.fields.empty() || !w.nb) return;
+	if (w.zones.fields.empty() || !w.nb) return;
 	w.uploadFields();
-	if (!w.fieldWords && !w.anyGlobalForce) return;
-	hipLaunchKernelGGL(k_apply_fields, dim3((w.nb + 255) / 256), dim3(256), 0, w.stream, w.nb, w.force.p, w.fieldMask.p, w.fieldWords, w.fieldForce.p,
-		w.globalForce[0], w.globalForce[1], w.globalForce[2], w.anyGlobalForce ? 1u : 0u, w.simMask.p);
+	if (!w.zones.fieldWords && !w.zones.anyGlobalForce) return;
+	hipLaunchKernelGGL(k_apply_fields, dim3((w.nb + 255) / 256), dim3(256), 0, w.stream, w.nb, w.force.p, w.zones.fieldMask.p, w.zones.fieldWords, w.zones.fieldForce.p,
+		w.zones.globalForce[0], w.zones.globalForce[1], w.zones.globalForce[2], w.zones.anyGlobalForce ? 1u : 0u, w.simMask.p);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -71,13 +71,13 @@ static PairSetView viewOf(DevBuf<u64>* tables, u32 size, u32 cur)
 	PairSetView v; v.cur = tables[cur].p; v.prev = tables[cur ^ 1].p; v.mask = size - 1; v.shift = 64u - (u32)__builtin_ctz(size);
 	return v;
 }
-EventSink sinkOf(World& w) { EventSink s = { (EventRec*)w.eventRing.p, w.dCounters.p, w.eventCap, w.stats.numInternalSteps, w.slabSize > 1 ? w.slabCode.p : nullptr }; return s; }
+EventSink sinkOf(World& w) { EventSink s = { (EventRec*)w.zones.eventRing.p, w.dCounters.p, w.zones.eventCap, w.stats.numInternalSteps, w.slab.size > 1 ? w.slab.code.p : nullptr }; return s; }
 
 void launch_trigger_events(World& w)
 {
-	if (w.triggers.empty() || !w.triggerSetSize) return;
-	hipLaunchKernelGGL(HIP_KERNEL_NAME(k_scan_previous_set<false>), dim3((w.triggerSetSize + 255) / 256), dim3(256), 0, w.stream, viewOf(w.triggerSet, w.triggerSetSize, w.triggerCur), sinkOf(w), w.colWorld.p, w.nb, 1u);
-	w.triggerCur ^= 1u;
+	if (w.zones.triggers.empty() || !w.zones.triggerSetSize) return;
+	hipLaunchKernelGGL(HIP_KERNEL_NAME(k_scan_previous_set<false>), dim3((w.zones.triggerSetSize + 255) / 256), dim3(256), 0, w.stream, viewOf(w.zones.triggerSet, w.zones.triggerSetSize, w.zones.triggerCur), sinkOf(w), w.colWorld.p, w.nb, 1u);
+	w.zones.triggerCur ^= 1u;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -119,12 +119,12 @@ __global__ void __launch_bounds__(256) k_collision_begin(u32* __restrict__ count
 
 void launch_collision_events(World& w, u32 numPairs)
 {
-	if (!(w.collisionBeginEvents || w.collisionEndEvents) || !w.collisionSetSize) return;
-	PairSetView v = viewOf(w.collisionSet, w.collisionSetSize, w.collisionCur);
+	if (!(w.zones.collisionBeginEvents || w.zones.collisionEndEvents) || !w.zones.collisionSetSize) return;
+	PairSetView v = viewOf(w.zones.collisionSet, w.zones.collisionSetSize, w.zones.collisionCur);
 	if (numPairs)
-		hipLaunchKernelGGL(k_collision_begin, dim3((numPairs + 255) / 256), dim3(256), 0, w.stream, w.dCounters.p, (const u64*)w.pairsSorted.p, w.manifolds.p, w.vel.p, w.cog.p, w.nb, v, sinkOf(w), w.collisionBeginEvents ? 1u : 0u);
-	hipLaunchKernelGGL(HIP_KERNEL_NAME(k_scan_previous_set<true>), dim3((w.collisionSetSize + 255) / 256), dim3(256), 0, w.stream, v, sinkOf(w), w.colWorld.p, w.nb, w.collisionEndEvents ? 1u : 0u);
-	w.collisionCur ^= 1u;
+		hipLaunchKernelGGL(k_collision_begin, dim3((numPairs + 255) / 256), dim3(256), 0, w.stream, w.dCounters.p, (const u64*)w.pairsSorted.p, w.manifolds.p, w.vel.p, w.cog.p, w.nb, v, sinkOf(w), w.zones.collisionBeginEvents ? 1u : 0u);
+	hipLaunchKernelGGL(HIP_KERNEL_NAME(k_scan_previous_set<true>), dim3((w.zones.collisionSetSize + 255) / 256), dim3(256), 0, w.stream, v, sinkOf(w), w.colWorld.p, w.nb, w.zones.collisionEndEvents ? 1u : 0u);
+	w.zones.collisionCur ^= 1u;
 }
 
 // ---- force fields / events: host side ------------------------------------------------------------------------------
@@ -135,26 +135,26 @@ static V3 fieldForceWorld(const World::HField& f) // physics.cpp:767-771
 }
 void World::uploadFields()
 {
-	if (!fieldsDirty) return;
-	fieldsDirty = false;
-	std::vector<float4> hf(std::max<size_t>(fields.size(), 1), make_float4(0.f, 0.f, 0.f, 0.f));
-	V3 sum = v3s(0.f); anyGlobalForce = false; bool anyLocal = false;
-	for (size_t i = fields.size(); i-- > 0;) // getForceFieldStates (physics.cpp:759-787): EnTT walks newest first
+	if (!zones.fieldsDirty) return;
+	zones.fieldsDirty = false;
+	std::vector<float4> hf(std::max<size_t>(zones.fields.size(), 1), make_float4(0.f, 0.f, 0.f, 0.f));
+	V3 sum = v3s(0.f); zones.anyGlobalForce = false; bool anyLocal = false;
+	for (size_t i = zones.fields.size(); i-- > 0;) // getForceFieldStates (physics.cpp:759-787): EnTT walks newest first
 	{
-		V3 f = fieldForceWorld(fields[i]);
-		if (fields[i].numColliders) { hf[i] = make_float4(f.x, f.y, f.z, 0.f); anyLocal = true; }
-		else { sum = sum + f; anyGlobalForce = true; }
+		V3 f = fieldForceWorld(zones.fields[i]);
+		if (zones.fields[i].numColliders) { hf[i] = make_float4(f.x, f.y, f.z, 0.f); anyLocal = true; }
+		else { sum = sum + f; zones.anyGlobalForce = true; }
 	}
-	globalForce[0] = sum.x; globalForce[1] = sum.y; globalForce[2] = sum.z;
-	u32 words = anyLocal ? ((u32)fields.size() + 31u) / 32u : 0u;
-	fieldForce.ensure(hf.size(), stream);
-	MI_CHECK(hipMemcpyAsync(fieldForce.p, hf.data(), sizeof(float4) * hf.size(), hipMemcpyHostToDevice, stream));
+	zones.globalForce[0] = sum.x; zones.globalForce[1] = sum.y; zones.globalForce[2] = sum.z;
+	u32 words = anyLocal ? ((u32)zones.fields.size() + 31u) / 32u : 0u;
+	zones.fieldForce.ensure(hf.size(), stream);
+	MI_CHECK(hipMemcpyAsync(zones.fieldForce.p, hf.data(), sizeof(float4) * hf.size(), hipMemcpyHostToDevice, stream));
 	size_t maskWords = std::max<size_t>((size_t)words * ((size_t)nb + 1), 1);
-	if (words != fieldWords || maskWords > fieldMask.cap)
+	if (words != zones.fieldWords || maskWords > zones.fieldMask.cap)
 	{
-		fieldWords = words;
-		fieldMask.ensure(maskWords, stream);
-		MI_CHECK(hipMemsetAsync(fieldMask.p, 0, sizeof(u32) * maskWords, stream)); // bits are set by k_zone_overlap and cleared by k_apply_fields
+		zones.fieldWords = words;
+		zones.fieldMask.ensure(maskWords, stream);
+		MI_CHECK(hipMemsetAsync(zones.fieldMask.p, 0, sizeof(u32) * maskWords, stream)); // bits are set by k_zone_overlap and cleared by k_apply_fields
 	}
 	MI_CHECK(hipStreamSynchronize(stream)); // `hf` goes out of scope
 }
@@ -190,25 +190,25 @@ static void resizePairSet(World& w, DevBuf<u64>* tables, u32& size, u32 cur, u32
 }
 void World::ensureEventBuffers(u32 numPairs)
 {
-	bool collisions = collisionBeginEvents || collisionEndEvents;
-	if (triggers.empty() && !collisions && fields.empty()) return;
-	if (!fields.empty()) uploadFields(); // the narrowphase's overlap kernel needs the per-body field bits
-	if (!eventRing.p)
+	bool collisions = zones.collisionBeginEvents || zones.collisionEndEvents;
+	if (zones.triggers.empty() && !collisions && zones.fields.empty()) return;
+	if (!zones.fields.empty()) uploadFields(); // the narrowphase's overlap kernel needs the per-body field bits
+	if (!zones.eventRing.p)
 	{
-		if (const char* e = getenv("MI_EVENT_CAPACITY")) eventCap = std::max(16, atoi(e));
-		eventRing.ensure((size_t)eventCap * sizeof(mi_event), stream);
+		if (const char* e = getenv("MI_EVENT_CAPACITY")) zones.eventCap = std::max(16, atoi(e));
+		zones.eventRing.ensure((size_t)zones.eventCap * sizeof(mi_event), stream);
 	}
-	if (!triggers.empty())
+	if (!zones.triggers.empty())
 	{
 		u32 want = std::max(4096u, nextPow2(4u * std::max(nb, 1u)));
-		if (hCounters[CTR_EVENT_OVERFLOW] & 2u) want = std::max(want, triggerSetSize * 4u); // a table was full last step
-		want = std::max(want, nextPow2(4u * (u32)restoredTriggerKeys.size()));
-		if (want > triggerSetSize) resizePairSet(*this, triggerSet, triggerSetSize, triggerCur, want, &restoredTriggerKeys);
+		if (hCounters[CTR_EVENT_OVERFLOW] & 2u) want = std::max(want, zones.triggerSetSize * 4u); // a table was full last step
+		want = std::max(want, nextPow2(4u * (u32)zones.restoredTriggerKeys.size()));
+		if (want > zones.triggerSetSize) resizePairSet(*this, zones.triggerSet, zones.triggerSetSize, zones.triggerCur, want, &zones.restoredTriggerKeys);
 	}
 	if (collisions)
 	{
 		u32 want = std::max(4096u, nextPow2(2u * std::max(numPairs, lastNumManifolds * 2u)));
-		want = std::max(want, nextPow2(4u * (u32)restoredCollisionKeys.size()));
-		if (want > collisionSetSize) resizePairSet(*this, collisionSet, collisionSetSize, collisionCur, want, &restoredCollisionKeys);
+		want = std::max(want, nextPow2(4u * (u32)zones.restoredCollisionKeys.size()));
+		if (want > zones.collisionSetSize) resizePairSet(*this, zones.collisionSet, zones.collisionSetSize, zones.collisionCur, want, &zones.restoredCollisionKeys);
 	}
 }

@@ -291,8 +291,8 @@ __global__ void k_heightmap_finish(u32* __restrict__ counters, const u32* __rest
 template <int TYPE>
 static void launchTerrainPass(World& w, bool write, const TerrainParams& P, u32 slotCap)
 {
-	hipLaunchKernelGGL(HIP_KERNEL_NAME(k_heightmap<TYPE>), dim3((w.nc + 63) / 64), dim3(64), 0, w.stream, write, w.nc, w.nb, w.colWorld.p, w.aabbMin.p, w.aabbMax.p, w.simMask.p, P, w.terrainHeights.p, w.terrainValid.p,
-		w.terrainCounts.p, w.terrainOffsets.p, w.dCounters.p, w.manifolds.p, (u64*)w.pairsSorted.p, slotCap);
+	hipLaunchKernelGGL(HIP_KERNEL_NAME(k_heightmap<TYPE>), dim3((w.nc + 63) / 64), dim3(64), 0, w.stream, write, w.nc, w.nb, w.colWorld.p, w.aabbMin.p, w.aabbMax.p, w.simMask.p, P, w.terrain.heights.p, w.terrain.valid.p,
+		w.terrain.counts.p, w.terrain.offsets.p, w.dCounters.p, w.manifolds.p, (u64*)w.pairsSorted.p, slotCap);
 }
 static void launchTerrainPasses(World& w, bool write, const TerrainParams& P, u32 slotCap)
 {
@@ -301,15 +301,15 @@ static void launchTerrainPasses(World& w, bool write, const TerrainParams& P, u3
 
 void launch_heightmap(World& w, u32 numPairs, u32 slotCap)
 {
-	if (!w.terrainChunksPerDim || !w.nc) return;
+	if (!w.terrain.chunksPerDim || !w.nc) return;
 	const TerrainParams P = terrainParams(w);
-	w.terrainCounts.ensure((size_t)w.nc + 1, w.stream); w.terrainOffsets.ensure((size_t)w.nc + 1, w.stream);
-	MI_CHECK(hipMemsetAsync(w.terrainCounts.p, 0, sizeof(u32) * ((size_t)w.nc + 1), w.stream)); // cylinders and hulls: no kernel touches their entry
+	w.terrain.counts.ensure((size_t)w.nc + 1, w.stream); w.terrain.offsets.ensure((size_t)w.nc + 1, w.stream);
+	MI_CHECK(hipMemsetAsync(w.terrain.counts.p, 0, sizeof(u32) * ((size_t)w.nc + 1), w.stream)); // cylinders and hulls: no kernel touches their entry
 	launchTerrainPasses(w, false, P, slotCap);
 	size_t bytes = 0;
-	MI_CHECK(rocprim::exclusive_scan(nullptr, bytes, w.terrainCounts.p, w.terrainOffsets.p, 0u, w.nc, rocprim::plus<u32>(), w.stream));
+	MI_CHECK(rocprim::exclusive_scan(nullptr, bytes, w.terrain.counts.p, w.terrain.offsets.p, 0u, w.nc, rocprim::plus<u32>(), w.stream));
 	w.tempStorage.ensure(bytes, w.stream);
-	MI_CHECK(rocprim::exclusive_scan(w.tempStorage.p, bytes, w.terrainCounts.p, w.terrainOffsets.p, 0u, w.nc, rocprim::plus<u32>(), w.stream));
+	MI_CHECK(rocprim::exclusive_scan(w.tempStorage.p, bytes, w.terrain.counts.p, w.terrain.offsets.p, 0u, w.nc, rocprim::plus<u32>(), w.stream));
 	launchTerrainPasses(w, true, P, slotCap);
-	hipLaunchKernelGGL(k_heightmap_finish, dim3(1), dim3(1), 0, w.stream, w.dCounters.p, w.terrainCounts.p, w.terrainOffsets.p, w.nc, slotCap);
+	hipLaunchKernelGGL(k_heightmap_finish, dim3(1), dim3(1), 0, w.stream, w.dCounters.p, w.terrain.counts.p, w.terrain.offsets.p, w.nc, slotCap);
 }

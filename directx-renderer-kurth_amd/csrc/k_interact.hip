@@ -46,5 +46,5 @@ __global__ void __launch_bounds__(64) k_interaction_batch(u32 numRays, u32 first
 void launch_interaction_batch(World& w, u32 numRays, u32 firstBody, u32 bodiesPerRay, const float* dRays, int32_t* dOutBody)
 {
 	hipLaunchKernelGGL(k_interaction_batch, dim3((numRays + 63) / 64), dim3(64), 0, w.stream, numRays, firstBody, bodiesPerRay, (const float4*)dRays, dOutBody,
-		w.pose.p, w.bprops.p, w.aliveMask.p, w.colLocal.p, w.bodyColStart.p, w.bodyColList.p, rcHulls(w), w.force.p);
+		w.pose.p, w.bprops.p, w.aliveMask.p, w.colLocal.p, w.queries.bodyColStart.p, w.queries.bodyColList.p, rcHulls(w), w.force.p);
 }

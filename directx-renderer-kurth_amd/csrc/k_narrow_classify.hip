@@ -57,7 +57,7 @@ void launch_narrowphase(World& w, u32 numPairs, u32 stepParity, bool deferSide)
 	w.narrowSidePairs = 0; // (a side chain still owed to an earlier launch is void: this launch replaces that one)
 	if (!numPairs)
 	{
-		if (w.terrainChunksPerDim) launch_bucket_offsets(w); // no pairs: all buckets empty, the terrain contacts start at slot 0
+		if (w.terrain.chunksPerDim) launch_bucket_offsets(w); // no pairs: all buckets empty, the terrain contacts start at slot 0
 		return;
 	}
 	hipLaunchKernelGGL(k_classify, dim3((numPairs + 255) / 256), dim3(256), 0, w.stream, w.dCounters.p, w.nb, w.pairs.p, w.colWorld.p, w.aabbMin.p, stepParity, w.pairKey.p, (u64*)w.pairsSorted.p + numPairs, numPairs);

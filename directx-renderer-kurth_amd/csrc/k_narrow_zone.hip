@@ -105,10 +105,10 @@ __global__ void __launch_bounds__(64) k_zone_overlap(u32* __restrict__ counters,
 // part of launch_narrowphase: it enters pairs into the trigger set and raises events, so it must run exactly once per step.
 void launch_zone_overlap(World& w, u32 numPairs)
 {
-	if (!numPairs || (w.fields.empty() && w.triggers.empty())) return;
+	if (!numPairs || (w.zones.fields.empty() && w.zones.triggers.empty())) return;
 	const u64* sortedPairs = (const u64*)w.pairsSorted.p;
-	PairSetView tv = { w.triggers.empty() ? nullptr : w.triggerSet[w.triggerCur].p, w.triggers.empty() ? nullptr : w.triggerSet[w.triggerCur ^ 1].p, w.triggerSetSize - 1, 64u - (u32)__builtin_ctz(w.triggerSetSize ? w.triggerSetSize : 2u) };
+	PairSetView tv = { w.zones.triggers.empty() ? nullptr : w.zones.triggerSet[w.zones.triggerCur].p, w.zones.triggers.empty() ? nullptr : w.zones.triggerSet[w.zones.triggerCur ^ 1].p, w.zones.triggerSetSize - 1, 64u - (u32)__builtin_ctz(w.zones.triggerSetSize ? w.zones.triggerSetSize : 2u) };
 	EventSink sink = sinkOf(w);
 	hipLaunchKernelGGL(k_zone_overlap, dim3((numPairs + 63) / 64), dim3(64), 0, w.stream, w.dCounters.p, sortedPairs, w.colWorld.p, w.hullInfo.p, w.hullVerts.p, w.nb,
-		w.fieldMask.p, w.fieldWords, tv, sink);
+		w.zones.fieldMask.p, w.zones.fieldWords, tv, sink);
 }

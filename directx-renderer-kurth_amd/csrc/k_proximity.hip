@@ -1,12 +1,12 @@
 // mi_proximity: many points, each against every candidate collider of the world: the nearest surface within a radius (signed distance,
 // closest point, outward normal) and the number of colliders within it ("Proximity sensors"; the rule is stated in
 // include/mi_physics.h, its float32 operation order in point_tests.h).  The candidates, their padded boxes and the tree over them are
-// mi_raycast_batch's, rebuilt by launch_raycast_build (k_raycast.hip) in World::rc* at every call; only the walk differs: a range
+// mi_raycast_batch's, rebuilt by launch_raycast_build (k_raycast.hip) in World::queries at every call; only the walk differs: a range
 // search pruned by the distance from the point to a node's box, not a ray walk pruned by slab intervals.
 //   (launch_raycast_build)  leaves, keys, sort, tree, fit; with MI_PROX_BRUTE_FORCE the leaves alone
 //   k_proximity             one lane per query: the world point from the mount's current pose (rcMount), then rcWalk with PxVisitor,
 //                           the box distance and the leaf test of a point; with MI_PROX_BRUTE_FORCE the same leaf test on every
-//                           candidate flag of rcLeafBox.  rcMount, rcWalk, rcFetch and the RcScene argument: raycast_shared.h
+//                           candidate flag of queries.leafBox.  rcMount, rcWalk, rcFetch and the RcScene argument: raycast_shared.h
 // The boxes only say which colliders need not be asked: a distance is decided by pointBodyCollider on the collider's LOCAL record and
 // pose alone, so the tree and brute force agree in every byte.
 #include "world.h"

@@ -1,6 +1,6 @@
 // mi_raycast_batch: many rays, each against every candidate collider of the world, closest hit with its point (DESIGN.md,
 // "Whole-world ray casts").  A structure of its own, rebuilt at every call from the current poses and kept in buffers nothing else
-// uses (World::rc*): the step's AABBs, world colliders, sorted boxes, cell tables and counters belong to a step that may still be in
+// uses (World::queries): the step's AABBs, world colliders, sorted boxes, cell tables and counters belong to a step that may still be in
 // flight and are neither read nor written here.
 //   k_rc_leaves   candidate flag + padded world AABB per collider; count, bounds of the box centres, largest box diagonal
 //   k_rc_keys     30-bit Morton key of every candidate's box centre (non-candidates: bit 30, so they sort behind the candidates)
@@ -229,7 +229,7 @@ __global__ void __launch_bounds__(64) k_raycast(u32 numRays, const float4* __res
 	out[2 * i + 1] = hit ? make_float4(best.point.x, best.point.y, best.point.z, 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
-// The tree over the current candidates in World::rc*, enqueued on the world's stream: what mi_raycast_batch and mi_proximity both walk.
+// The tree over the current candidates in World::queries, enqueued on the world's stream: what mi_raycast_batch and mi_proximity both walk.
 // brute: only the leaves (candidate flags, padded boxes, header words), which is all a brute-force walk reads.
 RcBuild launch_raycast_build(World& w, bool withStatic, bool brute)
 {
@@ -238,22 +238,22 @@ RcBuild launch_raycast_build(World& w, bool withStatic, bool brute)
 	for (const World::HCollider& c : w.colliders) if (c.zoneType == 0u && (c.body == MI_STATIC_BODY ? withStatic : !w.bodies[c.body].removed)) hostCandidates++;
 	if (!hostCandidates || !w.nc) return RC_BUILD_NO_CANDIDATES;
 	const u32 nc = w.nc;
-	w.rcLeafBox.ensure(2 * (size_t)nc, w.stream); w.rcCount.ensure(RC_HEADER + (size_t)nc, w.stream);
-	w.rcKeys.ensure(nc, w.stream); w.rcKeysSorted.ensure(nc, w.stream); w.rcVals.ensure(nc, w.stream); w.rcValsSorted.ensure(nc, w.stream);
-	w.rcNodes.ensure(4 * (size_t)nc, w.stream); w.rcParentInt.ensure(nc, w.stream); w.rcParentLeaf.ensure(nc, w.stream);
+	w.queries.leafBox.ensure(2 * (size_t)nc, w.stream); w.queries.count.ensure(RC_HEADER + (size_t)nc, w.stream);
+	w.queries.keys.ensure(nc, w.stream); w.queries.keysSorted.ensure(nc, w.stream); w.queries.vals.ensure(nc, w.stream); w.queries.valsSorted.ensure(nc, w.stream);
+	w.queries.nodes.ensure(4 * (size_t)nc, w.stream); w.queries.parentInt.ensure(nc, w.stream); w.queries.parentLeaf.ensure(nc, w.stream);
 	if (w.lastError) return RC_BUILD_FAILED;
 	const u32 blocks = (nc + 255u) / 256u;
-	MI_CHECK(hipMemsetAsync(w.rcCount.p, 0, sizeof(u32) * (brute ? (size_t)RC_HEADER : RC_HEADER + (size_t)nc), w.stream));
+	MI_CHECK(hipMemsetAsync(w.queries.count.p, 0, sizeof(u32) * (brute ? (size_t)RC_HEADER : RC_HEADER + (size_t)nc), w.stream));
 	hipLaunchKernelGGL(k_rc_leaves, dim3(std::min(blocks, 256u)), dim3(256), 0, w.stream, nc, w.nb, withStatic ? 1u : 0u, w.colLocal.p, w.pose.p, w.colStaticPose.p,
-		w.aliveMask.p, w.simMask.p, w.hullInfo.p, w.rcLeafBox.p, w.rcCount.p);
+		w.aliveMask.p, w.simMask.p, w.hullInfo.p, w.queries.leafBox.p, w.queries.count.p);
 	if (brute) return RC_BUILD_DONE;
-	hipLaunchKernelGGL(k_rc_keys, dim3(blocks), dim3(256), 0, w.stream, nc, w.rcLeafBox.p, w.rcCount.p, w.rcKeys.p, w.rcVals.p);
-	prim_sort_pairs_u32(w, w.rcKeys.p, w.rcKeysSorted.p, w.rcVals.p, w.rcValsSorted.p, nc, RC_KEY_BITS + 1);
+	hipLaunchKernelGGL(k_rc_keys, dim3(blocks), dim3(256), 0, w.stream, nc, w.queries.leafBox.p, w.queries.count.p, w.queries.keys.p, w.queries.vals.p);
+	prim_sort_pairs_u32(w, w.queries.keys.p, w.queries.keysSorted.p, w.queries.vals.p, w.queries.valsSorted.p, nc, RC_KEY_BITS + 1);
 	if (hostCandidates > 1u)
 	{
 		const u32 treeBlocks = (hostCandidates + 255u) / 256u; // (the device's count is at most the host's)
-		hipLaunchKernelGGL(k_rc_tree, dim3(treeBlocks), dim3(256), 0, w.stream, w.rcCount.p, w.rcKeysSorted.p, w.rcValsSorted.p, (u32*)w.rcNodes.p, w.rcParentInt.p, w.rcParentLeaf.p);
-		hipLaunchKernelGGL(k_rc_fit, dim3(treeBlocks), dim3(256), 0, w.stream, w.rcCount.p, w.rcValsSorted.p, w.rcLeafBox.p, w.rcParentInt.p, w.rcParentLeaf.p, (float*)w.rcNodes.p, w.rcCount.p + RC_HEADER);
+		hipLaunchKernelGGL(k_rc_tree, dim3(treeBlocks), dim3(256), 0, w.stream, w.queries.count.p, w.queries.keysSorted.p, w.queries.valsSorted.p, (u32*)w.queries.nodes.p, w.queries.parentInt.p, w.queries.parentLeaf.p);
+		hipLaunchKernelGGL(k_rc_fit, dim3(treeBlocks), dim3(256), 0, w.stream, w.queries.count.p, w.queries.valsSorted.p, w.queries.leafBox.p, w.queries.parentInt.p, w.queries.parentLeaf.p, (float*)w.queries.nodes.p, w.queries.count.p + RC_HEADER);
 	}
 	return RC_BUILD_DONE;
 }

@@ -1,10 +1,10 @@
 // mi_raycast_sensors: rays given in the frame of a body, a body range per ray that is no candidate, and the hit normal (DESIGN.md,
 // "Body-mounted ray sensors"; the rule is stated in include/mi_physics.h).  Around the one traversal of mi_raycast_batch:
 //   k_rc_sensor_rays      one lane per ray: the world ray from the mount's current pose (rcMount, raycast_shared.h, on World::pose, the
-//                         array the cast reads) into the caller's buffer or World::rcSensorRays, and the exclusion range into
-//                         World::rcSensorExclude
+//                         array the cast reads) into the caller's buffer or World::queries.sensorRays, and the exclusion range into
+//                         World::queries.sensorExclude
 //   (launch_raycast)      the BVH of k_raycast.hip, built once; k_raycast<.., EXCLUDE = true> writes 32-byte records into
-//                         World::rcSensorHits; with MI_RAY_TERRAIN k_rc_terrain runs on them unchanged
+//                         World::queries.sensorHits; with MI_RAY_TERRAIN k_rc_terrain runs on them unchanged
 //   k_rc_sensor_normals   one lane per ray: the winning collider again (rcFetch), its local ray (the expression of rayBodyCollider), the normal
 //                         rule of ray_normals.h, or the terrain triangle from its id; writes the 48-byte records
 // The two passes are kernels of their own and not folded into k_raycast: that kernel sits at 75 VGPRs with its 16 KiB stack, and the
@@ -73,14 +73,14 @@ __global__ void __launch_bounds__(64) k_rc_sensor_normals(u32 numRays, const flo
 
 void launch_raycast_sensors(World& w, u32 numRays, const mi_sensor_ray* dRays, u32 flags, bool terrain, mi_sensor_hit* dOutHits, float* dOutWorldRays)
 {
-	w.rcSensorHits.ensure(2 * (size_t)numRays, w.stream); w.rcSensorExclude.ensure(numRays, w.stream);
-	if (!dOutWorldRays) w.rcSensorRays.ensure(2 * (size_t)numRays, w.stream);
+	w.queries.sensorHits.ensure(2 * (size_t)numRays, w.stream); w.queries.sensorExclude.ensure(numRays, w.stream);
+	if (!dOutWorldRays) w.queries.sensorRays.ensure(2 * (size_t)numRays, w.stream);
 	if (w.lastError) return;
-	float4* worldRays = dOutWorldRays ? (float4*)dOutWorldRays : w.rcSensorRays.p;
-	hipLaunchKernelGGL(k_rc_sensor_rays, dim3((numRays + 255) / 256), dim3(256), 0, w.stream, numRays, (const float4*)dRays, w.nb, w.pose.p, w.aliveMask.p, w.simMask.p, worldRays, w.rcSensorExclude.p);
-	launch_raycast(w, numRays, (const float*)worldRays, flags, (mi_ray_hit*)w.rcSensorHits.p, w.rcSensorExclude.p); // (no candidate collider: the records are zeroed)
-	if (terrain && !w.lastError) launch_raycast_terrain(w, numRays, (const float*)worldRays, flags, (mi_ray_hit*)w.rcSensorHits.p);
+	float4* worldRays = dOutWorldRays ? (float4*)dOutWorldRays : w.queries.sensorRays.p;
+	hipLaunchKernelGGL(k_rc_sensor_rays, dim3((numRays + 255) / 256), dim3(256), 0, w.stream, numRays, (const float4*)dRays, w.nb, w.pose.p, w.aliveMask.p, w.simMask.p, worldRays, w.queries.sensorExclude.p);
+	launch_raycast(w, numRays, (const float*)worldRays, flags, (mi_ray_hit*)w.queries.sensorHits.p, w.queries.sensorExclude.p); // (no candidate collider: the records are zeroed)
+	if (terrain && !w.lastError) launch_raycast_terrain(w, numRays, (const float*)worldRays, flags, (mi_ray_hit*)w.queries.sensorHits.p);
 	if (w.lastError) return;
-	hipLaunchKernelGGL(k_rc_sensor_normals, dim3((numRays + 63) / 64), dim3(64), 0, w.stream, numRays, (const float4*)worldRays, (const float4*)w.rcSensorHits.p, (float4*)dOutHits, rcScene(w),
-		terrainParams(w), w.terrainHeights.p);
+	hipLaunchKernelGGL(k_rc_sensor_normals, dim3((numRays + 63) / 64), dim3(64), 0, w.stream, numRays, (const float4*)worldRays, (const float4*)w.queries.sensorHits.p, (float4*)dOutHits, rcScene(w),
+		terrainParams(w), w.terrain.heights.p);
 }

@@ -2,7 +2,7 @@
 // after k_raycast on the records it wrote (or on zeroed records when no collider is a candidate) and replaces a record where a terrain
 // triangle is hit strictly before the collider.
 //   k_rc_terrain_tiles   uint16 min / max of the heights per 8 x 8-cell tile (16 x 16 tiles per chunk) and per chunk; built when the
-//                        heights changed (World::rcTerrainTableValid), on the world's stream, before the next terrain cast
+//                        heights changed (World::queries.terrainTableValid), on the world's stream, before the next terrain cast
 //   k_rc_terrain<false>  one lane per ray: clip to the terrain's box, walk chunks -> tiles -> cells under the ray front to back
 //   k_rc_terrain<true>   MI_RAY_BRUTE_FORCE: the same cell body (rtCell) over every cell of every valid chunk, no table
 // The triangles are k_heightmap's: (A, B, C) and (C, B, D) of terrainCellVertices.  The hit rule is stated in include/mi_physics.h.
@@ -222,20 +222,20 @@ __global__ void __launch_bounds__(64) k_rc_terrain(u32 numRays, const float4* __
 
 void launch_raycast_terrain(World& w, u32 numRays, const float* dRays, u32 flags, mi_ray_hit* dOutHits)
 {
-	const u32 chunks = w.terrainChunksPerDim * w.terrainChunksPerDim;
+	const u32 chunks = w.terrain.chunksPerDim * w.terrain.chunksPerDim;
 	if (!chunks || !numRays) return;
 	const TerrainParams P = terrainParams(w);
 	if (flags & MI_RAY_BRUTE_FORCE)
 	{
-		hipLaunchKernelGGL(k_rc_terrain<true>, dim3((numRays + 63) / 64), dim3(64), 0, w.stream, numRays, (const float4*)dRays, (float4*)dOutHits, P, w.terrainHeights.p, w.terrainValid.p, (const u32*)nullptr, (const u32*)nullptr);
+		hipLaunchKernelGGL(k_rc_terrain<true>, dim3((numRays + 63) / 64), dim3(64), 0, w.stream, numRays, (const float4*)dRays, (float4*)dOutHits, P, w.terrain.heights.p, w.terrain.valid.p, (const u32*)nullptr, (const u32*)nullptr);
 		return;
 	}
-	if (!w.rcTerrainTableValid)
+	if (!w.queries.terrainTableValid)
 	{
-		w.rcTerrainTiles.ensure((size_t)chunks * RT_TILES * RT_TILES, w.stream); w.rcTerrainChunkRange.ensure(chunks, w.stream);
+		w.queries.terrainTiles.ensure((size_t)chunks * RT_TILES * RT_TILES, w.stream); w.queries.terrainChunkRange.ensure(chunks, w.stream);
 		if (w.lastError) return;
-		hipLaunchKernelGGL(k_rc_terrain_tiles, dim3(chunks), dim3(256), 0, w.stream, w.terrainHeights.p, w.rcTerrainTiles.p, w.rcTerrainChunkRange.p);
-		w.rcTerrainTableValid = true;
+		hipLaunchKernelGGL(k_rc_terrain_tiles, dim3(chunks), dim3(256), 0, w.stream, w.terrain.heights.p, w.queries.terrainTiles.p, w.queries.terrainChunkRange.p);
+		w.queries.terrainTableValid = true;
 	}
-	hipLaunchKernelGGL(k_rc_terrain<false>, dim3((numRays + 63) / 64), dim3(64), 0, w.stream, numRays, (const float4*)dRays, (float4*)dOutHits, P, w.terrainHeights.p, w.terrainValid.p, w.rcTerrainTiles.p, w.rcTerrainChunkRange.p);
+	hipLaunchKernelGGL(k_rc_terrain<false>, dim3((numRays + 63) / 64), dim3(64), 0, w.stream, numRays, (const float4*)dRays, (float4*)dOutHits, P, w.terrain.heights.p, w.terrain.valid.p, w.queries.terrainTiles.p, w.queries.terrainChunkRange.p);
 }

@@ -430,7 +430,7 @@ __global__ void __launch_bounds__(64) k_solve_replay(u32 numBatches, const u32* 
 void launch_solve_replay(World& w, u32 numBatches)
 {
 	if (!numBatches) return;
-	hipLaunchKernelGGL(k_solve_replay, dim3(1), dim3(64), 0, w.stream, numBatches, w.replayEntries.p, w.nb, w.rowCap, w.rowPlanes.p, w.rowShared.p, w.rowLambda.p, w.rowIds.p, w.vel.p);
+	hipLaunchKernelGGL(k_solve_replay, dim3(1), dim3(64), 0, w.stream, numBatches, w.replay.entries.p, w.nb, w.rowCap, w.rowPlanes.p, w.rowShared.p, w.rowLambda.p, w.rowIds.p, w.vel.p);
 }
 
 // One Gauss-Seidel iteration over all contact colours; colour c < firstTail is launched with gridBlocks[c] blocks (0 = skip),

@@ -1,11 +1,11 @@
 // mi_sphere_cast_batch: many swept spheres ("thick rays"), each against every candidate collider of the world: how far the sphere
 // travels before its gap to a collider is down to the tolerance, and where and on what it touches ("Sphere casts"; the rule
 // is stated in include/mi_physics.h, its float32 operation order in sphere_cast.h).  The candidates, their padded boxes and the tree
-// over them are mi_raycast_batch's, rebuilt by launch_raycast_build (k_raycast.hip) in World::rc* at every call.
+// over them are mi_raycast_batch's, rebuilt by launch_raycast_build (k_raycast.hip) in World::queries at every call.
 //   (launch_raycast_build)  leaves, keys, sort, tree, fit; with MI_SPHERE_BRUTE_FORCE the leaves alone
 //   k_sphere_cast           one lane per query: the world cast from the mount's current pose (rcMount), then rcWalk with ScVisitor: the
 //                           ray's slab test (rcBoxTest) on the node's box grown by radius + tolerance + slack, and the march of
-//                           sphere_cast.h at a leaf; with MI_SPHERE_BRUTE_FORCE the same leaf test on every candidate flag of rcLeafBox
+//                           sphere_cast.h at a leaf; with MI_SPHERE_BRUTE_FORCE the same leaf test on every candidate flag of queries.leafBox
 // The boxes only say which colliders need not be asked: a candidate's answer is decided by sphereCastCollider on the collider's LOCAL
 // record, its pose and the query alone.  The best hit so far only ends a march that is strictly beyond it and therefore cannot win,
 // so the tree and brute force agree in every byte.

@@ -3,7 +3,7 @@
 //   RcScene     what a walk over the world's colliders reads, as one kernel argument
 //   rcFetch     collider c of the scene in its current frame, and whether a query's exclusion range hides it
 //   rcMount     a query's mount index: off, world space, or the frame of a body
-//   rcWalk      the walk over the tree k_raycast.hip builds in World::rc* (its layout is declared here too), nearer child first
+//   rcWalk      the walk over the tree k_raycast.hip builds in World::queries (its layout is declared here too), nearer child first
 //   rcBoxTest   the slab test of a ray (RcRay, rcPrepareRay) against a node's box: the ray cast's and the sphere cast's box visitor
 #pragma once
 #include "world.h"
@@ -15,9 +15,9 @@ struct RcHulls
 	MI_DEV u32 numTriangles(u32 g) const { return range[g].y; }
 	MI_DEV V3 vertex(u32 g, u32 f, u32 k) const { uint4 t = tris[range[g].x + f]; return v3f4(verts[k == 0 ? t.x : (k == 1 ? t.y : t.z)]); }
 };
-inline RcHulls rcHulls(const World& w) { return RcHulls{ w.hullVerts.p, w.hullTris.p, w.hullTriRange.p }; } // (hullTris, hullTriRange: World::buildInteractTables)
+inline RcHulls rcHulls(const World& w) { return RcHulls{ w.hullVerts.p, w.queries.hullTris.p, w.queries.hullTriRange.p }; } // (hullTris, hullTriRange: World::buildInteractTables)
 
-// ---- header words of World::rcCount (zeroed before every build; every accumulated word has 0 as its neutral element) ----
+// ---- header words of World::queries.count (zeroed before every build; every accumulated word has 0 as its neutral element) ----
 enum
 {
 	RC_N = 0,        // candidates
@@ -40,8 +40,8 @@ static_assert(RC_KEY_BITS + 32 <= RC_STACK, "rcWalk's stack holds one entry per 
 #define RC_EPS 1.1920929e-7f
 #define RC_NODE_WORDS 16u // one internal node: 64 bytes (k_raycast.hip describes the record)
 
-// The bodies and colliders of the world at their current poses, and the tree over the candidates (hdr, nodes, vals, leafBox = World::rcCount,
-// rcNodes, rcValsSorted, rcLeafBox: valid after launch_raycast_build).  Passed to the kernels by value.
+// The bodies and colliders of the world at their current poses, and the tree over the candidates (hdr, nodes, vals, leafBox = World::queries.count,
+// queries.nodes, queries.valsSorted, queries.leafBox: valid after launch_raycast_build).  Passed to the kernels by value.
 struct RcScene
 {
 	u32 nb, nc;
@@ -50,7 +50,7 @@ struct RcScene
 };
 inline RcScene rcScene(const World& w)
 {
-	return RcScene{ w.nb, w.nc, w.pose.p, w.colStaticPose.p, w.colLocal.p, rcHulls(w), w.rcCount.p, (const float4*)w.rcNodes.p, w.rcValsSorted.p, w.rcLeafBox.p };
+	return RcScene{ w.nb, w.nc, w.pose.p, w.colStaticPose.p, w.colLocal.p, rcHulls(w), w.queries.count.p, (const float4*)w.queries.nodes.p, w.queries.valsSorted.p, w.queries.leafBox.p };
 }
 
 // The shape words of a collider record in the order rayBodyCollider and pointBodyCollider read them.

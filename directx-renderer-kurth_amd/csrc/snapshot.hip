@@ -60,16 +60,16 @@ namespace
 			out.pod(axis);
 		}
 		// force fields, triggers, and the previous step's overlap / collision sets (so that the next step raises the same events)
-		out.vec(w.fields); out.vec(w.triggers);
-		uint32_t flags = (w.collisionBeginEvents ? 1u : 0u) | (w.collisionEndEvents ? 2u : 0u); out.pod(flags);
-		out.vec(previousKeys(w, w.triggerSet, w.triggerSetSize, w.triggerCur)); out.vec(previousKeys(w, w.collisionSet, w.collisionSetSize, w.collisionCur));
+		out.vec(w.zones.fields); out.vec(w.zones.triggers);
+		uint32_t flags = (w.zones.collisionBeginEvents ? 1u : 0u) | (w.zones.collisionEndEvents ? 2u : 0u); out.pod(flags);
+		out.vec(previousKeys(w, w.zones.triggerSet, w.zones.triggerSetSize, w.zones.triggerCur)); out.vec(previousKeys(w, w.zones.collisionSet, w.zones.collisionSetSize, w.zones.collisionCur));
 		// heightmap terrain
-		out.pod(w.terrainChunksPerDim); out.pod(w.terrainChunkSize); out.pod(w.terrainAmplitude); out.put(w.terrainMinCorner, 12); out.put(w.terrainMaterial, 12);
-		out.vec(w.hTerrainHeights); out.vec(w.hTerrainValid);
+		out.pod(w.terrain.chunksPerDim); out.pod(w.terrain.chunkSize); out.pod(w.terrain.amplitude); out.put(w.terrain.minCorner, 12); out.put(w.terrain.material, 12);
+		out.vec(w.terrain.hHeights); out.vec(w.terrain.hValid);
 		// cloths: parameters, particle state, constraints
 		w.downloadCloths();
-		uint64_t ncl = w.cloths.size(); out.pod(ncl); out.put(w.clothIterations, sizeof(w.clothIterations));
-		for (const World::HCloth& c : w.cloths)
+		uint64_t ncl = w.cloth.cloths.size(); out.pod(ncl); out.put(w.cloth.iterations, sizeof(w.cloth.iterations));
+		for (const World::HCloth& c : w.cloth.cloths)
 		{
 			float params[8] = { c.width, c.height, c.totalMass, c.stiffness, c.damping, c.gravityFactor, c.oldTotalMass, c.oldStiffness };
 			out.put(params, sizeof(params)); out.pod(c.gridX); out.pod(c.gridY);
@@ -92,9 +92,9 @@ int mi_snapshot_save(mi_world* world, void* buffer, uint64_t capacity)
 	BlobWriter out; serialize(*W, out);
 	if (W->lastError) return W->lastError;
 	W->refreshCounters();     // the last step is counted now, not at the next step:
-	W->clusterSortDue = true; // the restored world orders its bodies at its first step: so does this one at its next ...
-	W->compIdle = false;      // ... and runs the component phase in it, as a world without a last step does (the step has been counted above)
-	W->clusterCooldown = 0; W->clusterFailStreak = 0; // ... with the cluster sweep on
+	W->cluster.sortDue = true; // the restored world orders its bodies at its first step: so does this one at its next ...
+	W->cluster.compIdle = false;      // ... and runs the component phase in it, as a world without a last step does (the step has been counted above)
+	W->cluster.cooldown = 0; W->cluster.failStreak = 0; // ... with the cluster sweep on
 	if (!buffer || capacity < out.bytes.size()) { W->fail(MI_ERR_CAPACITY, "mi_snapshot_save: buffer too small (ask mi_snapshot_size)"); return MI_ERR_CAPACITY; }
 	memcpy(buffer, out.bytes.data(), out.bytes.size());
 	return MI_OK;
@@ -126,23 +126,23 @@ mi_world* mi_world_restore(const mi_world_desc* desc, const void* buffer, uint64
 		if (in.ok && axis < 3u && w.dCounters.p) { MI_CHECK(hipMemcpyAsync(w.dCounters.p + CTR_SAP_AXIS, &axis, sizeof(u32), hipMemcpyHostToDevice, w.stream)); MI_CHECK(hipStreamSynchronize(w.stream)); } // the restored world's step 0 reads word 0
 	}
 	std::vector<u64> triggerKeys, collisionKeys; uint32_t flags = 0;
-	in.vec(w.fields); in.vec(w.triggers); in.pod(flags); in.vec(triggerKeys); in.vec(collisionKeys);
-	in.pod(w.terrainChunksPerDim); in.pod(w.terrainChunkSize); in.pod(w.terrainAmplitude); in.get(w.terrainMinCorner, 12); in.get(w.terrainMaterial, 12);
-	in.vec(w.hTerrainHeights); in.vec(w.hTerrainValid);
-	w.rcTerrainTableValid = false;
-	if (in.ok && w.terrainChunksPerDim)
+	in.vec(w.zones.fields); in.vec(w.zones.triggers); in.pod(flags); in.vec(triggerKeys); in.vec(collisionKeys);
+	in.pod(w.terrain.chunksPerDim); in.pod(w.terrain.chunkSize); in.pod(w.terrain.amplitude); in.get(w.terrain.minCorner, 12); in.get(w.terrain.material, 12);
+	in.vec(w.terrain.hHeights); in.vec(w.terrain.hValid);
+	w.queries.terrainTableValid = false;
+	if (in.ok && w.terrain.chunksPerDim)
 	{
-		size_t chunks = (size_t)w.terrainChunksPerDim * w.terrainChunksPerDim;
-		if (w.hTerrainValid.size() != chunks || w.hTerrainHeights.size() != chunks * 129 * 129) in.ok = false;
+		size_t chunks = (size_t)w.terrain.chunksPerDim * w.terrain.chunksPerDim;
+		if (w.terrain.hValid.size() != chunks || w.terrain.hHeights.size() != chunks * 129 * 129) in.ok = false;
 		else
 		{
-			w.terrainHeights.ensure(w.hTerrainHeights.size(), w.stream); w.terrainValid.ensure(chunks, w.stream);
-			MI_CHECK(hipMemcpyAsync(w.terrainHeights.p, w.hTerrainHeights.data(), sizeof(uint16_t) * w.hTerrainHeights.size(), hipMemcpyHostToDevice, w.stream));
-			MI_CHECK(hipMemcpyAsync(w.terrainValid.p, w.hTerrainValid.data(), sizeof(u32) * chunks, hipMemcpyHostToDevice, w.stream));
+			w.terrain.heights.ensure(w.terrain.hHeights.size(), w.stream); w.terrain.valid.ensure(chunks, w.stream);
+			MI_CHECK(hipMemcpyAsync(w.terrain.heights.p, w.terrain.hHeights.data(), sizeof(uint16_t) * w.terrain.hHeights.size(), hipMemcpyHostToDevice, w.stream));
+			MI_CHECK(hipMemcpyAsync(w.terrain.valid.p, w.terrain.hValid.data(), sizeof(u32) * chunks, hipMemcpyHostToDevice, w.stream));
 			MI_CHECK(hipStreamSynchronize(w.stream));
 		}
 	}
-	uint64_t ncl = 0; in.pod(ncl); in.get(w.clothIterations, sizeof(w.clothIterations));
+	uint64_t ncl = 0; in.pod(ncl); in.get(w.cloth.iterations, sizeof(w.cloth.iterations));
 	for (uint64_t i = 0; in.ok && i < ncl; ++i)
 	{
 		World::HCloth c; float params[8] = {};
@@ -150,7 +150,7 @@ mi_world* mi_world_restore(const mi_world_desc* desc, const void* buffer, uint64
 		c.width = params[0]; c.height = params[1]; c.totalMass = params[2]; c.stiffness = params[3]; c.damping = params[4]; c.gravityFactor = params[5]; c.oldTotalMass = params[6]; c.oldStiffness = params[7];
 		in.vec(c.pos); in.vec(c.prev); in.vec(c.vel); in.vec(c.invMass); in.vec(c.constraints);
 		if (in.ok && (c.pos.size() != 3 * (size_t)c.gridX * c.gridY || c.vel.size() != c.pos.size() || c.prev.size() != c.pos.size() || c.invMass.size() * 3 != c.pos.size())) in.ok = false;
-		w.cloths.push_back(std::move(c));
+		w.cloth.cloths.push_back(std::move(c));
 	}
 	if (!in.ok) { g_createError = "mi_world_restore: truncated snapshot"; delete world; return nullptr; }
 	{ // every index the kernels will follow must point inside this world
@@ -162,8 +162,8 @@ mi_world* mi_world_restore(const mi_world_desc* desc, const void* buffer, uint64
 			if (c.body != MI_STATIC_BODY && c.body >= numBodies) valid = false;
 			if (c.type > MI_HULL) valid = false;
 			if (c.type == MI_HULL && !(c.shape[7] >= 0.f && (size_t)c.shape[7] < numHulls)) valid = false;
-			if (c.zoneType == 2 && c.zoneIndex >= w.fields.size()) valid = false;
-			if (c.zoneType == 3 && c.zoneIndex >= w.triggers.size()) valid = false;
+			if (c.zoneType == 2 && c.zoneIndex >= w.zones.fields.size()) valid = false;
+			if (c.zoneType == 3 && c.zoneIndex >= w.zones.triggers.size()) valid = false;
 		}
 		for (const World::HHull& h : w.hulls) { if (h.vertices.size() % 3 || h.triangles.size() % 3) valid = false; for (u32 t : h.triangles) if ((size_t)t * 3 + 2 >= h.vertices.size()) valid = false; }
 		for (u32 t = 0; t < MI_JOINT_TYPES; ++t)
@@ -175,10 +175,10 @@ mi_world* mi_world_restore(const mi_world_desc* desc, const void* buffer, uint64
 		}
 		if (!valid) { g_createError = "mi_world_restore: snapshot holds an index outside the world"; delete world; return nullptr; }
 	}
-	w.clothsDirty = true;
-	w.collisionBeginEvents = (flags & 1u) != 0; w.collisionEndEvents = (flags & 2u) != 0;
-	w.topologyDirty = true; w.jointsChanged(); w.fieldsDirty = true;
-	w.restoredTriggerKeys = triggerKeys; w.restoredCollisionKeys = collisionKeys; // entered into the sets when the first step sizes them
+	w.cloth.dirty = true;
+	w.zones.collisionBeginEvents = (flags & 1u) != 0; w.zones.collisionEndEvents = (flags & 2u) != 0;
+	w.topologyDirty = true; w.jointsChanged(); w.zones.fieldsDirty = true;
+	w.zones.restoredTriggerKeys = triggerKeys; w.zones.restoredCollisionKeys = collisionKeys; // entered into the sets when the first step sizes them
 	return world;
 }
 

@@ -77,7 +77,7 @@ static void runSolverSweep(World& w, u32 iters, u32 numColors)
 // for the test), into that batch's lowest free lane; a batch that fills up is emitted at once, the partly filled ones follow bucket
 // by bucket at the end.  Contacts are enumerated the way the reference emits them: manifold by manifold in narrowphase order, a
 // manifold's contacts in order.  ids = the schedule's id quads {body a, body b, contacts, narrowphase slot} by schedule position.
-// Result: replayHost = entries (position | contact << 28, 0xFFFFFFFF = empty lane), MI_REPLAY_WIDTH per batch.
+// Result: replay.host = entries (position | contact << 28, 0xFFFFFFFF = empty lane), MI_REPLAY_WIDTH per batch.
 u32 World::scheduleReferenceBatches(const std::vector<uint4>& ids, u32 numPositions)
 {
 	const u32 W = MI_REPLAY_WIDTH, NONE = 0xFFFFFFFFu, numBuckets = 4, dummy = nb;
@@ -89,8 +89,8 @@ u32 World::scheduleReferenceBatches(const std::vector<uint4>& ids, u32 numPositi
 	std::vector<Batch> open[numBuckets];
 	u32 count[numBuckets] = { 0, 0, 0, 0 };
 	for (u32 q = 0; q < numBuckets; ++q) open[q].push_back(emptyBatch()); // the always-accepting batch behind the last open one
-	replayHost.clear();
-	auto emit = [&](const Batch& e) { for (u32 l = 0; l < W; ++l) replayHost.push_back(e.entry[l]); };
+	replay.host.clear();
+	auto emit = [&](const Batch& e) { for (u32 l = 0; l < W; ++l) replay.host.push_back(e.entry[l]); };
 	u32 index = 0;
 	for (u32 p : bySlot)
 		for (u32 k = 0; k < ids[p].z; ++k, ++index)
@@ -115,7 +115,7 @@ u32 World::scheduleReferenceBatches(const std::vector<uint4>& ids, u32 numPositi
 			else if (lane == W - 1) { Batch full = e; --c; es[j] = es[c]; emit(full); es[c] = emptyBatch(); }
 		}
 	for (u32 q = 0; q < numBuckets; ++q) for (u32 i = 0; i < count[q]; ++i) emit(open[q][i]);
-	return (u32)(replayHost.size() / W);
+	return (u32)(replay.host.size() / W);
 }
 
 // Global colouring + rows + the launch sweep: the whole solver stage of a step on the fallback path.
@@ -144,16 +144,16 @@ static void solveWithLaunchSweep(World& w, u32 numPairs, float dt, u32 iters)
 	else { clearSchedule(w); w.lastNumManifolds = 0; }
 	launch_contact_init(w, numPairs, dt);
 	launch_joint_init(w, dt);
-	if (w.replayReferenceOrder) // the reference's batch order instead of the colour schedule (debug facility: one workgroup sweeps all contacts)
+	if (w.replay.referenceOrder) // the reference's batch order instead of the colour schedule (debug facility: one workgroup sweeps all contacts)
 	{
 		const u32 numPositions = numPairs ? w.hCounters[CTR_NUM_MANIFOLDS] : 0u;
 		std::vector<uint4> ids(numPositions);
 		if (numPositions) { MI_CHECK(hipMemcpyAsync(ids.data(), w.rowIds.p, sizeof(uint4) * numPositions, hipMemcpyDeviceToHost, w.stream)); MI_CHECK(hipStreamSynchronize(w.stream)); }
-		w.replayBatches = w.scheduleReferenceBatches(ids, numPositions);
-		w.replayEntries.ensure(std::max<size_t>(w.replayHost.size(), 1), w.stream);
+		w.replay.batches = w.scheduleReferenceBatches(ids, numPositions);
+		w.replay.entries.ensure(std::max<size_t>(w.replay.host.size(), 1), w.stream);
 		if (w.lastError) return;
-		if (!w.replayHost.empty()) MI_CHECK(hipMemcpyAsync(w.replayEntries.p, w.replayHost.data(), sizeof(u32) * w.replayHost.size(), hipMemcpyHostToDevice, w.stream));
-		for (u32 it = 0; it < iters; ++it) { launch_joint_solve_iteration(w); launch_solve_replay(w, w.replayBatches); } // joints before contacts (constraints.cpp:3748-3772)
+		if (!w.replay.host.empty()) MI_CHECK(hipMemcpyAsync(w.replay.entries.p, w.replay.host.data(), sizeof(u32) * w.replay.host.size(), hipMemcpyHostToDevice, w.stream));
+		for (u32 it = 0; it < iters; ++it) { launch_joint_solve_iteration(w); launch_solve_replay(w, w.replay.batches); } // joints before contacts (constraints.cpp:3748-3772)
 		return;
 	}
 	runSolverSweep(w, iters, numColors);
@@ -184,8 +184,8 @@ void World::recoverFlow()
 			c[CTR_CL_LEFT], c[CTR_CL_LEFT + 1], c[CTR_CL_LEFT + 2], c[CTR_CL_LEFT + 3], c[CTR_CL_LEFT + 4], c[CTR_CL_SCRATCH]);
 	}
 	// (a world that keeps not fitting backs off: 4, 8, ... 256 steps of launch sweep between attempts)
-	if ((why & 64u) && !(why & 1u)) { clusterCooldown = std::min(256u, 4u << std::min(clusterFailStreak, 6u)); ++clusterFailStreak; }
-	else clusterCooldown = 256;
+	if ((why & 64u) && !(why & 1u)) { cluster.cooldown = std::min(256u, 4u << std::min(cluster.failStreak, 6u)); ++cluster.failStreak; }
+	else cluster.cooldown = 256;
 	coloringRounds = 64;
 	MI_CHECK(hipMemsetAsync(dCounters.p + CTR_FLOW_STATUS, 0, sizeof(u32), stream));
 	launch_restore_velocities(*this); // (the simulated bodies': the backup holds nothing of the others)
@@ -215,15 +215,15 @@ int World::resolvePendingFlow()
 
 void World::harvestTiming()
 {
-	if (!ringPending) return;
+	if (!timing.ringPending) return;
 	MI_CHECK(hipStreamSynchronize(stream));
-	for (u32 k = 0; k < ringPending; ++k)
+	for (u32 k = 0; k < timing.ringPending; ++k)
 	{
-		u32 slot = (ringHead + STAGE_RING - ringPending + k) % STAGE_RING;
-		for (int i = 0; i < 5; ++i) { float ms = 0.f; (void)hipEventElapsedTime(&ms, stageEvents[slot * 6 + i], stageEvents[slot * 6 + i + 1]); accMs[i] += ms; }
-		accTimed++;
+		u32 slot = (timing.ringHead + STAGE_RING - timing.ringPending + k) % STAGE_RING;
+		for (int i = 0; i < 5; ++i) { float ms = 0.f; (void)hipEventElapsedTime(&ms, timing.stageEvents[slot * 6 + i], timing.stageEvents[slot * 6 + i + 1]); timing.accMs[i] += ms; }
+		timing.accTimed++;
 	}
-	ringPending = 0;
+	timing.ringPending = 0;
 }
 
 // hCounters holds the colour / manifold / contact counts of the step before the current one whenever the host has just read the
@@ -243,12 +243,12 @@ void World::countPreviousStep()
 		stats.clusterManifolds[p] = hadCluster ? hCounters[CTR_CL_PHASE_COUNT + p] : 0;
 	}
 	stats.clusterSharedBodies = hadCluster ? hCounters[CTR_CL_SHARED] : 0; stats.clusterParts = last.cluster ? CL_CURVE_PARTS : 0;
-	if (hadCluster) clusterFailStreak = 0; // (a give-up never gets here: recoverFlow clears last.cluster)
-	compIdle = hadCluster && hCounters[CTR_CL_LEFT] == 0u && hCounters[CTR_CL_PHASE_COUNT + CL_MAX_PARTS] == 0u;
+	if (hadCluster) cluster.failStreak = 0; // (a give-up never gets here: recoverFlow clears last.cluster)
+	cluster.compIdle = hadCluster && hCounters[CTR_CL_LEFT] == 0u && hCounters[CTR_CL_PHASE_COUNT + CL_MAX_PARTS] == 0u;
 	if (hadCluster && (stats.numInternalSteps % 50u) == 0u && getenv("MI_CLUSTER_DEBUG"))
 		fprintf(stderr, "[mi_physics] step %u: component phase: %u manifolds left by the curve phases, %u tasks, weight %u, %u with ends in different components after the rounds, largest component sent to the rest task %u\n", stats.numInternalSteps,
 			hCounters[CTR_CL_LEFT], hCounters[CTR_CL_LEFT + 1], hCounters[CTR_CL_LEFT + 2], hCounters[CTR_CL_LEFT + 3], hCounters[CTR_CL_LEFT + 4]);
-	sumContacts += stats.numContacts; sumManifolds += stats.numCollisions; sumColors += stats.numColors; sumPairs += last.truePairs; sumProbes += stats.flowProbes; sumSteps++;
+	timing.sumContacts += stats.numContacts; timing.sumManifolds += stats.numCollisions; timing.sumColors += stats.numColors; timing.sumPairs += last.truePairs; timing.sumProbes += stats.flowProbes; timing.sumSteps++;
 }
 
 // Bring hCounters (and the statistics) up to date with the device: needed by whoever looks at the last step's schedule or counts
@@ -268,10 +268,10 @@ void World::refreshCounters()
 // Stage timing: this step's six events of the ring, the first one recorded; nullptr while timing is off.
 static hipEvent_t* beginStageTiming(World& w)
 {
-	if (!w.timeStages) return nullptr;
-	if (w.ringPending == World::STAGE_RING) w.harvestTiming();
-	hipEvent_t* ev = &w.stageEvents[w.ringHead * 6];
-	w.ringHead = (w.ringHead + 1) % World::STAGE_RING; w.ringPending++;
+	if (!w.timing.timeStages) return nullptr;
+	if (w.timing.ringPending == World::STAGE_RING) w.harvestTiming();
+	hipEvent_t* ev = &w.timing.stageEvents[w.timing.ringHead * 6];
+	w.timing.ringHead = (w.timing.ringHead + 1) % World::STAGE_RING; w.timing.ringPending++;
 	MI_CHECK(hipEventRecord(ev[0], w.stream));
 	return ev;
 }
@@ -292,7 +292,7 @@ static bool launchStepStart(World& w, hipEvent_t* ev, u32& guess)
 	MI_CHECK(hipEventRecord(w.countersEvent, w.stream));
 	if (!w.last.truePairs || w.validate) return false;
 	guess = w.last.truePairs + w.last.truePairs / 8u + 4096u;
-	if ((size_t)guess + w.terrainSlotCap() > w.pairCap) return false;
+	if ((size_t)guess + w.terrain.slotCap((u32)w.colliders.size()) > w.pairCap) return false;
 	launch_broadphase_write(w, guess, w.last.slabOverflow);
 	stamp(w, ev, 1);
 	launch_narrowphase(w, guess, w.stats.numInternalSteps & 1u, true); // (its side chain: launchCollisionStages, if this launch stands)
@@ -364,7 +364,7 @@ static bool launchCollisionStages(World& w, hipEvent_t* ev, const StepRecord& cu
 static bool launchForceStages(World& w, const StepRecord& cur)
 {
 	launch_apply_fields(w);                                // :963-967, :1273
-	if (cur.cluster) { w.velBackup.ensure(2 * ((size_t)w.nb + 1), w.stream); if (w.lastError) return false; } // (a failed allocation leaves the old, smaller buffer)
+	if (cur.cluster) { w.cluster.velBackup.ensure(2 * ((size_t)w.nb + 1), w.stream); if (w.lastError) return false; } // (a failed allocation leaves the old, smaller buffer)
 	launch_integrate_forces(w, cur.dt, cur.cluster);       // a cluster step keeps its pre-solve velocities, in case it has to be redone (World::recoverFlow)
 	launch_validate(w, 2, 0);
 	launch_collision_events(w, cur.numPairs);              // :1284 (handleCollisionCallbacks: after the force integration)
@@ -410,13 +410,13 @@ int World::stepInternal(float dt, u32 iters)
 	cur.axis = hCounters[CTR_SAP_AXIS + (stats.numInternalSteps & 1u)]; // (written by the previous step's broadphase: kept for a recovery at the next step)
 	cur.truePairs = hCounters[CTR_NUM_PAIRS];
 	cur.slabOverflow = hCounters[CTR_PAIR_OVERFLOW] != 0u;
-	cur.numPairs = cur.truePairs + terrainSlotCap();
+	cur.numPairs = cur.truePairs + terrain.slotCap((u32)colliders.size());
 	if (early && (cur.truePairs > guess || (cur.slabOverflow && !last.slabOverflow))) { early = false; stats.numNarrowphaseRedone++; }
 	if (!launchCollisionStages(*this, ev, cur, early, guess)) return lastError;
 
-	if (clusterCooldown) --clusterCooldown;
+	if (cluster.cooldown) --cluster.cooldown;
 	// (the launch sweep when the cluster sweep is switched off, recovering, or cannot hold the turn counters)
-	cur.cluster = useCluster && !replayReferenceOrder && !clusterCooldown && cur.numPairs && iters && iters < 4096u && cluster_available(*this);
+	cur.cluster = cluster.enabled && !replay.referenceOrder && !cluster.cooldown && cur.numPairs && iters && iters < 4096u && cluster_available(*this);
 	cur.unsettled = cur.cluster;
 	cur.jointPath = !numSortedJoints() ? MI_JOINT_PATH_NONE : !cur.cluster ? MI_JOINT_PATH_LAUNCH_SWEEP : (cluster_solves_joints(*this) ? MI_JOINT_PATH_CLUSTER : MI_JOINT_PATH_INTERLEAVED);
 	cur.counted = false;
@@ -442,7 +442,7 @@ int World::step(float* timer, const mi_physics_settings* s, float dt)
 	g_currentWorld = this;
 	upload(); uploadJoints();
 	if (lastError) return lastError;
-	clothIterations[0] = s->numClothVelocityIterations; clothIterations[1] = s->numClothPositionIterations; clothIterations[2] = s->numClothDriftIterations;
+	cloth.iterations[0] = s->numClothVelocityIterations; cloth.iterations[1] = s->numClothPositionIterations; cloth.iterations[2] = s->numClothDriftIterations;
 	if (s->fixedFrameRate)
 	{
 		const float fixedDt = 1.f / (float)s->frameRate;

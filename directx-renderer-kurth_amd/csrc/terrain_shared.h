@@ -10,9 +10,9 @@ struct TerrainParams { u32 chunksPerDim; float chunkSize, invChunkSize, chunkSca
 static inline TerrainParams terrainParams(const World& w)
 {
 	TerrainParams P;
-	P.chunksPerDim = w.terrainChunksPerDim; P.chunkSize = w.terrainChunkSize; P.invChunkSize = 1.f / w.terrainChunkSize; P.chunkScale = w.terrainChunkSize / (TERRAIN_VERTS - 1);
-	P.heightScale = w.terrainAmplitude / 65535; P.invAmplitudeScale = 1.f / w.terrainAmplitude;
-	P.minX = w.terrainMinCorner[0]; P.minY = w.terrainMinCorner[1]; P.minZ = w.terrainMinCorner[2]; P.friction = w.terrainMaterial[1]; P.restitution = w.terrainMaterial[0];
+	P.chunksPerDim = w.terrain.chunksPerDim; P.chunkSize = w.terrain.chunkSize; P.invChunkSize = 1.f / w.terrain.chunkSize; P.chunkScale = w.terrain.chunkSize / (TERRAIN_VERTS - 1);
+	P.heightScale = w.terrain.amplitude / 65535; P.invAmplitudeScale = 1.f / w.terrain.amplitude;
+	P.minX = w.terrain.minCorner[0]; P.minY = w.terrain.minCorner[1]; P.minZ = w.terrain.minCorner[2]; P.friction = w.terrain.material[1]; P.restitution = w.terrain.material[0];
 	return P;
 }
 

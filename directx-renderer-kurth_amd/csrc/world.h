@@ -6,6 +6,7 @@
 #include <vector>
 #include <string>
 #include <algorithm>
+#include <type_traits>
 
 // ---- persistent joint PODs: byte-for-byte the reference's structs (constraints.h:73-80,129-135,175-183,229-257,346-380,497-520)
 struct mi_distance_constraint { float localAnchorA[3], localAnchorB[3], globalLength; };
@@ -37,12 +38,19 @@ static const u32 MI_JOINT_POD_SIZE[MI_JOINT_TYPES] = { 28, 24, 40, 104, 120, 72 
 // Per-joint solver scratch ("update" record) in floats, by type; laid out by the kernels in k_joints.hip.
 static const u32 MI_JOINT_UPDATE_FLOATS[MI_JOINT_TYPES] = { 20, 20, 36, 56, 80, 72 };
 
+// A device buffer and its owner: freed when it goes out of scope (after the World's destructor body has drained both streams), so a
+// buffer is a member and nothing else; never copied.
 template <typename T> struct DevBuf
 {
 	T* p = nullptr; size_t cap = 0;
+	DevBuf() = default;
+	DevBuf(const DevBuf&) = delete;
+	DevBuf& operator=(const DevBuf&) = delete;
+	~DevBuf() { if (p) (void)hipFree(p); }
 	void ensure(size_t n, hipStream_t s, bool keep = false);
-	void release();
+	void release() { if (p) { (void)hipFree(p); p = nullptr; cap = 0; } } // (the status is ignored: nothing can be done about it)
 };
+static_assert(!std::is_copy_constructible<DevBuf<u32>>::value && !std::is_copy_assignable<DevBuf<u32>>::value, "DevBuf owns its memory");
 
 struct JointSet
 {
@@ -137,7 +145,7 @@ struct StepRecord
 	bool slabOverflow = false;         // its CTR_PAIR_OVERFLOW
 	u32 axis = 0;                      // its sorting axis (CTR_SAP_AXIS of its parity): its narrowphase is run again with it before a redo
 	float dt = 0.f; u32 iters = 0;     // what a redo of its solve + integration needs
-	bool cluster = false;              // solved by the cluster sweep (its pre-solve velocities are in velBackup)
+	bool cluster = false;              // solved by the cluster sweep (its pre-solve velocities are in cluster.velBackup)
 	bool unsettled = false;            // ... which is not yet known to have completed (CTR_FLOW_STATUS not looked at)
 	u32 jointPath = MI_JOINT_PATH_NONE;// where it solved its joints (mi_debug_read_joint_update)
 	bool counted = true;               // its counts are in the running sums (nothing to count before the first step)
@@ -160,12 +168,6 @@ struct World
 	struct HCollider { float shape[10]; float restitution, friction, density; u32 type, body; float spos[3], srot[4]; u32 zoneType, zoneIndex; }; // zoneType: 0 none, 2 force field, 3 trigger (physics_object_type, physics.h:49-57)
 	struct HField { float force[3]; float pos[3], rot[4]; u32 hasTransform, numColliders; };   // force_field_component (physics.h:182-185) + the entity's transform
 	struct HTrigger { float pos[3], rot[4]; u32 numColliders; };                                 // trigger_component (physics.h:200-203); the callback becomes mi_drain_events
-	std::vector<HField> fields; std::vector<HTrigger> triggers;
-	// heightmap_collider_component (heightmap_collider.h:127-152): chunksPerDim x chunksPerDim chunks of 129 x 129 uint16 heights
-	u32 terrainChunksPerDim = 0, terrainSlotsPerCollider = 8, terrainMinSlots = 8192; float terrainChunkSize = 0.f, terrainAmplitude = 1.f, terrainMinCorner[3] = { 0.f, 0.f, 0.f }, terrainMaterial[3] = { 0.f, 0.f, 0.f };
-	std::vector<uint16_t> hTerrainHeights; std::vector<u32> hTerrainValid;
-	DevBuf<uint16_t> terrainHeights; DevBuf<u32> terrainValid, terrainCounts, terrainOffsets;
-	u32 terrainSlotCap() const { return terrainChunksPerDim ? std::max(terrainMinSlots, terrainSlotsPerCollider * (u32)colliders.size()) : 0u; }
 	hipEvent_t countersEvent = nullptr;   // behind the step's asynchronous read of the counters
 	// cloth_component (cloth.h:5-60): parameters + host mirror of the particle state (authoritative until the first step; refreshed by downloadCloths)
 	struct HClothConstraint { u32 a, b; float restDistance, inverseMassSum; u32 color; };
@@ -175,15 +177,6 @@ struct World
 		std::vector<float> pos, prev, vel, invMass;          // 3 n, 3 n, 3 n, n
 		std::vector<HClothConstraint> constraints;            // sorted by colour (stable)
 	};
-	std::vector<HCloth> cloths;
-	bool clothsDirty = true, clothStateOnDevice = false; // dirty: the host mirror changed, upload before the next launch; onDevice: the device copy is newer than the mirror
-	u32 clothIterations[3] = { 0, 1, 0 };  // physics_settings::numCloth{Velocity,Position,Drift}Iterations of the last mi_step (mi_set_cloth_iterations for mi_step_internal)
-	DevBuf<float> clothPlanes; u32 clothStride = 0; // 10 planes of clothStride floats: position xyz, velocity xyz, previous position xyz, inverse mass
-	DevBuf<uint2> clothAB; DevBuf<float2> clothRestIms; DevBuf<float4> clothTemp; DevBuf<uint8_t> clothDescs; DevBuf<u32> clothList;
-	u32 numSmallCloths = 0, maxSmallClothParticles = 0; // cloths that fit the LDS variant come first in clothList
-	void uploadCloths(); void downloadCloths();
-	bool fieldsDirty = true;              // a force changed: re-upload the per-field world-space forces
-	bool collisionBeginEvents = false, collisionEndEvents = false;
 	std::vector<HBody> bodies;
 	std::vector<HCollider> colliders;
 	struct HHull { std::vector<float> vertices; std::vector<u32> triangles; float aabbMin[3], aabbMax[3]; }; // bounding_hull_geometry (bounding_volumes.h:208-218)
@@ -195,7 +188,7 @@ struct World
 	bool jointsDirty = true;
 	bool stateOnDevice = false;  // device holds the authoritative pose/velocity
 
-	// ---- device buffers ----
+	// ---- device buffers of the step's own pipeline: what every file shares ----
 	u32 nb = 0, nc = 0;
 	DevBuf<float4> pose, pose0, poseLerp, vel, bprops, force, cog, invIw;
 	DevBuf<ColliderRec> colLocal, colWorld;
@@ -203,11 +196,9 @@ struct World
 	DevBuf<float4> hullVerts, hullInfo;   // all hull vertices (xyz); per geometry {aabbMin.xyz, firstVertex}, {aabbMax.xyz, vertexCount}
 	DevBuf<uint8_t> aliveMask;            // per body: 0 = deleted (mi_delete_body); ANDed into every simulate mask handed in
 	DevBuf<uint8_t> simMask;              // per body: 1 = simulated here (owned or ghost), 0 = lives on another GPU's slab
-	// spatial slab (mi_slab_*): ownership code per body, stamp of the last refresh of a ghost, this rank's interval
-	DevBuf<uint8_t> slabCode; DevBuf<u32> slabFresh; u32 slabRank = 0, slabSize = 0, slabAxis = 0, slabStamp = 0; float slabLo = 0.f, slabHi = 0.f, slabMargin = 0.f;
 	// broadphase
 	DevBuf<u32> cellCount, cellBase;      // colliders per cell bucket (+ 'large', 'simulated elsewhere'), first / end position of every bucket in the sorted order
-	DevBuf<u32> hashKey, sortIdx, cellStart /* {first, end} per bucket */, largeFlag, largeScan, largeList, pairCount, pairOffset;
+	DevBuf<u32> hashKey, sortIdx, cellStart /* {first, end} per bucket */, pairCount, pairOffset;
 	DevBuf<float4> sBox; // sorted colliders: {min.xyz, collider index} {max.xyz, cell tag} per position
 	// active lists (k_bodies.hip): the simulated bodies, their colliders + the static ones, ascending; rebuilt when the simulate mask may have changed
 	DevBuf<u32> actBodies, actCols, actBlockCount, actBlockBase, colBody; bool activeDirty = true; u32 estActiveBodies = 0, estActiveCols = 0, pairBound = 0, sapBlocks = 0;
@@ -222,44 +213,7 @@ struct World
 	DevBuf<uint4> actIds;                 // active manifolds: (bodyA, bodyB, count, slot)
 	DevBuf<u32> epaList; DevBuf<float4> gjkSimplex; // GJK hits -> EPA work list (9 float4 per hit)
 	DevBuf<float4> rowPlanes, rowShared; DevBuf<float2> rowLambda; DevBuf<uint4> rowIds;
-	DevBuf<u64> flow;                     // cluster sweep: 32-byte hand-over record per (phase, shared body): two tagged 16-byte halves
-	// cluster sweep (cluster.h, k_cluster_*.hip)
 	bool validate = false;                // MI_PHYSICS_VALIDATE=1 / mi_enable_validation: NaN / Inf guard after every stage (the reference's VALIDATE macros, physics.cpp:807-926)
-	// replay of the reference's batch order (mi_debug_set_replay / MI_PHYSICS_REPLAY=1; a test facility: the whole contact sweep is ONE workgroup)
-	bool replayReferenceOrder = false; DevBuf<u32> replayEntries; std::vector<u32> replayHost; u32 replayBatches = 0;
-	u32 scheduleReferenceBatches(const std::vector<uint4>& ids, u32 numPositions);
-	bool useCluster = true;               // MI_PHYSICS_NO_CLUSTER=1: launch-per-colour sweep only
-	u32 clusterBlocksLimit = 0, clusterFailStreak = 0, clusterTaskWeight = 64u * 1000u, clusterTaskWeightLater = 64u * 500u; // MI_CLUSTER_BLOCKS / _TASK / _TASK_LATER
-	bool clusterSortDue = true; u32 clusterSortAge = 0, clusterSortBodies = 0; // body order along the curves: refreshed every few steps
-	u32 clusterLdsBytes = 0, clusterBlocks = 0, clusterCooldown = 0;
-	DevBuf<u32> clKeys, clKeysSorted, clVals, clSorted, clRank, clWsum, clCum, clPhaseMask, clTaskKey, clTaskPos, clPre, clLocal, clEntry, clTaskCount, clTaskStart, clBodyList, clSharedSlot; // clEntry: the contact schedule of every task (at 4 x its first manifold position): manifold position | contact << 12
-	DevBuf<uint8_t> clTasks;
-	DevBuf<float4> clRowScratch;
-	DevBuf<u32> clJointBodyMask; bool clJointListsValid = false; // per body: 1 if a joint of the sweep touches it (phase-0 bit of its phase mask); the joints' task lists of the last refresh are still good
-	DevBuf<u32> clCompLabel, clLeftList;  // the component phase
-	bool compIdle = false;                    // the last step's curve phases left nothing over (and its rest task was empty): this step skips the component phase's launches (what is left over goes to the rest task)
-	DevBuf<u32> clChunk; u32 clChunkJointVersion = ~0u; bool clChunkWithJoints = false; // chunk of every body per curve phase, kept between re-sorts (~0u: none cut yet)
-	// joints inside the cluster sweep: island representative per body (jointed bodies must share a task), the joints of all types in
-	// (type, colour) order {type | class << 8, index in the type's colour-sorted arrays, body a, body b}, and the per-step lists
-	DevBuf<u32> clRep, clJointTask, clJointPos, clJointCount, clJointStart, clJointList; DevBuf<uint4> clJointTable; DevBuf<uint2> clTaskJoints; DevBuf<u32> clJointClassStart;
-	bool useClusterJoints = true;         // MI_CLUSTER_NO_JOINTS=1: joints keep their per-colour launches (one cluster launch per iteration then)
-	u32 clNumJoints = 0, clNumJointClasses = 0; bool clJointsInCluster = false; // false: more (type, colour) classes than the kernel's table: joints keep their launches
-	DevBuf<u64> flowTrace;                // developer timeline (mi_debug_flow_trace): CL_TRACE_WORDS x u64 per slot (a row; CL_TRACE_ROWS of them per task / workgroup), allocated on request only
-	u32 flowEpoch = 0;
-	// Safety net of the persistent kernels: if one gives up waiting (only possible when the GPU is shared with another persistent
-	// kernel), the step's velocity integration is skipped on the device and the host redoes solve + integration with the launch
-	// sweep from the saved pre-solve velocities, at the next point where it synchronises anyway.
-	DevBuf<float4> velBackup; u32 flowTestAbortStep = ~0u;
-	void recoverFlow(); int resolvePendingFlow();
-	// force fields, triggers, events
-	DevBuf<float4> fieldForce;            // per field: world-space force (localized fields only; global ones are summed on the host into globalForce)
-	DevBuf<u32> fieldMask; u32 fieldWords = 0; // per body: bit f set = inside localized field f this step (set by k_zone_overlap, consumed + cleared by k_apply_fields)
-	float globalForce[3] = { 0.f, 0.f, 0.f }; bool anyGlobalForce = false;
-	DevBuf<u64> triggerSet[2], collisionSet[2]; u32 triggerSetSize = 0, collisionSetSize = 0, triggerCur = 0, collisionCur = 0;
-	DevBuf<uint8_t> eventRing; u32 eventCap = 1u << 16;
-	std::vector<u64> restoredTriggerKeys, restoredCollisionKeys; // mi_world_restore: the snapshot's previous-step sets, entered when the first step sizes the tables
-	std::vector<mi_event> pendingEvents;  // drained from the device, not yet handed to the caller
-	void uploadFields(); void ensureEventBuffers(u32 numPairs);
 	DevBuf<uint8_t> tempStorage;
 	DevBuf<u32> sortHist;                 // counting sort: per-tile bucket histograms + their scan
 	DevBuf<u32> dCounters; u32* hCounters = nullptr; // CTR_WORDS words each
@@ -273,15 +227,6 @@ struct World
 	u32 lastNumManifolds = 0;    // sizes the colouring-round launches of the next step
 	mi_stats stats = {};
 	StepRecord last;
-	// Stage timing: HIP events of the last STAGE_RING timed steps, read back without stalling every step (mi_get_stats harvests them)
-	static const u32 STAGE_RING = 32;
-	std::vector<hipEvent_t> stageEvents;  // STAGE_RING x 6
-	u32 ringHead = 0, ringPending = 0, accTimed = 0; double accMs[5] = { 0, 0, 0, 0, 0 };
-	bool timeStages = false;
-	void harvestTiming();
-	// Counts of the steps since the last mi_get_stats (the host learns a step's counts at its next synchronisation)
-	double sumContacts = 0, sumManifolds = 0, sumColors = 0, sumPairs = 0, sumProbes = 0; u32 sumSteps = 0;
-	void countPreviousStep(); void refreshCounters();
 	u32 jointVersion = 0;                 // bumped by every upload of the joints
 	// Device-written joint PODs (mi_joint_device_pods): once a caller has the device array, JointSet::dPods is authoritative and
 	// every host entry point that reads or changes JointSet::pods pulls it back first (pullJointPods).  jointGeneration changes
@@ -290,27 +235,137 @@ struct World
 	u32 jointGeneration = 0;
 	void pullJointPods();
 	void jointsChanged();                 // jointsDirty + a new jointGeneration
-	// mi_test_physics_interaction_batch: colliders of every body (CSR), hull triangles as global vertex indices; rebuilt after upload()
-	DevBuf<u32> bodyColStart, bodyColList; DevBuf<uint4> hullTris; DevBuf<uint2> hullTriRange; bool interactTablesValid = false;
+
+	// ---- state by owner: one struct per subsystem, each naming the files that touch it ----
+
+	// Heightmap terrain: api_scene.hip (mi_set_heightmap, mi_heightmap_*), k_heightmap.hip, terrain_shared.h, k_raycast_terrain.hip, step.hip, snapshot.hip
+	struct Terrain
+	{
+		// heightmap_collider_component (heightmap_collider.h:127-152): chunksPerDim x chunksPerDim chunks of 129 x 129 uint16 heights
+		u32 chunksPerDim = 0, slotsPerCollider = 8, minSlots = 8192; float chunkSize = 0.f, amplitude = 1.f, minCorner[3] = { 0.f, 0.f, 0.f }, material[3] = { 0.f, 0.f, 0.f };
+		std::vector<uint16_t> hHeights; std::vector<u32> hValid;
+		DevBuf<uint16_t> heights; DevBuf<u32> valid, counts, offsets;
+		u32 slotCap(u32 numColliders) const { return chunksPerDim ? std::max(minSlots, slotsPerCollider * numColliders) : 0u; }
+	} terrain;
+
+	// Cloth: k_cloth.hip (kernels, uploadCloths, downloadCloths), api_scene.hip (mi_add_cloth, mi_cloth_*), step.hip, snapshot.hip
+	struct Cloth
+	{
+		std::vector<HCloth> cloths;
+		bool dirty = true, stateOnDevice = false; // dirty: the host mirror changed, upload before the next launch; onDevice: the device copy is newer than the mirror
+		u32 iterations[3] = { 0, 1, 0 };  // physics_settings::numCloth{Velocity,Position,Drift}Iterations of the last mi_step (mi_set_cloth_iterations for mi_step_internal)
+		DevBuf<float> planes; u32 stride = 0; // 10 planes of stride floats: position xyz, velocity xyz, previous position xyz, inverse mass
+		DevBuf<uint2> ab; DevBuf<float2> restIms; DevBuf<float4> temp; DevBuf<uint8_t> descs; DevBuf<u32> list;
+		u32 numSmall = 0, maxSmallParticles = 0; // cloths that fit the LDS variant come first in list
+	} cloth;
+	void uploadCloths(); void downloadCloths();
+
+	// Spatial slab (mi_slab_*): api.hip, k_bodies.hip.  Ownership code per body, stamp of the last refresh of a ghost, this rank's interval
+	struct Slab
+	{
+		DevBuf<uint8_t> code; DevBuf<u32> fresh; u32 rank = 0, size = 0, axis = 0, stamp = 0; float lo = 0.f, hi = 0.f, margin = 0.f;
+	} slab;
+
+	// Cluster sweep (cluster.h): k_cluster_partition.hip, k_cluster_color.hip, k_cluster_solve.hip; step.hip decides and recovers, world.hip
+	// (uploadJoints) feeds the joint tables, snapshot.hip and api.hip reset and inspect
+	struct Cluster
+	{
+		bool enabled = true;                  // MI_PHYSICS_NO_CLUSTER=1: launch-per-colour sweep only
+		bool jointsEnabled = true;            // MI_CLUSTER_NO_JOINTS=1: joints keep their per-colour launches (one cluster launch per iteration then)
+		u32 blocksLimit = 0, failStreak = 0, taskWeight = 64u * 1000u, taskWeightLater = 64u * 500u; // MI_CLUSTER_BLOCKS / _TASK / _TASK_LATER
+		u32 ldsBytes = 0, blocks = 0, cooldown = 0;
+		bool compIdle = false;                    // the last step's curve phases left nothing over (and its rest task was empty): this step skips the component phase's launches (what is left over goes to the rest task)
+
+		// -- the partition's private scratch: k_cluster_partition.hip alone (the joint inputs are written by World::uploadJoints) --
+		bool sortDue = true; u32 sortAge = 0, sortBodies = 0; // body order along the curves: refreshed every few steps
+		DevBuf<u32> keys, keysSorted, vals, sorted, rank, wsum, cum, taskKey, taskPos, taskCount;
+		DevBuf<u32> jointBodyMask; bool jointListsValid = false; // per body: 1 if a joint of the sweep touches it (phase-0 bit of its phase mask); the joints' task lists of the last refresh are still good
+		DevBuf<u32> compLabel, leftList;      // the component phase
+		DevBuf<u32> chunk; u32 chunkJointVersion = ~0u; bool chunkWithJoints = false; // chunk of every body per curve phase, kept between re-sorts (~0u: none cut yet)
+		DevBuf<u32> rep, jointTask, jointPos, jointCount; u32 numJoints = 0; // rep: island representative per body (jointed bodies must share a task)
+
+		// -- what the partition leaves for k_cluster_color.hip and k_cluster_solve.hip --
+		DevBuf<u32> phaseMask, pre, local, entry, taskStart, bodyList, sharedSlot; // entry: the contact schedule of every task (at 4 x its first manifold position): manifold position | contact << 12
+		DevBuf<uint8_t> tasks;
+		DevBuf<float4> rowScratch;
+		// joints inside the cluster sweep: the joints of all types in (type, colour) order {type | class << 8, index in the type's
+		// colour-sorted arrays, body a, body b}, and the per-step lists
+		DevBuf<u32> jointStart, jointList; DevBuf<uint4> jointTable; DevBuf<uint2> taskJoints; DevBuf<u32> jointClassStart;
+		u32 numJointClasses = 0; bool jointsInCluster = false; // false: more (type, colour) classes than the kernel's table: joints keep their launches
+		DevBuf<u64> flow;                     // 32-byte hand-over record per (phase, shared body): two tagged 16-byte halves
+		DevBuf<u64> flowTrace;                // developer timeline (mi_debug_flow_trace): CL_TRACE_WORDS x u64 per slot (a row; CL_TRACE_ROWS of them per task / workgroup), allocated on request only
+		u32 flowEpoch = 0;
+		// Safety net of the persistent kernels: if one gives up waiting (only possible when the GPU is shared with another persistent
+		// kernel), the step's velocity integration is skipped on the device and the host redoes solve + integration with the launch
+		// sweep from the saved pre-solve velocities, at the next point where it synchronises anyway.
+		DevBuf<float4> velBackup; u32 flowTestAbortStep = ~0u;
+	} cluster;
+	void recoverFlow(); int resolvePendingFlow();
+
+	// Force fields, triggers, events: k_events.hip (kernels, uploadFields, ensureEventBuffers), events.h, k_narrow_zone.hip, api_scene.hip, step.hip, snapshot.hip
+	struct Zones
+	{
+		std::vector<HField> fields; std::vector<HTrigger> triggers;
+		bool fieldsDirty = true;              // a force changed: re-upload the per-field world-space forces
+		bool collisionBeginEvents = false, collisionEndEvents = false;
+		DevBuf<float4> fieldForce;            // per field: world-space force (localized fields only; global ones are summed on the host into globalForce)
+		DevBuf<u32> fieldMask; u32 fieldWords = 0; // per body: bit f set = inside localized field f this step (set by k_zone_overlap, consumed + cleared by k_apply_fields)
+		float globalForce[3] = { 0.f, 0.f, 0.f }; bool anyGlobalForce = false;
+		DevBuf<u64> triggerSet[2], collisionSet[2]; u32 triggerSetSize = 0, collisionSetSize = 0, triggerCur = 0, collisionCur = 0;
+		DevBuf<uint8_t> eventRing; u32 eventCap = 1u << 16;
+		std::vector<u64> restoredTriggerKeys, restoredCollisionKeys; // mi_world_restore: the snapshot's previous-step sets, entered when the first step sizes the tables
+		std::vector<mi_event> pendingEvents;  // drained from the device, not yet handed to the caller
+	} zones;
+	void uploadFields(); void ensureEventBuffers(u32 numPairs);
+
+	// World queries, rebuilt at every call: api.hip (entries, staging, buildInteractTables), k_interact.hip, k_raycast.hip, raycast_shared.h,
+	// k_raycast_terrain.hip, k_raycast_sensors.hip, k_proximity.hip, k_spherecast.hip, k_contact_sensors.hip
+	struct Queries
+	{
+		// mi_test_physics_interaction_batch: colliders of every body (CSR), hull triangles as global vertex indices; rebuilt after upload()
+		DevBuf<u32> bodyColStart, bodyColList; DevBuf<uint4> hullTris; DevBuf<uint2> hullTriRange; bool interactTablesValid = false;
+		// mi_raycast_batch (k_raycast.hip): rebuilt at every call, read and written by nothing else.  Per collider: candidate flag + padded
+		// world AABB; header words + arrival counter per internal node; Morton keys and collider indices, before and after the sort; the
+		// internal nodes (64 bytes each: both children's boxes and ids); the parent of every internal node and of every sorted leaf
+		DevBuf<float4> leafBox, nodes; DevBuf<u32> count, keys, keysSorted, vals, valsSorted, parentInt, parentLeaf;
+		// MI_RAY_TERRAIN (k_raycast_terrain.hip): (max << 16) | min of the uint16 heights per 8 x 8-cell tile (256 per chunk) and per chunk.  Depends on the
+		// heights alone (not on mi_heightmap_update's corner and amplitude): invalid after mi_set_heightmap, mi_heightmap_set_chunk and a restore
+		DevBuf<u32> terrainTiles, terrainChunkRange; bool terrainTableValid = false;
+		// mi_raycast_sensors (k_raycast_sensors.hip): per ray the world ray (2 x float4, used when the caller wants none back), the 32-byte
+		// record k_raycast and k_rc_terrain work on (2 x float4) and the exclusion range {first, count}
+		DevBuf<float4> sensorRays, sensorHits; DevBuf<uint2> sensorExclude;
+		// (mi_proximity, k_proximity.hip, and mi_sphere_cast_batch, k_spherecast.hip, walk the tree above and keep nothing of their own)
+		// mi_contact_sensors (k_contact_sensors.hip): rebuilt at every call.  Per body of the last step {wanted by a sensor, its manifolds, its
+		// first entry, fill cursor}; the entries (manifold slot << 32 | schedule position), a segment per wanted body, two per position at most;
+		// the bodies whose segment one lane does not sort; {entries handed out, length of that list}
+		DevBuf<uint4> csBody; DevBuf<u64> csEntries; DevBuf<u32> csLarge, csMeta;
+		// Staging of the queries' _host entries (api.hip, queryStaged), in bytes: the records in, the records out, the optional second output
+		// (world rays, world points).  One set for all of them: every _host entry drains the world's stream before it returns
+		DevBuf<uint8_t> hostIn, hostOut, hostAux;
+	} queries;
 	void buildInteractTables();
-	// mi_raycast_batch (k_raycast.hip): rebuilt at every call, read and written by nothing else.  Per collider: candidate flag + padded
-	// world AABB; header words + arrival counter per internal node; Morton keys and collider indices, before and after the sort; the
-	// internal nodes (64 bytes each: both children's boxes and ids); the parent of every internal node and of every sorted leaf
-	DevBuf<float4> rcLeafBox, rcNodes; DevBuf<u32> rcCount, rcKeys, rcKeysSorted, rcVals, rcValsSorted, rcParentInt, rcParentLeaf;
-	// MI_RAY_TERRAIN (k_raycast_terrain.hip): (max << 16) | min of the uint16 heights per 8 x 8-cell tile (256 per chunk) and per chunk.  Depends on the
-	// heights alone (not on mi_heightmap_update's corner and amplitude): invalid after mi_set_heightmap, mi_heightmap_set_chunk and a restore
-	DevBuf<u32> rcTerrainTiles, rcTerrainChunkRange; bool rcTerrainTableValid = false;
-	// mi_raycast_sensors (k_raycast_sensors.hip): per ray the world ray (2 x float4, used when the caller wants none back), the 32-byte
-	// record k_raycast and k_rc_terrain work on (2 x float4) and the exclusion range {first, count}
-	DevBuf<float4> rcSensorRays, rcSensorHits; DevBuf<uint2> rcSensorExclude;
-	// (mi_proximity, k_proximity.hip, and mi_sphere_cast_batch, k_spherecast.hip, walk the tree above and keep nothing of their own)
-	// mi_contact_sensors (k_contact_sensors.hip): rebuilt at every call.  Per body of the last step {wanted by a sensor, its manifolds, its
-	// first entry, fill cursor}; the entries (manifold slot << 32 | schedule position), a segment per wanted body, two per position at most;
-	// the bodies whose segment one lane does not sort; {entries handed out, length of that list}
-	DevBuf<uint4> csBody; DevBuf<u64> csEntries; DevBuf<u32> csLarge, csMeta;
-	// Staging of the queries' _host entries (api.hip, queryStaged), in bytes: the records in, the records out, the optional second output
-	// (world rays, world points).  One set for all of them: every _host entry drains the world's stream before it returns
-	DevBuf<uint8_t> queryHostIn, queryHostOut, queryHostAux;
+
+	// Stage timing and running sums: step.hip (harvestTiming, countPreviousStep), api.hip (mi_get_stats, mi_enable_stage_timing), world.hip
+	static const u32 STAGE_RING = 32;
+	struct Timing
+	{
+		// HIP events of the last STAGE_RING timed steps, read back without stalling every step (mi_get_stats harvests them)
+		std::vector<hipEvent_t> stageEvents;  // STAGE_RING x 6
+		u32 ringHead = 0, ringPending = 0, accTimed = 0; double accMs[5] = { 0, 0, 0, 0, 0 };
+		bool timeStages = false;
+		// Counts of the steps since the last mi_get_stats (the host learns a step's counts at its next synchronisation)
+		double sumContacts = 0, sumManifolds = 0, sumColors = 0, sumPairs = 0, sumProbes = 0; u32 sumSteps = 0;
+	} timing;
+	void harvestTiming();
+	void countPreviousStep(); void refreshCounters();
+
+	// Replay of the reference's batch order (mi_debug_set_replay / MI_PHYSICS_REPLAY=1; a test facility: the whole contact sweep is ONE
+	// workgroup): step.hip (scheduleReferenceBatches), k_solver.hip, api.hip
+	struct Replay
+	{
+		bool referenceOrder = false; DevBuf<u32> entries; std::vector<u32> host; u32 batches = 0;
+	} replay;
+	u32 scheduleReferenceBatches(const std::vector<uint4>& ids, u32 numPositions);
 
 	World(int dev);
 	~World();
@@ -329,7 +384,7 @@ void ensurePairBuffers(World& w, size_t numPairs);         // every buffer sized
 
 // ---- launchers (one per stage; each defined next to its kernels) --------------------------------------------------
 void launch_active_lists(World& w);                        // (re)builds the lists of simulated bodies / colliders if the simulate mask may have changed
-void launch_restore_velocities(World& w);                  // velocities of the simulated bodies <- velBackup
+void launch_restore_velocities(World& w);                  // velocities of the simulated bodies <- cluster.velBackup
 u32 active_grid(u32 estimate, u32 total);
 void launch_build_colliders(World& w);
 void launch_broadphase_count(World& w);                    // grid build + pair count + scan; leaves numPairs in dCounters
@@ -337,7 +392,7 @@ void launch_broadphase_write(World& w, u32 numPairs, bool slabOverflow);       /
 void launch_narrowphase(World& w, u32 numPairs, u32 stepParity, bool deferSide = false); // numPairs may exceed the device's pair count (a launch sized before the host knows it); stepParity: the internal step's k & 1 (its sorting-axis word); deferSide: the side-stream chain and the join are left to launch_narrow_side
 void launch_narrow_side(World& w);                           // side chain + join that the last launch_narrowphase deferred (nothing if it deferred none): before anything else is launched on the results
 void launch_zone_overlap(World& w, u32 numPairs);           // force-field / trigger overlap tests on the classified pairs (once per step)
-void launch_integrate_forces(World& w, float dt, bool backupVelocities); // backupVelocities: keep the pre-solve velocities in velBackup (a cluster step)
+void launch_integrate_forces(World& w, float dt, bool backupVelocities); // backupVelocities: keep the pre-solve velocities in cluster.velBackup (a cluster step)
 void launch_heightmap(World& w, u32 numPairs, u32 slotCap);  // terrain contacts appended after the pair manifolds (physics.cpp:1236-1249)
 void launch_cloth(World& w, float dt);                      // cloth_component::applyWindForce + simulate for every cloth (physics.cpp:1354-1358)
 u32 cloth_lds_particle_limit();
@@ -365,7 +420,7 @@ void launch_copy_pose0(World& w);
 void launch_interaction_batch(World& w, u32 numRays, u32 firstBody, u32 bodiesPerRay, const float* dRays, int32_t* dOutBody); // k_interact.hip
 void launch_raycast(World& w, u32 numRays, const float* dRays, u32 flags, mi_ray_hit* dOutHits, const uint2* dExclude = nullptr); // k_raycast.hip; dExclude: a body range per ray (mi_raycast_sensors)
 enum RcBuild { RC_BUILD_NO_CANDIDATES, RC_BUILD_FAILED, RC_BUILD_DONE }; // nothing enqueued: no collider can be a candidate / w.lastError is set / the tree is on the stream
-RcBuild launch_raycast_build(World& w, bool withStatic, bool brute); // k_raycast.hip: the tree in World::rc* that launch_raycast, launch_proximity and launch_sphere_cast walk
+RcBuild launch_raycast_build(World& w, bool withStatic, bool brute); // k_raycast.hip: the tree in World::queries that launch_raycast, launch_proximity and launch_sphere_cast walk
 void launch_proximity(World& w, u32 n, const mi_proximity_query* dQueries, u32 flags, mi_proximity_reading* dOut, float* dOutWorldPoints); // k_proximity.hip
 void launch_sphere_cast(World& w, u32 n, const mi_sphere_cast* dQueries, u32 flags, mi_sphere_hit* dOut, float* dOutWorldCasts); // k_spherecast.hip
 void launch_raycast_sensors(World& w, u32 numRays, const mi_sensor_ray* dRays, u32 flags, bool terrain, mi_sensor_hit* dOutHits, float* dOutWorldRays); // k_raycast_sensors.hip

@@ -28,7 +28,6 @@ template <typename T> void DevBuf<T>::ensure(size_t n, hipStream_t s, bool keep)
 	if (p) MI_CHECK(hipFree(p));
 	p = np; cap = newCap;
 }
-template <typename T> void DevBuf<T>::release() { if (p) { (void)hipFree(p); p = nullptr; cap = 0; } }
 
 template struct DevBuf<float4>; template struct DevBuf<float2>; template struct DevBuf<uint2>; template struct DevBuf<uint4>; template struct DevBuf<u32>;
 template struct DevBuf<double>; template struct DevBuf<u64>; template struct DevBuf<uint8_t>; template struct DevBuf<uint16_t>; template struct DevBuf<float>; template struct DevBuf<ColliderRec>; template struct DevBuf<ManifoldRec>;
@@ -51,18 +50,18 @@ World::World(int dev) : device(dev)
 	if (hCounters) memset(hCounters, 0, CTR_WORDS * sizeof(u32));
 	dCounters.ensure(CTR_WORDS, stream);
 	if (dCounters.p) MI_CHECK(hipMemsetAsync(dCounters.p, 0, CTR_WORDS * sizeof(u32), stream));
-	stageEvents.resize(STAGE_RING * 6);
+	timing.stageEvents.resize(STAGE_RING * 6);
 	// (device-scope events: a stage's time stamp needs no system-scope fence, and the host reads the counters from pinned memory behind an event it waits for)
-	for (auto& e : stageEvents) MI_CHECK(hipEventCreateWithFlags(&e, hipEventDisableSystemFence));
+	for (auto& e : timing.stageEvents) MI_CHECK(hipEventCreateWithFlags(&e, hipEventDisableSystemFence));
 	MI_CHECK(hipEventCreateWithFlags(&countersEvent, hipEventDisableTiming));
 	validate = getenv("MI_PHYSICS_VALIDATE") != nullptr;
-	useCluster = getenv("MI_PHYSICS_NO_CLUSTER") == nullptr;
-	useClusterJoints = getenv("MI_CLUSTER_NO_JOINTS") == nullptr; // LDS cluster contact sweep (one launch) vs global colouring + one launch per colour
-	if (const char* e = getenv("MI_FLOW_TEST_ABORT")) flowTestAbortStep = (u32)atoi(e); // tests: make the cluster sweep of that internal step give up
-	if (const char* e = getenv("MI_CLUSTER_TASK")) { clusterTaskWeight = 64u * (u32)std::max(16, atoi(e)); clusterTaskWeightLater = std::min(clusterTaskWeight, clusterTaskWeightLater); }  // manifolds per task
-	if (getenv("MI_PHYSICS_REPLAY")) replayReferenceOrder = true;
-	if (const char* e = getenv("MI_CLUSTER_BLOCKS")) clusterBlocksLimit = (u32)std::max(1, atoi(e));
-	if (const char* e = getenv("MI_CLUSTER_TASK_LATER")) clusterTaskWeightLater = 64u * (u32)std::max(16, atoi(e)); // ... of the phases after the first
+	cluster.enabled = getenv("MI_PHYSICS_NO_CLUSTER") == nullptr;
+	cluster.jointsEnabled = getenv("MI_CLUSTER_NO_JOINTS") == nullptr; // LDS cluster contact sweep (one launch) vs global colouring + one launch per colour
+	if (const char* e = getenv("MI_FLOW_TEST_ABORT")) cluster.flowTestAbortStep = (u32)atoi(e); // tests: make the cluster sweep of that internal step give up
+	if (const char* e = getenv("MI_CLUSTER_TASK")) { cluster.taskWeight = 64u * (u32)std::max(16, atoi(e)); cluster.taskWeightLater = std::min(cluster.taskWeight, cluster.taskWeightLater); }  // manifolds per task
+	if (getenv("MI_PHYSICS_REPLAY")) replay.referenceOrder = true;
+	if (const char* e = getenv("MI_CLUSTER_BLOCKS")) cluster.blocksLimit = (u32)std::max(1, atoi(e));
+	if (const char* e = getenv("MI_CLUSTER_TASK_LATER")) cluster.taskWeightLater = 64u * (u32)std::max(16, atoi(e)); // ... of the phases after the first
 	if (dCounters.p)
 	{
 		u32 box[6] = { 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u }; // empty bounding box (k_cl_bbox accumulates, k_cl_offsets resets)
@@ -76,20 +75,7 @@ World::~World()
 	g_currentWorld = this;
 	if (narrowStream) (void)hipStreamSynchronize(narrowStream);
 	if (stream) (void)hipStreamSynchronize(stream);
-	DevBuf<float4>* f4[] = { &pose, &pose0, &poseLerp, &vel, &bprops, &force, &cog, &invIw, &colStaticPose, &aabbMin, &aabbMax, &sBox, &rowPlanes, &rowShared };
-	for (auto b : f4) b->release();
-	DevBuf<u32>* u4[] = { &hashKey, &sortIdx, &cellStart, &largeFlag, &largeScan, &largeList, &pairCount, &pairOffset, &pairKey, &pairKeySorted,
-		&mColor, &mKey, &mKeySorted, &mIdx, &mOrder, &dCounters };
-	for (auto b : u4) b->release();
-	colLocal.release(); colWorld.release(); pairs.release(); pairsSorted.release(); manifolds.release(); bodyMask.release(); claim.release();
-	rowLambda.release(); rowIds.release(); tempStorage.release(); actIds.release(); epaList.release(); gjkSimplex.release(); pairSlab.release(); simMask.release();
-	for (auto& js : joints) { js.dPods.release(); js.dPairs.release(); js.dUpdate.release(); }
-	bodyColStart.release(); bodyColList.release(); hullTris.release(); hullTriRange.release();
-	rcLeafBox.release(); rcNodes.release(); rcCount.release(); rcKeys.release(); rcKeysSorted.release(); rcVals.release(); rcValsSorted.release(); rcParentInt.release(); rcParentLeaf.release(); rcTerrainTiles.release(); rcTerrainChunkRange.release();
-	rcSensorRays.release(); rcSensorHits.release(); rcSensorExclude.release();
-	csBody.release(); csEntries.release(); csLarge.release(); csMeta.release();
-	queryHostIn.release(); queryHostOut.release(); queryHostAux.release();
-	for (auto& e : stageEvents) if (e) (void)hipEventDestroy(e);
+	for (auto& e : timing.stageEvents) if (e) (void)hipEventDestroy(e);
 	if (countersEvent) (void)hipEventDestroy(countersEvent);
 	if (hCounters) (void)hipHostFree(hCounters);
 	if (narrowFork) (void)hipEventDestroy(narrowFork);
@@ -289,7 +275,7 @@ void World::upload()
 {
 	if (!topologyDirty) return;
 	pullJointPods();            // device-written motors survive the joint re-upload this forces
-	interactTablesValid = false;
+	queries.interactTablesValid = false;
 	if (stateOnDevice) downloadState(); // bodies added mid-simulation: pull the live state first
 	u32 newNb = (u32)bodies.size(), newNc = (u32)colliders.size();
 	std::vector<float4> hp(2 * (size_t)newNb), hv(2 * ((size_t)newNb + 1)), hprops(5 * (size_t)newNb), hf(2 * (size_t)newNb);
@@ -353,7 +339,7 @@ void World::upload()
 		MI_CHECK(hipMemcpyAsync(simMask.p, alive.data(), nb1, hipMemcpyHostToDevice, stream));
 		MI_CHECK(hipStreamSynchronize(stream)); // `alive` goes out of scope
 	}
-	fieldsDirty = true; // (re)sizes the per-body field bits
+	zones.fieldsDirty = true; // (re)sizes the per-body field bits
 	size_t ncap = std::max<size_t>(nc, 1);
 	colLocal.ensure(ncap, stream); colWorld.ensure(ncap, stream); colStaticPose.ensure(2 * ncap, stream); aabbMin.ensure(ncap, stream); aabbMax.ensure(ncap, stream);
 	hashKey.ensure(ncap, stream); sortIdx.ensure(ncap, stream);
@@ -476,16 +462,16 @@ void World::uploadJoints()
 				}
 		}
 		for (u32 i = 0; i < n; ++i) rep[i] = find(i);
-		clNumJoints = (u32)table.size(); clNumJointClasses = numClasses;
-		clJointsInCluster = clNumJoints > 0 && numClasses <= CL_MAX_JOINT_CLASSES;
-		if (getenv("MI_CLUSTER_DEBUG")) fprintf(stderr, "[mi_physics] joints: %u in %u levels -> %s\n", clNumJoints, numClasses, clJointsInCluster ? "inside the cluster sweep" : "own launches");
+		cluster.numJoints = (u32)table.size(); cluster.numJointClasses = numClasses;
+		cluster.jointsInCluster = cluster.numJoints > 0 && numClasses <= CL_MAX_JOINT_CLASSES;
+		if (getenv("MI_CLUSTER_DEBUG")) fprintf(stderr, "[mi_physics] joints: %u in %u levels -> %s\n", cluster.numJoints, numClasses, cluster.jointsInCluster ? "inside the cluster sweep" : "own launches");
 		std::vector<u32> jointBody(n + 1, 0u);
 		for (const uint4& e : table) { if (e.z < n) jointBody[e.z] = 1u; if (e.w < n) jointBody[e.w] = 1u; }
-		clJointBodyMask.ensure(n + 1, stream); clJointListsValid = false;
-		MI_CHECK(hipMemcpyAsync(clJointBodyMask.p, jointBody.data(), sizeof(u32) * (n + 1), hipMemcpyHostToDevice, stream));
-		clRep.ensure(n + 1, stream); clJointTable.ensure(std::max<size_t>(table.size(), 1), stream);
-		MI_CHECK(hipMemcpyAsync(clRep.p, rep.data(), sizeof(u32) * (n + 1), hipMemcpyHostToDevice, stream));
-		if (!table.empty()) MI_CHECK(hipMemcpyAsync(clJointTable.p, table.data(), sizeof(uint4) * table.size(), hipMemcpyHostToDevice, stream));
+		cluster.jointBodyMask.ensure(n + 1, stream); cluster.jointListsValid = false;
+		MI_CHECK(hipMemcpyAsync(cluster.jointBodyMask.p, jointBody.data(), sizeof(u32) * (n + 1), hipMemcpyHostToDevice, stream));
+		cluster.rep.ensure(n + 1, stream); cluster.jointTable.ensure(std::max<size_t>(table.size(), 1), stream);
+		MI_CHECK(hipMemcpyAsync(cluster.rep.p, rep.data(), sizeof(u32) * (n + 1), hipMemcpyHostToDevice, stream));
+		if (!table.empty()) MI_CHECK(hipMemcpyAsync(cluster.jointTable.p, table.data(), sizeof(uint4) * table.size(), hipMemcpyHostToDevice, stream));
 		MI_CHECK(hipStreamSynchronize(stream));
 	}
 	jointsDirty = false; jointVersion++;
