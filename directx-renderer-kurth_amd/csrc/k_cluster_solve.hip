@@ -45,6 +45,7 @@ struct ClArgs
 	u32* counters; const ClTask* tasks; const u32* bodyList; const u32* phaseMask; const u32* sharedSlot;
 	const u32* mKeySorted; const u32* mLocal; const u32* cEntry;
 	const float4* rowPlanes; const float4* rowShared; float2* rowLambda; float4* rowScratch; u32 scratchContacts;
+	u32 regContactsCap; // MI_CLUSTER_REG_CONTACTS: most contacts a first task keeps in registers (tests; ~0u: as many as the sets hold)
 	u32 predictDiv, pollSleep; // pacing of the hand-over polls (CL_PREDICT_DIV / CL_POLL_SLEEP)
 	float4* vel; u64* flow; u64* trace; // trace: developer timeline (mi_debug_flow_trace), normally null
 	size_t rowCap; u32 nb, flowBytes, epoch, itBegin, itEnd, ldsFloat4s;
@@ -93,6 +94,7 @@ MI_DEV void clBuildQuadRow(QuadRow& r, u32& addr, const ClLocal& L, const ClArgs
 }
 // Row storage outside the registers (P = the contact's CLQ_ROW_FLOAT4S float4): every lane stores its vectors, lane 0 the scalars and lane
 // 0 / 2 the packed addresses of their pair of lanes (the addresses of a quad: two bodies x {linear, angular} = base and base + 1).
+template <typename T> MI_DEV T clLdsAt(const float4* lds, u32 byte) { return *(const T*)((const char*)lds + byte); }
 template <typename PTR> MI_DEV void clStoreQuadRow(PTR P, u32 q, const QuadRow& r, u32 addr)
 {
 	P[3u * q] = make_float4(r.dT.x, r.dT.y, r.dT.z, r.aT.x); P[3u * q + 1u] = make_float4(r.aT.y, r.aT.z, r.dN.x, r.dN.y); P[3u * q + 2u] = make_float4(r.dN.z, r.aN.x, r.aN.y, r.aN.z);
@@ -101,13 +103,14 @@ template <typename PTR> MI_DEV void clStoreQuadRow(PTR P, u32 q, const QuadRow& 
 	const u32 otherPair = (u32)__builtin_amdgcn_update_dpp(0, (int)(addr | (other << 16)), 0x4E, 0xF, 0xF, false); // lanes 2 | 3 << 16 seen from lane 0
 	if (q == 0u) P[13] = make_float4(r.lamN, r.lamT, __uint_as_float(addr | (other << 16)), __uint_as_float(otherPair));
 }
+MI_DEV u32 clPairAddr(u32 pair, u32 q) { return (q & 1u) ? (pair >> 16) : (pair & 0xFFFFu); } // a lane's address out of its pair's word
+#define CLQ_PAIR_WORD(q) (54u + ((q) >> 1)) // u32 index of that word inside a row: P[13].z for lanes 0 and 1, P[13].w for lanes 2 and 3
 template <typename PTR> MI_DEV void clLoadQuadRow(QuadRow& r, u32& addr, PTR P, u32 q)
 {
 	float4 a = P[3u * q], b = P[3u * q + 1u], c = P[3u * q + 2u], d = P[12], e = P[13];
 	r.dT = v3f4(a); r.aT = v3(a.w, b.x, b.y); r.dN = v3(b.z, b.w, c.x); r.aN = v3(c.y, c.z, c.w);
 	r.mT = d.x; r.mN = d.y; r.bias = d.z; r.friction = d.w; r.lamN = e.x; r.lamT = e.y;
-	const u32 pair = __float_as_uint(q < 2u ? e.z : e.w);
-	addr = (q & 1u) ? (pair >> 16) : (pair & 0xFFFFu);
+	addr = clPairAddr(__float_as_uint(q < 2u ? e.z : e.w), q);
 }
 
 // JOINTS: the instantiation for worlds whose joints run inside the sweep (its extra registers and code stay out of the other one).
@@ -154,7 +157,7 @@ template <bool JOINTS> __global__ void __launch_bounds__(CLS_LANES) k_cl_solve(C
 				L.colorStart[CL_SERIAL_COLOR + 2u] = L.colorStart[CL_SERIAL_COLOR + 1u]; L.colorStart[CL_SERIAL_COLOR + 3u] = L.colorStart[CL_SERIAL_COLOR + 1u]; // (the colour loop reads two entries ahead)
 				L.bodyOff = used; used += 2u * L.numBodies;
 				L.infoOff = used * 4u; used += (3u * L.numBodies + 3u) / 4u;
-				L.regContacts = (nT == 0) ? min(L.numContacts, CLQ_QUADS * SETS) : 0u;
+				L.regContacts = (nT == 0) ? min(L.numContacts, min(CLQ_QUADS * SETS, A.regContactsCap)) : 0u;
 				L.rowOff = 0; L.rowCap = 0;
 				++nT;
 			}
@@ -275,19 +278,57 @@ template <bool JOINTS> __global__ void __launch_bounds__(CLS_LANES) k_cl_solve(C
 	// One step = the contacts at positions [cs, end) of a task (one colour, or one contact of the serial tail).  Positions below the
 	// task's regContacts: register set position / CLQ_QUADS of quad position % CLQ_QUADS; beyond: rows from LDS / the scratch.  The
 	// colour loops below are written SET BY SET (a colour's positions are consecutive, so the colours that begin in set S are a run
-	// of the loop; one that reaches beyond set S + 1 is cut into two steps), so that the code of a step names its one or two
-	// register sets statically: no dispatch, and nothing of the other sets passes through the loop.
+	// of the loop; one that reaches beyond set S + 1, or beyond the registers, is cut into two steps), so that the code of a step names
+	// its one or two register sets statically: no dispatch, nothing of the other sets passes through the loop, and no row step stands
+	// between the set loops (each carried a copy of it, ~190 instructions, for the one colour that straddles regContacts, and the
+	// register-run tasks stepped over all of them every turn).  The colours beyond the registers follow in a loop of their own, CLQ_SOLVE_ROWS_LDS or CLQ_SOLVE_ROWS.
 #define CLQ_SOLVE_SET(S_, CS_, END_) if ((S_) < SETS) { const u32 pos = (S_) * CLQ_QUADS + quad; if (pos >= (CS_) && pos < (END_)) { float4 b = lds[addr[(S_) < SETS ? (S_) : 0u]]; V3 x = v3f4(b); clSolveQuad(rows[(S_) < SETS ? (S_) : 0u], x); lds[addr[(S_) < SETS ? (S_) : 0u]] = make_float4(x.x, x.y, x.z, b.w); } }
+	// A row in LDS carries its body addresses in its last float4: read with the row, the body read would be a SECOND dependent LDS round
+	// trip per step.  So a lane asks for the address word of the row it solves next one step early (pfW): a step's start is the end of
+	// the step before it, the lane's first row of the step that follows [CS_, END_) is max(END_, regC) + quad, and the register-only
+	// steps in front of the first row step leave that at regC + quad, which the request made for the task's turn covers (CLQ_PREFETCH_TURN).  The
+	// address words are written by the prologue alone (a step writes back its row's two impulses, never the float2 beside them), so the
+	// word a lane holds across a barrier cannot be stale.  Further passes of a colour with more than CLQ_QUADS rows outside the
+	// registers get their word from the pass before them.  Rows in the global scratch keep the two trips.
+#define CLQ_PREFETCH(POS_) { const u32 in_ = max((POS_), regC) + quad - regC; if (in_ < rowCap) pfW = ((const u32*)(lds + rowOff + in_ * CLQ_ROW_FLOAT4S))[CLQ_PAIR_WORD(q)]; }
 #define CLQ_SOLVE_ROWS(CS_, END_) \
-	for (u32 p = max((CS_), regC) + quad; p < (END_); p += CLQ_QUADS) \
 	{ \
-		const u32 i = p - regC; \
-		QuadRow r; u32 a; \
-		float4* P = lds + rowOff + i * CLQ_ROW_FLOAT4S; \
-		float4* S = A.rowScratch + (size_t)(scratchBase + i - rowCap) * CLQ_ROW_FLOAT4S; \
-		if (i < rowCap) clLoadQuadRow(r, a, P, q); else clLoadQuadRow(r, a, S, q); \
-		float4 b = lds[a]; V3 x = v3f4(b); clSolveQuad(r, x); lds[a] = make_float4(x.x, x.y, x.z, b.w); \
-		if (q == 0u) { if (i < rowCap) ((float2*)(P + 13))[0] = make_float2(r.lamN, r.lamT); else ((float2*)(S + 13))[0] = make_float2(r.lamN, r.lamT); } \
+		u32 w = pfW; \
+		CLQ_PREFETCH(END_) \
+		for (u32 p = max((CS_), regC) + quad; p < (END_); p += CLQ_QUADS) \
+		{ \
+			const u32 i = p - regC; \
+			QuadRow r; u32 a; float4 b; \
+			float4* P = lds + rowOff + i * CLQ_ROW_FLOAT4S; \
+			float4* S = A.rowScratch + (size_t)(scratchBase + i - rowCap) * CLQ_ROW_FLOAT4S; \
+			u32 wn = 0u; if (p + CLQ_QUADS < (END_) && i + CLQ_QUADS < rowCap) wn = ((const u32*)(P + CLQ_QUADS * CLQ_ROW_FLOAT4S))[CLQ_PAIR_WORD(q)]; \
+			if (i < rowCap) { u32 unused; a = clPairAddr(w, q); b = lds[a]; clLoadQuadRow(r, unused, P, q); } else { clLoadQuadRow(r, a, S, q); b = lds[a]; } \
+			V3 x = v3f4(b); clSolveQuad(r, x); lds[a] = make_float4(x.x, x.y, x.z, b.w); \
+			if (q == 0u) { if (i < rowCap) ((float2*)(P + 13))[0] = make_float2(r.lamN, r.lamT); else ((float2*)(S + 13))[0] = make_float2(r.lamN, r.lamT); } \
+			w = wn; \
+		} \
+	}
+	// The same step for a task whose rows outside the registers are ALL in LDS, in the loop of the colours that lie entirely beyond the
+	// registers (CS_ >= regC): every task but a workgroup's first runs all its colours here.  Measured, such a step cost 0.43 us against
+	// the register step's 0.28, and what it costs is its instruction count far more than its LDS round trips (a wave gets through the ~45
+	// instructions of a register step in ~650 cycles).  So this form keeps it short: a step takes at most CLQ_QUADS rows (the loop cuts a
+	// larger colour into several steps, as the set loops do at a set's end), so there is no loop over passes; no branch on where a row
+	// lives; row addresses by one 24-bit multiply-add; and the request for the lane's next row is clamped to the task's last row
+	// instead of guarded (a lane without a next row reads a word it never uses).
+#define CLQ_SOLVE_ROWS_LDS(CS_, END_) \
+	{ \
+		const u32 i = (CS_) - regC + quad, endR = (END_) - regC, w = pfW; \
+		pfW = clLdsAt<u32>(lds, __umul24(min(endR + quad, lastRow), CLQ_ROW_FLOAT4S * 16u) + pairByte); \
+		if (i < endR) \
+		{ \
+			const u32 a = clPairAddr(w, q), rowByte = __umul24(i, CLQ_ROW_FLOAT4S * 16u) + rowsByte, own = rowByte + q * 48u; \
+			const float4 b = lds[a], r0 = clLdsAt<float4>(lds, own), r1 = clLdsAt<float4>(lds, own + 16u), r2 = clLdsAt<float4>(lds, own + 32u), r3 = clLdsAt<float4>(lds, rowByte + 192u); \
+			const float2 lam = clLdsAt<float2>(lds, rowByte + 208u); \
+			QuadRow r; r.dT = v3f4(r0); r.aT = v3(r0.w, r1.x, r1.y); r.dN = v3(r1.z, r1.w, r2.x); r.aN = v3(r2.y, r2.z, r2.w); \
+			r.mT = r3.x; r.mN = r3.y; r.bias = r3.z; r.friction = r3.w; r.lamN = lam.x; r.lamT = lam.y; \
+			V3 x = v3f4(b); clSolveQuad(r, x); lds[a] = make_float4(x.x, x.y, x.z, b.w); \
+			if (q == 0u) *(float2*)((char*)lds + (rowByte + 208u)) = make_float2(r.lamN, r.lamT); \
+		} \
 	}
 #define CLQ_ADVANCE(END_) \
 	__syncthreads(); \
@@ -297,15 +338,20 @@ template <bool JOINTS> __global__ void __launch_bounds__(CLS_LANES) k_cl_solve(C
 	if ((S_) < SETS) while (c < mainColors && csCur < min(regC, ((S_) + 1u) * CLQ_QUADS)) \
 	{ \
 		const u32 csAfter = L.colorStart[c + 2u]; /* (requested now, needed at the next colour: the LDS round trip hides behind this step) */ \
-		const u32 end = min(csNext, ((S_) + 2u) * CLQ_QUADS), endReg = min(end, regC); \
-		CLQ_SOLVE_SET(S_, csCur, endReg) \
-		if (end > ((S_) + 1u) * CLQ_QUADS) { CLQ_SOLVE_SET((S_) + 1u, csCur, endReg) if (end > regC) { CLQ_SOLVE_ROWS(csCur, end) } } \
+		const u32 end = min(csNext, min(regC, ((S_) + 2u) * CLQ_QUADS)); /* (a colour that reaches beyond set S_ + 1 or beyond the registers is cut there: the row steps stay out of these loops) */ \
+		CLQ_SOLVE_SET(S_, csCur, end) \
+		if (end > ((S_) + 1u) * CLQ_QUADS) { CLQ_SOLVE_SET((S_) + 1u, csCur, end) } \
 		CLQ_ADVANCE(end) \
 	}
 	static_assert(CLQ_SETS <= 8u, "the colour loop below names eight sets");
 
 	// ---- iterations ----
 	bool aborted = false;
+	// The first request of a task's turn reads the task record and then the row, two LDS round trips: it is made right after the turn
+	// before it has published its bodies (and once in front of the loop), where it is in nobody's way, and returns while the workgroup waits for bodies.
+#define CLQ_PREFETCH_TURN(K_) { const ClLocal& N = sTask[K_]; const u32 rc = N.regContacts, in_ = max(N.colorStart[0], rc) + quad - rc; if (in_ < N.rowCap) pfW = ((const u32*)(lds + N.rowOff + in_ * CLQ_ROW_FLOAT4S))[CLQ_PAIR_WORD(q)]; }
+	u32 pfW = 0u; // the address word of this lane's next row outside the registers (CLQ_PREFETCH)
+	CLQ_PREFETCH_TURN(0u)
 	u64 lastPublish = 0; u32 lastWait = 0; // when this workgroup last handed its bodies on, and how long (10 ns ticks) the bodies of its first task then took to come back
 	for (u32 it = A.itBegin; it < A.itEnd && !aborted; ++it)
 	{
@@ -403,7 +449,19 @@ template <bool JOINTS> __global__ void __launch_bounds__(CLS_LANES) k_cl_solve(C
 				const u32 mainColors = (k == 0u) ? tailStart0 : numColors;
 				u32 c = 0, csCur = __builtin_amdgcn_readfirstlane(L.colorStart[0]), csNext = __builtin_amdgcn_readfirstlane(L.colorStart[1]);
 				CLQ_SET_LOOP(0) CLQ_SET_LOOP(1) CLQ_SET_LOOP(2) CLQ_SET_LOOP(3) CLQ_SET_LOOP(4) CLQ_SET_LOOP(5) CLQ_SET_LOOP(6) CLQ_SET_LOOP(7)
-				while (c < mainColors) // colours that lie entirely beyond the register sets (a task that is not the workgroup's first, or larger than the sets)
+				// colours that lie entirely beyond the register sets (a task that is not the workgroup's first, or larger than the sets)
+				if (rowCap >= numContacts - regC) // (all of them in LDS)
+				{
+					const u32 rowsByte = rowOff * 16u, lastRow = max(numContacts - regC, 1u) - 1u, pairByte = rowsByte + 4u * CLQ_PAIR_WORD(q);
+					while (c < mainColors)
+					{
+						const u32 csAfter = L.colorStart[c + 2u];
+						const u32 end = min(csNext, csCur + CLQ_QUADS);
+						CLQ_SOLVE_ROWS_LDS(csCur, end)
+						CLQ_ADVANCE(end)
+					}
+				}
+				else while (c < mainColors)
 				{
 					const u32 csAfter = L.colorStart[c + 2u];
 					CLQ_SOLVE_ROWS(csCur, csNext)
@@ -417,6 +475,7 @@ template <bool JOINTS> __global__ void __launch_bounds__(CLS_LANES) k_cl_solve(C
 					__syncthreads();
 					if (stamp) for (u32 ct = mainColors; ct < numColors && ct < 63u; ++ct) { trace[5 * 32 + 1 + ct] = clock64(); trace[7 * 32 + ct] = L.colorStart[ct + 1u] - L.colorStart[ct]; }
 				}
+				if (serialStart < numContacts) CLQ_PREFETCH(serialStart) // (colorStart[numColors] = serialStart: the colours left this very word; asked for again so that the tail does not lean on it)
 				for (u32 sp = serialStart; sp < numContacts; ++sp) // the serial tail (manifolds that found no colour run below 64): one contact per step
 				{
 					if (sp < regC)
@@ -450,6 +509,7 @@ template <bool JOINTS> __global__ void __launch_bounds__(CLS_LANES) k_cl_solve(C
 				}
 			}
 			if (k + 1u == numTasks) lastPublish = wall_clock64();
+			CLQ_PREFETCH_TURN(k + 1u < numTasks ? k + 1u : 0u)
 		}
 	}
 	if (aborted) return; // the host redoes the step (World::recoverSolve)
@@ -487,6 +547,9 @@ template <bool JOINTS> __global__ void __launch_bounds__(CLS_LANES) k_cl_solve(C
 #undef CLQ_SET_LOOP
 #undef CLQ_ADVANCE
 #undef CLQ_SOLVE_ROWS
+#undef CLQ_SOLVE_ROWS_LDS
+#undef CLQ_PREFETCH
+#undef CLQ_PREFETCH_TURN
 #undef CLQ_SOLVE_SET
 }
 
@@ -552,7 +615,7 @@ void launch_cluster_solve(World& w, u32 itBegin, u32 itEnd)
 	if (w.lastError) return;
 	if (itBegin) MI_CHECK(hipMemsetAsync(w.dCounters.p + CTR_CL_SCRATCH, 0, sizeof(u32), w.stream)); // (the step's first launch finds it cleared by k_cl_clear)
 	ClArgs A;
-	A.rowScratch = w.cluster.rowScratch.p; A.scratchContacts = (u32)scratchContacts;
+	A.rowScratch = w.cluster.rowScratch.p; A.scratchContacts = (u32)scratchContacts; A.regContactsCap = w.cluster.regContactsCap;
 	A.counters = w.dCounters.p; A.tasks = (const ClTask*)w.cluster.tasks.p; A.bodyList = w.cluster.bodyList.p; A.phaseMask = w.cluster.phaseMask.p; A.sharedSlot = w.cluster.sharedSlot.p;
 	A.mKeySorted = w.mKeySorted.p; A.mLocal = w.cluster.local.p; A.cEntry = w.cluster.entry.p;
 	A.rowPlanes = w.rowPlanes.p; A.rowShared = w.rowShared.p; A.rowLambda = w.rowLambda.p; A.vel = w.vel.p; A.flow = w.cluster.flow.p; A.trace = w.cluster.flowTrace.p; A.predictDiv = CL_PREDICT_DIV; A.pollSleep = CL_POLL_SLEEP;

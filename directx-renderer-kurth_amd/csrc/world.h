@@ -274,6 +274,7 @@ struct World
 		bool jointsEnabled = true;            // MI_CLUSTER_NO_JOINTS=1: joints keep their per-colour launches (one cluster launch per iteration then)
 		u32 blocksLimit = 0, failStreak = 0, taskWeight = 64u * 1000u, taskWeightLater = 64u * 500u; // MI_CLUSTER_BLOCKS / _TASK / _TASK_LATER
 		u32 ldsBytes = 0, blocks = 0, cooldown = 0;
+		u32 regContactsCap = ~0u;             // MI_CLUSTER_REG_CONTACTS: most contacts of a workgroup's first task kept in registers (tests: where rows are stored, never what is computed)
 		bool compIdle = false;                    // the last step's curve phases left nothing over (and its rest task was empty): this step skips the component phase's launches (what is left over goes to the rest task)
 
 		// -- the partition's private scratch: k_cluster_partition.hip alone (the joint inputs are written by World::uploadJoints) --

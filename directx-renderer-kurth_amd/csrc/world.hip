@@ -61,6 +61,7 @@ World::World(int dev) : device(dev)
 	if (const char* e = getenv("MI_CLUSTER_TASK")) { cluster.taskWeight = 64u * (u32)std::max(16, atoi(e)); cluster.taskWeightLater = std::min(cluster.taskWeight, cluster.taskWeightLater); }  // manifolds per task
 	if (getenv("MI_PHYSICS_REPLAY")) replay.referenceOrder = true;
 	if (const char* e = getenv("MI_CLUSTER_BLOCKS")) cluster.blocksLimit = (u32)std::max(1, atoi(e));
+	if (const char* e = getenv("MI_CLUSTER_REG_CONTACTS")) cluster.regContactsCap = (u32)std::max(0, atoi(e)); // tests: rows beyond it live in LDS / the scratch
 	if (const char* e = getenv("MI_CLUSTER_TASK_LATER")) cluster.taskWeightLater = 64u * (u32)std::max(16, atoi(e)); // ... of the phases after the first
 	if (dCounters.p)
 	{
