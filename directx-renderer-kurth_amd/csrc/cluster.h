@@ -11,7 +11,7 @@
 //       and the curve is chunked by weight into tasks of ~1000 (later phases ~500) contacts; a manifold whose two bodies fall into
 //       the same chunk is INTERIOR to that task.  Phase p only looks at what phases < p left over.
 //   phase P ("component phase"): what the curves leave over is not cut again; its connected components are dealt whole to the tasks
-//       of one more phase.  A rest task (phase CL_MAX_PARTS) only takes what that cannot place (nothing, in practice).
+//       of one more phase (~200 contacts each: they mostly run behind a first task and must fit the LDS it leaves).  A rest task (phase CL_MAX_PARTS) only takes what that cannot place (nothing, in practice).
 //
 // Tasks of one phase share no body, so they run concurrently, one workgroup each; a workgroup runs its (at most two per phase)
 // tasks in phase order, iteration after iteration.  Inside a task the CONTACTS are coloured locally (k_cl_color: a manifold with K

@@ -418,11 +418,14 @@ __global__ void __launch_bounds__(256) k_cl_comp_weights(u32* __restrict__ count
 	if ((threadIdx.x & 63u) == 0u && mine) atomicAdd(&counters[CTR_CL_LEFT + 2], mine);
 }
 // Deal the manifolds: both ends in one component of fitting size -> that component's task (hash of its label); otherwise the rest task.
-__global__ void __launch_bounds__(CL_ASSIGN_LANES) k_cl_comp_assign(u32* __restrict__ counters, u32 nb, u32 phase, u32 taskWeight, u32 leftCap, const u32* __restrict__ leftList, const uint4* __restrict__ actIds, u32* label,
+// The components share no body and a manifold's colour follows from its component alone, so the number of tasks they are dealt to
+// changes no body's sequence of row solves: taskWeight (World::cluster.taskWeightComp) is chosen for where the tasks run, behind a
+// first task whose bodies and rows already sit in the workgroup's LDS.  maxTasks: what the sweep's launch runs of one phase.
+__global__ void __launch_bounds__(CL_ASSIGN_LANES) k_cl_comp_assign(u32* __restrict__ counters, u32 nb, u32 phase, u32 taskWeight, u32 maxTasks, u32 leftCap, const u32* __restrict__ leftList, const uint4* __restrict__ actIds, u32* label,
 	const u32* __restrict__ compWeight, u32* __restrict__ taskKey, u32* __restrict__ taskPos, u32* __restrict__ taskCount, u32* __restrict__ phaseMask)
 {
 	const u32 n = min(counters[CTR_CL_LEFT], leftCap), total = counters[CTR_CL_LEFT + 2];
-	const u32 numTasks = min(max(1u, (total + taskWeight - 1u) / taskWeight), CL_MAX_TASKS);
+	const u32 numTasks = min(max(1u, (total + taskWeight - 1u) / taskWeight), maxTasks);
 	if (blockIdx.x == 0 && threadIdx.x == 0) counters[CTR_CL_LEFT + 1] = numTasks;
 	for (u32 i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
 	{
@@ -636,7 +639,8 @@ static void clAssignComponents(World& w)
 		hipLaunchKernelGGL(k_cl_comp_round, dim3(CL_COMP_BLOCKS), CL_BLOCK, 0, w.stream, w.dCounters.p, nb, leftCap, w.cluster.leftList.p, w.actIds.p,
 			(const u32*)(w.cluster.compLabel.p + (size_t)(r % CL_COMP_LABEL_BUFFERS) * nb1), w.cluster.compLabel.p + (size_t)((r + 1u) % CL_COMP_LABEL_BUFFERS) * nb1);
 	hipLaunchKernelGGL(k_cl_comp_weights, dim3(CL_COMP_BLOCKS), CL_BLOCK, 0, w.stream, w.dCounters.p, nb, leftCap, w.cluster.leftList.p, w.actIds.p, w.cluster.compLabel.p, compWeight);
-	hipLaunchKernelGGL(k_cl_comp_assign, dim3(CL_COMP_BLOCKS), dim3(CL_ASSIGN_LANES), 0, w.stream, w.dCounters.p, nb, CL_CURVE_PARTS, w.cluster.taskWeightLater, leftCap, w.cluster.leftList.p, w.actIds.p, w.cluster.compLabel.p, compWeight,
+	const u32 maxTasks = std::min<u32>(CL_MAX_TASKS, CL_TASKS_PER_PHASE * std::max(1u, w.cluster.blocks)); // (beyond it k_cl_solve gives the step up: status 128)
+	hipLaunchKernelGGL(k_cl_comp_assign, dim3(CL_COMP_BLOCKS), dim3(CL_ASSIGN_LANES), 0, w.stream, w.dCounters.p, nb, CL_CURVE_PARTS, w.cluster.taskWeightComp, maxTasks, leftCap, w.cluster.leftList.p, w.actIds.p, w.cluster.compLabel.p, compWeight,
 		w.cluster.taskKey.p, w.cluster.taskPos.p, w.cluster.taskCount.p, w.cluster.phaseMask.p);
 }
 // First slot of every task, then every manifold (and, unless kept, joint) to its slot.

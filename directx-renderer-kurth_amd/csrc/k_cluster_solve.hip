@@ -267,12 +267,13 @@ template <bool JOINTS> __global__ void __launch_bounds__(CLS_LANES) k_cl_solve(C
 	__syncthreads();
 	// developer timeline: 16 rows of 32 stamps per workgroup: row 3 k = "task k acquired its shared bodies" in iteration (column), row
 	// 3 k + 1 = "task k's colours done"; rows 5-6: core-clock stamp after every colour of iteration 10 of the first task, rows 7-8: the
-	// colours' sizes; row 15: [0] kernel start, [1] prologue done, [2 + 4 k ..] task k's size, colours, shared bodies, phase
+	// colours' sizes; row 15: [0] kernel start, [1] prologue done, [2 + 4 k ..] task k's size, colours, shared bodies, phase;
+	// [22 + k] task k's rows in LDS | in registers << 32 (the rest of its contacts: in the global scratch)
 	u64* trace = A.trace ? A.trace + (size_t)blockIdx.x * CL_TRACE_ROWS * CL_TRACE_WORDS : nullptr;
 	if (trace && tid == 0)
 	{
 		trace[15 * 32 + 1] = wall_clock64();
-		for (u32 k = 0; k < numTasks && k < 5u; ++k) { trace[15 * 32 + 2 + 4 * k] = sTask[k].count; trace[15 * 32 + 3 + 4 * k] = sTask[k].numColors; trace[15 * 32 + 4 + 4 * k] = sTask[k].numShared; trace[15 * 32 + 5 + 4 * k] = sTask[k].phase | (sTask[k].numBodies << 8) | ((u64)sTask[k].numContacts << 32); }
+		for (u32 k = 0; k < numTasks && k < 5u; ++k) { trace[15 * 32 + 2 + 4 * k] = sTask[k].count; trace[15 * 32 + 3 + 4 * k] = sTask[k].numColors; trace[15 * 32 + 4 + 4 * k] = sTask[k].numShared; trace[15 * 32 + 5 + 4 * k] = sTask[k].phase | (sTask[k].numBodies << 8) | ((u64)sTask[k].numContacts << 32); trace[15 * 32 + 22 + k] = sTask[k].rowCap | ((u64)sTask[k].regContacts << 32); }
 	}
 
 	// One step = the contacts at positions [cs, end) of a task (one colour, or one contact of the serial tail).  Positions below the

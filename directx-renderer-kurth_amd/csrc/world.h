@@ -273,6 +273,7 @@ struct World
 		bool enabled = true;                  // MI_PHYSICS_NO_CLUSTER=1: launch-per-colour sweep only
 		bool jointsEnabled = true;            // MI_CLUSTER_NO_JOINTS=1: joints keep their per-colour launches (one cluster launch per iteration then)
 		u32 blocksLimit = 0, failStreak = 0, taskWeight = 64u * 1000u, taskWeightLater = 64u * 500u; // MI_CLUSTER_BLOCKS / _TASK / _TASK_LATER
+		u32 taskWeightComp = 64u * 200u;      // MI_CLUSTER_TASK_COMP: the component phase's tasks, sized to fit LDS BEHIND a first task, where most of them run (profiles/sweep_comp_fit.txt)
 		u32 ldsBytes = 0, blocks = 0, cooldown = 0;
 		u32 regContactsCap = ~0u;             // MI_CLUSTER_REG_CONTACTS: most contacts of a workgroup's first task kept in registers (tests: where rows are stored, never what is computed)
 		bool compIdle = false;                    // the last step's curve phases left nothing over (and its rest task was empty): this step skips the component phase's launches (what is left over goes to the rest task)

@@ -58,11 +58,12 @@ World::World(int dev) : device(dev)
 	cluster.enabled = getenv("MI_PHYSICS_NO_CLUSTER") == nullptr;
 	cluster.jointsEnabled = getenv("MI_CLUSTER_NO_JOINTS") == nullptr; // LDS cluster contact sweep (one launch) vs global colouring + one launch per colour
 	if (const char* e = getenv("MI_FLOW_TEST_ABORT")) cluster.flowTestAbortStep = (u32)atoi(e); // tests: make the cluster sweep of that internal step give up
-	if (const char* e = getenv("MI_CLUSTER_TASK")) { cluster.taskWeight = 64u * (u32)std::max(16, atoi(e)); cluster.taskWeightLater = std::min(cluster.taskWeight, cluster.taskWeightLater); }  // manifolds per task
+	if (const char* e = getenv("MI_CLUSTER_TASK")) { cluster.taskWeight = 64u * (u32)std::max(16, atoi(e)); cluster.taskWeightLater = std::min(cluster.taskWeight, cluster.taskWeightLater); cluster.taskWeightComp = std::min(cluster.taskWeight, cluster.taskWeightComp); }  // manifolds per task
 	if (getenv("MI_PHYSICS_REPLAY")) replay.referenceOrder = true;
 	if (const char* e = getenv("MI_CLUSTER_BLOCKS")) cluster.blocksLimit = (u32)std::max(1, atoi(e));
 	if (const char* e = getenv("MI_CLUSTER_REG_CONTACTS")) cluster.regContactsCap = (u32)std::max(0, atoi(e)); // tests: rows beyond it live in LDS / the scratch
 	if (const char* e = getenv("MI_CLUSTER_TASK_LATER")) cluster.taskWeightLater = 64u * (u32)std::max(16, atoi(e)); // ... of the phases after the first
+	if (const char* e = getenv("MI_CLUSTER_TASK_COMP")) cluster.taskWeightComp = 64u * (u32)std::min(1 << 20, std::max(16, atoi(e))); // ... of the component phase (dealing its components otherwise changes no result)
 	if (dCounters.p)
 	{
 		u32 box[6] = { 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u }; // empty bounding box (k_cl_bbox accumulates, k_cl_offsets resets)
