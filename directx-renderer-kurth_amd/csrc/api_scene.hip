@@ -190,7 +190,7 @@ uint32_t mi_drain_events(mi_world* world, mi_event* out, uint32_t capacity)
 		}
 		if (head[0] || head[1]) MI_CHECK(hipMemsetAsync(W->dCounters.p + CTR_EVENT_COUNT, 0, sizeof(head), W->stream));
 		if (head[1] & 1u) W->fail(MI_ERR_CAPACITY, "the event ring overflowed: events were lost (drain more often or raise MI_EVENT_CAPACITY)");
-		if (head[1] & 2u) W->hCounters[CTR_EVENT_OVERFLOW] |= 2u; // ensureEventBuffers grows the table
+		if (head[1] & 2u) W->fail(MI_ERR_CAPACITY, "a trigger / collision overlap set was full: events were lost");
 	}
 	uint32_t n = (uint32_t)std::min<size_t>(capacity, W->zones.pendingEvents.size());
 	if (n && out) memcpy(out, W->zones.pendingEvents.data(), sizeof(mi_event) * n);

@@ -200,8 +200,10 @@ void World::ensureEventBuffers(u32 numPairs)
 	}
 	if (!zones.triggers.empty())
 	{
+		// One key per overlapping (trigger, body): any number of triggers may hold one body, so the bodies do not bound the keys.  This
+		// step's pair count does (every key comes from a pair of the zone bucket) and is on the host: the table is at most half full.
 		u32 want = std::max(4096u, nextPow2(4u * std::max(nb, 1u)));
-		if (hCounters[CTR_EVENT_OVERFLOW] & 2u) want = std::max(want, zones.triggerSetSize * 4u); // a table was full last step
+		want = std::max(want, nextPow2(2u * std::min(numPairs, 1u << 29)));
 		want = std::max(want, nextPow2(4u * (u32)zones.restoredTriggerKeys.size()));
 		if (want > zones.triggerSetSize) resizePairSet(*this, zones.triggerSet, zones.triggerSetSize, zones.triggerCur, want, &zones.restoredTriggerKeys);
 	}

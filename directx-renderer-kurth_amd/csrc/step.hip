@@ -335,6 +335,7 @@ static bool settlePreviousStep(World& w, bool& early)
 	}
 	w.countPreviousStep();                                 // the counters just read hold the previous step's colour / contact counts
 	if (hc[CTR_TERRAIN_OVERFLOW]) { w.fail(MI_ERR_CAPACITY, "more terrain contacts than manifold slots: contacts were dropped (raise MI_TERRAIN_SLOTS_PER_COLLIDER)"); return false; }
+	if (hc[CTR_EVENT_OVERFLOW] & 2u) { w.fail(MI_ERR_CAPACITY, "a trigger / collision overlap set was full: events of the last step were lost"); return false; }
 	return true;
 }
 
