@@ -106,7 +106,7 @@ class ProximityReading(C.Structure):
 PROXIMITY_QUERY_DTYPE = np.dtype([("point", "<f4", 3), ("radius", "<f4"), ("mount", "<u4"), ("excludeFirst", "<u4"), ("excludeCount", "<u4"), ("enabled", "<u4")])
 PROXIMITY_READING_DTYPE = np.dtype([("distance", "<f4"), ("collider", "<u4"), ("body", "<u4"), ("found", "<u4"), ("point", "<f4", 3), ("numWithin", "<u4"),
                                     ("normal", "<f4", 3), ("reserved", "<f4")])
-PROX_STATIC, PROX_BRUTE_FORCE, PROX_COUNT = 1, 2, 4   # mi_proximity's flags (MI_PROX_*)
+PROX_STATIC, PROX_BRUTE_FORCE, PROX_COUNT, PROX_TERRAIN = 1, 2, 4, 8   # mi_proximity's flags (MI_PROX_*)
 
 
 class SphereCast(C.Structure):
@@ -125,7 +125,7 @@ SPHERE_CAST_DTYPE = np.dtype([("origin", "<f4", 3), ("maxT", "<f4"), ("direction
                               ("mount", "<u4"), ("excludeFirst", "<u4"), ("excludeCount", "<u4"), ("enabled", "<u4")])
 SPHERE_HIT_DTYPE = np.dtype([("t", "<f4"), ("collider", "<u4"), ("body", "<u4"), ("hit", "<u4"), ("point", "<f4", 3), ("gap", "<f4"),
                              ("normal", "<f4", 3), ("iterations", "<u4")])
-SPHERE_STATIC, SPHERE_BRUTE_FORCE = 1, 2   # mi_sphere_cast_batch's flags (MI_SPHERE_*)
+SPHERE_STATIC, SPHERE_BRUTE_FORCE, SPHERE_TERRAIN = 1, 2, 4   # mi_sphere_cast_batch's flags (MI_SPHERE_*)
 TERRAIN_COLLIDER = 0xFFFFFFFE   # mi_ray_hit.collider of a hit on the heightmap terrain (MI_TERRAIN_COLLIDER)
 
 
@@ -615,9 +615,12 @@ class World:
         return out + (wr,) if world_rays else out
 
     def proximity(self, points, radius=np.inf, mount=None, exclude_first=None, exclude_count=None, static=True, brute_force=False, count=True,
-                  world_points=False, device=False):
+                  world_points=False, device=False, terrain=False):
         """mi_proximity: per point the nearest collider surface within `radius` (signed distance, negative inside; closest point; outward
-        normal) and, with `count`, the number of colliders within it (the rule is in include/mi_physics.h; the heightmap is no candidate).
+        normal) and, with `count`, the number of colliders within it (the rule is in include/mi_physics.h).  terrain: the heightmap is one more
+        candidate, the solid under its surface (PROX_TERRAIN; nothing changes without a heightmap): such a reading has collider
+        TERRAIN_COLLIDER, body STATIC_BODY, a negative distance below the surface, and in `reserved` the bits of the nearest triangle's id
+        (reading["reserved"].view(np.uint32), for heightmap_triangle); it counts 1 in numWithin; exclusion never hides it.
         points [n, 3] in the frame of body mount[i] at its current pose (mount: an index or an array [n]; None / STATIC_BODY: world space);
         radius: a number or an array [n], may be inf; blind to the colliders of the bodies exclude_first[i] ... + exclude_count[i] - 1.
         `points` may also be a PROXIMITY_QUERY_DTYPE array (radius, mount and the exclusion arguments are then not used).
@@ -626,7 +629,7 @@ class World:
         A torch tensor on the device (float32, contiguous, [n, 8]: the bits of mi_proximity_query) is queried in place: returns one float32
         tensor [n, 12] of mi_proximity_reading records (with world_points=True a tuple with the [n, 4] world points), enqueued on the
         world's stream with no synchronisation.  (The tensor is recorded on that stream, as in raycast: release it before close().)"""
-        flags = (PROX_STATIC if static else 0) | (PROX_BRUTE_FORCE if brute_force else 0) | (PROX_COUNT if count else 0)
+        flags = (PROX_STATIC if static else 0) | (PROX_BRUTE_FORCE if brute_force else 0) | (PROX_COUNT if count else 0) | (PROX_TERRAIN if terrain else 0)
 
         def entry(fn):
             return lambda n, d_in, d_out, d_aux: fn(self.w, C.c_uint32(n), C.c_void_p(d_in), C.c_uint32(flags), C.c_void_p(d_out), C.c_void_p(d_aux))
@@ -644,10 +647,12 @@ class World:
         return (out, wp) if world_points else out
 
     def sphere_cast(self, origins, directions=None, radius=0.0, max_t=np.inf, mount=None, exclude_first=None, exclude_count=None, static=True, brute_force=False,
-                    world_casts=False, device=False):
+                    world_casts=False, device=False, terrain=False):
         """mi_sphere_cast_batch: per query how far a sphere of `radius` travels from origins[i] along directions[i] (t in units of the
-        direction's length, at most max_t) before it touches a collider, and where and on what (the rule is in include/mi_physics.h; the
-        heightmap is no candidate).  origins, directions [n, 3] in the frame of body mount[i] at its current pose (mount: an index or an
+        direction's length, at most max_t) before it touches a collider, and where and on what (the rule is in include/mi_physics.h).
+        terrain: the heightmap's triangles are candidates too, as a two-sided sheet (SPHERE_TERRAIN; nothing changes without a heightmap):
+        such a hit has collider TERRAIN_COLLIDER, body STATIC_BODY, the touched point and the normal from it to the sphere's centre, and
+        no triangle id (proximity(terrain=True) at origin + t * direction names the triangle).  origins, directions [n, 3] in the frame of body mount[i] at its current pose (mount: an index or an
         array [n]; None / STATIC_BODY: world space); radius, max_t: numbers or arrays [n]; blind to the colliders of the bodies
         exclude_first[i] ... + exclude_count[i] - 1.  `origins` may also be a SPHERE_CAST_DTYPE array (the other query arguments are then
         not used).
@@ -657,7 +662,7 @@ class World:
         A torch tensor on the device (float32, contiguous, [n, 12]: the bits of mi_sphere_cast) is cast in place: returns one float32
         tensor [n, 12] of mi_sphere_hit records (with world_casts=True a tuple with the [n, 8] world casts), enqueued on the world's
         stream with no synchronisation.  (The tensor is recorded on that stream, as in raycast: release it before close().)"""
-        flags = (SPHERE_STATIC if static else 0) | (SPHERE_BRUTE_FORCE if brute_force else 0)
+        flags = (SPHERE_STATIC if static else 0) | (SPHERE_BRUTE_FORCE if brute_force else 0) | (SPHERE_TERRAIN if terrain else 0)
 
         def entry(fn):
             return lambda n, d_in, d_out, d_aux: fn(self.w, C.c_uint32(n), C.c_void_p(d_in), C.c_uint32(flags), C.c_void_p(d_out), C.c_void_p(d_aux))

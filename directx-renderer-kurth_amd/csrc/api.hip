@@ -363,10 +363,11 @@ static bool queryBegin(World* w, u32 count, bool pointers, bool tables, int& cod
 	code = w->lastError;
 	return !code;
 }
-// Does a cast with these flags meet the heightmap?  MI_ERR_INVALID_ARGUMENT for a terrain with more chunks than the 17 chunk bits of a triangle id count.
-static int queryTerrain(const World* w, u32 flags, bool& terrain)
+// Does a query with these flags meet the heightmap?  bit: the entry's terrain flag (MI_RAY_TERRAIN, MI_PROX_TERRAIN, MI_SPHERE_TERRAIN).
+// MI_ERR_INVALID_ARGUMENT for a terrain with more chunks than the 17 chunk bits of a triangle id count.
+static int queryTerrain(const World* w, u32 flags, u32 bit, bool& terrain)
 {
-	terrain = (flags & MI_RAY_TERRAIN) != 0 && w->terrain.chunksPerDim != 0;
+	terrain = (flags & bit) != 0 && w->terrain.chunksPerDim != 0;
 	return terrain && (uint64_t)w->terrain.chunksPerDim * w->terrain.chunksPerDim > 131071u ? MI_ERR_INVALID_ARGUMENT : MI_OK;
 }
 // A _host entry: `count` records of inBytes each to the device, deviceEntry(dIn, dOut, dAux) on them, outBytes per record back into `out`
@@ -392,7 +393,7 @@ int mi_raycast_batch(mi_world* world, uint32_t numRays, const float* dRays, uint
 {
 	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
 	int code; bool terrain;
-	if (!queryBegin(W, numRays, dRays && dOutHits, true, code) || (code = queryTerrain(W, flags, terrain)) != MI_OK) return code;
+	if (!queryBegin(W, numRays, dRays && dOutHits, true, code) || (code = queryTerrain(W, flags, MI_RAY_TERRAIN, terrain)) != MI_OK) return code;
 	launch_raycast(*W, numRays, dRays, flags, dOutHits); // (no candidate collider: the records are zeroed)
 	if (terrain && !W->lastError) launch_raycast_terrain(*W, numRays, dRays, flags, dOutHits);
 	return W->lastError;
@@ -407,7 +408,7 @@ int mi_raycast_sensors(mi_world* world, uint32_t numRays, const mi_sensor_ray* d
 {
 	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
 	int code; bool terrain;
-	if (!queryBegin(W, numRays, dRays && dOutHits, true, code) || (code = queryTerrain(W, flags, terrain)) != MI_OK) return code;
+	if (!queryBegin(W, numRays, dRays && dOutHits, true, code) || (code = queryTerrain(W, flags, MI_RAY_TERRAIN, terrain)) != MI_OK) return code;
 	launch_raycast_sensors(*W, numRays, dRays, flags, terrain, dOutHits, dOutWorldRays);
 	return W->lastError;
 }
@@ -422,9 +423,10 @@ int mi_raycast_sensors_host(mi_world* world, uint32_t numRays, const mi_sensor_r
 int mi_proximity(mi_world* world, uint32_t numQueries, const mi_proximity_query* dQueries, uint32_t flags, mi_proximity_reading* dOut, float* dOutWorldPoints)
 {
 	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
-	int code;
-	if (!queryBegin(W, numQueries, dQueries && dOut, true, code)) return code;
-	launch_proximity(*W, numQueries, dQueries, flags, dOut, dOutWorldPoints);
+	int code; bool terrain;
+	if (!queryBegin(W, numQueries, dQueries && dOut, true, code) || (code = queryTerrain(W, flags, MI_PROX_TERRAIN, terrain)) != MI_OK) return code;
+	launch_proximity(*W, numQueries, dQueries, flags, dOut, dOutWorldPoints); // (no candidate collider: the readings are zeroed)
+	if (terrain && !W->lastError) launch_proximity_terrain(*W, numQueries, dQueries, flags, dOut);
 	return W->lastError;
 }
 int mi_proximity_host(mi_world* world, uint32_t numQueries, const mi_proximity_query* queries, uint32_t flags, mi_proximity_reading* out, float* outWorldPoints)
@@ -438,9 +440,10 @@ int mi_proximity_host(mi_world* world, uint32_t numQueries, const mi_proximity_q
 int mi_sphere_cast_batch(mi_world* world, uint32_t numQueries, const mi_sphere_cast* dQueries, uint32_t flags, mi_sphere_hit* dOut, float* dOutWorldCasts)
 {
 	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
-	int code;
-	if (!queryBegin(W, numQueries, dQueries && dOut, true, code)) return code;
-	launch_sphere_cast(*W, numQueries, dQueries, flags, dOut, dOutWorldCasts);
+	int code; bool terrain;
+	if (!queryBegin(W, numQueries, dQueries && dOut, true, code) || (code = queryTerrain(W, flags, MI_SPHERE_TERRAIN, terrain)) != MI_OK) return code;
+	launch_sphere_cast(*W, numQueries, dQueries, flags, dOut, dOutWorldCasts); // (no candidate collider: the hits are zeroed)
+	if (terrain && !W->lastError) launch_sphere_cast_terrain(*W, numQueries, dQueries, flags, dOut);
 	return W->lastError;
 }
 int mi_sphere_cast_host(mi_world* world, uint32_t numQueries, const mi_sphere_cast* queries, uint32_t flags, mi_sphere_hit* out, float* outWorldCasts)

@@ -2,29 +2,14 @@
 // after k_raycast on the records it wrote (or on zeroed records when no collider is a candidate) and replaces a record where a terrain
 // triangle is hit strictly before the collider.
 //   k_rc_terrain_tiles   uint16 min / max of the heights per 8 x 8-cell tile (16 x 16 tiles per chunk) and per chunk; built when the
-//                        heights changed (World::queries.terrainTableValid), on the world's stream, before the next terrain cast
+//                        heights changed (World::queries.terrainTableValid), on the world's stream, before the next terrain query
+//                        (launch_terrain_tables: the proximity and sphere-cast terrain passes read the same table)
 //   k_rc_terrain<false>  one lane per ray: clip to the terrain's box, walk chunks -> tiles -> cells under the ray front to back
+//                        (the sweep, its slack and the table's constants: terrain_walk.h)
 //   k_rc_terrain<true>   MI_RAY_BRUTE_FORCE: the same cell body (rtCell) over every cell of every valid chunk, no table
 // The triangles are k_heightmap's: (A, B, C) and (C, B, D) of terrainCellVertices.  The hit rule is stated in include/mi_physics.h.
 #include "world.h"
-#include "terrain_shared.h"
-
-#define RT_EPS 1.1920929e-7f
-#define RT_NO_TRIANGLE 0xFFFFFFFFu
-#define RT_CELLS (TERRAIN_VERTS - 1u)      // 128 cells per chunk and axis
-#define RT_TILE 8u                         // cells per tile and axis
-#define RT_TILES (RT_CELLS / RT_TILE)      // 16 tiles per chunk and axis
-// Slack of the walk, in space: RT_SLACK_ULPS ulps of (largest |coordinate| of the origin + largest |coordinate| of the terrain's box).
-// What it has to cover (M = that sum, eps = 2^-23): the triangle test accepts a hit by the rounded point q = fl(o + t d), which is
-// within eps (|t d| + |q|) <= 3 eps M of the exact line; the vertex coordinates fl(chunkMin + fl(c * chunkScale)) differ from the
-// walk's grid lines g + i * s by <= 3 eps M; the walk's own arithmetic (the position at an interval end, 2 roundings at <= 2 M; the
-// distance to a grid line, (line - o) * (1 / d), 3 relative roundings on a product <= 2 M) adds <= 10 eps M.  16 eps M in all; the
-// slack is twice that and is applied to both sides of every column and of every minor range.
-// In height the hit point lies on the triangle's plane within the residual of t's formula, <= 20 eps M measured along the normal
-// (6 roundings at |n| (|o| + |a|) in the numerator, 4 relative ones on t), i.e. <= 20 eps M / n.y vertically, plus the plane's slope
-// times the 3 eps M the point may lie outside the cell.  With S = amplitude / cell size (the largest height difference over a cell
-// side): slope <= sqrt(2) S and 1 / n.y <= 1 + 1.5 S, so 20 (1 + 1.5 S) + 5 S <= 32 (4 + 8 S) / 4: slackY = slack * (4 + 8 S).
-#define RT_SLACK_ULPS 32.f
+#include "terrain_walk.h"
 
 struct RtBest { float t; u32 id; V3 point; };
 
@@ -71,63 +56,7 @@ __global__ void __launch_bounds__(256) k_rc_terrain_tiles(const uint16_t* __rest
 	if (threadIdx.x == 0u) chunkRange[chunk] = (max(max(sHi[0], sHi[1]), max(sHi[2], sHi[3])) << 16) | min(min(sLo[0], sLo[1]), min(sLo[2], sLo[3]));
 }
 
-// ---- the walk ----------------------------------------------------------------------------------------------------------------------
-// The walk runs in its own parameter s = t * dmax (dmax = the direction's largest |component|), with the direction divided by dmax:
-// the axis the ray moves fastest along has |component| 1, nothing overflows for a tiny or huge direction, and an axis whose component
-// is below 1e-12 of the largest is treated as not moved along (over the terrain's extent it moves 1e-12 of that extent, far below
-// the slack), so nothing divides by zero: a vertical ray covers one cell column, or up to four cells when its origin lies on grid lines.
-struct RtRay
-{
-	V3 o, d; float dmax;             // d: direction / dmax
-	bool parX, parY, parZ;
-	float slack, slackY;
-};
-MI_DEV int rtIndex(float v, int lo, int hi) { return (int)fminf(fmaxf(floorf(v), (float)lo), (float)hi); } // (a NaN gives lo)
-
-// The squares (ix, iz), ix0 <= ix <= ix1, iz0 <= iz <= iz1, of a grid with lines gx + ix * s, gz + iz * s whose slack-widened extent
-// the ray touches within [sa, sb] (walk parameter), front to back along the axis the ray moves faster on: visit(ix, iz, a, b) with
-// [a, b] the widened interval the ray spends in the square's column; visit returns true to end this sweep (nothing further along
-// can be entered before the best hit).  Conservative: a square is left out only if the widened ray misses its widened column.
-template <class F>
-MI_DEV void rtSweep(const RtRay& q, float gx, float gz, float s, int ix0, int ix1, int iz0, int iz1, float sa, float sb, F&& visit)
-{
-	const float invS = 1.f / s;
-	if (q.parX && q.parZ)
-	{
-		const int xa = rtIndex((q.o.x - q.slack - gx) * invS, ix0, ix1), xb = rtIndex((q.o.x + q.slack - gx) * invS, ix0, ix1);
-		const int za = rtIndex((q.o.z - q.slack - gz) * invS, iz0, iz1), zb = rtIndex((q.o.z + q.slack - gz) * invS, iz0, iz1);
-		for (int iz = za; iz <= zb; ++iz) for (int ix = xa; ix <= xb; ++ix) if (visit(ix, iz, sa, sb)) return;
-		return;
-	}
-	const bool majorX = !q.parX && (q.parZ || fabsf(q.d.x) >= fabsf(q.d.z));
-	const float om = majorX ? q.o.x : q.o.z, dm = majorX ? q.d.x : q.d.z, gm = majorX ? gx : gz;
-	const float on = majorX ? q.o.z : q.o.x, dn = majorX ? q.d.z : q.d.x, gn = majorX ? gz : gx;
-	const int m0 = majorX ? ix0 : iz0, m1 = majorX ? ix1 : iz1, n0 = majorX ? iz0 : ix0, n1 = majorX ? iz1 : ix1;
-	const float invM = 1.f / dm, slackS = q.slack * fabsf(invM);
-	const float pa = om + sa * dm, pb = om + sb * dm;
-	const int ma = rtIndex((fminf(pa, pb) - q.slack - gm) * invS, m0, m1), mb = rtIndex((fmaxf(pa, pb) + q.slack - gm) * invS, m0, m1);
-	for (int k = 0; k <= mb - ma; ++k)
-	{
-		const int im = dm > 0.f ? ma + k : mb - k;
-		const float s0 = ((gm + (float)im * s - q.slack) - om) * invM, s1 = ((gm + (float)(im + 1) * s + q.slack) - om) * invM;
-		const float a = fmaxf(fminf(s0, s1) - slackS, sa), b = fminf(fmaxf(s0, s1) + slackS, sb);
-		if (a > b) continue;
-		const float na = on + a * dn, nb = on + b * dn;
-		const int ia = rtIndex((fminf(na, nb) - q.slack - gn) * invS, n0, n1), ib = rtIndex((fmaxf(na, nb) + q.slack - gn) * invS, n0, n1);
-		for (int j = 0; j <= ib - ia; ++j)
-		{
-			const int in = dn >= 0.f ? ia + j : ib - j;
-			if (visit(majorX ? im : in, majorX ? in : im, a, b)) return;
-		}
-	}
-}
-// Does the ray's height over [a, b], widened by slackY, miss the heights [lo, hi] (uint16)?  (A NaN does not miss.)
-MI_DEV bool rtMissesHeights(const RtRay& q, const TerrainParams& P, float a, float b, u32 lo, u32 hi)
-{
-	const float ya = q.o.y + a * q.d.y, yb = q.o.y + b * q.d.y;
-	return fminf(ya, yb) - q.slackY > (float)hi * P.heightScale + P.minY || fmaxf(ya, yb) + q.slackY < (float)lo * P.heightScale + P.minY;
-}
-
+// ---- the walk (RtRay, rtSweep, rtMissesHeights: terrain_walk.h) -------------------------------------------------------------------
 // Ray i: reads the record k_raycast wrote, replaces it if a terrain triangle is hit strictly before the collider.
 template <bool BRUTE>
 MI_DEV void rtRay(u32 i, const float4* __restrict__ rays, float4* __restrict__ out, const TerrainParams& P, const uint16_t* __restrict__ heights,
@@ -220,6 +149,17 @@ __global__ void __launch_bounds__(64) k_rc_terrain(u32 numRays, const float4* __
 	if (i < numRays) rtRay<BRUTE>(i, rays, out, P, heights, valid, tiles, chunkRange);
 }
 
+bool launch_terrain_tables(World& w)
+{
+	const u32 chunks = w.terrain.chunksPerDim * w.terrain.chunksPerDim;
+	if (w.queries.terrainTableValid || !chunks) return !w.lastError;
+	w.queries.terrainTiles.ensure((size_t)chunks * RT_TILES * RT_TILES, w.stream); w.queries.terrainChunkRange.ensure(chunks, w.stream);
+	if (w.lastError) return false;
+	hipLaunchKernelGGL(k_rc_terrain_tiles, dim3(chunks), dim3(256), 0, w.stream, w.terrain.heights.p, w.queries.terrainTiles.p, w.queries.terrainChunkRange.p);
+	w.queries.terrainTableValid = true;
+	return true;
+}
+
 void launch_raycast_terrain(World& w, u32 numRays, const float* dRays, u32 flags, mi_ray_hit* dOutHits)
 {
 	const u32 chunks = w.terrain.chunksPerDim * w.terrain.chunksPerDim;
@@ -230,12 +170,6 @@ void launch_raycast_terrain(World& w, u32 numRays, const float* dRays, u32 flags
 		hipLaunchKernelGGL(k_rc_terrain<true>, dim3((numRays + 63) / 64), dim3(64), 0, w.stream, numRays, (const float4*)dRays, (float4*)dOutHits, P, w.terrain.heights.p, w.terrain.valid.p, (const u32*)nullptr, (const u32*)nullptr);
 		return;
 	}
-	if (!w.queries.terrainTableValid)
-	{
-		w.queries.terrainTiles.ensure((size_t)chunks * RT_TILES * RT_TILES, w.stream); w.queries.terrainChunkRange.ensure(chunks, w.stream);
-		if (w.lastError) return;
-		hipLaunchKernelGGL(k_rc_terrain_tiles, dim3(chunks), dim3(256), 0, w.stream, w.terrain.heights.p, w.queries.terrainTiles.p, w.queries.terrainChunkRange.p);
-		w.queries.terrainTableValid = true;
-	}
+	if (!launch_terrain_tables(w)) return;
 	hipLaunchKernelGGL(k_rc_terrain<false>, dim3((numRays + 63) / 64), dim3(64), 0, w.stream, numRays, (const float4*)dRays, (float4*)dOutHits, P, w.terrain.heights.p, w.terrain.valid.p, w.queries.terrainTiles.p, w.queries.terrainChunkRange.p);
 }

@@ -22,16 +22,18 @@ struct ScHit { u32 hit; float t, gap; V3 c, n; u32 iterations; };
 
 MI_DEV float scTol(float lenO, float t, float L, float radius) { return SC_GAP + (SC_GUARD_ULPS * SC_EPS) * ((lenO + t * L) + radius); }
 
+// The march over any distance function dist(p) -> PtHit {d, c, n} that is convex along a line and 1-Lipschitz: a collider's signed
+// distance (below) or the unsigned distance to one terrain triangle (terrain_point.h).
 // L = |world direction|, formed once per query; maxT >= 0, radius >= 0 (the caller has sorted out the rest).
-template <typename Hull>
-MI_DEV ScHit sphereCastCollider(V3 o, V3 v, float L, float radius, float maxT, float beyond, u32 type, const float* s, const Hull& hull)
+template <typename Dist>
+MI_DEV ScHit sphereCastMarch(V3 o, V3 v, float L, float radius, float maxT, float beyond, const Dist& dist)
 {
 	ScHit h; h.hit = SC_MISS; h.t = 0.f; h.gap = 0.f; h.c = v3s(0.f); h.n = v3s(0.f); h.iterations = 0u;
 	const float lenO = length(o);
 	float t = 0.f, tPrev = 0.f, gPrev = 0.f;
 	for (u32 it = 0; it < SC_MAX_ITER; ++it)
 	{
-		const PtHit p = pointBodyCollider(o + t * v, type, s, hull);
+		const PtHit p = dist(o + t * v);
 		const float g = p.d - radius;
 		h.t = t; h.gap = g; h.c = p.c; h.n = p.n; h.iterations = it + 1u;
 		if (g <= scTol(lenO, t, L, radius)) { h.hit = SC_HIT; return h; } // (also an origin in touch or inside: t = 0, the gap negative)
@@ -50,4 +52,10 @@ MI_DEV ScHit sphereCastCollider(V3 o, V3 v, float L, float radius, float maxT, f
 	}
 	h.hit = SC_UNRESOLVED;                                                  // free up to h.t, and the caller sees the flag
 	return h;
+}
+// A collider (type, s = the 10 shape floats of its LOCAL record) in its own frame.
+template <typename Hull>
+MI_DEV ScHit sphereCastCollider(V3 o, V3 v, float L, float radius, float maxT, float beyond, u32 type, const float* s, const Hull& hull)
+{
+	return sphereCastMarch(o, v, L, radius, maxT, beyond, [&](V3 p) { return pointBodyCollider(p, type, s, hull); });
 }

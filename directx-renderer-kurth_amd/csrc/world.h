@@ -426,6 +426,8 @@ RcBuild launch_raycast_build(World& w, bool withStatic, bool brute); // k_raycas
 void launch_proximity(World& w, u32 n, const mi_proximity_query* dQueries, u32 flags, mi_proximity_reading* dOut, float* dOutWorldPoints); // k_proximity.hip
 void launch_sphere_cast(World& w, u32 n, const mi_sphere_cast* dQueries, u32 flags, mi_sphere_hit* dOut, float* dOutWorldCasts); // k_spherecast.hip
 void launch_raycast_sensors(World& w, u32 numRays, const mi_sensor_ray* dRays, u32 flags, bool terrain, mi_sensor_hit* dOutHits, float* dOutWorldRays); // k_raycast_sensors.hip
+void launch_proximity_terrain(World& w, u32 n, const mi_proximity_query* dQueries, u32 flags, mi_proximity_reading* dOut); // k_proximity_terrain.hip: after launch_proximity, on its records
+void launch_sphere_cast_terrain(World& w, u32 n, const mi_sphere_cast* dQueries, u32 flags, mi_sphere_hit* dOut); // k_spherecast_terrain.hip: after launch_sphere_cast, on its records
 void launch_raycast_terrain(World& w, u32 numRays, const float* dRays, u32 flags, mi_ray_hit* dOutHits); // k_raycast_terrain.hip: after launch_raycast, on its records
 void launch_contact_sensors(World& w, u32 numSensors, const mi_contact_sensor* dSensors, mi_contact_reading* dOut, bool withRows); // k_contact_sensors.hip
 void launch_lerp_pose(World& w, float t);

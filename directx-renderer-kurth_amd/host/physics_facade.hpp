@@ -458,67 +458,72 @@ namespace mi
 	// A proximity sensor fixed to a rigid body: localPoint is in the body's frame at its current pose; the nearest collider surface within
 	// `radius` of it (signed distance, negative inside; the closest point and the outward normal in world space; include/mi_physics.h
 	// states the rule), the number of colliders within the radius, or false.  excludeSelf: the body's own colliders are no candidates.
-	// The heightmap is no candidate.  One query through mi_proximity.
-	struct proximity_hit { float distance = 0.f; vec3 point, normal; uint32_t collider = 0, body = MI_STATIC_BODY, numWithin = 0; };
-	inline bool nearestSurface(game_scene& scene, const scene_entity& body, vec3 localPoint, float radius, proximity_hit& out, bool excludeSelf = true)
+	// withTerrain: the heightmap is a candidate too, the solid under its surface (MI_PROX_TERRAIN): such a reading has collider ==
+	// MI_TERRAIN_COLLIDER, a negative distance below the surface and the nearest triangle's id in `triangle`; it counts in numWithin and
+	// is never excluded.  One query through mi_proximity.
+	struct proximity_hit { float distance = 0.f; vec3 point, normal; uint32_t collider = 0, body = MI_STATIC_BODY, numWithin = 0, triangle = 0; };
+	inline bool nearestSurface(game_scene& scene, const scene_entity& body, vec3 localPoint, float radius, proximity_hit& out, bool excludeSelf = true, bool withTerrain = false)
 	{
 		scene.flushStaticColliders();
 		mi_proximity_query in{};
 		in.point[0] = localPoint.x; in.point[1] = localPoint.y; in.point[2] = localPoint.z; in.radius = radius;
 		in.mount = body.body(); in.excludeFirst = in.mount; in.excludeCount = excludeSelf ? 1u : 0u; in.enabled = 1u;
 		mi_proximity_reading r{};
-		scene.check(mi_proximity_host(scene.world, 1u, &in, (uint32_t)(MI_PROX_STATIC | MI_PROX_COUNT), &r, nullptr), "nearestSurface");
+		scene.check(mi_proximity_host(scene.world, 1u, &in, (uint32_t)(MI_PROX_STATIC | MI_PROX_COUNT | (withTerrain ? MI_PROX_TERRAIN : 0)), &r, nullptr), "nearestSurface");
 		if (!r.found) return false;
 		out.distance = r.distance; out.point = vec3(r.point[0], r.point[1], r.point[2]); out.normal = vec3(r.normal[0], r.normal[1], r.normal[2]);
 		out.collider = r.collider; out.body = r.body; out.numWithin = r.numWithin;
+		memcpy(&out.triangle, &r.reserved, sizeof(uint32_t));
 		return true;
 	}
-	// How many colliders (rigid bodies' and static ones) lie within `radius` of a world-space point: 0 means that sphere of space is free.
-	inline uint32_t countWithin(game_scene& scene, vec3 worldPoint, float radius)
+	// How many colliders (rigid bodies' and static ones; withTerrain: plus 1 for the heightmap) lie within `radius` of a world-space point:
+	// 0 means that sphere of space is free.
+	inline uint32_t countWithin(game_scene& scene, vec3 worldPoint, float radius, bool withTerrain = false)
 	{
 		scene.flushStaticColliders();
 		mi_proximity_query in{};
 		in.point[0] = worldPoint.x; in.point[1] = worldPoint.y; in.point[2] = worldPoint.z; in.radius = radius;
 		in.mount = MI_STATIC_BODY; in.enabled = 1u;
 		mi_proximity_reading r{};
-		scene.check(mi_proximity_host(scene.world, 1u, &in, (uint32_t)(MI_PROX_STATIC | MI_PROX_COUNT), &r, nullptr), "countWithin");
+		scene.check(mi_proximity_host(scene.world, 1u, &in, (uint32_t)(MI_PROX_STATIC | MI_PROX_COUNT | (withTerrain ? MI_PROX_TERRAIN : 0)), &r, nullptr), "countWithin");
 		return r.numWithin;
 	}
 
-	// A sphere cast ("thick ray") against the whole scene (rigid bodies and static colliders; the heightmap is no candidate): how far a
+	// A sphere cast ("thick ray") against the whole scene (rigid bodies and static colliders; withTerrain: also the heightmap's triangles,
+	// a two-sided sheet, MI_SPHERE_TERRAIN: such a hit has collider == MI_TERRAIN_COLLIDER and carries no triangle id): how far a
 	// sphere of `radius` travels from origin along direction, in units of the direction's length and at most maxT, before it touches
 	// something (include/mi_physics.h states the rule), or false.  distance: the t at which it stops (0 when it starts in touch), its
 	// centre is then origin + distance * direction; point and normal: the closest surface point and the outward normal there, in world
 	// space; gap: what is left between sphere and surface (negative when overlapping); unresolved: the cast used up its iterations and the
 	// sphere is only known to be free up to distance.  One query through mi_sphere_cast_batch.
 	struct sphere_hit { float distance = 0.f, gap = 0.f; vec3 point, normal; uint32_t collider = 0, body = MI_STATIC_BODY; bool unresolved = false; };
-	inline bool castSphereQuery(game_scene& scene, const mi_sphere_cast& in, sphere_hit& out, const char* what)
+	inline bool castSphereQuery(game_scene& scene, const mi_sphere_cast& in, sphere_hit& out, const char* what, bool withTerrain = false)
 	{
 		scene.flushStaticColliders();
 		mi_sphere_hit h{};
-		scene.check(mi_sphere_cast_host(scene.world, 1u, &in, (uint32_t)MI_SPHERE_STATIC, &h, nullptr), what);
+		scene.check(mi_sphere_cast_host(scene.world, 1u, &in, (uint32_t)(MI_SPHERE_STATIC | (withTerrain ? MI_SPHERE_TERRAIN : 0)), &h, nullptr), what);
 		if (!h.hit) return false;
 		out.distance = h.t; out.gap = h.gap; out.point = vec3(h.point[0], h.point[1], h.point[2]); out.normal = vec3(h.normal[0], h.normal[1], h.normal[2]);
 		out.collider = h.collider; out.body = h.body; out.unresolved = h.hit == 2u;
 		return true;
 	}
-	inline bool castSphere(game_scene& scene, vec3 origin, vec3 direction, float radius, float maxT, sphere_hit& out)
+	inline bool castSphere(game_scene& scene, vec3 origin, vec3 direction, float radius, float maxT, sphere_hit& out, bool withTerrain = false)
 	{
 		mi_sphere_cast in{};
 		in.origin[0] = origin.x; in.origin[1] = origin.y; in.origin[2] = origin.z; in.maxT = maxT;
 		in.direction[0] = direction.x; in.direction[1] = direction.y; in.direction[2] = direction.z; in.radius = radius;
 		in.mount = MI_STATIC_BODY; in.enabled = 1u;
-		return castSphereQuery(scene, in, out, "castSphere");
+		return castSphereQuery(scene, in, out, "castSphere", withTerrain);
 	}
 	// The same cast fixed to a rigid body: localOrigin and localDirection are in the body's frame at its current pose.  excludeSelf: the
 	// body's own colliders are no candidates, so the sphere may start inside its carrier (a foot probe).
-	inline bool castSensorSphere(game_scene& scene, const scene_entity& body, vec3 localOrigin, vec3 localDirection, float radius, float maxT, sphere_hit& out, bool excludeSelf = true)
+	inline bool castSensorSphere(game_scene& scene, const scene_entity& body, vec3 localOrigin, vec3 localDirection, float radius, float maxT, sphere_hit& out, bool excludeSelf = true, bool withTerrain = false)
 	{
 		mi_sphere_cast in{};
 		in.origin[0] = localOrigin.x; in.origin[1] = localOrigin.y; in.origin[2] = localOrigin.z; in.maxT = maxT;
 		in.direction[0] = localDirection.x; in.direction[1] = localDirection.y; in.direction[2] = localDirection.z; in.radius = radius;
 		in.mount = body.body(); in.excludeFirst = in.mount; in.excludeCount = excludeSelf ? 1u : 0u; in.enabled = 1u;
-		return castSphereQuery(scene, in, out, "castSensorSphere");
+		return castSphereQuery(scene, in, out, "castSensorSphere", withTerrain);
 	}
 
 	// What the contacts of the last internal step did to a rigid body (no counterpart in the reference's physics.h; include/mi_physics.h

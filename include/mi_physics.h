@@ -342,7 +342,7 @@ int mi_raycast_sensors_host(mi_world* w, uint32_t numRays, const mi_sensor_ray* 
  * NULL) receives 4 floats per query: the world point and the radius.  The colliders of the bodies b with b - excludeFirst < excludeCount,
  * in uint32 arithmetic (the subtraction wraps), are no candidates of this query; static colliders are never excluded.
  * Candidates are mi_raycast_batch's: the colliders of alive bodies simulated here and, with MI_PROX_STATIC, those of entities without a
- * rigid body; never force-field or trigger colliders, never cloth.  The heightmap terrain is NOT a candidate of this entry point.
+ * rigid body; never force-field or trigger colliders, never cloth; with MI_PROX_TERRAIN also the heightmap terrain (below).
  * Distance: the signed Euclidean distance d from the world point to each candidate, negative inside, with the closest surface point c
  * and the outward unit normal n there.  It is evaluated in the collider's own frame, p = conjugate(rot) * (world point - pos), for an
  * OBB and a hull further through the conjugate of the shape's quaternion; c and n are rotated (and c translated) back the same way.
@@ -375,9 +375,32 @@ int mi_raycast_sensors_host(mi_world* w, uint32_t numRays, const mi_sensor_ray* 
  * without the flag 0.  With nothing within the whole record is zero.
  * The candidates and the tree over them are mi_raycast_batch's, rebuilt from the current poses at every call in the same buffers;
  * MI_PROX_BRUTE_FORCE asks every candidate instead (same bytes; a yardstick).  Calls of the two kinds may follow each other freely.
+ * MI_PROX_TERRAIN: the heightmap terrain is one more candidate, the solid under its surface.  Without the flag every byte of every
+ * record is what it is without a heightmap; with the flag and no heightmap the flag does nothing.  The triangles are mi_raycast_batch's
+ * (MI_RAY_TERRAIN above): cell (cellX, cellZ) of a chunk that has heights has the vertices A, B, C, D in world coordinates, triangle
+ * 0 = (A, B, C), triangle 1 = (C, B, D), id = ((chunkZ * chunksPerDim + chunkX) * 16384 + cellZ * 128 + cellX) * 2 + triangle.  Per
+ * triangle f = (a, b, c): n_f = unit(cross(b - a, c - a)), c_f = the hull rule's closest point of the triangle to the world point p,
+ * d_f = |p - c_f|.  Arithmetic is float32 without contraction in the order csrc/terrain_point.h writes out.
+ *   nearest   the triangle with the smallest d_f, of equal d_f the lowest id
+ *   sign      among the triangles that own p's (x, z) by the ray rule's closed containment with q = p (u = (p.x - A.x) / (D.x - A.x),
+ *             v = (p.z - A.z) / (D.z - A.z), both in [0, 1]; triangle 0 owns u + v <= 1, triangle 1 owns u + v >= 1) the one with the
+ *             lowest id decides: p is below iff dot(p - a_f, n_f) < 0.  A point over no chunk that has heights (outside the footprint,
+ *             over a hole) is never below: the terrain has no side walls and no floor.  This is a stated limit: beside the rim, or under
+ *             a hole's border, a point lower than the surface next to it reads a positive distance to that surface.
+ *   reading   d = d_f above, -d_f below; point = c_f; normal = unit(p - c_f) above, unit(c_f - p) below, n_f where p == c_f
+ * The terrain is within iff d <= radius, so a point below the surface is within for every radius >= 0, however deep (the search for
+ * its nearest triangle is bounded by the distance to the triangles of its own column, never by the radius).  The terrain's reading
+ * replaces the colliders' only if its d is strictly smaller (MI_TERRAIN_COLLIDER is the largest index: "the lowest collider index on a
+ * tie").  A terrain reading has collider = MI_TERRAIN_COLLIDER, body = MI_STATIC_BODY and in `reserved` the bits of the uint32 triangle
+ * id of the nearest triangle, as mi_ray_hit has; for a collider reading reserved stays 0.  With MI_PROX_COUNT the terrain adds exactly 1
+ * to numWithin when it is within, also when a collider is nearer.  Exclusion ranges never exclude the terrain; mounts, switched-off
+ * queries and dOutWorldPoints are unchanged.  A world point that is not finite does not meet the terrain.  A heightmap of more than
+ * 131071 chunks makes a call with the flag return MI_ERR_INVALID_ARGUMENT.  The search uses the ray cast's min/max table of the heights
+ * (rebuilt after mi_set_heightmap / mi_heightmap_set_chunk / a restore; mi_heightmap_update needs no rebuild);
+ * MI_PROX_BRUTE_FORCE | MI_PROX_TERRAIN asks every triangle of every chunk instead (same bytes).
  * mi_proximity_host: queries, readings and world points in HOST memory, staged through buffers of the world; returns after the
  * readings have arrived. */
-enum { MI_PROX_STATIC = 1, MI_PROX_BRUTE_FORCE = 2, MI_PROX_COUNT = 4 };
+enum { MI_PROX_STATIC = 1, MI_PROX_BRUTE_FORCE = 2, MI_PROX_COUNT = 4, MI_PROX_TERRAIN = 8 };
 typedef struct mi_proximity_query { float point[3], radius; uint32_t mount, excludeFirst, excludeCount, enabled; } mi_proximity_query; /* 32 bytes */
 typedef struct mi_proximity_reading { float distance; uint32_t collider, body, found; float point[3]; uint32_t numWithin;
                                       float normal[3], reserved; } mi_proximity_reading; /* 48 bytes */
@@ -395,7 +418,7 @@ int mi_proximity_host(mi_world* w, uint32_t numQueries, const mi_proximity_query
  * 8 floats per query: {world origin, maxT, world direction, radius}.  The colliders of the bodies b with b - excludeFirst <
  * excludeCount, in uint32 arithmetic (the subtraction wraps), are no candidates of this query; static colliders are never excluded.
  * Candidates: the colliders of alive bodies simulated here and, with MI_SPHERE_STATIC, those of entities without a rigid body; never
- * force-field or trigger colliders, never cloth.  The heightmap terrain is NOT a candidate of this entry point.
+ * force-field or trigger colliders, never cloth; with MI_SPHERE_TERRAIN also the heightmap terrain (below).
  * Query: the direction need not be a unit vector and t is in units of its length, as for the ray cast; L = |world direction| is formed
  * once per query.  maxT may be +INFINITY.  A negative or NaN radius and a negative or NaN maxT find nothing, also from inside a shape.
  * radius == 0 is allowed: a ray cast by the distance rule below (not by the reference's ray tests).
@@ -417,9 +440,25 @@ int mi_proximity_host(mi_world* w, uint32_t numQueries, const mi_proximity_query
  * the samples the winner took.  The sphere's centre at the stop is world origin + t * world direction.  A miss is all zero.
  * The candidates and the tree over them are mi_raycast_batch's, rebuilt from the current poses at every call in the same buffers;
  * MI_SPHERE_BRUTE_FORCE asks every candidate instead (same bytes; a yardstick).  Calls of all query kinds may follow each other freely.
+ * MI_SPHERE_TERRAIN: the heightmap terrain is a two-sided sheet of convex candidates, as it is for rays.  Without the flag every byte of
+ * every record is what it is without a heightmap; with the flag and no heightmap the flag does nothing.  Each triangle f = (a, b, c) of
+ * mi_proximity's terrain rule (above) is one candidate, in world space (o = world origin, v = world direction), with the unsigned gap
+ * g_f(t) = |(o + t v) - c_f(o + t v)| - radius: the distance to a triangle is convex along a line and 1-Lipschitz, so the march above
+ * applies to it unchanged (the same tolerance, step rule, SC_MAX_ITER and unresolved flag; csrc/terrain_point.h on csrc/sphere_cast.h).
+ * The smallest t wins; of equal t a collider wins before the terrain, and among triangles the lowest id.  A terrain hit: hit = 1 (or 2),
+ * t, collider = MI_TERRAIN_COLLIDER, body = MI_STATIC_BODY, point = c_f at the stop, normal = unit(centre - c_f) with centre = o + t v,
+ * and n_f where they coincide; gap and iterations of the winning triangle.  mi_sphere_hit has no spare field: a terrain hit carries no
+ * triangle id (mi_proximity with MI_PROX_TERRAIN at the centre names the triangle).  Limits, the sheet against mi_proximity's solid: an
+ * origin nearer to the sheet than radius + tolerance, on either side, hits at t = 0 with its gap; an origin under the sheet by more than
+ * that travels freely until it touches the sheet from below (the normal then points down).  radius == 0 is a ray cast by this rule, not
+ * by MI_RAY_TERRAIN's plane test.  Chunks without heights are holes.  A zero direction is an overlap test at the origin, as above; a
+ * cast whose world origin, direction or radius is not finite does not meet the terrain.  Exclusion ranges never exclude the terrain.
+ * A heightmap of more than 131071 chunks makes a call with the flag return MI_ERR_INVALID_ARGUMENT.  The walk visits the cells under
+ * the swept sphere front to back with the ray cast's min/max table; MI_SPHERE_BRUTE_FORCE | MI_SPHERE_TERRAIN marches every triangle of
+ * every chunk instead (same bytes).
  * mi_sphere_cast_host: queries, hits and world casts in HOST memory, staged through buffers of the world; returns after the hits have
  * arrived. */
-enum { MI_SPHERE_STATIC = 1, MI_SPHERE_BRUTE_FORCE = 2 };
+enum { MI_SPHERE_STATIC = 1, MI_SPHERE_BRUTE_FORCE = 2, MI_SPHERE_TERRAIN = 4 };
 typedef struct mi_sphere_cast { float origin[3], maxT, direction[3], radius; uint32_t mount, excludeFirst, excludeCount, enabled; } mi_sphere_cast; /* 48 bytes */
 typedef struct mi_sphere_hit { float t; uint32_t collider, body, hit; float point[3], gap; float normal[3]; uint32_t iterations; } mi_sphere_hit; /* 48 bytes */
 int mi_sphere_cast_batch(mi_world* w, uint32_t numQueries, const mi_sphere_cast* dQueries, uint32_t flags, mi_sphere_hit* dOut, float* dOutWorldCasts);
