@@ -126,6 +126,14 @@ SPHERE_CAST_DTYPE = np.dtype([("origin", "<f4", 3), ("maxT", "<f4"), ("direction
 SPHERE_HIT_DTYPE = np.dtype([("t", "<f4"), ("collider", "<u4"), ("body", "<u4"), ("hit", "<u4"), ("point", "<f4", 3), ("gap", "<f4"),
                              ("normal", "<f4", 3), ("iterations", "<u4")])
 SPHERE_STATIC, SPHERE_BRUTE_FORCE, SPHERE_TERRAIN = 1, 2, 4   # mi_sphere_cast_batch's flags (MI_SPHERE_*)
+# mi_overlap_query / mi_overlap_summary / mi_overlap_hit (include/mi_physics.h): one volume of mi_overlap_batch in the frame of body `mount`, 96 bytes;
+# the head of a query's output block, 16 bytes; one of the max_hits records behind it, 8 bytes
+OVERLAP_QUERY_DTYPE = np.dtype([("shape", "<f4", 10), ("type", "<u4"), ("enabled", "<u4"), ("pos", "<f4", 3), ("mount", "<u4"), ("rot", "<f4", 4),
+                                ("excludeFirst", "<u4"), ("excludeCount", "<u4"), ("reserved", "<u4", 2)])
+OVERLAP_SUMMARY_DTYPE = np.dtype([("numOverlaps", "<u4"), ("numWritten", "<u4"), ("valid", "<u4"), ("reserved", "<u4")])
+OVERLAP_HIT_DTYPE = np.dtype([("collider", "<u4"), ("body", "<u4")])
+OVERLAP_STATIC, OVERLAP_BRUTE_FORCE = 1, 2   # mi_overlap_batch's flags (MI_OVERLAP_*)
+OVERLAP_MAX_HITS = 1024                      # MI_OVERLAP_MAX_HITS
 TERRAIN_COLLIDER = 0xFFFFFFFE   # mi_ray_hit.collider of a hit on the heightmap terrain (MI_TERRAIN_COLLIDER)
 
 
@@ -183,6 +191,7 @@ EXPORTED_SYMBOLS = [
     "mi_contact_sensors", "mi_contact_sensors_host", "mi_debug_read_contact_rows",
     "mi_proximity", "mi_proximity_host",
     "mi_sphere_cast_batch", "mi_sphere_cast_host",
+    "mi_overlap_batch", "mi_overlap_host",
 ]
 
 
@@ -679,6 +688,49 @@ class World:
         out, wc = np.zeros(len(rec), SPHERE_HIT_DTYPE), np.zeros((len(rec), 8), np.float32)
         self._query_numpy(entry(self.lib.mi_sphere_cast_batch if device else self.lib.mi_sphere_cast_host), rec, out, wc if world_casts else None, device)
         return (out, wc) if world_casts else out
+
+    def overlap(self, ctype, shape=None, pos=(0, 0, 0), rot=(0, 0, 0, 1), mount=None, exclude_first=None, exclude_count=None, max_hits=16, static=True,
+                brute_force=False, world_shapes=False, device=False):
+        """mi_overlap_batch: per volume the colliders it touches right now, "a trigger you ask once": the step's own decision for a trigger
+        collider of that shape at that pose: the world boxes meet and the trigger's boolean test answers true (the rule is in
+        include/mi_physics.h).  ctype, shape: what add_collider takes (SPHERE ... HULL and up to 10 floats; missing words are zero), one
+        volume or arrays [n], [n, k]; pos [n, 3], rot [n, 4]: the volume's pose in the frame of body mount[i] at its current pose (mount:
+        an index or an array [n]; None / STATIC_BODY: the world pose, the one a trigger entity has); blind to the colliders of the bodies
+        exclude_first[i] ... + exclude_count[i] - 1; static: the colliders of entities without a rigid body are candidates too.
+        `ctype` may also be an OVERLAP_QUERY_DTYPE array (the other query arguments are then not used).
+        numpy queries return (summary [n] of OVERLAP_SUMMARY_DTYPE, colliders [n, max_hits], bodies [n, max_hits]): numOverlaps counts every
+        overlapping candidate, the lists hold the numWritten = min(numOverlaps, max_hits) lowest collider indices, ascending, and zeros
+        behind them; with world_shapes=True a fourth array [n, 20] follows: the world record's 10 shape words, the bits of its type, 0, the
+        world box min xyz, 0, max xyz, 0.  Through the world's staging buffers (mi_overlap_host), or with device=True through device
+        tensors of the caller's (mi_overlap_batch).
+        A torch tensor on the device (float32, contiguous, [n, 24]: the bits of mi_overlap_query) is queried in place: returns one float32
+        tensor [n, 4 + 2 * max_hits] of raw blocks (view them with .view(torch.int32)), with world_shapes=True a tuple with the [n, 20]
+        world shapes; enqueued on the world's stream with no synchronisation.  (The tensor is recorded on that stream, as in raycast:
+        release it before close().)"""
+        flags = (OVERLAP_STATIC if static else 0) | (OVERLAP_BRUTE_FORCE if brute_force else 0)
+        max_hits = int(max_hits)
+        if max_hits < 0:
+            raise ValueError("overlap: max_hits must not be negative")
+
+        def entry(fn):
+            return lambda n, d_in, d_out, d_aux: fn(self.w, C.c_uint32(n), C.c_void_p(d_in), C.c_uint32(max_hits), C.c_uint32(flags), C.c_void_p(d_out), C.c_void_p(d_aux))
+        if _is_tensor(ctype):
+            return self._query_in_place("overlap", entry(self.lib.mi_overlap_batch), ctype, 24, 4 + 2 * max_hits, 20 if world_shapes else 0)
+        if isinstance(ctype, np.ndarray) and ctype.dtype == OVERLAP_QUERY_DTYPE:
+            rec = np.ascontiguousarray(ctype).reshape(-1)
+        else:
+            sh = np.atleast_2d(np.asarray(shape, np.float32))
+            n = max(len(sh), np.atleast_1d(ctype).size, np.atleast_2d(np.asarray(pos)).shape[0], np.atleast_2d(np.asarray(rot)).shape[0], np.atleast_1d(0 if mount is None else mount).size)
+            rec = np.zeros(n, OVERLAP_QUERY_DTYPE)
+            rec["shape"][:, :sh.shape[1]] = sh
+            rec["type"], rec["enabled"], rec["pos"], rec["rot"] = np.asarray(ctype, np.uint32), 1, np.asarray(pos, np.float32), np.asarray(rot, np.float32)
+            _fill_mount(rec, mount, exclude_first, exclude_count)
+        n = len(rec)
+        out, ws = np.zeros(n, np.dtype([("words", "<u4", (4 + 2 * max_hits,))])), np.zeros((n, 20), np.float32)
+        self._query_numpy(entry(self.lib.mi_overlap_batch if device else self.lib.mi_overlap_host), rec, out, ws if world_shapes else None, device)
+        words = out["words"].reshape(n, 4 + 2 * max_hits)
+        result = (words[:, :4].copy().view(OVERLAP_SUMMARY_DTYPE).reshape(n), words[:, 4::2].copy(), words[:, 5::2].copy())
+        return result + (ws,) if world_shapes else result
 
     def contact_sensors(self, sensors, device=False):
         """mi_contact_sensors: per sensor the impulses the contacts of the last internal step applied to its body, summed on the device

@@ -321,7 +321,7 @@ struct World
 	void uploadFields(); void ensureEventBuffers(u32 numPairs);
 
 	// World queries, rebuilt at every call: api.hip (entries, staging, buildInteractTables), k_interact.hip, k_raycast.hip, raycast_shared.h,
-	// k_raycast_terrain.hip, k_raycast_sensors.hip, k_proximity.hip, k_spherecast.hip, k_contact_sensors.hip
+	// k_raycast_terrain.hip, k_raycast_sensors.hip, k_proximity.hip, k_spherecast.hip, k_overlap.hip, k_contact_sensors.hip
 	struct Queries
 	{
 		// mi_test_physics_interaction_batch: colliders of every body (CSR), hull triangles as global vertex indices; rebuilt after upload()
@@ -336,7 +336,7 @@ struct World
 		// mi_raycast_sensors (k_raycast_sensors.hip): per ray the world ray (2 x float4, used when the caller wants none back), the 32-byte
 		// record k_raycast and k_rc_terrain work on (2 x float4) and the exclusion range {first, count}
 		DevBuf<float4> sensorRays, sensorHits; DevBuf<uint2> sensorExclude;
-		// (mi_proximity, k_proximity.hip, and mi_sphere_cast_batch, k_spherecast.hip, walk the tree above and keep nothing of their own)
+		// (mi_proximity, k_proximity.hip, mi_sphere_cast_batch, k_spherecast.hip, and mi_overlap_batch, k_overlap.hip, walk the tree above and keep nothing of their own)
 		// mi_contact_sensors (k_contact_sensors.hip): rebuilt at every call.  Per body of the last step {wanted by a sensor, its manifolds, its
 		// first entry, fill cursor}; the entries (manifold slot << 32 | schedule position), a segment per wanted body, two per position at most;
 		// the bodies whose segment one lane does not sort; {entries handed out, length of that list}
@@ -422,9 +422,10 @@ void launch_copy_pose0(World& w);
 void launch_interaction_batch(World& w, u32 numRays, u32 firstBody, u32 bodiesPerRay, const float* dRays, int32_t* dOutBody); // k_interact.hip
 void launch_raycast(World& w, u32 numRays, const float* dRays, u32 flags, mi_ray_hit* dOutHits, const uint2* dExclude = nullptr); // k_raycast.hip; dExclude: a body range per ray (mi_raycast_sensors)
 enum RcBuild { RC_BUILD_NO_CANDIDATES, RC_BUILD_FAILED, RC_BUILD_DONE }; // nothing enqueued: no collider can be a candidate / w.lastError is set / the tree is on the stream
-RcBuild launch_raycast_build(World& w, bool withStatic, bool brute); // k_raycast.hip: the tree in World::queries that launch_raycast, launch_proximity and launch_sphere_cast walk
+RcBuild launch_raycast_build(World& w, bool withStatic, bool brute); // k_raycast.hip: the tree in World::queries that launch_raycast, launch_proximity, launch_sphere_cast and launch_overlap walk
 void launch_proximity(World& w, u32 n, const mi_proximity_query* dQueries, u32 flags, mi_proximity_reading* dOut, float* dOutWorldPoints); // k_proximity.hip
 void launch_sphere_cast(World& w, u32 n, const mi_sphere_cast* dQueries, u32 flags, mi_sphere_hit* dOut, float* dOutWorldCasts); // k_spherecast.hip
+void launch_overlap(World& w, u32 n, const mi_overlap_query* dQueries, u32 maxHits, u32 flags, void* dOut, float* dOutWorldShapes); // k_overlap.hip
 void launch_raycast_sensors(World& w, u32 numRays, const mi_sensor_ray* dRays, u32 flags, bool terrain, mi_sensor_hit* dOutHits, float* dOutWorldRays); // k_raycast_sensors.hip
 void launch_proximity_terrain(World& w, u32 n, const mi_proximity_query* dQueries, u32 flags, mi_proximity_reading* dOut); // k_proximity_terrain.hip: after launch_proximity, on its records
 void launch_sphere_cast_terrain(World& w, u32 n, const mi_sphere_cast* dQueries, u32 flags, mi_sphere_hit* dOut); // k_spherecast_terrain.hip: after launch_sphere_cast, on its records

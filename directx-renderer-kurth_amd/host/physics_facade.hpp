@@ -526,6 +526,52 @@ namespace mi
 		return castSphereQuery(scene, in, out, "castSensorSphere", withTerrain);
 	}
 
+	// What is inside a volume right now ("a trigger you ask once"; include/mi_physics.h states the rule): the colliders of rigid bodies and
+	// static colliders that a trigger collider of this shape at this pose would report, lowest collider index first.  `out` receives up
+	// to maxHits of them; the return value is the total count.  One query through mi_overlap_batch.
+	struct overlap_hit { uint32_t collider = 0, body = MI_STATIC_BODY; };
+	inline uint32_t overlapQuery(game_scene& scene, mi_overlap_query in, std::vector<overlap_hit>& out, uint32_t maxHits, const char* what)
+	{
+		scene.flushStaticColliders();
+		in.enabled = 1u;
+		std::vector<uint32_t> block(4u + 2u * (size_t)maxHits);
+		scene.check(mi_overlap_host(scene.world, 1u, &in, maxHits, (uint32_t)MI_OVERLAP_STATIC, block.data(), nullptr), what);
+		out.clear();
+		for (uint32_t k = 0; k < block[1]; ++k) { overlap_hit h; h.collider = block[4 + 2 * k]; h.body = block[5 + 2 * k]; out.push_back(h); }
+		return block[0];
+	}
+	// volume: one of the collider factories' values (its material is not used) in the frame (position, rotation), world space.
+	inline uint32_t overlapVolume(game_scene& scene, const collider_component& volume, vec3 position, quat rotation, std::vector<overlap_hit>& out, uint32_t maxHits = 64u)
+	{
+		mi_overlap_query in{};
+		memcpy(in.shape, volume.shape, sizeof(in.shape)); in.type = volume.type;
+		in.pos[0] = position.x; in.pos[1] = position.y; in.pos[2] = position.z;
+		in.rot[0] = rotation.x; in.rot[1] = rotation.y; in.rot[2] = rotation.z; in.rot[3] = rotation.w;
+		in.mount = MI_STATIC_BODY;
+		return overlapQuery(scene, in, out, maxHits, "overlapVolume");
+	}
+	// The same volume fixed to a rigid body: (localPosition, localRotation) is in the body's frame at its current pose.  excludeSelf: the
+	// body's own colliders are no candidates (a gripper asking what is between its fingers).
+	inline uint32_t overlapVolume(game_scene& scene, const scene_entity& body, const collider_component& volume, vec3 localPosition, quat localRotation, std::vector<overlap_hit>& out,
+		bool excludeSelf = true, uint32_t maxHits = 64u)
+	{
+		mi_overlap_query in{};
+		memcpy(in.shape, volume.shape, sizeof(in.shape)); in.type = volume.type;
+		in.pos[0] = localPosition.x; in.pos[1] = localPosition.y; in.pos[2] = localPosition.z;
+		in.rot[0] = localRotation.x; in.rot[1] = localRotation.y; in.rot[2] = localRotation.z; in.rot[3] = localRotation.w;
+		in.mount = body.body(); in.excludeFirst = in.mount; in.excludeCount = excludeSelf ? 1u : 0u;
+		return overlapQuery(scene, in, out, maxHits, "overlapVolume");
+	}
+	inline uint32_t overlapSphere(game_scene& scene, vec3 centre, float radius, std::vector<overlap_hit>& out)
+	{
+		return overlapVolume(scene, collider_component::asSphere(bounding_sphere{ vec3(0.f, 0.f, 0.f), radius }, physics_material{}), centre, quat(), out);
+	}
+	// A box of half extents `radius` around `centre`, turned by `rotation` (the identity keeps it an axis-aligned box).
+	inline uint32_t overlapBox(game_scene& scene, vec3 centre, quat rotation, vec3 radius, std::vector<overlap_hit>& out)
+	{
+		return overlapVolume(scene, collider_component::asAABB(bounding_box::fromCenterRadius(vec3(0.f, 0.f, 0.f), radius), physics_material{}), centre, rotation, out);
+	}
+
 	// What the contacts of the last internal step did to a rigid body (no counterpart in the reference's physics.h; include/mi_physics.h
 	// states the rule): the linear and angular impulse they applied to it, the sum of the normal impulses, how many contacts and manifolds
 	// were summed and the partner that pressed hardest.  partners: MI_CONTACT_DYNAMIC | MI_CONTACT_STATIC; the bodies excludeFirst ..

@@ -464,6 +464,61 @@ typedef struct mi_sphere_hit { float t; uint32_t collider, body, hit; float poin
 int mi_sphere_cast_batch(mi_world* w, uint32_t numQueries, const mi_sphere_cast* dQueries, uint32_t flags, mi_sphere_hit* dOut, float* dOutWorldCasts);
 int mi_sphere_cast_host(mi_world* w, uint32_t numQueries, const mi_sphere_cast* queries, uint32_t flags, mi_sphere_hit* out, float* outWorldCasts);
 
+/* Overlap queries: which colliders a volume touches right now: "a trigger you ask once".  One call on the world's stream; like the ray
+ * entries it first settles a step whose cluster sweep is not yet known to have completed, uploads, and otherwise does not synchronise
+ * with the host; no step buffer and no accumulator is written; numQueries == 0 launches nothing.  (The reference has no counterpart as a
+ * query: the rule is this project's, built from the reference's trigger test.)
+ * Query: shape and type are exactly what mi_add_collider takes: sphere c3,r | capsule/cylinder A3,B3,r | aabb min3,max3 | obb
+ * quat4,center3,radius3 | hull quat4,position3,geometry index (word 7, as a float value).  As there, only the words the type uses are
+ * read (4, 7, 7, 6, 10, 8); the rest of the record counts as zero.
+ * Volume frame: (pos, rot) is the volume's own pose in the frame of body `mount` at its current pose (the pose array the call itself
+ * reads, so poses written through mi_device_state are seen): world rotation = mountRot * rot (quaternion product), world position =
+ * mountRot * pos + mountPos, float32 without contraction.  mount == MI_STATIC_BODY: (pos, rot) is the world pose, taken bit for bit:
+ * the pose a trigger entity or a static collider has.
+ * World record: the volume's world record and world box are what the step builds for a collider with these shape words whose entity has
+ * that world pose, bit for bit (csrc/collider_world.h, the function the step itself calls; reference physics.cpp:631-756): a sphere's
+ * centre, a capsule's and a cylinder's end points, an OBB's and a hull's composed rotation and position; a cylinder's box is the tight
+ * one, e = r * sqrt(max(0, 1 - a_k^2 / dot(a, a))) per axis around both end points; an AABB stays an AABB (its 8 transformed corners'
+ * box) only under the rotation (0, 0, 0, 1) exactly and otherwise becomes the OBB {rot, rot * centre + pos, half extents}, type MI_OBB;
+ * every other box is that of the 8 transformed corners of the local box (for a hull: of its geometry's box).  With MI_STATIC_BODY and the
+ * same (pos, rot, shape) the record and the box equal those of a trigger collider placed there (mi_add_trigger, mi_add_trigger_collider).
+ * Switched off: enabled == 0; a mount >= the number of bodies other than MI_STATIC_BODY, a deleted body, in a slab run a body not
+ * simulated here; type >= 6; a hull geometry index that is negative, NaN or >= the number of geometries; a world box that is not finite:
+ * a coordinate that is infinite or NaN, or min > max on an axis (the box of 8 corners drops a corner's NaN coordinate, so a NaN in the
+ * pose can leave an empty box instead).  Such a query has valid = 0, an all-zero block and an all-zero world shape.
+ * Candidates are mi_raycast_batch's: the colliders of alive bodies simulated here and, with MI_OVERLAP_STATIC, those of entities without
+ * a rigid body; never force-field or trigger colliders, never cloth, never the heightmap terrain.  The colliders of the bodies b with
+ * b - excludeFirst < excludeCount, in uint32 arithmetic (the subtraction wraps), are no candidates of this query; static colliders are
+ * never excluded.
+ * Verdict per candidate: the step's own two-stage decision for a trigger collider.  (1) The candidate's world box, as the step builds it
+ * from the current pose, meets the volume's world box inclusively on all three axes: the broadphase's comparison, not (amax < bmin or
+ * amin > bmax) per axis.  (2) The trigger's boolean test (overlapColliders, csrc/zone_overlap.h; reference overlapCheck,
+ * collision_narrow.cpp:1593-1689) answers true on the two world records, with operand A = the record of the lower collider type after
+ * promotion, and for equal types A = the query volume.  It is that test with every property tests/zone64.py documents in float64: the
+ * sphere-cylinder cap rule (beside a cap the squared distance is held against the radius, not its square), the epsilon the box-box SAT
+ * adds to every |R_ij|, and the GJK walk of the tube-box, cylinder-cylinder and hull pairings, which reports pairs less than about 0.2 m
+ * apart (it stops at |dir|^2 < 1e-4 and answers false only on a separating support point).  Stage (1) is part of the rule, not merely
+ * pruning: some of those tests answer true beyond the boxes; the step never sees such pairs and the query does not see them either.
+ * Output: per query one block of 16 + 8 * maxHits bytes in dOut (device, 8-byte aligned): mi_overlap_summary, then maxHits records of
+ * mi_overlap_hit.  numOverlaps counts every overlapping candidate, whatever maxHits is; numWritten = min(numOverlaps, maxHits); the hits
+ * are the numWritten lowest collider indices that overlap, ascending; body is MI_STATIC_BODY for a static collider; the slots behind
+ * numWritten are zero; valid = 1 for a query that is not switched off, also when nothing overlaps.  maxHits == 0 is a pure count;
+ * maxHits > MI_OVERLAP_MAX_HITS returns MI_ERR_INVALID_ARGUMENT.
+ * dOutWorldShapes (device, may be NULL) receives 20 floats per query: the 10 shape words of the world record, the bits of its type after
+ * promotion, 0, box min xyz, 0, box max xyz, 0.
+ * The candidates and the tree over them are mi_raycast_batch's, rebuilt from the current poses at every call in the same buffers;
+ * MI_OVERLAP_BRUTE_FORCE asks every candidate instead (same bytes; a yardstick).  Calls of all query kinds may follow each other freely.
+ * mi_overlap_host: queries, blocks and world shapes in HOST memory, staged through buffers of the world; returns after the blocks have
+ * arrived. */
+enum { MI_OVERLAP_STATIC = 1, MI_OVERLAP_BRUTE_FORCE = 2 };
+#define MI_OVERLAP_MAX_HITS 1024u
+typedef struct mi_overlap_query { float shape[10]; uint32_t type, enabled; float pos[3]; uint32_t mount; float rot[4];
+                                  uint32_t excludeFirst, excludeCount, reserved[2]; } mi_overlap_query;      /* 96 bytes */
+typedef struct mi_overlap_summary { uint32_t numOverlaps, numWritten, valid, reserved; } mi_overlap_summary; /* 16 bytes */
+typedef struct mi_overlap_hit { uint32_t collider, body; } mi_overlap_hit;                                   /* 8 bytes */
+int mi_overlap_batch(mi_world* w, uint32_t numQueries, const mi_overlap_query* dQueries, uint32_t maxHits, uint32_t flags, void* dOut, float* dOutWorldShapes);
+int mi_overlap_host(mi_world* w, uint32_t numQueries, const mi_overlap_query* queries, uint32_t maxHits, uint32_t flags, void* out, float* outWorldShapes);
+
 /* Contact sensors: what the contacts of the LAST INTERNAL STEP did to a body, summed on the device from the rows its solve left behind.
  * One call on the world's stream; like the ray entries it first settles a step whose cluster sweep is not yet known to have completed
  * (after a give-up the readings describe the redone solve) and otherwise does not synchronise with the host.  The step's buffers are only
