@@ -33,10 +33,11 @@ struct ClLocal // a task of this workgroup, in LDS
 	u32 first, count, numBodies, numShared, numColors, serialStart, numContacts, phase, key, sharedBase, numJoints;
 	u32 bodyOff;     // float4 index of the task's bodies (2 float4 each)
 	u32 infoOff;     // u32 index of per-body {global id, turn info, hand-over record}
-	u32 regContacts; // contacts [0, regContacts) live in the lanes' register sets (the workgroup's first task only)
-	u32 rowOff;      // float4 index of the rows kept in LDS: contacts [regContacts, regContacts + rowCap)
-	u32 rowCap;      // ... the rest, contacts [regContacts + rowCap, numContacts), in the global scratch from scratchBase on
-	u32 scratchBase;
+	// Where a contact position's row lives, best tier at the CLOSING end: [0, spill) in the global scratch from scratchBase on, [spill,
+	// regBase = numContacts - regContacts) in LDS (rowCap = regBase - spill rows from rowOff on), [regBase, numContacts) in the lanes'
+	// register sets (the workgroup's first task only; set s of quad j holds position regBase + s * CLQ_QUADS + j)
+	u32 regContacts, spill, rowOff, rowCap, scratchBase;
+	u32 ldsColors;   // the task's first colours that end at or below regBase (a task with no contact in registers: all of them)
 	u32 colorStart[68];
 };
 
@@ -46,6 +47,7 @@ struct ClArgs
 	const u32* mKeySorted; const u32* mLocal; const u32* cEntry;
 	const float4* rowPlanes; const float4* rowShared; float2* rowLambda; float4* rowScratch; u32 scratchContacts;
 	u32 regContactsCap; // MI_CLUSTER_REG_CONTACTS: most contacts a first task keeps in registers (tests; ~0u: as many as the sets hold)
+	u32 ldsRowsCap;     // MI_CLUSTER_LDS_ROWS: most rows a workgroup keeps in LDS (tests; ~0u: as many as fit)
 	u32 predictDiv, pollSleep; // pacing of the hand-over polls (CL_PREDICT_DIV / CL_POLL_SLEEP)
 	float4* vel; u64* flow; u64* trace; // trace: developer timeline (mi_debug_flow_trace), normally null
 	size_t rowCap; u32 nb, flowBytes, epoch, itBegin, itEnd, ldsFloat4s;
@@ -119,6 +121,7 @@ template <bool JOINTS> __global__ void __launch_bounds__(CLS_LANES) k_cl_solve(C
 	extern __shared__ float4 lds[];
 	__shared__ ClLocal sTask[CL_MAX_LOCAL_TASKS];
 	__shared__ u32 sNumTasks, sAbort;
+	__shared__ u32 sRegStart[CL_SERIAL_COLOR + 4u]; // the first task's colorStart counted from its regBase, as its register sets count (what lies below wraps and is never read)
 	const u32 tid = threadIdx.x, G = gridDim.x, quad = tid >> 2, q = tid & 3u;
 	constexpr u32 SETS = JOINTS ? CLQ_SETS_JOINTS : CLQ_SETS;
 	u32* status = A.counters + CTR_FLOW_STATUS;
@@ -158,20 +161,28 @@ template <bool JOINTS> __global__ void __launch_bounds__(CLS_LANES) k_cl_solve(C
 				L.bodyOff = used; used += 2u * L.numBodies;
 				L.infoOff = used * 4u; used += (3u * L.numBodies + 3u) / 4u;
 				L.regContacts = (nT == 0) ? min(L.numContacts, min(CLQ_QUADS * SETS, A.regContactsCap)) : 0u;
-				L.rowOff = 0; L.rowCap = 0;
+				L.rowOff = 0; L.rowCap = 0; L.spill = 0;
+				const u32 regBase = L.numContacts - L.regContacts;
+				// (The colour loop runs these while c < ldsColors, the rest while c < mainColors.  ldsColors <= mainColors for non-empty colours:
+				// the one-wave tail's colours begin at or beyond regBase.  An EMPTY colour that sits at regBase and opens the tail is counted here
+				// too: the LDS loop then takes one step without a row past mainColors and the tail runs the empty colour again, no row either way.
+				// The scratch loop in front ends on csCur == spill whenever colours remain, whether it cut a colour there or not.)
+				L.ldsColors = 0; while (L.ldsColors < L.numColors && L.colorStart[L.ldsColors + 1u] <= regBase) ++L.ldsColors;
+				if (nT == 0) for (u32 c = 0; c < CL_SERIAL_COLOR + 4u; ++c) sRegStart[c] = L.colorStart[c] - regBase;
 				++nT;
 			}
 		}
 		if (used + CLQ_ZERO_FLOAT4S > A.ldsFloat4s) { bad = true; atomicOr(status, 512u); } // the bodies alone exceed LDS: cannot run this launch
-		// rows beyond the register sets: whatever LDS is left, in task order
+		// rows outside the register sets: whatever LDS is left, in task order
+		u32 ldsRowsLeft = A.ldsRowsCap;
 		for (u32 k = 0; k < nT && !bad; ++k)
 		{
 			ClLocal& L = sTask[k];
 			u32 want = L.numContacts - L.regContacts;
 			u32 left = A.ldsFloat4s - used - CLQ_ZERO_FLOAT4S; // (the end of LDS holds the static body's all-zero records and the sink)
-			u32 fit = left / CLQ_ROW_FLOAT4S;
-			u32 cap = want < fit ? want : fit;              // what does not fit goes to the global scratch (L2-resident, every step of such a task waits for it: the cluster build sizes the later phases' tasks so that this is rare)
-			L.rowOff = used; L.rowCap = cap; used += CLQ_ROW_FLOAT4S * cap; L.scratchBase = 0;
+			u32 fit = min(left / CLQ_ROW_FLOAT4S, ldsRowsLeft);
+			u32 cap = want < fit ? want : fit;              // what does not fit, the task's FIRST positions, goes to the global scratch (L2-resident, every step on such a row waits for it: the cluster build sizes the later phases' tasks so that this is rare)
+			L.rowOff = used; L.rowCap = cap; used += CLQ_ROW_FLOAT4S * cap; ldsRowsLeft -= cap; L.scratchBase = 0; L.spill = want - cap;
 			if (want > cap) { L.scratchBase = atomicAdd(&A.counters[CTR_CL_SCRATCH], want - cap); if (L.scratchBase + (want - cap) > A.scratchContacts) { bad = true; atomicOr(status, 1024u); break; } }
 		}
 		if (bad) atomicOr(status, 64u);
@@ -203,47 +214,48 @@ template <bool JOINTS> __global__ void __launch_bounds__(CLS_LANES) k_cl_solve(C
 	}
 	for (u32 i = tid; i < CLQ_ZERO_FLOAT4S; i += CLS_LANES) lds[zeroBase + i] = make_float4(0.f, 0.f, 0.f, 0.f);
 	__syncthreads();
-	// the first task's contacts in registers: set s of this lane's quad holds contact position s * CLQ_QUADS + quad
+	// the first task's last regContacts contacts in registers: set s of this lane's quad holds contact position regBase + s * CLQ_QUADS + quad
 	QuadRow rows[SETS]; u32 addr[SETS];
 	{
 		const ClLocal& L = sTask[0];
+		const u32 regBase = L.numContacts - L.regContacts;
 #pragma unroll
 		for (u32 s = 0; s < SETS; ++s)
 		{
 			const u32 p = s * CLQ_QUADS + quad;
 			rows[s].dT = rows[s].aT = rows[s].dN = rows[s].aN = v3(0.f, 0.f, 0.f); rows[s].mT = rows[s].mN = rows[s].bias = rows[s].friction = rows[s].lamN = rows[s].lamT = 0.f; addr[s] = sinkRec;
-			if (p < L.regContacts) { u32 slot, kk; clBuildQuadRow(rows[s], addr[s], L, A, lds, p, q, zeroBase + 2u * quad, slot, kk); }
+			if (p < L.regContacts) { u32 slot, kk; clBuildQuadRow(rows[s], addr[s], L, A, lds, regBase + p, q, zeroBase + 2u * quad, slot, kk); }
 		}
 	}
-	// every other contact of the workgroup's tasks: its four lane rows in LDS while there is room
+	// every other contact of the workgroup's tasks, the positions below regBase: its four lane rows in LDS, the first spill of them in the scratch
 	for (u32 k = 0; k < numTasks; ++k)
 	{
 		const ClLocal& L = sTask[k];
-		for (u32 i = quad; i < L.numContacts - L.regContacts; i += CLQ_QUADS)
+		for (u32 p = quad; p < L.numContacts - L.regContacts; p += CLQ_QUADS)
 		{
 			QuadRow r; u32 a, slot, kk;
-			clBuildQuadRow(r, a, L, A, lds, L.regContacts + i, q, zeroBase + 2u * quad, slot, kk);
-			if (i < L.rowCap) clStoreQuadRow(lds + L.rowOff + i * CLQ_ROW_FLOAT4S, q, r, a);
-			else clStoreQuadRow(A.rowScratch + (size_t)(L.scratchBase + i - L.rowCap) * CLQ_ROW_FLOAT4S, q, r, a);
+			clBuildQuadRow(r, a, L, A, lds, p, q, zeroBase + 2u * quad, slot, kk);
+			if (p >= L.spill) clStoreQuadRow(lds + L.rowOff + (p - L.spill) * CLQ_ROW_FLOAT4S, q, r, a);
+			else clStoreQuadRow(A.rowScratch + (size_t)(L.scratchBase + p) * CLQ_ROW_FLOAT4S, q, r, a);
 		}
 	}
-	// The last colours of a task hold a handful of contacts (the busiest body's last rows).  Those of the first task whose positions all
-	// fall into ONE block of 16 positions belong to one wave (16 quads of one register set): that wave runs them back to back, in
-	// program order, without the workgroup barrier in between (LDS serves a wave's accesses in order).  tailStart0 = first such
-	// colour, tailSet = their register set, myTail = this lane's colour among them (255: none).
+	// The last colours of a task hold a handful of contacts (the busiest body's last rows).  Those of the first task that lie in the
+	// registers and whose positions, counted from regBase, all fall into ONE block of 16 belong to one wave (16 quads of one register
+	// set): that wave runs them back to back, in program order, without the workgroup barrier in between (LDS serves a wave's accesses
+	// in order).  tailStart0 = first such colour, tailSet = their register set, myTail = this lane's colour among them (255: none).
 	u32 tailStart0 = sTask[0].numColors, tailSet = 0, myTail = 255u;
 	{
 		const ClLocal& L = sTask[0];
-		const u32 endPos = L.colorStart[L.numColors];
-		if (L.numColors && endPos && endPos <= L.regContacts)
+		const u32 regBase = L.numContacts - L.regContacts, endPos = L.colorStart[L.numColors];
+		if (L.numColors && endPos > regBase)
 		{
-			const u32 blk = (endPos - 1u) >> 4;
-			while (tailStart0 > 0u && (L.colorStart[tailStart0 - 1u] >> 4) == blk) --tailStart0;
+			const u32 blk = (endPos - regBase - 1u) >> 4;
+			while (tailStart0 > 0u && L.colorStart[tailStart0 - 1u] >= regBase && ((L.colorStart[tailStart0 - 1u] - regBase) >> 4) == blk) --tailStart0;
 			if (L.numColors - tailStart0 < 2u) tailStart0 = L.numColors;
 			else
 			{
-				tailSet = L.colorStart[tailStart0] / CLQ_QUADS;
-				const u32 p = tailSet * CLQ_QUADS + quad;
+				tailSet = (L.colorStart[tailStart0] - regBase) / CLQ_QUADS;
+				const u32 p = regBase + tailSet * CLQ_QUADS + quad;
 				if (p >= L.colorStart[tailStart0] && p < endPos) { myTail = tailStart0; while (L.colorStart[myTail + 1u] <= p) ++myTail; }
 			}
 		}
@@ -268,57 +280,68 @@ template <bool JOINTS> __global__ void __launch_bounds__(CLS_LANES) k_cl_solve(C
 	// developer timeline: 16 rows of 32 stamps per workgroup: row 3 k = "task k acquired its shared bodies" in iteration (column), row
 	// 3 k + 1 = "task k's colours done"; rows 5-6: core-clock stamp after every colour of iteration 10 of the first task, rows 7-8: the
 	// colours' sizes; row 15: [0] kernel start, [1] prologue done, [2 + 4 k ..] task k's size, colours, shared bodies, phase;
-	// [22 + k] task k's rows in LDS | in registers << 32 (the rest of its contacts: in the global scratch)
+	// [22 + k] task k's rows in LDS | in registers << 32 (the rest of its contacts: in the global scratch); [27 + k] task k's rows in the
+	// scratch (its positions below that) | colours run by the one-wave tail << 32
 	u64* trace = A.trace ? A.trace + (size_t)blockIdx.x * CL_TRACE_ROWS * CL_TRACE_WORDS : nullptr;
 	if (trace && tid == 0)
 	{
 		trace[15 * 32 + 1] = wall_clock64();
-		for (u32 k = 0; k < numTasks && k < 5u; ++k) { trace[15 * 32 + 2 + 4 * k] = sTask[k].count; trace[15 * 32 + 3 + 4 * k] = sTask[k].numColors; trace[15 * 32 + 4 + 4 * k] = sTask[k].numShared; trace[15 * 32 + 5 + 4 * k] = sTask[k].phase | (sTask[k].numBodies << 8) | ((u64)sTask[k].numContacts << 32); trace[15 * 32 + 22 + k] = sTask[k].rowCap | ((u64)sTask[k].regContacts << 32); }
+		for (u32 k = 0; k < numTasks && k < 5u; ++k) { trace[15 * 32 + 2 + 4 * k] = sTask[k].count; trace[15 * 32 + 3 + 4 * k] = sTask[k].numColors; trace[15 * 32 + 4 + 4 * k] = sTask[k].numShared; trace[15 * 32 + 5 + 4 * k] = sTask[k].phase | (sTask[k].numBodies << 8) | ((u64)sTask[k].numContacts << 32); trace[15 * 32 + 22 + k] = sTask[k].rowCap | ((u64)sTask[k].regContacts << 32); trace[15 * 32 + 27 + k] = sTask[k].spill | ((u64)(k == 0u ? sTask[0].numColors - tailStart0 : 0u) << 32); }
 	}
 
-	// One step = the contacts at positions [cs, end) of a task (one colour, or one contact of the serial tail).  Positions below the
-	// task's regContacts: register set position / CLQ_QUADS of quad position % CLQ_QUADS; beyond: rows from LDS / the scratch.  The
-	// colour loops below are written SET BY SET (a colour's positions are consecutive, so the colours that begin in set S are a run
-	// of the loop; one that reaches beyond set S + 1, or beyond the registers, is cut into two steps), so that the code of a step names
-	// its one or two register sets statically: no dispatch, nothing of the other sets passes through the loop, and no row step stands
-	// between the set loops (each carried a copy of it, ~190 instructions, for the one colour that straddles regContacts, and the
-	// register-run tasks stepped over all of them every turn).  The colours beyond the registers follow in a loop of their own, CLQ_SOLVE_ROWS_LDS or CLQ_SOLVE_ROWS.
+	// One step = the contacts at positions [cs, end) of a task (one colour, or one contact of the serial tail).  A task's positions lie in
+	// up to three tiers, the best at the closing end (ClLocal): [0, spill) rows in the global scratch, [spill, regBase) rows in LDS,
+	// [regBase, numContacts) register set (position - regBase) / CLQ_QUADS of quad (position - regBase) % CLQ_QUADS.  The closing colours
+	// are the many small ones (the busiest body's last rows), the opening ones the few large ones: a colour step costs the same whatever it
+	// holds, so the cheap tier goes where the steps are, and the one-wave tail below is open to every first task.  The colour loop runs
+	// tier by tier, and a colour that straddles spill or regBase is cut there (one more barrier): the scratch colours through the general
+	// step CLQ_SOLVE_ROWS, the LDS colours through the short CLQ_SOLVE_ROWS_LDS (per colour, not per task: a task with rows in the scratch
+	// pays for them in its opening colours only), then the register colours on positions counted from regBase, written SET BY SET (a
+	// colour's positions are consecutive, so the colours that begin in set S are a run of the loop; one that reaches beyond set S + 1 is
+	// cut into two steps), so that the code of a step names its one or two register sets statically: no dispatch, nothing of the other
+	// sets passes through the loop, and no row step stands between the set loops.
 #define CLQ_SOLVE_SET(S_, CS_, END_) if ((S_) < SETS) { const u32 pos = (S_) * CLQ_QUADS + quad; if (pos >= (CS_) && pos < (END_)) { float4 b = lds[addr[(S_) < SETS ? (S_) : 0u]]; V3 x = v3f4(b); clSolveQuad(rows[(S_) < SETS ? (S_) : 0u], x); lds[addr[(S_) < SETS ? (S_) : 0u]] = make_float4(x.x, x.y, x.z, b.w); } }
 	// A row in LDS carries its body addresses in its last float4: read with the row, the body read would be a SECOND dependent LDS round
 	// trip per step.  So a lane asks for the address word of the row it solves next one step early (pfW): a step's start is the end of
-	// the step before it, the lane's first row of the step that follows [CS_, END_) is max(END_, regC) + quad, and the register-only
-	// steps in front of the first row step leave that at regC + quad, which the request made for the task's turn covers (CLQ_PREFETCH_TURN).  The
-	// address words are written by the prologue alone (a step writes back its row's two impulses, never the float2 beside them), so the
-	// word a lane holds across a barrier cannot be stale.  Further passes of a colour with more than CLQ_QUADS rows outside the
-	// registers get their word from the pass before them.  Rows in the global scratch keep the two trips.
-#define CLQ_PREFETCH(POS_) { const u32 in_ = max((POS_), regC) + quad - regC; if (in_ < rowCap) pfW = ((const u32*)(lds + rowOff + in_ * CLQ_ROW_FLOAT4S))[CLQ_PAIR_WORD(q)]; }
+	// the step before it, the lane's first LDS row of the step that follows [CS_, END_) is max(END_, spill) + quad, and the scratch
+	// steps in front of the first LDS step leave that at spill + quad, which the request made for the task's turn covers (CLQ_PREFETCH_TURN);
+	// the register steps come last and ask for nothing.  The address words are written by the prologue alone (a step writes back its
+	// row's two impulses, never the float2 beside them), so the word a lane holds across a barrier cannot be stale.  Further passes of a
+	// step with more than CLQ_QUADS rows get their word from the pass before them.  Rows in the global scratch keep the two trips.
+#define CLQ_PREFETCH(POS_) { const u32 in_ = max((POS_), spill) + quad - spill; if (in_ < rowCap) pfW = ((const u32*)(lds + rowOff + in_ * CLQ_ROW_FLOAT4S))[CLQ_PAIR_WORD(q)]; }
+	// The general step: positions [CS_, END_) below regBase, wherever their rows live, in passes of CLQ_QUADS (the scratch colours, cut at
+	// spill, and the serial tail's contacts outside the registers).  [CS_, END_) must lie on ONE side of spill: the word a lane brings
+	// along (pfW) is that of LDS row max(CS_, spill) + quad - spill, its first row only if the step does not begin below spill and reach beyond it.
 #define CLQ_SOLVE_ROWS(CS_, END_) \
 	{ \
 		u32 w = pfW; \
 		CLQ_PREFETCH(END_) \
-		for (u32 p = max((CS_), regC) + quad; p < (END_); p += CLQ_QUADS) \
+		for (u32 p = (CS_) + quad; p < (END_); p += CLQ_QUADS) \
 		{ \
-			const u32 i = p - regC; \
+			const bool inLds = p >= spill; \
 			QuadRow r; u32 a; float4 b; \
-			float4* P = lds + rowOff + i * CLQ_ROW_FLOAT4S; \
-			float4* S = A.rowScratch + (size_t)(scratchBase + i - rowCap) * CLQ_ROW_FLOAT4S; \
-			u32 wn = 0u; if (p + CLQ_QUADS < (END_) && i + CLQ_QUADS < rowCap) wn = ((const u32*)(P + CLQ_QUADS * CLQ_ROW_FLOAT4S))[CLQ_PAIR_WORD(q)]; \
-			if (i < rowCap) { u32 unused; a = clPairAddr(w, q); b = lds[a]; clLoadQuadRow(r, unused, P, q); } else { clLoadQuadRow(r, a, S, q); b = lds[a]; } \
+			float4* P = lds + rowOff + (inLds ? p - spill : 0u) * CLQ_ROW_FLOAT4S; \
+			float4* S = A.rowScratch + (size_t)(scratchBase + (inLds ? 0u : p)) * CLQ_ROW_FLOAT4S; \
+			u32 wn = 0u; if (p + CLQ_QUADS < (END_) && p + CLQ_QUADS >= spill) wn = ((const u32*)(lds + rowOff + (p + CLQ_QUADS - spill) * CLQ_ROW_FLOAT4S))[CLQ_PAIR_WORD(q)]; \
+			if (inLds) { u32 unused; a = clPairAddr(w, q); b = lds[a]; clLoadQuadRow(r, unused, P, q); } else { clLoadQuadRow(r, a, S, q); b = lds[a]; } \
 			V3 x = v3f4(b); clSolveQuad(r, x); lds[a] = make_float4(x.x, x.y, x.z, b.w); \
-			if (q == 0u) { if (i < rowCap) ((float2*)(P + 13))[0] = make_float2(r.lamN, r.lamT); else ((float2*)(S + 13))[0] = make_float2(r.lamN, r.lamT); } \
+			if (q == 0u) { if (inLds) ((float2*)(P + 13))[0] = make_float2(r.lamN, r.lamT); else ((float2*)(S + 13))[0] = make_float2(r.lamN, r.lamT); } \
 			w = wn; \
 		} \
 	}
-	// The same step for a task whose rows outside the registers are ALL in LDS, in the loop of the colours that lie entirely beyond the
-	// registers (CS_ >= regC): every task but a workgroup's first runs all its colours here.  Measured, such a step cost 0.43 us against
-	// the register step's 0.28, and what it costs is its instruction count far more than its LDS round trips (a wave gets through the ~45
-	// instructions of a register step in ~650 cycles).  So this form keeps it short: a step takes at most CLQ_QUADS rows (the loop cuts a
-	// larger colour into several steps, as the set loops do at a set's end), so there is no loop over passes; no branch on where a row
-	// lives; row addresses by one 24-bit multiply-add; and the request for the lane's next row is clamped to the task's last row
-	// instead of guarded (a lane without a next row reads a word it never uses).
+	// The same step for positions whose rows are ALL in LDS, spill <= CS_ < END_ <= regBase: every task but a workgroup's first runs all
+	// its colours here, but for the few whose first rows did not fit.  Measured, a row step cost 0.43 us against the register step's 0.28,
+	// and what it costs is its instruction count far more than its LDS round trips (a wave gets through the ~45 instructions of a
+	// register step in ~650 cycles).  So this form keeps it short: a step takes at most CLQ_QUADS rows (the loop cuts a larger colour
+	// into several steps, as the set loops do at a set's end), so there is no loop over passes; no branch on where a row lives; row
+	// addresses by one 24-bit multiply-add; and the request for the lane's next row is clamped to the task's last LDS row instead of
+	// guarded (a lane without a next row reads a word it never uses).  Rows count from spill: i and endR are LDS row numbers, endR <=
+	// rowCap, and a step that has a row has csCur < regBase, that is rowCap >= 1, so min(endR + quad, lastRow = rowCap - 1) names one of
+	// the task's own rows [0, rowCap) whatever spill is (an empty colour of a task without LDS rows asks for the word at rowOff, inside
+	// the workgroup's LDS in front of the zero records, and uses nothing).
 #define CLQ_SOLVE_ROWS_LDS(CS_, END_) \
 	{ \
-		const u32 i = (CS_) - regC + quad, endR = (END_) - regC, w = pfW; \
+		const u32 i = (CS_) - spill + quad, endR = (END_) - spill, w = pfW; \
 		pfW = clLdsAt<u32>(lds, __umul24(min(endR + quad, lastRow), CLQ_ROW_FLOAT4S * 16u) + pairByte); \
 		if (i < endR) \
 		{ \
@@ -333,13 +356,14 @@ template <bool JOINTS> __global__ void __launch_bounds__(CLS_LANES) k_cl_solve(C
 	}
 #define CLQ_ADVANCE(END_) \
 	__syncthreads(); \
-	if (stamp && c < 63u && (END_) == csNext) { trace[5 * 32 + 1 + c] = clock64(); trace[7 * 32 + c] = csNext - L.colorStart[c]; } \
+	if (stamp && c < 63u && (END_) == csNext) { trace[5 * 32 + 1 + c] = clock64(); trace[7 * 32 + c] = L.colorStart[c + 1u] - L.colorStart[c]; } \
 	if ((END_) == csNext) { csCur = csNext; csNext = __builtin_amdgcn_readfirstlane(csAfter); ++c; } else csCur = (END_);
+	// (in the set loops csCur, csNext and csAfter count from regBase, as the sets do: sRegStart; only a workgroup's first task gets here)
 #define CLQ_SET_LOOP(S_) \
 	if ((S_) < SETS) while (c < mainColors && csCur < min(regC, ((S_) + 1u) * CLQ_QUADS)) \
 	{ \
-		const u32 csAfter = L.colorStart[c + 2u]; /* (requested now, needed at the next colour: the LDS round trip hides behind this step) */ \
-		const u32 end = min(csNext, min(regC, ((S_) + 2u) * CLQ_QUADS)); /* (a colour that reaches beyond set S_ + 1 or beyond the registers is cut there: the row steps stay out of these loops) */ \
+		const u32 csAfter = sRegStart[c + 2u]; /* (requested now, needed at the next colour: the LDS round trip hides behind this step) */ \
+		const u32 end = min(csNext, min(regC, ((S_) + 2u) * CLQ_QUADS)); /* (a colour that reaches beyond set S_ + 1 is cut there) */ \
 		CLQ_SOLVE_SET(S_, csCur, end) \
 		if (end > ((S_) + 1u) * CLQ_QUADS) { CLQ_SOLVE_SET((S_) + 1u, csCur, end) } \
 		CLQ_ADVANCE(end) \
@@ -350,7 +374,7 @@ template <bool JOINTS> __global__ void __launch_bounds__(CLS_LANES) k_cl_solve(C
 	bool aborted = false;
 	// The first request of a task's turn reads the task record and then the row, two LDS round trips: it is made right after the turn
 	// before it has published its bodies (and once in front of the loop), where it is in nobody's way, and returns while the workgroup waits for bodies.
-#define CLQ_PREFETCH_TURN(K_) { const ClLocal& N = sTask[K_]; const u32 rc = N.regContacts, in_ = max(N.colorStart[0], rc) + quad - rc; if (in_ < N.rowCap) pfW = ((const u32*)(lds + N.rowOff + in_ * CLQ_ROW_FLOAT4S))[CLQ_PAIR_WORD(q)]; }
+#define CLQ_PREFETCH_TURN(K_) { const ClLocal& N = sTask[K_]; const u32 sp_ = N.spill, in_ = max(N.colorStart[0], sp_) + quad - sp_; if (in_ < N.rowCap) pfW = ((const u32*)(lds + N.rowOff + in_ * CLQ_ROW_FLOAT4S))[CLQ_PAIR_WORD(q)]; }
 	u32 pfW = 0u; // the address word of this lane's next row outside the registers (CLQ_PREFETCH)
 	CLQ_PREFETCH_TURN(0u)
 	u64 lastPublish = 0; u32 lastWait = 0; // when this workgroup last handed its bodies on, and how long (10 ns ticks) the bodies of its first task then took to come back
@@ -445,29 +469,48 @@ template <bool JOINTS> __global__ void __launch_bounds__(CLS_LANES) k_cl_solve(C
 				const u32 numColors = __builtin_amdgcn_readfirstlane(L.numColors), serialStart = __builtin_amdgcn_readfirstlane(L.serialStart), numContacts = __builtin_amdgcn_readfirstlane(L.numContacts);
 				// (what a step needs of the task record, in scalar registers: read from LDS once per turn, not behind every barrier)
 				const u32 regC = __builtin_amdgcn_readfirstlane(L.regContacts), rowOff = __builtin_amdgcn_readfirstlane(L.rowOff), rowCap = __builtin_amdgcn_readfirstlane(L.rowCap), scratchBase = __builtin_amdgcn_readfirstlane(L.scratchBase);
+				const u32 spill = __builtin_amdgcn_readfirstlane(L.spill), ldsColors = __builtin_amdgcn_readfirstlane(L.ldsColors), regBase = numContacts - regC; // (the cut points: the same in every lane, in scalar registers)
 				const bool stamp = trace && tid == 0 && it == A.itBegin + 10u && k == 0;
 				if (stamp) trace[5 * 32] = clock64();
 				const u32 mainColors = (k == 0u) ? tailStart0 : numColors;
 				u32 c = 0, csCur = __builtin_amdgcn_readfirstlane(L.colorStart[0]), csNext = __builtin_amdgcn_readfirstlane(L.colorStart[1]);
-				CLQ_SET_LOOP(0) CLQ_SET_LOOP(1) CLQ_SET_LOOP(2) CLQ_SET_LOOP(3) CLQ_SET_LOOP(4) CLQ_SET_LOOP(5) CLQ_SET_LOOP(6) CLQ_SET_LOOP(7)
-				// colours that lie entirely beyond the register sets (a task that is not the workgroup's first, or larger than the sets)
-				if (rowCap >= numContacts - regC) // (all of them in LDS)
+				// (a first task that fits the register sets, every task of the sparse steps, falls straight through to the set loops: three loop
+				// tests it had to branch over in front of them cost it 0.03 us per turn)
+				if (__builtin_expect(regBase != 0u, 0))
 				{
-					const u32 rowsByte = rowOff * 16u, lastRow = max(numContacts - regC, 1u) - 1u, pairByte = rowsByte + 4u * CLQ_PAIR_WORD(q);
-					while (c < mainColors)
+					// the opening colours whose rows did not fit LDS (rare: a later task behind large ones), cut at spill
+					while (c < mainColors && csCur < spill)
 					{
 						const u32 csAfter = L.colorStart[c + 2u];
-						const u32 end = min(csNext, csCur + CLQ_QUADS);
-						CLQ_SOLVE_ROWS_LDS(csCur, end)
+						const u32 end = min(csNext, spill);
+						CLQ_SOLVE_ROWS(csCur, end)
 						CLQ_ADVANCE(end)
 					}
+					// the colours in LDS rows (a task that is not the workgroup's first: all its other colours; a first task larger than the sets: its
+					// opening ones).  Those that end at or below regBase run in a loop bounded by their number, which is all a later task needs (three
+					// limits in one min() made the compiler take the step's end through a vector register); then the piece below regBase of a first
+					// task's colour that straddles it.
+					{
+						const u32 rowsByte = rowOff * 16u, lastRow = max(rowCap, 1u) - 1u, pairByte = rowsByte + 4u * CLQ_PAIR_WORD(q);
+						while (c < ldsColors)
+						{
+							const u32 csAfter = L.colorStart[c + 2u];
+							const u32 end = min(csNext, csCur + CLQ_QUADS);
+							CLQ_SOLVE_ROWS_LDS(csCur, end)
+							CLQ_ADVANCE(end)
+						}
+						while (c < mainColors && csCur < regBase)
+						{
+							const u32 csAfter = L.colorStart[c + 2u];
+							const u32 end = min(regBase, csCur + CLQ_QUADS); // (< csNext: the colour goes on in the registers)
+							CLQ_SOLVE_ROWS_LDS(csCur, end)
+							CLQ_ADVANCE(end)
+						}
+					}
+					csCur -= regBase; csNext -= regBase;
 				}
-				else while (c < mainColors)
-				{
-					const u32 csAfter = L.colorStart[c + 2u];
-					CLQ_SOLVE_ROWS(csCur, csNext)
-					CLQ_ADVANCE(csNext)
-				}
+				// the colours in the register sets, on positions counted from regBase (a first task that fits the sets: regBase = 0, all of them)
+				CLQ_SET_LOOP(0) CLQ_SET_LOOP(1) CLQ_SET_LOOP(2) CLQ_SET_LOOP(3) CLQ_SET_LOOP(4) CLQ_SET_LOOP(5) CLQ_SET_LOOP(6) CLQ_SET_LOOP(7)
 				if (mainColors < numColors) // the first task's trailing colours: one wave, no workgroup barrier in between
 				{
 #define CLQ_TAIL(S_) case S_: if ((S_) < SETS && myTail != 255u) for (u32 ct = mainColors; ct < numColors; ++ct) { if (myTail == ct) { float4 b = lds[addr[(S_) < SETS ? (S_) : 0u]]; V3 x = v3f4(b); clSolveQuad(rows[(S_) < SETS ? (S_) : 0u], x); lds[addr[(S_) < SETS ? (S_) : 0u]] = make_float4(x.x, x.y, x.z, b.w); } __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); } break;
@@ -479,12 +522,13 @@ template <bool JOINTS> __global__ void __launch_bounds__(CLS_LANES) k_cl_solve(C
 				if (serialStart < numContacts) CLQ_PREFETCH(serialStart) // (colorStart[numColors] = serialStart: the colours left this very word; asked for again so that the tail does not lean on it)
 				for (u32 sp = serialStart; sp < numContacts; ++sp) // the serial tail (manifolds that found no colour run below 64): one contact per step
 				{
-					if (sp < regC)
+					if (sp >= regBase)
 					{
-						switch (sp / CLQ_QUADS)
+						const u32 rp = sp - regBase;
+						switch (rp / CLQ_QUADS)
 						{
-							case 0: CLQ_SOLVE_SET(0u, sp, sp + 1u) break; case 1: CLQ_SOLVE_SET(1u, sp, sp + 1u) break; case 2: CLQ_SOLVE_SET(2u, sp, sp + 1u) break; case 3: CLQ_SOLVE_SET(3u, sp, sp + 1u) break;
-							case 4: CLQ_SOLVE_SET(4u, sp, sp + 1u) break; case 5: CLQ_SOLVE_SET(5u, sp, sp + 1u) break; case 6: CLQ_SOLVE_SET(6u, sp, sp + 1u) break; default: CLQ_SOLVE_SET(7u, sp, sp + 1u) break;
+							case 0: CLQ_SOLVE_SET(0u, rp, rp + 1u) break; case 1: CLQ_SOLVE_SET(1u, rp, rp + 1u) break; case 2: CLQ_SOLVE_SET(2u, rp, rp + 1u) break; case 3: CLQ_SOLVE_SET(3u, rp, rp + 1u) break;
+							case 4: CLQ_SOLVE_SET(4u, rp, rp + 1u) break; case 5: CLQ_SOLVE_SET(5u, rp, rp + 1u) break; case 6: CLQ_SOLVE_SET(6u, rp, rp + 1u) break; default: CLQ_SOLVE_SET(7u, rp, rp + 1u) break;
 						}
 					}
 					else { CLQ_SOLVE_ROWS(sp, sp + 1u) }
@@ -534,13 +578,13 @@ template <bool JOINTS> __global__ void __launch_bounds__(CLS_LANES) k_cl_solve(C
 				for (u32 s = 0; s < SETS; ++s)
 				{
 					const u32 p = s * CLQ_QUADS + quad;
-					if (p < L.regContacts) { const u32 e = A.cEntry[(size_t)4u * L.first + p]; A.rowLambda[(size_t)(e >> 12) * A.rowCap + L.first + (e & 0xFFFu)] = make_float2(rows[s].lamN, rows[s].lamT); }
+					if (p < L.regContacts) { const u32 e = A.cEntry[(size_t)4u * L.first + (L.numContacts - L.regContacts) + p]; A.rowLambda[(size_t)(e >> 12) * A.rowCap + L.first + (e & 0xFFFu)] = make_float2(rows[s].lamN, rows[s].lamT); }
 				}
 			}
-			for (u32 i = quad; i < L.numContacts - L.regContacts; i += CLQ_QUADS)
+			for (u32 p = quad; p < L.numContacts - L.regContacts; p += CLQ_QUADS)
 			{
-				const u32 e = A.cEntry[(size_t)4u * L.first + L.regContacts + i];
-				const float4 lam = i < L.rowCap ? lds[L.rowOff + i * CLQ_ROW_FLOAT4S + 13u] : A.rowScratch[(size_t)(L.scratchBase + i - L.rowCap) * CLQ_ROW_FLOAT4S + 13u];
+				const u32 e = A.cEntry[(size_t)4u * L.first + p];
+				const float4 lam = p >= L.spill ? lds[L.rowOff + (p - L.spill) * CLQ_ROW_FLOAT4S + 13u] : A.rowScratch[(size_t)(L.scratchBase + p) * CLQ_ROW_FLOAT4S + 13u];
 				A.rowLambda[(size_t)(e >> 12) * A.rowCap + L.first + (e & 0xFFFu)] = make_float2(lam.x, lam.y);
 			}
 		}
@@ -616,7 +660,7 @@ void launch_cluster_solve(World& w, u32 itBegin, u32 itEnd)
 	if (w.lastError) return;
 	if (itBegin) MI_CHECK(hipMemsetAsync(w.dCounters.p + CTR_CL_SCRATCH, 0, sizeof(u32), w.stream)); // (the step's first launch finds it cleared by k_cl_clear)
 	ClArgs A;
-	A.rowScratch = w.cluster.rowScratch.p; A.scratchContacts = (u32)scratchContacts; A.regContactsCap = w.cluster.regContactsCap;
+	A.rowScratch = w.cluster.rowScratch.p; A.scratchContacts = (u32)scratchContacts; A.regContactsCap = w.cluster.regContactsCap; A.ldsRowsCap = w.cluster.ldsRowsCap;
 	A.counters = w.dCounters.p; A.tasks = (const ClTask*)w.cluster.tasks.p; A.bodyList = w.cluster.bodyList.p; A.phaseMask = w.cluster.phaseMask.p; A.sharedSlot = w.cluster.sharedSlot.p;
 	A.mKeySorted = w.mKeySorted.p; A.mLocal = w.cluster.local.p; A.cEntry = w.cluster.entry.p;
 	A.rowPlanes = w.rowPlanes.p; A.rowShared = w.rowShared.p; A.rowLambda = w.rowLambda.p; A.vel = w.vel.p; A.flow = w.cluster.flow.p; A.trace = w.cluster.flowTrace.p; A.predictDiv = CL_PREDICT_DIV; A.pollSleep = CL_POLL_SLEEP;

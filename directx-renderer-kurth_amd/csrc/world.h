@@ -276,6 +276,7 @@ struct World
 		u32 taskWeightComp = 64u * 200u;      // MI_CLUSTER_TASK_COMP: the component phase's tasks, sized to fit LDS BEHIND a first task, where most of them run (profiles/sweep_comp_fit.txt)
 		u32 ldsBytes = 0, blocks = 0, cooldown = 0;
 		u32 regContactsCap = ~0u;             // MI_CLUSTER_REG_CONTACTS: most contacts of a workgroup's first task kept in registers (tests: where rows are stored, never what is computed)
+		u32 ldsRowsCap = ~0u;                 // MI_CLUSTER_LDS_ROWS: most contact rows a workgroup keeps in LDS, the rest in the global scratch (tests: storage only, as above)
 		bool compIdle = false;                    // the last step's curve phases left nothing over (and its rest task was empty): this step skips the component phase's launches (what is left over goes to the rest task)
 
 		// -- the partition's private scratch: k_cluster_partition.hip alone (the joint inputs are written by World::uploadJoints) --

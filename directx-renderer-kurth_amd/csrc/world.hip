@@ -62,6 +62,7 @@ World::World(int dev) : device(dev)
 	if (getenv("MI_PHYSICS_REPLAY")) replay.referenceOrder = true;
 	if (const char* e = getenv("MI_CLUSTER_BLOCKS")) cluster.blocksLimit = (u32)std::max(1, atoi(e));
 	if (const char* e = getenv("MI_CLUSTER_REG_CONTACTS")) cluster.regContactsCap = (u32)std::max(0, atoi(e)); // tests: rows beyond it live in LDS / the scratch
+	if (const char* e = getenv("MI_CLUSTER_LDS_ROWS")) cluster.ldsRowsCap = (u32)std::max(0, atoi(e)); // tests: a workgroup's rows beyond it live in the scratch
 	if (const char* e = getenv("MI_CLUSTER_TASK_LATER")) cluster.taskWeightLater = 64u * (u32)std::max(16, atoi(e)); // ... of the phases after the first
 	if (const char* e = getenv("MI_CLUSTER_TASK_COMP")) cluster.taskWeightComp = 64u * (u32)std::min(1 << 20, std::max(16, atoi(e))); // ... of the component phase (dealing its components otherwise changes no result)
 	if (dCounters.p)
