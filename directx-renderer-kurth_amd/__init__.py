@@ -134,6 +134,15 @@ OVERLAP_SUMMARY_DTYPE = np.dtype([("numOverlaps", "<u4"), ("numWritten", "<u4"),
 OVERLAP_HIT_DTYPE = np.dtype([("collider", "<u4"), ("body", "<u4")])
 OVERLAP_STATIC, OVERLAP_BRUTE_FORCE = 1, 2   # mi_overlap_batch's flags (MI_OVERLAP_*)
 OVERLAP_MAX_HITS = 1024                      # MI_OVERLAP_MAX_HITS
+# mi_contact_query (= mi_overlap_query) / mi_contact_query_summary / mi_contact_query_record (include/mi_physics.h): the head of a query's output
+# block, 32 bytes; one of the max_hits records behind it, 96 bytes: points[k] = xyz, depth
+CONTACT_QUERY_DTYPE = OVERLAP_QUERY_DTYPE
+CONTACT_QUERY_SUMMARY_DTYPE = np.dtype([("numContacts", "<u4"), ("numWritten", "<u4"), ("valid", "<u4"), ("reserved0", "<u4"),
+                                        ("deepestCollider", "<u4"), ("deepestBody", "<u4"), ("deepestDepth", "<f4"), ("reserved1", "<u4")])
+CONTACT_QUERY_RECORD_DTYPE = np.dtype([("collider", "<u4"), ("body", "<u4"), ("count", "<u4"), ("reserved", "<u4"), ("normal", "<f4", 3), ("maxDepth", "<f4"),
+                                       ("points", "<f4", (4, 4))])
+CONTACT_QUERY_STATIC, CONTACT_QUERY_BRUTE_FORCE = 1, 2   # mi_contact_query_batch's flags (MI_CONTACT_QUERY_*)
+CONTACT_QUERY_MAX_HITS = 1024                            # MI_CONTACT_QUERY_MAX_HITS
 TERRAIN_COLLIDER = 0xFFFFFFFE   # mi_ray_hit.collider of a hit on the heightmap terrain (MI_TERRAIN_COLLIDER)
 
 
@@ -192,6 +201,7 @@ EXPORTED_SYMBOLS = [
     "mi_proximity", "mi_proximity_host",
     "mi_sphere_cast_batch", "mi_sphere_cast_host",
     "mi_overlap_batch", "mi_overlap_host",
+    "mi_contact_query_batch", "mi_contact_query_host",
 ]
 
 
@@ -730,6 +740,44 @@ class World:
         self._query_numpy(entry(self.lib.mi_overlap_batch if device else self.lib.mi_overlap_host), rec, out, ws if world_shapes else None, device)
         words = out["words"].reshape(n, 4 + 2 * max_hits)
         result = (words[:, :4].copy().view(OVERLAP_SUMMARY_DTYPE).reshape(n), words[:, 4::2].copy(), words[:, 5::2].copy())
+        return result + (ws,) if world_shapes else result
+
+    def contact_query(self, ctype, shape=None, pos=(0, 0, 0), rot=(0, 0, 0, 1), mount=None, exclude_first=None, exclude_count=None, max_hits=16, static=True,
+                      brute_force=False, world_shapes=False, device=False):
+        """mi_contact_query_batch: per volume and per collider it touches the manifold the step's narrowphase would build for a collider of
+        that shape at that pose, "a collider you ask once" (the rule is in include/mi_physics.h).  The query arguments are overlap()'s.
+        numpy queries return (summary [n] of CONTACT_QUERY_SUMMARY_DTYPE, records [n, max_hits] of CONTACT_QUERY_RECORD_DTYPE): numContacts
+        counts every contact, the records are the numWritten = min(numContacts, max_hits) lowest collider indices, ascending, zeros behind
+        them; the normal points from the volume into the collider; deepestCollider / deepestBody / deepestDepth name the largest |depth| over
+        all contacts (STATIC_BODY, STATIC_BODY, 0 without one).  With world_shapes=True a third array [n, 20] follows, as in overlap().
+        Through the world's staging buffers (mi_contact_query_host), or with device=True through device tensors of the caller's
+        (mi_contact_query_batch).
+        A torch tensor on the device (float32, contiguous, [n, 24]: the bits of mi_contact_query) is queried in place: returns one float32
+        tensor [n, 8 + 24 * max_hits] of raw blocks, with world_shapes=True a tuple with the [n, 20] world shapes.  The call reads one
+        4-byte count back from the device, so it synchronises the world's stream once."""
+        flags = (CONTACT_QUERY_STATIC if static else 0) | (CONTACT_QUERY_BRUTE_FORCE if brute_force else 0)
+        max_hits = int(max_hits)
+        if max_hits < 0:
+            raise ValueError("contact_query: max_hits must not be negative")
+
+        def entry(fn):
+            return lambda n, d_in, d_out, d_aux: fn(self.w, C.c_uint32(n), C.c_void_p(d_in), C.c_uint32(max_hits), C.c_uint32(flags), C.c_void_p(d_out), C.c_void_p(d_aux))
+        if _is_tensor(ctype):
+            return self._query_in_place("contact_query", entry(self.lib.mi_contact_query_batch), ctype, 24, 8 + 24 * max_hits, 20 if world_shapes else 0)
+        if isinstance(ctype, np.ndarray) and ctype.dtype == CONTACT_QUERY_DTYPE:
+            rec = np.ascontiguousarray(ctype).reshape(-1)
+        else:
+            sh = np.atleast_2d(np.asarray(shape, np.float32))
+            n = max(len(sh), np.atleast_1d(ctype).size, np.atleast_2d(np.asarray(pos)).shape[0], np.atleast_2d(np.asarray(rot)).shape[0], np.atleast_1d(0 if mount is None else mount).size)
+            rec = np.zeros(n, CONTACT_QUERY_DTYPE)
+            rec["shape"][:, :sh.shape[1]] = sh
+            rec["type"], rec["enabled"], rec["pos"], rec["rot"] = np.asarray(ctype, np.uint32), 1, np.asarray(pos, np.float32), np.asarray(rot, np.float32)
+            _fill_mount(rec, mount, exclude_first, exclude_count)
+        n = len(rec)
+        out, ws = np.zeros(n, np.dtype([("words", "<u4", (8 + 24 * max_hits,))])), np.zeros((n, 20), np.float32)
+        self._query_numpy(entry(self.lib.mi_contact_query_batch if device else self.lib.mi_contact_query_host), rec, out, ws if world_shapes else None, device)
+        words = out["words"].reshape(n, 8 + 24 * max_hits)
+        result = (words[:, :8].copy().view(CONTACT_QUERY_SUMMARY_DTYPE).reshape(n), words[:, 8:].copy().view(CONTACT_QUERY_RECORD_DTYPE).reshape(n, max_hits))
         return result + (ws,) if world_shapes else result
 
     def contact_sensors(self, sensors, device=False):

@@ -347,7 +347,7 @@ int mi_test_physics_interaction_batch(mi_world* world, uint32_t numRays, uint32_
 	return W->lastError;
 }
 
-// ---- world queries: ray casts, ray sensors, proximity sensors, sphere casts, overlap queries, contact sensors.  Each has a device entry (the caller's device
+// ---- world queries: ray casts, ray sensors, proximity sensors, sphere casts, overlap queries, contact queries, contact sensors.  Each has a device entry (the caller's device
 // buffers, enqueued on the world's stream) and a _host entry that stages host arrays around it. ----
 // What every device entry does first: settle a pending give-up of the last step's cluster sweep (the queries see the redone solve),
 // upload, answer a count of zero and missing pointers, build the collider / hull tables if the entry reads them.  true: go on and
@@ -469,6 +469,24 @@ int mi_overlap_host(mi_world* world, uint32_t numQueries, const mi_overlap_query
 	if (maxHits > MI_OVERLAP_MAX_HITS) return MI_ERR_INVALID_ARGUMENT;
 	return queryStaged(W, numQueries, queries, sizeof(mi_overlap_query), out, sizeof(mi_overlap_summary) + sizeof(mi_overlap_hit) * (size_t)maxHits, outWorldShapes, 80,
 		[&](void* dIn, void* dOut, void* dAux) { return mi_overlap_batch(world, numQueries, (const mi_overlap_query*)dIn, maxHits, flags, dOut, (float*)dAux); });
+}
+
+// (contact queries: the rule is in include/mi_physics.h, the volume in overlap_volume.h, the passes in k_contact_query.hip)
+int mi_contact_query_batch(mi_world* world, uint32_t numQueries, const mi_contact_query* dQueries, uint32_t maxHits, uint32_t flags, void* dOut, float* dOutWorldShapes)
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	int code;
+	if (maxHits > MI_CONTACT_QUERY_MAX_HITS) return MI_ERR_INVALID_ARGUMENT; // (like a missing pointer: the world stays usable)
+	if (!queryBegin(W, numQueries, dQueries && dOut, true, code)) return code;
+	launch_contact_query(*W, numQueries, dQueries, maxHits, flags, dOut, dOutWorldShapes); // (no candidate collider: the blocks are empty)
+	return W->lastError;
+}
+int mi_contact_query_host(mi_world* world, uint32_t numQueries, const mi_contact_query* queries, uint32_t maxHits, uint32_t flags, void* out, float* outWorldShapes)
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	if (maxHits > MI_CONTACT_QUERY_MAX_HITS) return MI_ERR_INVALID_ARGUMENT;
+	return queryStaged(W, numQueries, queries, sizeof(mi_contact_query), out, sizeof(mi_contact_query_summary) + sizeof(mi_contact_query_record) * (size_t)maxHits, outWorldShapes, 80,
+		[&](void* dIn, void* dOut, void* dAux) { return mi_contact_query_batch(world, numQueries, (const mi_contact_query*)dIn, maxHits, flags, dOut, (float*)dAux); });
 }
 
 // (contact sensors: the rule is in include/mi_physics.h, the reduction in k_contact_sensors.hip)

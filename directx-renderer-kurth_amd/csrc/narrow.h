@@ -8,7 +8,9 @@
 // This header holds what every stage shares: the pair keys that name the buckets, the shape records and the manifold.  The stages,
 // one translation unit each with its kernels and the host code that launches them: k_narrow_classify.hip (keys, sort, bucket
 // offsets; launch_narrowphase), k_narrow_pairs.hip (closed forms and box-box), k_narrow_gjk.hip (GJK, then EPA on the hits) and
-// k_narrow_zone.hip (boolean overlap tests for force fields and triggers).  narrow_clip.h and narrow_gjk.h hold what two of them use.
+// k_narrow_zone.hip (boolean overlap tests for force fields and triggers).  narrow_clip.h and narrow_gjk.h hold what two of them use;
+// narrow_pairs.h and narrow_epa.h hold the per-pair device functions of the pair and GJK / EPA stages, which the contact query
+// (k_contact_query.hip) runs on its own pair list as well.
 #pragma once
 #include "world.h"
 

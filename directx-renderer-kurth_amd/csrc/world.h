@@ -322,7 +322,7 @@ struct World
 	void uploadFields(); void ensureEventBuffers(u32 numPairs);
 
 	// World queries, rebuilt at every call: api.hip (entries, staging, buildInteractTables), k_interact.hip, k_raycast.hip, raycast_shared.h,
-	// k_raycast_terrain.hip, k_raycast_sensors.hip, k_proximity.hip, k_spherecast.hip, k_overlap.hip, k_contact_sensors.hip
+	// k_raycast_terrain.hip, k_raycast_sensors.hip, k_proximity.hip, k_spherecast.hip, k_overlap.hip, k_contact_query.hip, k_contact_sensors.hip
 	struct Queries
 	{
 		// mi_test_physics_interaction_batch: colliders of every body (CSR), hull triangles as global vertex indices; rebuilt after upload()
@@ -342,6 +342,11 @@ struct World
 		// first entry, fill cursor}; the entries (manifold slot << 32 | schedule position), a segment per wanted body, two per position at most;
 		// the bodies whose segment one lane does not sort; {entries handed out, length of that list}
 		DevBuf<uint4> csBody; DevBuf<u64> csEntries; DevBuf<u32> csLarge, csMeta;
+		// mi_contact_query_batch (k_contact_query.hip): rebuilt at every call, the narrowphase of the query's own, apart from the step's.  Its
+		// counter block (CTR_WORDS words in the step's layout); per query {first pair, pairs, not switched off, 0}; per pair {query, collider,
+		// body, key | operand order}, the two world records in operand order, the manifold, {collider, pair} of the gather pass; the EPA work
+		// list and the simplices of the GJK hits.  The per-pair buffers grow to the pair count the call reads back
+		DevBuf<u32> cqCounters, cqEpaList; DevBuf<uint4> cqSeg, cqPairs; DevBuf<ColliderRec> cqCols; DevBuf<ManifoldRec> cqManifolds; DevBuf<float4> cqSimplex; DevBuf<uint2> cqSorted;
 		// Staging of the queries' _host entries (api.hip, queryStaged), in bytes: the records in, the records out, the optional second output
 		// (world rays, world points).  One set for all of them: every _host entry drains the world's stream before it returns
 		DevBuf<uint8_t> hostIn, hostOut, hostAux;
@@ -427,6 +432,7 @@ RcBuild launch_raycast_build(World& w, bool withStatic, bool brute); // k_raycas
 void launch_proximity(World& w, u32 n, const mi_proximity_query* dQueries, u32 flags, mi_proximity_reading* dOut, float* dOutWorldPoints); // k_proximity.hip
 void launch_sphere_cast(World& w, u32 n, const mi_sphere_cast* dQueries, u32 flags, mi_sphere_hit* dOut, float* dOutWorldCasts); // k_spherecast.hip
 void launch_overlap(World& w, u32 n, const mi_overlap_query* dQueries, u32 maxHits, u32 flags, void* dOut, float* dOutWorldShapes); // k_overlap.hip
+void launch_contact_query(World& w, u32 n, const mi_overlap_query* dQueries, u32 maxHits, u32 flags, void* dOut, float* dOutWorldShapes); // k_contact_query.hip
 void launch_raycast_sensors(World& w, u32 numRays, const mi_sensor_ray* dRays, u32 flags, bool terrain, mi_sensor_hit* dOutHits, float* dOutWorldRays); // k_raycast_sensors.hip
 void launch_proximity_terrain(World& w, u32 n, const mi_proximity_query* dQueries, u32 flags, mi_proximity_reading* dOut); // k_proximity_terrain.hip: after launch_proximity, on its records
 void launch_sphere_cast_terrain(World& w, u32 n, const mi_sphere_cast* dQueries, u32 flags, mi_sphere_hit* dOut); // k_spherecast_terrain.hip: after launch_sphere_cast, on its records

@@ -572,6 +572,82 @@ namespace mi
 		return overlapVolume(scene, collider_component::asAABB(bounding_box::fromCenterRadius(vec3(0.f, 0.f, 0.f), radius), physics_material{}), centre, rotation, out);
 	}
 
+	// How a volume touches the world right now ("a collider you ask once"; include/mi_physics.h states the rule): per collider of a rigid
+	// body or static collider the manifold the step's narrowphase would build for a collider of this shape at this pose, lowest collider
+	// index first.  normal points from the volume into the collider; depth keeps the reference's sign (negative on some AABB-AABB
+	// pairs), maxDepth is the largest |depth| of the contact's points.  `out` receives up to maxHits contacts; the return value is the
+	// total count.  One query through mi_contact_query_batch.
+	struct volume_contact { uint32_t collider = 0, body = MI_STATIC_BODY, count = 0; vec3 normal; float maxDepth = 0.f; vec3 points[4]; float depths[4] = { 0.f, 0.f, 0.f, 0.f }; };
+	struct volume_penetration { bool touching = false; uint32_t collider = 0, body = MI_STATIC_BODY; float depth = 0.f; vec3 normal; };
+	inline mi_contact_query contactQueryOf(const collider_component& volume, vec3 position, quat rotation)
+	{
+		mi_contact_query in{};
+		memcpy(in.shape, volume.shape, sizeof(in.shape)); in.type = volume.type;
+		in.pos[0] = position.x; in.pos[1] = position.y; in.pos[2] = position.z;
+		in.rot[0] = rotation.x; in.rot[1] = rotation.y; in.rot[2] = rotation.z; in.rot[3] = rotation.w;
+		in.mount = MI_STATIC_BODY; in.enabled = 1u;
+		return in;
+	}
+	// deepest (may be null): the deepest contact of ALL, also when it lies behind the maxHits written ones; its normal is only known when
+	// it is among them (maxHits >= the count), otherwise zero.
+	inline uint32_t contactQuery(game_scene& scene, const mi_contact_query& in, std::vector<volume_contact>& out, uint32_t maxHits, volume_penetration* deepest, const char* what)
+	{
+		scene.flushStaticColliders();
+		std::vector<uint32_t> block(8u + 24u * (size_t)maxHits);
+		scene.check(mi_contact_query_host(scene.world, 1u, &in, maxHits, (uint32_t)MI_CONTACT_QUERY_STATIC, block.data(), nullptr), what);
+		const mi_contact_query_summary* s = (const mi_contact_query_summary*)block.data();
+		const mi_contact_query_record* r = (const mi_contact_query_record*)(block.data() + 8);
+		out.clear();
+		if (deepest) { *deepest = volume_penetration{}; deepest->touching = s->numContacts != 0u; deepest->collider = s->deepestCollider; deepest->body = s->deepestBody; deepest->depth = s->deepestDepth; }
+		for (uint32_t k = 0; k < s->numWritten; ++k)
+		{
+			volume_contact c; c.collider = r[k].collider; c.body = r[k].body; c.count = r[k].count; c.maxDepth = r[k].maxDepth;
+			c.normal = vec3(r[k].normal[0], r[k].normal[1], r[k].normal[2]);
+			for (uint32_t p = 0; p < c.count && p < 4u; ++p) { c.points[p] = vec3(r[k].points[p][0], r[k].points[p][1], r[k].points[p][2]); c.depths[p] = r[k].points[p][3]; }
+			if (deepest && s->numContacts && c.collider == s->deepestCollider) deepest->normal = c.normal;
+			out.push_back(c);
+		}
+		return s->numContacts;
+	}
+	// volume: one of the collider factories' values (its material is not used) in the frame (position, rotation), world space.
+	inline uint32_t contactsOfVolume(game_scene& scene, const collider_component& volume, vec3 position, quat rotation, std::vector<volume_contact>& out, uint32_t maxHits = 64u)
+	{
+		return contactQuery(scene, contactQueryOf(volume, position, rotation), out, maxHits, nullptr, "contactsOfVolume");
+	}
+	// The same volume fixed to a rigid body: (localPosition, localRotation) is in the body's frame at its current pose.  excludeSelf: the
+	// body's own colliders are no candidates.
+	inline uint32_t contactsOfVolume(game_scene& scene, const scene_entity& body, const collider_component& volume, vec3 localPosition, quat localRotation, std::vector<volume_contact>& out,
+		bool excludeSelf = true, uint32_t maxHits = 64u)
+	{
+		mi_contact_query in = contactQueryOf(volume, localPosition, localRotation);
+		in.mount = body.body(); in.excludeFirst = in.mount; in.excludeCount = excludeSelf ? 1u : 0u;
+		return contactQuery(scene, in, out, maxHits, nullptr, "contactsOfVolume");
+	}
+	// The deepest contact of the volume: touching = false when it touches nothing.  depth = |depth| (>= 0).
+	inline volume_penetration penetrationOf(game_scene& scene, const collider_component& volume, vec3 position, quat rotation, uint32_t maxHits = 64u)
+	{
+		std::vector<volume_contact> contacts; volume_penetration p;
+		contactQuery(scene, contactQueryOf(volume, position, rotation), contacts, maxHits, &p, "penetrationOf");
+		return p;
+	}
+	// Pushes a hand-placed volume out of what it overlaps: up to `iterations` times, moves `position` by -|depth| * normal of the deepest
+	// contact (|depth|: AABB-AABB depths carry the sign of the centre offset) until nothing is deeper than `slop`.  Returns the
+	// iterations used; `remaining` (may be null) receives the deepest |depth| that is left.  A kinematic character's push-out; with
+	// castSphere (how far can I move) the two halves of a character controller.
+	inline uint32_t depenetrate(game_scene& scene, const collider_component& volume, vec3& position, quat rotation, uint32_t iterations = 8u, float slop = 1e-3f, float* remaining = nullptr)
+	{
+		uint32_t used = 0;
+		volume_penetration p = penetrationOf(scene, volume, position, rotation);
+		while (p.touching && p.depth > slop && used < iterations)
+		{
+			position = vec3(position.x - p.depth * p.normal.x, position.y - p.depth * p.normal.y, position.z - p.depth * p.normal.z);
+			++used;
+			p = penetrationOf(scene, volume, position, rotation);
+		}
+		if (remaining) *remaining = p.touching ? p.depth : 0.f;
+		return used;
+	}
+
 	// What the contacts of the last internal step did to a rigid body (no counterpart in the reference's physics.h; include/mi_physics.h
 	// states the rule): the linear and angular impulse they applied to it, the sum of the normal impulses, how many contacts and manifolds
 	// were summed and the partner that pressed hardest.  partners: MI_CONTACT_DYNAMIC | MI_CONTACT_STATIC; the bodies excludeFirst ..

@@ -519,6 +519,52 @@ typedef struct mi_overlap_hit { uint32_t collider, body; } mi_overlap_hit;      
 int mi_overlap_batch(mi_world* w, uint32_t numQueries, const mi_overlap_query* dQueries, uint32_t maxHits, uint32_t flags, void* dOut, float* dOutWorldShapes);
 int mi_overlap_host(mi_world* w, uint32_t numQueries, const mi_overlap_query* queries, uint32_t maxHits, uint32_t flags, void* out, float* outWorldShapes);
 
+/* Contact queries: "a collider you ask once".  For a volume of any of the six collider types at a pose, per candidate collider of the
+ * world the manifold the step's narrowphase would build for a collider of that shape at that pose: how deep, in which direction, at
+ * which points.  Nothing is added to the world and nothing of the step is touched: the step's pair list, manifolds, EPA lists, counters
+ * and mi_debug_narrow_limits read the same before and after a call.  (The reference has no such query: the rule is this project's, built
+ * from the reference's narrowphase.)
+ * Query: mi_contact_query is mi_overlap_query itself, 96 bytes.  The shape words, the volume frame and mount composition, the world
+ * record and world box (csrc/collider_world.h), the switched-off conditions and dOutWorldShapes are mi_overlap_batch's, word for word
+ * (above); a query that is switched off has valid = 0 and an all-zero block.
+ * Candidates are mi_overlap_batch's: the colliders of alive bodies simulated here and, with MI_CONTACT_QUERY_STATIC, those of entities
+ * without a rigid body; never force-field or trigger colliders, never cloth, never the heightmap terrain.  The colliders of the bodies b
+ * with b - excludeFirst < excludeCount, in uint32 arithmetic, are no candidates of this query; static colliders are never excluded.
+ * Decision per candidate, in two stages.  (1) The candidate's world box meets the volume's world box inclusively on all three axes, as
+ * in mi_overlap_batch: part of the rule, not merely pruning.  (2) The step's narrowphase on the two world records: operand A is the
+ * record of the lower collider type after promotion, and of equal types A is the VOLUME (the reference gives different manifolds for
+ * the two orders of capsule-capsule, cylinder-cylinder and hull-hull).  The code is the step's own device functions (csrc/narrow_pairs.h,
+ * narrow_gjk.h, narrow_epa.h): closed forms, box-box SAT with clipping, GJK with EPA, the OBB back-transform; 21 type pairs.
+ * Contact: a candidate whose manifold has count > 0.  It is reported as if the volume were operand A: where the collider was A the three
+ * sign bits of the normal are flipped and nothing else; points and depths are verbatim.  So the normal points from the volume into the
+ * collider, and moving the volume by -|depth| * normal separates the two.  The reference's quirks arrive as they are: AABB-AABB depths
+ * carry the sign of the centre offset on the least-overlap axis; a sphere centre inside a box gives depth = radius along +y; a GJK pair
+ * of centrally symmetric shapes with coincident centres gives no manifold.  No friction or restitution is reported: a volume has no
+ * material.
+ * Output: per query one block of 32 + 96 * maxHits bytes in dOut (device, 16-byte aligned): mi_contact_query_summary, then maxHits
+ * records of mi_contact_query_record.  numContacts counts every contact, whatever maxHits is; numWritten = min(numContacts, maxHits); the
+ * records are the numWritten lowest collider indices with a contact, ascending; the slots behind them are zero; body is MI_STATIC_BODY
+ * for a static collider; count is the manifold's 1 .. 4 points, the points behind it are zero; maxDepth is the largest |depth| of the
+ * record.  deepestCollider, deepestBody, deepestDepth: the largest maxDepth over ALL contacts (it may lie outside the written records),
+ * ties to the lower collider index; without a contact 0xFFFFFFFF, 0xFFFFFFFF and 0.  valid = 1 for a query that is not switched off.
+ * maxHits == 0 is a pure count plus the deepest contact; maxHits > MI_CONTACT_QUERY_MAX_HITS returns MI_ERR_INVALID_ARGUMENT.
+ * Sizing: the pair list (candidates that pass stage 1) is counted on the device first; the call reads that one 4-byte count back, which
+ * synchronises the world's stream once, grows the world's scratch to it and then fills and runs the list: no contact is ever lost to a
+ * capacity.  The scratch and the counter block are the query's own and are freed with the world.
+ * The candidates and the tree over them are mi_raycast_batch's, rebuilt from the current poses at every call in the same buffers;
+ * MI_CONTACT_QUERY_BRUTE_FORCE asks every candidate instead (same bytes; a yardstick).  No result depends on the order of an atomic
+ * operation: two calls give the same bytes.  Calls of all query kinds may follow each other freely.
+ * mi_contact_query_host: queries, blocks and world shapes in HOST memory, staged through buffers of the world. */
+enum { MI_CONTACT_QUERY_STATIC = 1, MI_CONTACT_QUERY_BRUTE_FORCE = 2 };
+#define MI_CONTACT_QUERY_MAX_HITS 1024u
+typedef mi_overlap_query mi_contact_query;                                                                   /* 96 bytes */
+typedef struct mi_contact_query_summary { uint32_t numContacts, numWritten, valid, reserved0, deepestCollider, deepestBody; float deepestDepth;
+                                          uint32_t reserved1; } mi_contact_query_summary;                    /* 32 bytes */
+typedef struct mi_contact_query_record { uint32_t collider, body, count, reserved; float normal[3], maxDepth;
+                                         float points[4][4]; /* xyz, depth */ } mi_contact_query_record;     /* 96 bytes */
+int mi_contact_query_batch(mi_world* w, uint32_t numQueries, const mi_contact_query* dQueries, uint32_t maxHits, uint32_t flags, void* dOut, float* dOutWorldShapes);
+int mi_contact_query_host(mi_world* w, uint32_t numQueries, const mi_contact_query* queries, uint32_t maxHits, uint32_t flags, void* out, float* outWorldShapes);
+
 /* Contact sensors: what the contacts of the LAST INTERNAL STEP did to a body, summed on the device from the rows its solve left behind.
  * One call on the world's stream; like the ray entries it first settles a step whose cluster sweep is not yet known to have completed
  * (after a give-up the readings describe the redone solve) and otherwise does not synchronise with the host.  The step's buffers are only
