@@ -191,7 +191,7 @@ EXPORTED_SYMBOLS = [
     "mi_add_cloth", "mi_cloth_set_fixed_vertices", "mi_cloth_set_properties", "mi_set_cloth_iterations", "mi_num_cloths", "mi_cloth_num_particles", "mi_cloth_read",
     "mi_test_physics_interaction", "mi_apply_force_torque", "mi_set_velocity",
     "mi_set_transform", "mi_write_transforms", "mi_write_velocities", "mi_step", "mi_step_internal", "mi_synchronize", "mi_read_transforms", "mi_read_velocities", "mi_read_mass_properties",
-    "mi_get_stats", "mi_enable_validation", "mi_enable_stage_timing", "mi_num_bodies", "mi_num_colliders", "mi_device_pointers", "mi_state_to_device_buffers", "mi_state_from_device_buffers", "mi_slab_configure", "mi_slab_message_bytes", "mi_slab_pack", "mi_slab_unpack", "mi_slab_read_codes", "mi_debug_num_pairs", "mi_debug_read_pairs", "mi_debug_sorting_axis", "mi_debug_narrow_limits",
+    "mi_get_stats", "mi_enable_validation", "mi_enable_stage_timing", "mi_num_bodies", "mi_num_colliders", "mi_device_pointers", "mi_state_to_device_buffers", "mi_state_from_device_buffers", "mi_slab_configure", "mi_slab_message_bytes", "mi_slab_pack", "mi_slab_unpack", "mi_slab_read_codes", "mi_debug_num_pairs", "mi_debug_read_pairs", "mi_debug_sorting_axis", "mi_debug_narrow_limits", "mi_debug_color_tasks", "mi_debug_task_items",
     "mi_debug_read_world_colliders", "mi_debug_num_manifold_slots", "mi_debug_read_manifolds", "mi_debug_num_colors", "mi_debug_read_schedule", "mi_debug_read_contact_impulses",
     "mi_debug_read_joint_order", "mi_debug_read_joint_update", "mi_debug_read_body_state", "mi_debug_read_accumulators", "mi_debug_flow_trace",
     "mi_debug_set_replay", "mi_debug_num_replay_batches", "mi_debug_read_replay_batches",
@@ -915,6 +915,20 @@ class World:
         out = np.zeros(8, np.uint32)
         self._check(self.lib.mi_debug_narrow_limits(self.w, _p(out)))
         return dict(gjk_max_iters=int(out[0]), epa_max_triangles=int(out[1]), epa_max_edges=int(out[2]), epa_max_border=int(out[3]), epa_out_of_memory=int(out[4]))
+
+    def color_tasks(self):
+        """Task colouring of the last step that ran the cluster sweep: tasks the narrow and the wide instance of k_cl_color coloured, tasks
+        too large for the narrow one, and the narrow launch's shape (workgroups, most items of a task it takes, workgroups resident per
+        compute unit).  Dispatch only: no result depends on which instance coloured a task."""
+        out = np.zeros(8, np.uint32)
+        self._check(self.lib.mi_debug_color_tasks(self.w, _p(out)))
+        return dict(narrow=int(out[0]), wide=int(out[1]), oversize=int(out[2]), narrow_blocks=int(out[3]), narrow_max=int(out[4]), resident=int(out[5]))
+
+    def task_items(self):
+        """Items (manifolds + joints) of every task the last cluster build laid out: one array per phase."""
+        items, tasks = np.zeros(5 * 512, np.uint32), np.zeros(8, np.uint32)
+        self._check(self.lib.mi_debug_task_items(self.w, _p(items), _p(tasks)))
+        return [items[p * 512:p * 512 + int(tasks[p])].copy() for p in range(5)]
 
     def world_colliders(self):
         n = self.num_colliders

@@ -2,6 +2,7 @@
 // multi-GPU slabs and the mi_debug_* inspection calls.  (What a world is made of is added in api_scene.hip; mi_snapshot_* and
 // mi_world_restore are in snapshot.hip.)
 #include "api.h"
+#include "cluster.h"
 #include "ray_tests.h"
 #include <cstring>
 #include <cmath>
@@ -649,6 +650,36 @@ int mi_debug_narrow_limits(mi_world* world, uint32_t out[8])
 	u32 words[5] = { 0, 0, 0, 0, 0 };
 	d2h(W, words, W->dCounters.p + CTR_NARROW_LIMITS, sizeof(words));
 	for (u32 i = 0; i < 8; ++i) out[i] = i < 5 ? words[i] : 0u;
+	return W->lastError;
+}
+int mi_debug_color_tasks(mi_world* world, uint32_t out[8])
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	u32 words[3] = { 0, 0, 0 };
+	d2h(W, words, W->dCounters.p + CTR_CL_COLOR_TASKS, sizeof(words));
+	out[0] = words[1]; out[1] = words[2]; out[2] = words[0];
+	out[3] = W->cluster.colorNarrowBlocks; out[4] = W->cluster.colorNarrowLimit ? W->cluster.colorNarrowLimit - 1u : 0u; out[5] = W->cluster.colorResident; out[6] = out[7] = 0u;
+	return W->lastError;
+}
+int mi_debug_task_items(mi_world* world, uint32_t* outItems, uint32_t outTasks[8])
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	W->refreshCounters();
+	const u32 keys = CL_MAX_PHASES * CL_MAX_TASKS;
+	static_assert(CL_MAX_PHASES <= 8u && CL_MAX_PHASES * CL_MAX_TASKS == 2560u, "the layout mi_physics.h documents");
+	memset(outItems, 0, sizeof(u32) * keys);
+	const bool built = W->last.cluster && W->cluster.taskStart.p;
+	for (u32 p = 0; p < 8u; ++p) outTasks[p] = (built && p < CL_MAX_PHASES) ? std::min<u32>(W->hCounters[CTR_CL_NUM_TASKS + p], CL_MAX_TASKS) : 0u;
+	if (!built) return W->lastError;
+	std::vector<u32> start((size_t)keys * CL_SUBCOUNTERS + 1u), jStart(CL_MAX_TASKS + 1u, 0u);
+	d2h(W, start.data(), W->cluster.taskStart.p, sizeof(u32) * start.size());
+	if (cluster_solves_joints(*W) && W->cluster.numJoints && W->cluster.jointStart.p) d2h(W, jStart.data(), W->cluster.jointStart.p, sizeof(u32) * jStart.size());
+	for (u32 p = 0; p < CL_MAX_PHASES; ++p)
+		for (u32 t = 0; t < outTasks[p]; ++t)
+		{
+			const u32 key = p * CL_MAX_TASKS + t;
+			outItems[key] = start[(size_t)(key + 1u) * CL_SUBCOUNTERS] - start[(size_t)key * CL_SUBCOUNTERS] + (p == 0u ? jStart[t + 1u] - jStart[t] : 0u);
+		}
 	return W->lastError;
 }
 uint32_t mi_debug_num_colors(mi_world* world) { CHECK_WORLD(0); return MI_MAX_COLORS + 1; }

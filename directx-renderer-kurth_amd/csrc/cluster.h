@@ -55,6 +55,6 @@ struct ClTask
 static_assert(sizeof(ClTask) == 320, "task header");
 
 // ---- host side: each stage sets up and launches its own kernels ----------------------------------------------------
-bool cluster_color_setup();                 // k_cl_color's dynamic-LDS attribute; false = the device refuses it
+bool cluster_color_setup(World& w, u32 computeUnits); // k_cl_color's dynamic-LDS attributes and the narrow launch's size; false = the device refuses the wide tables
 void cluster_color_launch(World& w, u32 nj); // nj: joints the sweep runs (0: their tables are not read)
 u32 cluster_solve_setup(const World& w);    // k_cl_solve's dynamic-LDS budget in bytes on w's device, set on both instantiations; 0 = the device refuses it

@@ -463,13 +463,14 @@ MI_DEV u32 clBlockInclusive1024(u32 v, u32* waveTotals /* [16], LDS */)
 	__syncthreads(); // (waveTotals is reused by the next call)
 	return v + before;
 }
-__global__ void __launch_bounds__(1024) k_cl_offsets(u32* __restrict__ counters, u32 numParts, const u32* __restrict__ taskCount, u32* __restrict__ taskStart, const u32* __restrict__ jointCount, u32* __restrict__ jointStart)
+__global__ void __launch_bounds__(1024) k_cl_offsets(u32* __restrict__ counters, u32 numParts, u32 narrowLimit, const u32* __restrict__ taskCount, u32* __restrict__ taskStart, const u32* __restrict__ jointCount, u32* __restrict__ jointStart)
 {
 	__shared__ u32 part[16];
-	__shared__ u32 lastTask[CL_MAX_PHASES];
+	__shared__ u32 lastTask[CL_MAX_PHASES], oversize;
 	const u32 total = CL_TASK_CURSORS, per = (total + 1023u) / 1024u;
 	u32 t = threadIdx.x;
 	if (t < CL_MAX_PHASES) lastTask[t] = 0;
+	if (t == 0) oversize = 0;
 	__shared__ uint16_t cnt[CL_TASK_CURSORS]; // the counters, read once with neighbouring lanes on neighbouring words (a sub-counter holds < 64 k)
 	for (u32 e = t; e < total; e += 1024u) cnt[e] = (uint16_t)min(taskCount[e], 0xFFFFu);
 	__syncthreads(); // (cnt, lastTask)
@@ -498,6 +499,15 @@ __global__ void __launch_bounds__(1024) k_cl_offsets(u32* __restrict__ counters,
 		const u32 jIncl = jointCount ? clBlockInclusive1024(jc, part) : 0u; // (uniform branch)
 		if (jointStart && t < CL_MAX_TASKS) { jointStart[t] = jIncl - jc; if (t == CL_MAX_TASKS - 1u) jointStart[CL_MAX_TASKS] = jIncl; }
 		if (jc) atomicMax(&lastTask[0], t + 1u);
+		// tasks of narrowLimit items (manifolds + joints) or more: k_cl_color's wide instance colours those, and only those
+		u32 big = 0;
+		for (u32 key = t; key < total / CL_SUBCOUNTERS; key += 1024u)
+		{
+			u32 items = key < CL_MAX_TASKS ? jc : 0u; // (key = t there)
+			for (u32 k = 0; k < CL_SUBCOUNTERS; ++k) items += cnt[key * CL_SUBCOUNTERS + k];
+			big += items >= narrowLimit ? 1u : 0u;
+		}
+		if (big) atomicAdd(&oversize, big);
 		__syncthreads();
 	}
 	const u32 totalManifolds = taskStart[total];
@@ -507,6 +517,7 @@ __global__ void __launch_bounds__(1024) k_cl_offsets(u32* __restrict__ counters,
 	{
 		counters[CTR_NUM_MANIFOLDS] = totalManifolds;
 		counters[CTR_NUM_COLORS] = 0; // k_cl_color: atomicMax of the local colour counts
+		counters[CTR_CL_COLOR_TASKS] = oversize; counters[CTR_CL_COLOR_TASKS + 1] = 0; counters[CTR_CL_COLOR_TASKS + 2] = 0; // ... and the tasks each instance coloured
 		for (int k = 0; k < 3; ++k) { counters[CTR_CL_BBOX + k] = 0xFFFFFFFFu; counters[CTR_CL_BBOX + 3 + k] = 0u; } // consumed by k_cl_keys: ready for the next step
 	}
 }
@@ -646,7 +657,7 @@ static void clAssignComponents(World& w)
 // First slot of every task, then every manifold (and, unless kept, joint) to its slot.
 static void clOffsetsAndScatter(World& w, u32 numPairs, u32 nj, bool keepJointLists)
 {
-	hipLaunchKernelGGL(k_cl_offsets, dim3(1), dim3(1024), 0, w.stream, w.dCounters.p, CL_CURVE_PARTS, w.cluster.taskCount.p, w.cluster.taskStart.p, nj ? w.cluster.jointCount.p : (u32*)nullptr, nj ? w.cluster.jointStart.p : (u32*)nullptr);
+	hipLaunchKernelGGL(k_cl_offsets, dim3(1), dim3(1024), 0, w.stream, w.dCounters.p, CL_CURVE_PARTS, w.cluster.colorNarrowLimit, w.cluster.taskCount.p, w.cluster.taskStart.p, nj ? w.cluster.jointCount.p : (u32*)nullptr, nj ? w.cluster.jointStart.p : (u32*)nullptr);
 	if (nj && !keepJointLists) hipLaunchKernelGGL(k_cl_joint_scatter, clGrid(nj), CL_BLOCK, 0, w.stream, nj, w.cluster.jointTask.p, w.cluster.jointPos.p, w.cluster.jointStart.p, w.cluster.jointList.p);
 	w.cluster.jointListsValid = nj != 0u;
 	hipLaunchKernelGGL(k_cl_scatter, clManifoldGrid(numPairs), dim3(CL_ASSIGN_LANES), 0, w.stream, w.dCounters.p, w.cluster.taskKey.p, w.cluster.taskPos.p, w.cluster.taskStart.p, w.cluster.pre.p);

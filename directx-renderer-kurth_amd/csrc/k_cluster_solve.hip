@@ -623,7 +623,7 @@ bool cluster_available(World& w)
 	int cus = 0;
 	MI_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, w.device));
 	const u32 dyn = cluster_solve_setup(w);
-	if (!dyn || !cluster_color_setup())
+	if (!dyn || !cluster_color_setup(w, (u32)std::max(1, cus)))
 	{
 		(void)hipGetLastError();
 		w.cluster.ldsBytes = ~0u;

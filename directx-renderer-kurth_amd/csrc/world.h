@@ -108,6 +108,7 @@ enum
 	CTR_CL_REMAIN = 442,    // 6 words: manifolds still unassigned when partition phase p starts ([0] unused: all active ones)
 	CTR_VALIDATE = 448,     // 2 words: non-finite values found by the debug guard (MI_PHYSICS_VALIDATE=1), first offender (stage << 28 | index)
 	CTR_NARROW_LIMITS = 450,// 5 words: high-water marks of the GJK / EPA caps since the world was created (k_gjk, k_epa): GJK iterations, EPA triangles, edges, border edges; EPA runs that left through an out-of-memory exit (mi_debug_narrow_limits)
+	CTR_CL_COLOR_TASKS = 456,// 3 words: task colouring of the last step: tasks too large for the narrow instance (k_cl_offsets; the wide launch leaves at once on 0), tasks the narrow / the wide instance coloured (mi_debug_color_tasks)
 	CTR_WORDS = 512,
 };
 struct CtrRange { u32 first, words; };
@@ -117,7 +118,7 @@ static constexpr CtrRange CTR_LAYOUT[] = // every entry of the enum, ascending
 	{ CTR_CELL_SIZE, 1 }, { CTR_NUM_ACTIVE, 1 }, { CTR_NUM_CONTACTS, 1 }, { CTR_PAIR_OVERFLOW, 1 }, { CTR_FIRST_INACTIVE, 1 }, { CTR_FLOW_STATUS, 1 }, { CTR_FLOW_PROBES, 1 }, { CTR_EPA_COUNT_HULL, 1 },
 	{ CTR_BUCKET_START, 65 }, { CTR_KEY_START, (MI_MAX_COLORS + 1) * 4 + 1 }, { CTR_COLOR_BARRIER, 4 }, { CTR_SAP_AXIS, 2 }, { CTR_CL_SCRATCH, 1 }, { CTR_CL_LEFT, 5 },
 	{ CTR_ACTIVE_BODIES, 1 }, { CTR_ACTIVE_COLS, 1 }, { CTR_ACTIVE_OVERFLOW, 1 }, { CTR_CELL_SIZE_USED, 1 }, { CTR_EVENT_COUNT, 1 }, { CTR_EVENT_OVERFLOW, 1 }, { CTR_TERRAIN_BASE, 1 }, { CTR_TERRAIN_OVERFLOW, 1 },
-	{ CTR_CL_NUM_TASKS, 5 }, { CTR_CL_STATUS, 1 }, { CTR_CL_SHARED, 1 }, { CTR_CL_PHASE_COUNT, 5 }, { CTR_CL_BBOX, 6 }, { CTR_CL_REMAIN, 6 }, { CTR_VALIDATE, 2 }, { CTR_NARROW_LIMITS, 5 },
+	{ CTR_CL_NUM_TASKS, 5 }, { CTR_CL_STATUS, 1 }, { CTR_CL_SHARED, 1 }, { CTR_CL_PHASE_COUNT, 5 }, { CTR_CL_BBOX, 6 }, { CTR_CL_REMAIN, 6 }, { CTR_VALIDATE, 2 }, { CTR_NARROW_LIMITS, 5 }, { CTR_CL_COLOR_TASKS, 3 },
 };
 constexpr bool ctrLayoutDisjoint() { u32 end = 0; for (const CtrRange& r : CTR_LAYOUT) { if (r.first < end) return false; end = r.first + r.words; } return end <= CTR_WORDS; }
 constexpr u32 ctrWords(u32 first) { for (const CtrRange& r : CTR_LAYOUT) if (r.first == first) return r.words; return 0; } // extent of the entry that begins at `first`
@@ -277,6 +278,8 @@ struct World
 		u32 ldsBytes = 0, blocks = 0, cooldown = 0;
 		u32 regContactsCap = ~0u;             // MI_CLUSTER_REG_CONTACTS: most contacts of a workgroup's first task kept in registers (tests: where rows are stored, never what is computed)
 		u32 ldsRowsCap = ~0u;                 // MI_CLUSTER_LDS_ROWS: most contact rows a workgroup keeps in LDS, the rest in the global scratch (tests: storage only, as above)
+		u32 colorNarrowMax = ~0u, colorBlocksLimit = 0; // MI_CLUSTER_COLOR_NARROW_MAX: most items (manifolds + joints) of a task the narrow colouring instance takes (0: the wide kernel colours everything); MI_CLUSTER_COLOR_BLOCKS: most workgroups of the narrow launch (tests).  Dispatch only: no result depends on either
+		u32 colorResident = 0, colorNarrowBlocks = 0, colorNarrowLimit = 0; // cluster_color_setup: narrow workgroups resident per compute unit, the narrow launch's grid (0: not launched), first item count that goes to the wide kernel
 		bool compIdle = false;                    // the last step's curve phases left nothing over (and its rest task was empty): this step skips the component phase's launches (what is left over goes to the rest task)
 
 		// -- the partition's private scratch: k_cluster_partition.hip alone (the joint inputs are written by World::uploadJoints) --

@@ -65,6 +65,8 @@ World::World(int dev) : device(dev)
 	if (const char* e = getenv("MI_CLUSTER_LDS_ROWS")) cluster.ldsRowsCap = (u32)std::max(0, atoi(e)); // tests: a workgroup's rows beyond it live in the scratch
 	if (const char* e = getenv("MI_CLUSTER_TASK_LATER")) cluster.taskWeightLater = 64u * (u32)std::max(16, atoi(e)); // ... of the phases after the first
 	if (const char* e = getenv("MI_CLUSTER_TASK_COMP")) cluster.taskWeightComp = 64u * (u32)std::min(1 << 20, std::max(16, atoi(e))); // ... of the component phase (dealing its components otherwise changes no result)
+	if (const char* e = getenv("MI_CLUSTER_COLOR_NARROW_MAX")) cluster.colorNarrowMax = (u32)std::max(0, atoi(e)); // tasks of more items are coloured by the wide instance (0: all of them)
+	if (const char* e = getenv("MI_CLUSTER_COLOR_BLOCKS")) cluster.colorBlocksLimit = (u32)std::max(1, atoi(e)); // tests: a small narrow launch, whose workgroups colour several tasks in turn
 	if (dCounters.p)
 	{
 		u32 box[6] = { 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u }; // empty bounding box (k_cl_bbox accumulates, k_cl_offsets resets)

@@ -634,6 +634,13 @@ int mi_debug_sorting_axis(mi_world* w, uint32_t out[2]);
 /* High-water marks of the narrowphase's fixed-size GJK / EPA state since the world was created: [0] GJK iterations, [1] EPA triangles,
    [2] EPA edges, [3] EPA border edges of one expansion, [4] EPA runs that stopped at an out-of-memory exit; [5..7] zero. */
 int mi_debug_narrow_limits(mi_world* w, uint32_t out[8]);
+/* Task colouring of the last step that ran the cluster sweep: [0] tasks the narrow instance coloured, [1] tasks the wide one coloured,
+   [2] tasks too large for the narrow instance as the partition counted them, [3] workgroups of the narrow launch (0: not launched),
+   [4] most items (manifolds + joints) of a task it takes, [5] its workgroups resident per compute unit; [6..7] zero. */
+int mi_debug_color_tasks(mi_world* w, uint32_t out[8]);
+/* Sizes of the tasks the last cluster build laid out: outTasks[p] = tasks of phase p (p < 5; [5..7] zero), outItems[p * 512 + t] = manifolds +
+   joints of task t of phase p (2560 words; zero beyond a phase's tasks). */
+int mi_debug_task_items(mi_world* w, uint32_t* outItems, uint32_t outTasks[8]);
 int mi_debug_read_world_colliders(mi_world* w, void* outColliders64, float* outAabbs6); /* worldSpaceColliders / worldSpaceAABBs */
 uint32_t mi_debug_num_manifold_slots(mi_world* w);
 /* Per candidate pair after prune/classify/bucket (collision_narrow.cpp:2346-2453): ordered collider pair, contact count, and up to 4
