@@ -109,6 +109,17 @@ PROXIMITY_READING_DTYPE = np.dtype([("distance", "<f4"), ("collider", "<u4"), ("
 PROX_STATIC, PROX_BRUTE_FORCE, PROX_COUNT, PROX_TERRAIN = 1, 2, 4, 8   # mi_proximity's flags (MI_PROX_*)
 
 
+class ClothCollision(C.Structure):
+    """struct mi_cloth_collision (include/mi_physics.h): the settings of a cloth's projection pass, 32 bytes"""
+    _fields_ = [("thickness", C.c_float), ("friction", C.c_float), ("flags", C.c_uint32), ("excludeFirst", C.c_uint32), ("excludeCount", C.c_uint32),
+                ("reserved", C.c_uint32 * 3)]
+
+
+CLOTH_COLLISION_DTYPE = np.dtype([("thickness", "<f4"), ("friction", "<f4"), ("flags", "<u4"), ("excludeFirst", "<u4"), ("excludeCount", "<u4"), ("reserved", "<u4", 3)])
+CLOTH_COLLIDE_STATIC, CLOTH_COLLIDE_TERRAIN = 1, 2   # mi_cloth_collision.flags (MI_CLOTH_COLLIDE_*)
+CLOTH_NO_CONTACT = 0xFFFFFFFF                        # mi_cloth_read_contacts: the particle was pushed off nothing
+
+
 class SphereCast(C.Structure):
     """struct mi_sphere_cast (include/mi_physics.h): one swept sphere of mi_sphere_cast_batch in the frame of body `mount`, 48 bytes"""
     _fields_ = [("origin", C.c_float * 3), ("maxT", C.c_float), ("direction", C.c_float * 3), ("radius", C.c_float),
@@ -189,6 +200,7 @@ EXPORTED_SYMBOLS = [
     "mi_add_force_field", "mi_set_force_field", "mi_add_trigger", "mi_add_force_field_collider", "mi_add_trigger_collider", "mi_set_force_field_transform", "mi_set_trigger_transform", "mi_enable_collision_events", "mi_drain_events",
     "mi_set_heightmap", "mi_heightmap_set_chunk", "mi_heightmap_update", "mi_heightmap_height_at",
     "mi_add_cloth", "mi_cloth_set_fixed_vertices", "mi_cloth_set_properties", "mi_set_cloth_iterations", "mi_num_cloths", "mi_cloth_num_particles", "mi_cloth_read",
+    "mi_cloth_set_collision", "mi_cloth_get_collision", "mi_cloth_read_contacts", "mi_debug_set_cloth_collision_brute_force",
     "mi_test_physics_interaction", "mi_apply_force_torque", "mi_set_velocity",
     "mi_set_transform", "mi_write_transforms", "mi_write_velocities", "mi_step", "mi_step_internal", "mi_synchronize", "mi_read_transforms", "mi_read_velocities", "mi_read_mass_properties",
     "mi_get_stats", "mi_enable_validation", "mi_enable_stage_timing", "mi_num_bodies", "mi_num_colliders", "mi_device_pointers", "mi_state_to_device_buffers", "mi_state_from_device_buffers", "mi_slab_configure", "mi_slab_message_bytes", "mi_slab_pack", "mi_slab_unpack", "mi_slab_read_codes", "mi_debug_num_pairs", "mi_debug_read_pairs", "mi_debug_sorting_axis", "mi_debug_narrow_limits", "mi_debug_color_tasks", "mi_debug_task_items",
@@ -460,6 +472,37 @@ class World:
         p = np.zeros((n, 3), np.float32); v = np.zeros((n, 3), np.float32)
         self._check(self.lib.mi_cloth_read(self.w, C.c_uint32(cloth), _p(p), _p(v)))
         return p, v
+
+    def cloth_set_collision(self, cloth, thickness, friction=0.0, static=True, terrain=False, exclude=(0, 0)):
+        """mi_cloth_set_collision: from the next internal step on the cloth's free particles are pushed to `thickness` from the nearest
+        collider surface (static: also the colliders without a rigid body; terrain: also the heightmap) and lose their approaching
+        velocity relative to it, with Coulomb `friction` on the rest (the rule is in include/mi_physics.h).  exclude = (first, count): the
+        colliders of these bodies are not met (the body the cloth hangs from)."""
+        s = ClothCollision(thickness, friction, (CLOTH_COLLIDE_STATIC if static else 0) | (CLOTH_COLLIDE_TERRAIN if terrain else 0), exclude[0], exclude[1])
+        self._check(self.lib.mi_cloth_set_collision(self.w, C.c_uint32(cloth), C.byref(s)))
+
+    def cloth_clear_collision(self, cloth):
+        self._check(self.lib.mi_cloth_set_collision(self.w, C.c_uint32(cloth), None))
+
+    def cloth_collision(self, cloth):
+        """None while collision is off, else dict(thickness, friction, static, terrain, exclude)"""
+        s, on = ClothCollision(), C.c_int(0)
+        self._check(self.lib.mi_cloth_get_collision(self.w, C.c_uint32(cloth), C.byref(s), C.byref(on)))
+        if not on.value:
+            return None
+        return dict(thickness=s.thickness, friction=s.friction, static=bool(s.flags & CLOTH_COLLIDE_STATIC), terrain=bool(s.flags & CLOTH_COLLIDE_TERRAIN),
+                    exclude=(s.excludeFirst, s.excludeCount))
+
+    def cloth_contacts(self, cloth):
+        """uint32 [n]: the collider every particle was pushed off in the last internal step (TERRAIN_COLLIDER: the heightmap;
+        CLOTH_NO_CONTACT: none)"""
+        out = np.zeros(self.lib.mi_cloth_num_particles(self.w, C.c_uint32(cloth)), np.uint32)
+        self._check(self.lib.mi_cloth_read_contacts(self.w, C.c_uint32(cloth), _p(out)))
+        return out
+
+    def set_cloth_collision_brute_force(self, on=True):
+        """debug: the projection pass asks every candidate instead of walking the tree (same bytes)"""
+        self._check(self.lib.mi_debug_set_cloth_collision_brute_force(self.w, int(on)))
 
     def add_constraint(self, ctype, a, b, pod):
         """addConstraint(a, b, const T&) (reference physics.h:239-244): the constraint as its POD bytes (layout of constraint_get)."""

@@ -361,6 +361,55 @@ int mi_cloth_read(mi_world* world, uint32_t cloth, float* positions3, float* vel
 	if (velocities3) memcpy(velocities3, c.vel.data(), sizeof(float) * c.vel.size());
 	return W->lastError;
 }
+// ---- cloth collision: the settings of the projection pass (k_cloth_collide.hip); the particle state is neither uploaded nor downloaded ----
+static u32 clothFirstParticle(const World* w, u32 cloth) { u32 first = 0; for (u32 i = 0; i < cloth; ++i) first += w->cloth.cloths[i].gridX * w->cloth.cloths[i].gridY; return first; }
+int mi_cloth_set_collision(mi_world* world, uint32_t cloth, const mi_cloth_collision* settings)
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	if (cloth >= W->cloth.cloths.size()) return MI_ERR_INVALID_ARGUMENT;
+	if (settings)
+	{
+		const mi_cloth_collision& s = *settings;
+		if (!(s.thickness >= 0.f && s.thickness <= MI_FLT_MAX) || !(s.friction >= 0.f && s.friction <= MI_FLT_MAX)) return MI_ERR_INVALID_ARGUMENT;
+		if ((s.flags & ~(uint32_t)(MI_CLOTH_COLLIDE_STATIC | MI_CLOTH_COLLIDE_TERRAIN)) || s.reserved[0] || s.reserved[1] || s.reserved[2]) return MI_ERR_INVALID_ARGUMENT;
+	}
+	W->resolvePendingFlow(); // a step that is redone is redone with the settings it ran with
+	World::HCloth& c = W->cloth.cloths[cloth];
+	if (c.collide && !settings)
+	{
+		W->cloth.numColliding--;
+		if (W->cloth.contacts.p && W->cloth.contactsStride == W->cloth.stride && !W->cloth.dirty) // nothing pushes its particles off anything any more
+			MI_CHECK(hipMemsetAsync(W->cloth.contacts.p + clothFirstParticle(W, cloth), 0xFF, sizeof(u32) * c.gridX * c.gridY, W->stream));
+	}
+	if (!c.collide && settings) W->cloth.numColliding++;
+	c.collide = settings != nullptr;
+	if (settings) c.collision = *settings; else c.collision = mi_cloth_collision{};
+	W->cloth.collideDirty = true;
+	return W->lastError;
+}
+int mi_cloth_get_collision(mi_world* world, uint32_t cloth, mi_cloth_collision* out, int* outEnabled)
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	if (cloth >= W->cloth.cloths.size()) return MI_ERR_INVALID_ARGUMENT;
+	const World::HCloth& c = W->cloth.cloths[cloth];
+	if (out) *out = c.collision;
+	if (outEnabled) *outEnabled = c.collide ? 1 : 0;
+	return MI_OK;
+}
+int mi_cloth_read_contacts(mi_world* world, uint32_t cloth, uint32_t* outColliderPerParticle)
+{
+	CHECK_WORLD(MI_ERR_INVALID_ARGUMENT);
+	if (cloth >= W->cloth.cloths.size() || !outColliderPerParticle) return MI_ERR_INVALID_ARGUMENT;
+	const World::HCloth& c = W->cloth.cloths[cloth];
+	const size_t n = (size_t)c.gridX * c.gridY;
+	// none: collision off, no pass has run yet, or the particle layout has changed since the last one
+	if (!c.collide || !W->cloth.contacts.p || W->cloth.contactsStride != W->cloth.stride || W->cloth.dirty) { memset(outColliderPerParticle, 0xFF, sizeof(uint32_t) * n); return W->lastError; }
+	W->resolvePendingFlow();
+	MI_CHECK(hipMemcpyAsync(outColliderPerParticle, W->cloth.contacts.p + clothFirstParticle(W, cloth), sizeof(uint32_t) * n, hipMemcpyDeviceToHost, W->stream));
+	MI_CHECK(hipStreamSynchronize(W->stream));
+	return W->lastError;
+}
+int mi_debug_set_cloth_collision_brute_force(mi_world* world, int on) { CHECK_WORLD(MI_ERR_INVALID_ARGUMENT); W->cloth.collideBrute = on != 0; return MI_OK; }
 
 // ---- constraints (physics.cpp:128-333) ----
 struct Trs { Q4 q; V3 p; };

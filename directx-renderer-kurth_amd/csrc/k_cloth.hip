@@ -246,4 +246,5 @@ void World::uploadCloths()
 	MI_CHECK(hipMemcpyAsync(cloth.list.p, small.data(), sizeof(u32) * small.size(), hipMemcpyHostToDevice, stream));
 	MI_CHECK(hipStreamSynchronize(stream));
 	cloth.dirty = false; cloth.stateOnDevice = false; // both copies are equal until the next launch
+	cloth.collideDirty = true;                        // (the particle layout may have changed: k_cloth_collide.hip writes its tables again)
 }

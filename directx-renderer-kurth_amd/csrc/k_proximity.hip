@@ -9,54 +9,7 @@
 //                           candidate flag of queries.leafBox.  rcMount, rcWalk, rcFetch and the RcScene argument: raycast_shared.h
 // The boxes only say which colliders need not be asked: a distance is decided by pointBodyCollider on the collider's LOCAL record and
 // pose alone, so the tree and brute force agree in every byte.
-#include "world.h"
-#include "point_tests.h"
-#include "raycast_shared.h"
-
-// Slack of the pruning test: a node is skipped only if the float32 distance from the point to its padded box exceeds
-// bound + PX_SLACK_ULPS ulps of (|point| + largest |coordinate| of the scene + largest leaf diagonal) + PX_SLACK_REL * bound.  DESIGN.md derives them.
-#define PX_SLACK_ULPS 32.f
-#define PX_SLACK_REL (1.f / 65536.f)
-#define PX_NONE 0xFFFFFFFFu
-
-struct PxQuery { V3 p; float radius, slackAbs; u32 exFirst, exCount; };
-struct PxBest { float d; u32 col, body, within; V3 c, n; };
-
-// Distance from p to the box b = {min xyz, max xyz}: 0 inside.  A NaN coordinate gives 0 on its axis (fmaxf drops it): such a node is visited.
-MI_DEV float pxBoxDistance(V3 p, const float* b)
-{
-	const float gx = fmaxf(fmaxf(b[0] - p.x, p.x - b[3]), 0.f), gy = fmaxf(fmaxf(b[1] - p.y, p.y - b[4]), 0.f), gz = fmaxf(fmaxf(b[2] - p.z, p.z - b[5]), 0.f);
-	return sqrtf(gx * gx + gy * gy + gz * gz);
-}
-// What a node's box distance is held against.  COUNT: every candidate within the radius has to be met.  Otherwise only one that beats or
-// ties the best so far (a lower collider index may win the tie); never below 0, the distance of a box that contains the point.
-template <bool COUNT>
-MI_DEV float pxLimit(const PxQuery& q, const PxBest& best)
-{
-	const float bound = COUNT ? q.radius : fmaxf(fminf(q.radius, best.d), 0.f);
-	return bound + (q.slackAbs + PX_SLACK_REL * bound);
-}
-
-// rcWalk's visitor of a point: a box is held against pxLimit, a leaf within the radius is counted and may become the nearest.
-template <bool COUNT>
-struct PxVisitor
-{
-	const PxQuery& q; const RcScene& sc; PxBest& best;
-	MI_DEV bool box(const float* b, float& d) const { d = pxBoxDistance(q.p, b); return !(d > pxLimit<COUNT>(q, best)); } // (a tie and a NaN visit)
-	MI_DEV void leaf(u32 c)
-	{
-		RcCollider col;
-		if (!rcFetch(sc, c, RcExclude{ q.exFirst, q.exCount }, col)) return;
-		const PtHit h = pointBodyCollider(conjugate(col.rot) * (q.p - col.pos), col.type, col.s, sc.hulls);
-		if (!(h.d <= q.radius)) return;
-		if (COUNT) best.within++;
-		if (best.col == PX_NONE || h.d < best.d || (h.d == best.d && c < best.col))
-		{
-			best.d = h.d; best.col = c; best.body = col.reported;
-			best.c = col.rot * h.c + col.pos; best.n = col.rot * h.n;
-		}
-	}
-};
+#include "proximity_shared.h" // PxQuery, PxBest, PxVisitor, pxBoxDistance: shared with the cloth's projection pass (k_cloth_collide.hip)
 
 // queries: 2 x float4 per query = mi_proximity_query {point.xyz, radius}, {mount, excludeFirst, excludeCount, enabled} (bits);
 // out: 3 x float4 = mi_proximity_reading; worldPoints: NULL or 1 x float4 = {world point.xyz, radius}.  built == 0: no tree, nothing within.
@@ -78,8 +31,8 @@ __global__ void __launch_bounds__(64) k_proximity(u32 numQueries, const float4* 
 		if (m == RC_MOUNT_BODY) q.p = rot * q.p + pos;
 	}
 	if (worldPoints) worldPoints[i] = on ? make_float4(q.p.x, q.p.y, q.p.z, q.radius) : make_float4(0.f, 0.f, 0.f, 0.f);
-	PxBest best; best.d = __builtin_inff(); best.col = PX_NONE; best.body = 0u; best.within = 0u; best.c = v3s(0.f); best.n = v3s(0.f);
-	PxVisitor<COUNT> v{ q, sc, best };
+	PxBest best = pxBestNone();
+	PxVisitor<COUNT> v{ q, sc, best, true }; // (the tree holds the static colliders iff the call wants them)
 	const u32 n = built ? sc.hdr[RC_N] : 0u;
 	if (on && q.radius >= 0.f && n != 0u) // (a negative or NaN radius finds nothing)
 	{
@@ -89,8 +42,7 @@ __global__ void __launch_bounds__(64) k_proximity(u32 numQueries, const float4* 
 		}
 		else
 		{
-			const V3 ap = vabs(q.p);
-			q.slackAbs = PX_SLACK_ULPS * RC_EPS * (fmaxf(fmaxf(ap.x, ap.y), ap.z) + mi_u2f(sc.hdr[RC_ABS]) + mi_u2f(sc.hdr[RC_DIAG]));
+			q.slackAbs = pxSlackAbs(q.p, sc);
 			rcWalk(v, sc, n, &stack[0][threadIdx.x], 64u);
 		}
 	}

@@ -30,34 +30,7 @@
 // sqrt(2) S e within that rim, which the next level's S, taken over the larger box, covers.  The box distance itself: 3 subtractions at
 // M, then 5 relative roundings.  PXT_SLACK_ULPS = 64 is twice the sum, PXT_SLACK_REL = 2^-16 covers the relative roundings of both
 // distances (k_proximity.hip's PX_SLACK_REL).
-#include "world.h"
-#include "terrain_point.h"
-#include "terrain_walk.h"
-#include "raycast_shared.h"
-
-#define PXT_SLACK_ULPS 64.f
-#define PXT_SLACK_REL (1.f / 65536.f)
-
-struct PxtQuery { V3 p; float radius, slackCol, slackBase, invCell; };
-
-// Distance from p to the box [x0, x1] x [heights lo .. hi] x [z0, z1]; 0 inside.
-MI_DEV float pxtBoxDistance(const TerrainParams& P, V3 p, float x0, float x1, float z0, float z1, u32 lo, u32 hi)
-{
-	const float y0 = (float)lo * P.heightScale + P.minY, y1 = (float)hi * P.heightScale + P.minY;
-	const float gx = fmaxf(fmaxf(x0 - p.x, p.x - x1), 0.f), gy = fmaxf(fmaxf(y0 - p.y, p.y - y1), 0.f), gz = fmaxf(fmaxf(z0 - p.z, p.z - z1), 0.f);
-	return sqrtf(gx * gx + gy * gy + gz * gz);
-}
-// What a box distance is held against (a tie and a NaN visit).
-MI_DEV float pxtLimit(const TerrainParams& P, const PxtQuery& q, const TpBest& best, u32 lo, u32 hi)
-{
-	const float bound = best.below ? best.d : fminf(q.radius, best.d);
-	const float S = (float)(hi - lo) * P.heightScale * q.invCell;
-	return bound + (q.slackBase * (1.f + S * S) + PXT_SLACK_REL * bound);
-}
-MI_DEV void pxtCell(const TerrainParams& P, const uint16_t* __restrict__ H, V3 chunkMin, u32 chunk, u32 cx, u32 cz, V3 p, TpBest& best)
-{
-	tpPointCell(P, chunkMin, chunk, cx, cz, H[TERRAIN_VERTS * cz + cx], H[TERRAIN_VERTS * (cz + 1u) + cx], H[TERRAIN_VERTS * cz + cx + 1u], H[TERRAIN_VERTS * (cz + 1u) + cx + 1u], p, best);
-}
+#include "proximity_shared.h" // PxtQuery, pxtBoxDistance, pxtLimit, pxtSearch: shared with the cloth's projection pass (k_cloth_collide.hip)
 
 // queries, out: k_proximity's.  nb, pose, alive, simMask: rcMount's.
 template <bool BRUTE, bool COUNT>
@@ -69,91 +42,20 @@ __global__ void __launch_bounds__(64) k_px_terrain(u32 numQueries, const float4*
 	if (i >= numQueries) return;
 	const float4 q0 = queries[2 * i], q1 = queries[2 * i + 1];
 	if (mi_f2u(q1.w) == 0u) return;
-	PxtQuery q; q.p = v3(q0.x, q0.y, q0.z); q.radius = q0.w;
+	V3 p = v3(q0.x, q0.y, q0.z); const float radius = q0.w;
 	{
 		Q4 rot; V3 pos;
 		const RcMount m = rcMount(mi_f2u(q1.x), nb, pose, alive, simMask, rot, pos);
 		if (m == RC_MOUNT_OFF) return;
-		if (m == RC_MOUNT_BODY) q.p = rot * q.p + pos;
+		if (m == RC_MOUNT_BODY) p = rot * p + pos;
 	}
-	if (!(q.radius >= 0.f)) return; // (a negative or NaN radius finds nothing)
-	const V3 p = q.p, corner = v3(P.minX, P.minY, P.minZ);
-	const u32 cpd = P.chunksPerDim;
-	const V3 ap = vabs(p);
-	const float pMax = fmaxf(fmaxf(ap.x, ap.y), ap.z);
+	if (!(radius >= 0.f)) return; // (a negative or NaN radius finds nothing)
+	const float pMax = pxtPointMax(p);
 	if (!(pMax <= MI_FLT_MAX)) return; // a point that is not finite has no nearest triangle (the walk and brute force alike)
-	TpBest best = tpBestNone();
-	if (BRUTE)
-	{
-		for (u32 chunk = 0; chunk < cpd * cpd; ++chunk)
-		{
-			if (!valid[chunk]) continue;
-			const V3 chunkMin = terrainChunkMin(P, corner, chunk % cpd, chunk / cpd);
-			const uint16_t* H = heights + (size_t)chunk * TERRAIN_VERTS * TERRAIN_VERTS;
-			for (u32 cz = 0; cz < RT_CELLS; ++cz)
-				for (u32 cx = 0; cx < RT_CELLS; ++cx) pxtCell(P, H, chunkMin, chunk, cx, cz, p, best);
-		}
-	}
-	else
-	{
-		const float span = P.chunkSize * (float)cpd, top = 65535.f * P.heightScale;
-		const V3 am = vmax(vabs(corner), vabs(corner + v3(span, top, span)));
-		const float M = pMax + fmaxf(fmaxf(am.x, am.y), am.z);
-		q.slackCol = RT_SLACK_ULPS * RT_EPS * M; q.slackBase = PXT_SLACK_ULPS * RT_EPS * M; q.invCell = 1.f / P.chunkScale;
-		const int last = (int)cpd - 1, lastCell = (int)RT_CELLS - 1;
-		// the column: every cell whose widened extent holds (p.x, p.z); clamped indices only add real triangles
-		{
-			const int Xa = rtIndex((p.x - q.slackCol - P.minX) * P.invChunkSize, 0, last), Xb = rtIndex((p.x + q.slackCol - P.minX) * P.invChunkSize, 0, last);
-			const int Za = rtIndex((p.z - q.slackCol - P.minZ) * P.invChunkSize, 0, last), Zb = rtIndex((p.z + q.slackCol - P.minZ) * P.invChunkSize, 0, last);
-			for (int Z = Za; Z <= Zb; ++Z)
-				for (int X = Xa; X <= Xb; ++X)
-				{
-					const u32 chunk = (u32)Z * cpd + (u32)X;
-					if (!valid[chunk]) continue;
-					const V3 chunkMin = terrainChunkMin(P, corner, (u32)X, (u32)Z);
-					const uint16_t* H = heights + (size_t)chunk * TERRAIN_VERTS * TERRAIN_VERTS;
-					const int xa = rtIndex((p.x - q.slackCol - chunkMin.x) * q.invCell, 0, lastCell), xb = rtIndex((p.x + q.slackCol - chunkMin.x) * q.invCell, 0, lastCell);
-					const int za = rtIndex((p.z - q.slackCol - chunkMin.z) * q.invCell, 0, lastCell), zb = rtIndex((p.z + q.slackCol - chunkMin.z) * q.invCell, 0, lastCell);
-					for (int cz = za; cz <= zb; ++cz)
-						for (int cx = xa; cx <= xb; ++cx) pxtCell(P, H, chunkMin, chunk, (u32)cx, (u32)cz, p, best);
-				}
-		}
-		// the range search: chunks -> tiles -> cells.  The index ranges only spare box tests (they are cut by the same limit plus the
-		// column's slack); the box test decides.
-		const float tileSize = P.chunkScale * (float)RT_TILE, invTile = 1.f / tileSize;
-		for (u32 chunk = 0; chunk < cpd * cpd; ++chunk)
-		{
-			if (!valid[chunk]) continue;
-			const u32 cr = chunkRange[chunk];
-			const V3 chunkMin = terrainChunkMin(P, corner, chunk % cpd, chunk / cpd);
-			const float limC = pxtLimit(P, q, best, cr & 0xFFFFu, cr >> 16);
-			if (pxtBoxDistance(P, p, chunkMin.x, chunkMin.x + P.chunkSize, chunkMin.z, chunkMin.z + P.chunkSize, cr & 0xFFFFu, cr >> 16) > limC) continue;
-			const uint16_t* H = heights + (size_t)chunk * TERRAIN_VERTS * TERRAIN_VERTS;
-			const float wC = limC + q.slackCol;
-			const int txa = rtIndex((p.x - wC - chunkMin.x) * invTile, 0, (int)RT_TILES - 1), txb = rtIndex((p.x + wC - chunkMin.x) * invTile, 0, (int)RT_TILES - 1);
-			const int tza = rtIndex((p.z - wC - chunkMin.z) * invTile, 0, (int)RT_TILES - 1), tzb = rtIndex((p.z + wC - chunkMin.z) * invTile, 0, (int)RT_TILES - 1);
-			for (int tz = tza; tz <= tzb; ++tz)
-				for (int tx = txa; tx <= txb; ++tx)
-				{
-					const u32 tr = tiles[chunk * (RT_TILES * RT_TILES) + (u32)tz * RT_TILES + (u32)tx];
-					const float tx0 = chunkMin.x + (float)tx * tileSize, tz0 = chunkMin.z + (float)tz * tileSize;
-					const float limT = pxtLimit(P, q, best, tr & 0xFFFFu, tr >> 16);
-					if (pxtBoxDistance(P, p, tx0, tx0 + tileSize, tz0, tz0 + tileSize, tr & 0xFFFFu, tr >> 16) > limT) continue;
-					for (u32 cz = (u32)tz * RT_TILE; cz < (u32)tz * RT_TILE + RT_TILE; ++cz)
-						for (u32 cx = (u32)tx * RT_TILE; cx < (u32)tx * RT_TILE + RT_TILE; ++cx)
-						{
-							const u32 ha = H[TERRAIN_VERTS * cz + cx], hb = H[TERRAIN_VERTS * (cz + 1u) + cx], hc = H[TERRAIN_VERTS * cz + cx + 1u], hd = H[TERRAIN_VERTS * (cz + 1u) + cx + 1u];
-							const u32 lo = min(min(ha, hb), min(hc, hd)), hi = max(max(ha, hb), max(hc, hd));
-							const float cx0 = chunkMin.x + (float)cx * P.chunkScale, cz0 = chunkMin.z + (float)cz * P.chunkScale;
-							if (pxtBoxDistance(P, p, cx0, cx0 + P.chunkScale, cz0, cz0 + P.chunkScale, lo, hi) > pxtLimit(P, q, best, lo, hi)) continue;
-							tpPointCell(P, chunkMin, chunk, cx, cz, ha, hb, hc, hd, p, best);
-						}
-				}
-		}
-	}
+	const TpBest best = pxtSearch<BRUTE>(P, heights, valid, tiles, chunkRange, p, radius, pMax);
 	if (best.id == TP_NO_TRIANGLE) return;
 	const TpReading r = tpReading(p, best);
-	if (!(r.d <= q.radius)) return;
+	if (!(r.d <= radius)) return;
 	const float4 rec0 = out[3 * i], rec1 = out[3 * i + 1];
 	const bool colFound = mi_f2u(rec0.w) != 0u;
 	const u32 within = COUNT ? mi_f2u(rec1.w) + 1u : 0u;

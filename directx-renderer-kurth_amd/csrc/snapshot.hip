@@ -5,7 +5,7 @@
 
 namespace
 {
-	const uint32_t SNAPSHOT_MAGIC = 0x4850494Du, SNAPSHOT_VERSION = 5;
+	const uint32_t SNAPSHOT_MAGIC = 0x4850494Du, SNAPSHOT_VERSION = 6;
 	struct BlobWriter
 	{
 		std::vector<uint8_t> bytes;
@@ -74,6 +74,7 @@ namespace
 			float params[8] = { c.width, c.height, c.totalMass, c.stiffness, c.damping, c.gravityFactor, c.oldTotalMass, c.oldStiffness };
 			out.put(params, sizeof(params)); out.pod(c.gridX); out.pod(c.gridY);
 			out.vec(c.pos); out.vec(c.prev); out.vec(c.vel); out.vec(c.invMass); out.vec(c.constraints);
+			uint32_t collide = c.collide ? 1u : 0u; out.pod(collide); out.pod(c.collision); // the settings of the projection pass; the contact plane does not travel
 		}
 	}
 }
@@ -149,6 +150,8 @@ mi_world* mi_world_restore(const mi_world_desc* desc, const void* buffer, uint64
 		in.get(params, sizeof(params)); in.pod(c.gridX); in.pod(c.gridY);
 		c.width = params[0]; c.height = params[1]; c.totalMass = params[2]; c.stiffness = params[3]; c.damping = params[4]; c.gravityFactor = params[5]; c.oldTotalMass = params[6]; c.oldStiffness = params[7];
 		in.vec(c.pos); in.vec(c.prev); in.vec(c.vel); in.vec(c.invMass); in.vec(c.constraints);
+		uint32_t collide = 0; in.pod(collide); in.pod(c.collision); c.collide = collide != 0;
+		if (c.collide) w.cloth.numColliding++;
 		if (in.ok && (c.pos.size() != 3 * (size_t)c.gridX * c.gridY || c.vel.size() != c.pos.size() || c.prev.size() != c.pos.size() || c.invMass.size() * 3 != c.pos.size())) in.ok = false;
 		w.cloth.cloths.push_back(std::move(c));
 	}

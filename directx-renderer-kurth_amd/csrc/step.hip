@@ -192,6 +192,7 @@ void World::recoverFlow()
 	colorFromScratch(*this);
 	solveWithLaunchSweep(*this, last.numPairs, last.dt, last.iters);
 	launch_integrate_velocities(*this, last.dt);
+	launch_cloth_collide(*this);      // the step's own pass skipped itself on the status word, as the integration did (it runs before the next step's cloth kernel either way)
 	last.cluster = false;
 	if (last.jointPath != MI_JOINT_PATH_NONE) last.jointPath = MI_JOINT_PATH_LAUNCH_SWEEP;
 }
@@ -429,6 +430,7 @@ int World::stepInternal(float dt, u32 iters)
 	launch_integrate_velocities(*this, dt);
 	launch_validate(*this, 3, 0);
 	launch_cloth(*this, dt);                               // physics.cpp:1354-1358
+	launch_cloth_collide(*this);                           // mi_cloth_set_collision: nothing unless a cloth has it on
 	stamp(*this, ev, 5);
 
 	stats.numRigidBodies = nb; stats.numColliders = nc; stats.numJoints = numSortedJoints(); stats.coloringRounds = coloringRounds;

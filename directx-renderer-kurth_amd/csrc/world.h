@@ -177,6 +177,7 @@ struct World
 		float width, height, totalMass, stiffness, damping, gravityFactor, oldTotalMass, oldStiffness; u32 gridX, gridY;
 		std::vector<float> pos, prev, vel, invMass;          // 3 n, 3 n, 3 n, n
 		std::vector<HClothConstraint> constraints;            // sorted by colour (stable)
+		bool collide = false; mi_cloth_collision collision = {}; // mi_cloth_set_collision: a parameter of the projection pass (k_cloth_collide.hip), not of the particle state
 	};
 	std::vector<HBody> bodies;
 	std::vector<HCollider> colliders;
@@ -249,7 +250,7 @@ struct World
 		u32 slotCap(u32 numColliders) const { return chunksPerDim ? std::max(minSlots, slotsPerCollider * numColliders) : 0u; }
 	} terrain;
 
-	// Cloth: k_cloth.hip (kernels, uploadCloths, downloadCloths), api_scene.hip (mi_add_cloth, mi_cloth_*), step.hip, snapshot.hip
+	// Cloth: k_cloth.hip (kernels, uploadCloths, downloadCloths), k_cloth_collide.hip (the projection pass), api_scene.hip (mi_add_cloth, mi_cloth_*), step.hip, snapshot.hip
 	struct Cloth
 	{
 		std::vector<HCloth> cloths;
@@ -258,6 +259,12 @@ struct World
 		DevBuf<float> planes; u32 stride = 0; // 10 planes of stride floats: position xyz, velocity xyz, previous position xyz, inverse mass
 		DevBuf<uint2> ab; DevBuf<float2> restIms; DevBuf<float4> temp; DevBuf<uint8_t> descs; DevBuf<u32> list;
 		u32 numSmall = 0, maxSmallParticles = 0; // cloths that fit the LDS variant come first in list
+		// Collision (mi_cloth_set_collision; k_cloth_collide.hip): cloths with collision on (0: the step launches nothing for it), the pass's
+		// tables {one record per colliding cloth, one {record, first particle} per 64-lane workgroup} and whether they have to be written
+		// again (a setting or the particle layout changed); one word per particle of `planes`: the collider it was pushed off in the last
+		// internal step (0xFFFFFFFF: none), laid out for contactsStride particles
+		u32 numColliding = 0, collideBlocks = 0, collideFlags = 0, contactsStride = 0; bool collideDirty = true, collideBrute = false;
+		DevBuf<uint8_t> collideDescs; DevBuf<uint2> collideBlockList; DevBuf<u32> contacts;
 	} cloth;
 	void uploadCloths(); void downloadCloths();
 
@@ -407,6 +414,7 @@ void launch_integrate_forces(World& w, float dt, bool backupVelocities); // back
 void launch_heightmap(World& w, u32 numPairs, u32 slotCap);  // terrain contacts appended after the pair manifolds (physics.cpp:1236-1249)
 void launch_cloth(World& w, float dt);                      // cloth_component::applyWindForce + simulate for every cloth (physics.cpp:1354-1358)
 u32 cloth_lds_particle_limit();
+void launch_cloth_collide(World& w);                        // k_cloth_collide.hip: the projection pass of the cloths with collision on, after launch_cloth (and after a recovery's integration); nothing without such a cloth
 void launch_apply_fields(World& w);                        // localized + global force fields -> force accumulators (before the force integration)
 void launch_trigger_events(World& w);                      // leave events + table hand-over of the trigger overlap set (after the narrowphase)
 void launch_collision_events(World& w, u32 numPairs);      // begin / end events of this step's manifolds (after the force integration)

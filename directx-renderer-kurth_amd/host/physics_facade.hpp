@@ -165,6 +165,10 @@ namespace mi
 		transform_component transform() const; // transform_component after the last physicsStep (interpolated)
 		vec3 linearVelocity() const;
 		std::vector<vec3> clothPositions() const; // cloth_component::positions (what cloth_render_component::getRenderData uploads, cloth.cpp:357-363)
+		// mi_cloth_set_collision for the entity's cloth (no counterpart in the reference): flags = MI_CLOTH_COLLIDE_*; clothContacts: per
+		// particle the collider it was pushed off in the last step, 0xFFFFFFFF for none (mi_cloth_read_contacts)
+		void setClothCollision(float thickness, float friction = 0.f, uint32_t flags = MI_CLOTH_COLLIDE_STATIC);
+		std::vector<uint32_t> clothContacts() const;
 		bool operator==(const scene_entity& o) const { return scene == o.scene && index == o.index; }
 	};
 	struct trigger_event { scene_entity trigger, other; trigger_event_type type; };                                       // physics.h:193-198
@@ -353,6 +357,21 @@ namespace mi
 		return transform_component({ p[0], p[1], p[2] }, { p[3], p[4], p[5], p[6] });
 	}
 
+	inline void scene_entity::setClothCollision(float thickness, float friction, uint32_t flags)
+	{
+		uint32_t c = scene->entities[index].cloth;
+		if (c == 0xFFFFFFFFu) throw physics_error("entity has no cloth_component");
+		mi_cloth_collision s{}; s.thickness = thickness; s.friction = friction; s.flags = flags;
+		scene->check(mi_cloth_set_collision(scene->world, c, &s), "mi_cloth_set_collision");
+	}
+	inline std::vector<uint32_t> scene_entity::clothContacts() const
+	{
+		uint32_t c = scene->entities[index].cloth;
+		if (c == 0xFFFFFFFFu) throw physics_error("entity has no cloth_component");
+		std::vector<uint32_t> out(mi_cloth_num_particles(scene->world, c));
+		scene->check(mi_cloth_read_contacts(scene->world, c, out.data()), "mi_cloth_read_contacts");
+		return out;
+	}
 	inline std::vector<vec3> scene_entity::clothPositions() const
 	{
 		uint32_t c = scene->entities[index].cloth;

@@ -189,6 +189,47 @@ uint32_t mi_cloth_num_particles(mi_world* w, uint32_t cloth);
 /* Particle positions / velocities, row-major over the grid, n x 3 floats each (either pointer may be NULL). */
 int mi_cloth_read(mi_world* w, uint32_t cloth, float* positions3, float* velocities3);
 
+/* Cloth collision: the particles of a cloth are pushed out of the world's colliders and of the heightmap terrain.  (The reference's cloth
+ * has no collision: the rule is this project's, as the proximity rule below is, and it is written on top of that rule.)
+ * Per cloth, collision is off until mi_cloth_set_collision turns it on; a world without such a cloth launches nothing for it.  A cloth
+ * that is on gets one projection pass per internal step, after the cloth kernel has written that step's positions and damped
+ * velocities; it reads the body poses and velocities the step's velocity integration left.  Every particle i with invMass > 0 is handled
+ * on its own: it reads no other particle, so the result does not depend on the order of the lanes.
+ * Reading: exactly what mi_proximity (below) reports for a world-space query (mount = MI_STATIC_BODY) at the particle's position p with
+ * radius = thickness, excludeFirst / excludeCount of the settings, and the flags MI_PROX_STATIC iff MI_CLOTH_COLLIDE_STATIC,
+ * MI_PROX_TERRAIN iff MI_CLOTH_COLLIDE_TERRAIN, without MI_PROX_COUNT: the same candidates, float32 operation order, tie rules, and the
+ * terrain replaces the collider reading only if its distance is strictly smaller.  Nothing found leaves the particle untouched, byte
+ * for byte; so does a reading whose normal is zero (a particle at a sphere's centre, on a capsule's or a cylinder's axis).
+ * Projection: with d, c, n, body of the reading, in float32 without contraction, dot, cross and length as csrc/mi_common.h writes them
+ * (left to right), a vector times a scalar per component:
+ *   push = thickness - d;  p' = p + n * push
+ *   vs = 0 for a static collider and for the terrain, otherwise vs = v_b + cross(w_b, c - cog_b) with (v_b, w_b) the body's linear and
+ *        angular velocity (mi_read_velocities) and cog_b = pos_b + rot_b * localCOG_b from its pose after the integration
+ *        (mi_read_transforms, mi_read_mass_properties).  The device's centre-of-gravity array (mi_debug_read_body_state) is NOT used: the
+ *        velocity integration reads it and moves the pose, and the array is formed again only by the next step's force integration.
+ *   u = v - vs;  un = dot(u, n)
+ *   if un < 0:  u = u - n * un;  jn = -un;  lt = |u|;  if friction > 0: u = u * s with s = 1 - (friction * jn) / lt if lt > friction * jn,
+ *               else s = 0;  v' = vs + u
+ *   otherwise (a NaN included) v' = v, byte for byte; the position is pushed all the same.
+ * Contact plane: one uint32 per particle, the collider it was pushed off in the last internal step, MI_TERRAIN_COLLIDER for the terrain,
+ * 0xFFFFFFFF for none; it reads none before the first step, for fixed particles (invMass == 0) and for a cloth whose collision is off.
+ * A step whose cluster sweep gave up skips the pass with the velocity integration; the recovery runs it behind its own integration,
+ * before the next step's cloth kernel, so the order above holds there too.
+ * Limits: one-way (the bodies feel nothing); particles only (a collider smaller than the grid spacing slips between them); the nearest
+ * candidate only, one correction per step; no self-collision; a particle that crosses more than half a thin collider in one step comes
+ * out on the far side.
+ * mi_cloth_set_collision(NULL) turns collision off.  MI_ERR_INVALID_ARGUMENT: a thickness or friction that is not finite or is negative,
+ * unknown flag bits, non-zero reserved words, a cloth index out of range.  Setting and clearing settle a step whose cluster sweep is not
+ * yet known to have completed and neither upload nor download particle state.  The settings travel with mi_snapshot_save /
+ * mi_world_restore; the contact plane does not.
+ * mi_debug_set_cloth_collision_brute_force: every candidate collider (and every terrain triangle) instead of the tree: same bytes. */
+enum { MI_CLOTH_COLLIDE_STATIC = 1, MI_CLOTH_COLLIDE_TERRAIN = 2 };
+typedef struct mi_cloth_collision { float thickness, friction; uint32_t flags, excludeFirst, excludeCount, reserved[3]; } mi_cloth_collision; /* 32 bytes */
+int mi_cloth_set_collision(mi_world* w, uint32_t cloth, const mi_cloth_collision* settings);
+int mi_cloth_get_collision(mi_world* w, uint32_t cloth, mi_cloth_collision* out, int* outEnabled);
+int mi_cloth_read_contacts(mi_world* w, uint32_t cloth, uint32_t* outColliderPerParticle);
+int mi_debug_set_cloth_collision_brute_force(mi_world* w, int on);
+
 /* void testPhysicsInteraction(game_scene&, ray, float strength = 1000.f): physics.h:404, physics.cpp:556-628 — the closest rigid-body
  * collider hit by the ray gets force = direction * strength at the hit point.  Returns 1 + the index of the body that was
  * pushed, 0 when the ray hits nothing (this one function does not return a status code). */
