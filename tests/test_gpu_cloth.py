@@ -1,4 +1,6 @@
-"""Cloth (row N4 of SURVEY §8f; reference cloth.cpp, physics.cpp:1354-1358) on the GPU against the oracle's colour-ordered restatement."""
+"""Cloth (row N4 of SURVEY §8f; reference cloth.cpp, physics.cpp:1354-1358) on the GPU against the oracle's colour-ordered restatement:
+the scenes, over hundreds of steps.  The grid, iteration, dt and LDS-limit edges, the comparison with a float64 reading that does not go
+through the oracle, and the life of the particle state between host and device are in test_gpu_cloth_edges.py (battery: cloth64.py)."""
 import numpy as np
 import pytest
 
